@@ -16,6 +16,18 @@ Rank 0 prints ONE JSON line.  `roofline` is the dominant (EM pass) kernel's
 algorithmic bytes per launch / its HIP-event-timed duration against the 8 TB/s
 HBM peak; `cpu_baseline` times the oracle (scipy operator sequence of the
 reference) on a bounded sample of the same workload on this box's host cores.
+
+A plain run sets up, warms up, times the steps and prints the line: the
+headline, the `check` fold of the parameters it left and the roofline of the
+timed launches.  Everything that costs work of its own — `phase_us`, the N = 1
+reference of a multi-rank run, `whole_em_call`, `report_pass`, the measured
+stream peak, `code16_layout`, the CPU baselines and parity sample,
+`precision_sweep`, `reproducible_mode` — runs only with `--full` (the
+`--no-...` options still switch single legs of it off).
+
+`--dump-outputs DIR` writes what the timed call left its caller after the last
+timed step as float64 .npy files (`dump_outputs`); the inputs depend on the
+arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -40,6 +52,8 @@ EMBEDDED_CHECK = {
     23: dict(pi_sum=0.9999999999999775, pi_weighted=0.055838211628101916, theta_weighted=0.49818481973259593),
 }
 PHASE_ITERS = 8         # iterations timed phase by phase (HIP events between the kernels) after the timed region
+DUMP_Z_ROWS = 16384     # rows of z sampled by --dump-outputs (<= 255 entries each: at most 32 MB of z)
+DUMP_MAX_BYTES = 64 << 20
 
 
 class Opts(object):
@@ -112,7 +126,16 @@ def parse():
                     help='N > 1: skip the N = 1 run of the whole problem on rank 0\'s GPU (speedup_vs_n1, check.matches_n1)')
     ap.add_argument('--force-comm', action='store_true',
                     help='use the multi-rank code path (RCCL group, per-iteration all-reduce) even at world size 1')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run every leg that takes work of its own: phase timing, the N = 1 reference (N > 1), '
+                         'the whole em() call, the report pass, the stream peak, the code16 layout, the CPU baselines, the precision '
+                         'sweep and the reproducible mode (each --no-... option still skips its leg)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed call left its caller after the last timed step to DIR/<name>.npy (float64): '
+                         'pi, theta, pi_init, theta_init and z on a fixed, seeded sample of rows')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     args.config_note = None
     if args.config:
         n = max(1, args.gpus)
@@ -407,18 +430,21 @@ def main():
         return all(abs(a[k] - b[k]) <= CHECK_RTOL * max(abs(b[k]), 1e-300) for k in ('pi_sum', 'pi_weighted', 'theta_weighted'))
 
     check = fold(eng, args.warmup + args.steps) if rank == 0 else None
+    dumped = dump_outputs(args.dump_outputs, tl, eng, args, r0, r1) if (args.dump_outputs and rank == 0) else None
 
-    # ---- where an iteration's time goes: PHASE_ITERS more iterations on EVERY rank (the all-reduce is collective) with a HIP event at
-    # every phase boundary — pass | column reduce | all-reduce | update | gap to the next pass.  Outside the timed region; the events
-    # cost the stream a few microseconds each, so the phases add up to slightly more than `ms_per_step`.
-    eng.set_option('kernel_timing', 0)
-    eng.set_option('phase_timing', 1)
-    eng.phase_times(reset=True)
-    run(PHASE_ITERS)
-    fence()
-    phases = eng.phase_times(reset=True)
-    eng.set_option('phase_timing', 0)
-    eng.set_option('kernel_timing', args.kernel_timing)
+    phases = None
+    if args.full:
+        # ---- where an iteration's time goes: PHASE_ITERS more iterations on EVERY rank (the all-reduce is collective) with a HIP event
+        # at every phase boundary — pass | column reduce | all-reduce | update | gap to the next pass.  Outside the timed region; the
+        # events cost the stream a few microseconds each, so the phases add up to slightly more than `ms_per_step`.
+        eng.set_option('kernel_timing', 0)
+        eng.set_option('phase_timing', 1)
+        eng.phase_times(reset=True)
+        run(PHASE_ITERS)
+        fence()
+        phases = eng.phase_times(reset=True)
+        eng.set_option('phase_timing', 0)
+        eng.set_option('kernel_timing', args.kernel_timing)
     props = None
     if args.properties:
         props = properties_leg(tl, eng, comm, total_rows, nnz_total, args)     # collective: every rank
@@ -427,7 +453,7 @@ def main():
         return
 
     n1 = None
-    if world > 1 and args.scaling == 'strong' and not args.no_n1_reference:
+    if args.full and world > 1 and args.scaling == 'strong' and not args.no_n1_reference:
         # the N = 1 reference in THIS process: the whole problem on rank 0's GPU (it fits: 24 GB of entries), same options, same
         # warm-up + steps, no communicator — its time is what `speedup_vs_n1` divides by, its parameters what `check.matches_n1`
         # compares with.  (The other ranks have left; nothing here is collective.)
@@ -470,11 +496,12 @@ def main():
         check['matches_n1_how'] = 'against the N = 1 values embedded in bench.py (EMBEDDED_CHECK), rtol %g' % CHECK_RTOL
     else:
         check['matches_n1'] = None
-        check['matches_n1_how'] = 'no N = 1 reference for this workload / iteration count'
+        check['matches_n1_how'] = 'no N = 1 reference for this workload / iteration count' + \
+            ('' if args.full or world == 1 else ' (the N = 1 run of a multi-rank line is part of --full)')
     if emb is not None:
         check['matches_embedded'] = same(check, emb)
     whole = None
-    if world == 1:
+    if args.full and world == 1:
         # the same call as a user makes it: `steps` iterations and the final log-likelihood pass (model.py:800-801)
         eng.set_option('kernel_timing', 0)
         tl.keep_kernel_timing = False
@@ -491,7 +518,7 @@ def main():
                      note='tl.em() with max_iter = steps, em_epsilon = 0, incl. the log-likelihood pass after the loop; '
                           'no per-pass HIP events')
     report_pass = None
-    if world == 1:
+    if args.full and world == 1:
         # the report pass over the final z (conf | exclude | average of output_report, model.py:432-457) on the bench's matrix, after the
         # timed region: HIP events around its dominant kernel (tsem_report_stats), wall clock of the whole call.  Not part of `value`.
         try:
@@ -520,19 +547,21 @@ def main():
     k_ms = ks['em_ms'] / max(1, ks['em_launches'])
     achieved = ks['algo_bytes_per_pass'] / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
     # the nominal AND the measured-stream peak.  A pure streaming read of an 8 GB scratch buffer on this GPU, in this
-    # run (tsem_debug_stream_read: 16-byte non-temporal loads, eight in flight per thread, best of three launches)
-    try:
-        from telescope_amd._lib import stream_read_gbs
-        peak_measured = stream_read_gbs(local, 8 << 30, 3)
-    except Exception as e:   # noqa: BLE001 — e.g. no room for the scratch buffer beside a very large workload
-        peak_measured = None
-        print('bench.py: stream probe failed: %r' % (e,), file=sys.stderr)
+    # run (tsem_debug_stream_read: 16-byte non-temporal loads, eight in flight per thread, best of three launches); --full only
+    peak_measured = None
+    if args.full:
+        try:
+            from telescope_amd._lib import stream_read_gbs
+            peak_measured = stream_read_gbs(local, 8 << 30, 3)
+        except Exception as e:   # noqa: BLE001 — e.g. no room for the scratch buffer beside a very large workload
+            print('bench.py: stream probe failed: %r' % (e,), file=sys.stderr)
     out = {
         'metric': 'EM iterations/sec on fragment x locus CSR (nnz/sec alongside)',
         'value': args.steps / elapsed, 'unit': 'iter/s',
         'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
         'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
         'scaling': args.scaling, 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+        'full': args.full, 'outputs_dumped': dumped,
         'nnz_per_sec': nnz_total * args.steps / elapsed,
         'check': check,
         'phase_us': dict(phases, how='HIP events at the phase boundaries of %d iterations AFTER the timed region (rank 0): EM pass kernel(s) | '
@@ -573,7 +602,7 @@ def main():
             'algo_bytes_per_launch': ks['algo_bytes_per_pass'],
         },
     }
-    if world == 1 and args.value_format == 'f64' and info.get('fused') and not args.no_alt_layout:
+    if args.full and world == 1 and args.value_format == 'f64' and info.get('fused') and not args.no_alt_layout:
         # the same workload with 2-byte score codes + LDS score table (the library's `auto` layout: half the
         # HBM bytes, the same fp64 arithmetic): reported beside the headline; not part of `value`
         eng.close()
@@ -610,7 +639,7 @@ def main():
             }
         eng2.close()
         del tl2
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(args, dist_code, cdf)
         out['cpu_baseline'] = {
             'value': cb['nnz_per_sec'] / nnz_total, 'unit': 'iter/s', 'cores': 1, 'kind': 'port',
@@ -640,7 +669,7 @@ def main():
         out['parity_on_sample'] = {k: cb[k] for k in ('lnl_ref', 'lnl_gpu', 'lnl_rel_delta', 'pi_max_rel_delta',
                                                       'final_count_mismatches', 'near_tie_rows', 'final_conf_max_rel_delta',
                                                       'sample_rows', 'iters', 'converged_run')}
-    if world == 1 and not args.no_precision_sweep:
+    if args.full and world == 1 and not args.no_precision_sweep:
         # BASELINE config 3 (10M x 30k x ~40): error of reduced-precision storage / accumulation against fp64
         try:
             sys.path.insert(0, os.path.join(ROOT, 'tools'))
@@ -652,7 +681,7 @@ def main():
             logging.disable(logging.NOTSET)
         except Exception as e:   # noqa: BLE001 — never let the extra block break the bench line
             out['precision_sweep'] = dict(error=repr(e))
-    if world == 1 and not args.no_reproducible_leg:
+    if args.full and world == 1 and not args.no_reproducible_leg:
         # option `reproducible` (exact, order-independent sums, profiles/HISTORY.md 5.1) on a 10M-row sample of the workload: what it costs
         # per EM pass and whether two independent contexts agree bit for bit (the default mode is timed beside it)
         try:
@@ -758,6 +787,35 @@ def reproducible_leg(device, rows, args, cdf, dist_code, iters=10):
                 form='one pass, three tables per part' if a[4] else 'two passes (three tables per part do not fit / rows too short for teams of 5-8)',
                 two_runs_bit_identical=bool((a[1] == b[1]).all() and (a[2] == b[2]).all()),
                 pi_max_rel_delta_vs_default=float(abs(a[1] - d[1]).max() / d[1].max()))
+
+
+def dump_outputs(path, tl, eng, args, r0, r1):
+    """--dump-outputs: what `TelescopeLikelihood.em()` left its caller after the last timed step, as float64 DIR/<name>.npy —
+    `pi`, `theta` (tl.pi / tl.theta), `pi_init`, `theta_init` (the parameters after the first iteration of the call) and tl.z (the
+    posteriors of the last E-step) on DUMP_Z_ROWS rows drawn with a fixed seed from this rank's rows [r0, r1) (all rows at N = 1):
+    `z_sample_rows` the global row indices (ascending), `z_sample_indptr` where each row's entries start in `z_sample`, `z_sample` the
+    entries in CSR order (-1 where the reference drops one from z's pattern).  The lnl is not computed by the timed call
+    (final_lnl=False), so it is not written.  Returns the written names."""
+    from telescope_amd import synthetic
+    from telescope_amd._lib import Z_PREV
+    n_local = r1 - r0
+    rng = np.random.default_rng(20240501)
+    rows = np.sort(rng.choice(n_local, size=min(DUMP_Z_ROWS, n_local), replace=False)).astype(np.int64) if n_local else \
+        np.zeros(0, np.int64)
+    lens = synthetic.row_lengths(args.seed, rows + r0, args.nnz_row, args.cols, args.uniq_frac)   # the generator's own row lengths
+    off = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    z, _ = eng.rows_lookup('exclude', 0.9, Z_PREV, rows, off, want_z=True, want_mask=False)   # (the library checks off against the rows)
+    arrays = {'pi': tl.pi, 'theta': tl.theta, 'pi_init': tl.pi_init, 'theta_init': tl.theta_init,
+              'z_sample': z, 'z_sample_rows': rows + r0, 'z_sample_indptr': off}
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError('--dump-outputs: %d bytes exceed the %d-byte budget' % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), a)
+    return sorted(arrays)
 
 
 def _is_default_workload(args, total_rows):

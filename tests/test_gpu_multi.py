@@ -23,7 +23,7 @@ GOLD = os.path.join(ROOT, 'tests', 'golden')
 pytestmark = pytest.mark.gpu
 
 _COMMON = ['--rows', '4000000', '--steps', '6', '--warmup', '2', '--no-cpu-baseline', '--no-alt-layout', '--no-precision-sweep',
-           '--no-reproducible-leg', '--uniq-frac', '0.05']
+           '--no-reproducible-leg', '--uniq-frac', '0.05', '--full']
 _LINES = {}
 
 
@@ -180,7 +180,7 @@ def eight_gpus(gpu_device):
 
 def _bench_config(extra, timeout=3000):
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + extra + ['--no-cpu-baseline', '--no-alt-layout', '--no-precision-sweep',
-                                                                                 '--no-reproducible-leg'],
+                                                                                 '--no-reproducible-leg', '--full'],
                        cwd=ROOT, capture_output=True, text=True, timeout=timeout, env=_clean_env())
     assert r.returncode == 0, r.stderr[-4000:]
     return json.loads(r.stdout.strip().splitlines()[-1])

@@ -483,7 +483,7 @@ def test_reproducible_mode_reports_rows_it_cannot_vouch_for(gpu_device):
 
 
 _BENCH_COMMON = ['--rows', '3000000', '--steps', '6', '--warmup', '2', '--no-cpu-baseline', '--no-alt-layout', '--no-precision-sweep',
-                 '--no-reproducible-leg', '--uniq-frac', '0.05']
+                 '--no-reproducible-leg', '--uniq-frac', '0.05', '--full']
 _BENCH_LINES = {}
 
 

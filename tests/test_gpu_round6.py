@@ -113,7 +113,7 @@ def _bench_json(extra, timeout=1500):
     for k in ('TSEM_ONE_DEVICE', 'TSEM_GLOO_HOST_STAGED', 'TSEM_BACKEND', 'TSEM_TORCH_COLLECTIVES', 'RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + extra + ['--no-cpu-baseline', '--no-alt-layout', '--no-precision-sweep',
-                                                                                 '--no-reproducible-leg', '--steps', '4', '--warmup', '1'],
+                                                                                 '--no-reproducible-leg', '--full', '--steps', '4', '--warmup', '1'],
                        cwd=ROOT, capture_output=True, text=True, timeout=timeout, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     import json

@@ -9,7 +9,7 @@ OUT=gpurun_out/prof/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 # (round 6: the driver's own step counts — with 2 warm-up steps the 6 timed launches were still on the ramp after the generator: 4.5 .. 4.14 ms)
-B="python bench.py --steps ${PROF_STEPS:-20} --warmup ${PROF_WARMUP:-5} --no-cpu-baseline --no-precision-sweep --no-reproducible-leg --kernel-timing 1"
+B="python bench.py --full --steps ${PROF_STEPS:-20} --warmup ${PROF_WARMUP:-5} --no-cpu-baseline --no-precision-sweep --no-reproducible-leg --kernel-timing 1"
 STAGES=${STAGES:-"trace pmc lds rest"}
 has() { [[ " $STAGES " == *" $1 "* ]]; }
 if has trace; then
@@ -42,7 +42,7 @@ timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/tl -- python be
 python tools/iter_timeline.py $(ls $OUT/tl/*/*_kernel_trace.csv | head -1) 12 2 > $OUT/iter_timeline.txt 2>&1
 python tools/time_setup.py > $OUT/time_setup.txt 2>&1
 python tools/time_e2e.py > $OUT/time_e2e.txt 2>&1
-python bench.py --steps 20 --warmup 3 > $OUT/bench.log 2>&1
+python bench.py --full --steps 20 --warmup 3 > $OUT/bench.log 2>&1
 tail -1 $OUT/bench.log > $OUT/bench.json
 fi
 ls $OUT

@@ -74,7 +74,7 @@ def main():
         steps, WARMUP = int(own['steps']), int(own['warmup'])
     except Exception:   # noqa: BLE001
         own = None
-    cmd = 'python bench.py --steps %d --warmup %d --no-cpu-baseline --no-precision-sweep --no-reproducible-leg' % (steps, WARMUP)
+    cmd = 'python bench.py --full --steps %d --warmup %d --no-cpu-baseline --no-precision-sweep --no-reproducible-leg' % (steps, WARMUP)
     kl, avg = kernel_table(one('trace/*/*_kernel_trace.csv'), steps=steps)
     with open(os.path.join(ROOT, 'profiles', prefix + '_fused_kernel_stats.txt'), 'w') as f:
         f.write('# rocprofv3 --kernel-trace --stats -- %s   (default workload; the run times the headline fp64\n'

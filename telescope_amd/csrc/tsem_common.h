@@ -102,11 +102,8 @@ struct tsem_ctx {
   bool em_cur = false, em_prev = false;    // current / previous pi, theta come from tsem_set_model or the M-step, not from tsem_set_params
   int64_t opt_split = -1;                  // split layout: -1 when K needs it, 1 forced (tests), 0 never
   int64_t opt_issue = -1;                  // fused kernel, exchange wave: partner loads before the combine (1), after it (0), -1 auto
-  int64_t opt_rowpass_wgs = 2;             // workgroups per CU of the reassign row pass (modes other than `all`)
-  int64_t opt_report_kernel = 1;           // tsem_report_colsums runs k_report_rows (0: the generic k_rowpass<RP_REPORT>)
-  int64_t opt_report_dbg = 0;
-  int64_t opt_report_wgs2 = 0;             // 1: two of its workgroups per CU with half the LDS tables each (experiments)
-  int64_t opt_report_lanes = 0;            // its capacity per row, lanes x entries per lane (0 = auto)
+  int64_t opt_report_kernel = 1;           // the report passes run the streaming kernels (0: the generic k_rowpass)
+  int64_t opt_report_dbg = 0;              // the final z's report kernel: 8 k_report_rows, 128 / 256 k_report_pack32 with 8 / 16 entries per lane
   unsigned long long len_gt[6] = {0, 0, 0, 0, 0, 0};   // rows with more than 8, 16, 32, 64, 128, 256 entries (tsem_rowstats)
   int64_t opt_shortcuts = 1;               // tsem_reassign answers `all`(initial) and `unique` from the setup counts
   int32_t* d_twin_rep = nullptr;  // [K] representative column of each exact-twin class

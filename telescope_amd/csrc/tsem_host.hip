@@ -195,11 +195,14 @@ int tsem_set_option(tsem_ctx* h, const char* key, int64_t v) {
   else if (k == "drop_csr_indices") h->opt_drop_indices = v;   // -1 auto (>= 4e9 entries), 0 never, 1 always: see tsem_common.h
   else if (k == "phase_timing") h->opt_phase = v;          // HIP events between the phases of every chunked iteration (tsem_phase_times); a diagnostic: ~5 events per iteration
   else if (k == "report_shortcuts") h->opt_shortcuts = v;
-  else if (k == "rowpass_wgs") h->opt_rowpass_wgs = v;
-  else if (k == "report_kernel") h->opt_report_kernel = v;   // 0: the generic row pass (k_rowpass<RP_REPORT>) instead of k_report_rows
-  else if (k == "report_wgs2") h->opt_report_wgs2 = v;
-  else if (k == "report_dbg") h->opt_report_dbg = v;
-  else if (k == "report_lanes") h->opt_report_lanes = v;     // capacity (lanes per row x entries per lane) of k_report_rows: 8 .. 256 (0 = from the row lengths)
+  else if (k == "report_kernel") {                         // 1 (default) the streaming report kernels, 0 the generic row pass
+    if (v != 0 && v != 1) TSEM_FAIL(TSEM_ERR_ARG, "report_kernel must be 0 or 1");
+    h->opt_report_kernel = v;
+  }
+  else if (k == "report_dbg") {                            // the final z's report kernel: 8 k_report_rows, 128 / 256 k_report_pack32 at 8 / 16 entries per lane
+    if (v & ~(int64_t)(8 | 128 | 256)) TSEM_FAIL(TSEM_ERR_ARG, "report_dbg takes the bits 8, 128 and 256 only");
+    h->opt_report_dbg = v;
+  }
   else if (k == "issue_early") h->opt_issue = v;       // (kept for old scripts; the exchange has one order now)
   else if (k == "group_tile_bytes") h->opt_group_tile = v;   // per-group sums: bytes of output (groups x K doubles) computed per pass over the matrix
   else if (k == "use_likelihood") h->opt_lnl_fused = v;      // before the matrix is laid out (tsem_set_model), or followed by tsem_prepare_likelihood

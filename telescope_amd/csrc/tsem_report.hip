@@ -443,7 +443,6 @@ struct ReportArgs {
   int32_t* defer_rows; unsigned long long* defer_n;   // rows left to k_report_slow: too long for the lanes of a row, or (stored as ~row) a near-tie,
                                                       // whose sum k_report_slow forms in the reference's order of additions (near_band)
   unsigned long long* exact_n = nullptr;              // counts the latter
-  int dbg;                             // timing experiments (wrong results): 1 drop the emits that miss the LDS slots, 2 the row-count stores, 4 the ties
   // per-GROUP sums (GM != 0; the per-barcode count matrix of scTelescope.output_report, model.py:611-625): rows of the groups
   // [g0, g1) add into a tile [g1 - g0][IDN] in HBM, by id — 32-bit counters for `exclude` (GM 1), doubles for `average` (GM 2) and
   // `conf` (GM 3); other rows are skipped (their length is taken as 0).  No LDS accumulators: (group, column) pairs do not repeat
@@ -502,7 +501,7 @@ struct ReportEmit {                                        // where a row's valu
       return;
     }
     if ((int)id < Hs) lds_add(&hotF[id], v);
-    else if (!(A.dbg & 1)) unsafeAtomicAdd(&A.g_conf[id], v);
+    else unsafeAtomicAdd(&A.g_conf[id], v);
   }
   __device__ __forceinline__ void one(uint32_t id, int64_t goff) const {           // the row's only best hit
     if (GM != 0) {
@@ -511,13 +510,13 @@ struct ReportEmit {                                        // where a row's valu
       return;
     }
     if ((int)id < Hs) atomicAdd(&hot1[id], 1u);
-    else if (!(A.dbg & 1)) unsafeAtomicAdd(&A.g_n1[id], 1.0);
+    else unsafeAtomicAdd(&A.g_n1[id], 1.0);
   }
   __device__ __forceinline__ void tie(uint32_t id, int nb, double share, int64_t goff) const {   // one of nb > 1 best hits
     if (GM != 0) { if (GM == 2) unsafeAtomicAdd(&A.t_val[goff + id], share); return; }
     if (nb == 2) {
       if ((int)id < Hs) atomicAdd(&hot2[id], 1u);
-      else if (!(A.dbg & 1)) unsafeAtomicAdd(&A.g_n2[id], 1.0);
+      else unsafeAtomicAdd(&A.g_n2[id], 1.0);
     } else if (A.g_avgt_lo) {
       double hi, lo;
       exact_split01(share, hi, lo);
@@ -659,13 +658,13 @@ __global__ __launch_bounds__(rr_nt(INIT)) void k_report_rows(ReportArgs A) {
     }
     if (near) return true;
     const int64_t goff = p.goff;
-    if (GM == 0 && gl == 0 && row < A.N && !(A.dbg & 2)) A.nbest[row] = any ? nb : 0;
+    if (GM == 0 && gl == 0 && row < A.N) A.nbest[row] = any ? nb : 0;
     if (one_winner) {
       if (nbl != 0 && nb == 1) {                           // this lane holds the row's only best hit
         EM.one(wid, goff);
         if (zmax >= A.thresh) { const double vc = zmax * recip0(zmax); if (vc != 0.0) EM.conf(wid, vc, goff); }   // vsum = the winner's z
       }
-      if (__builtin_amdgcn_ballot_w64(nb > 1) != 0ull && !(A.dbg & 4)) {   // tied rows
+      if (__builtin_amdgcn_ballot_w64(nb > 1) != 0ull) {   // tied rows
         if (nbl == 1 && nb == 2) EM.tie(wid, 2, 0.5, goff);      // (the usual tie: two best hits, this lane holds one of them)
         if (__builtin_amdgcn_ballot_w64(nb > 1 && !(nbl == 1 && nb == 2) && nbl != 0) != 0ull) {
           const double share = 1.0 * recip0((double)nb);
@@ -793,7 +792,7 @@ __global__ __launch_bounds__(1024) void k_report_init_codes(ReportArgs A) {
     const uint32_t eq = any ? (~nz & full) : 0u;
     const int nbl = __popc(eq);
     const int nb = rr_sum_i<G>(nbl);
-    if (gl == 0 && row < A.N && !(A.dbg & 2)) A.nbest[row] = any ? nb : 0;
+    if (gl == 0 && row < A.N) A.nbest[row] = any ? nb : 0;
     // the popularity id behind bit b of `eq` (a select chain over the lane's words: once per lane and row, not per entry)
     auto id_of = [&](int b) -> uint32_t {
       const int w = b & 15;
@@ -805,7 +804,7 @@ __global__ __launch_bounds__(1024) void k_report_init_codes(ReportArgs A) {
     const int b0 = nbl ? __ffs((int)eq) - 1 : 0;
     const uint32_t id0 = id_of(b0);
     if (nb == 1 && nbl == 1) EM.one(id0, 0);
-    if (__builtin_amdgcn_ballot_w64(nb > 1) != 0ull && !(A.dbg & 4)) {      // rows with several best hits
+    if (__builtin_amdgcn_ballot_w64(nb > 1) != 0ull) {      // rows with several best hits
       const double share = 1.0 * recip0((double)nb);
       if (nb > 1 && nbl >= 1) EM.tie(id0, nb, nb == 2 ? 0.5 : share, 0);
       uint32_t rest = nb > 1 && nbl > 1 ? eq & (eq - 1u) : 0u;
@@ -1070,6 +1069,23 @@ template <bool FIX> static RowKern rowpass_kern(int mode, int meth) {
   }
 }
 
+// the streaming report kernels for a launch: GM 0 the column sums (k_report_init_codes where codes_only), 1 .. 4 the per-group sums
+typedef void (*ReportKern)(ReportArgs);
+template <int G, int E, int GM> static ReportKern report_rows_at(bool init, bool codes_only) {
+  if constexpr (GM == 0) { if (codes_only) return k_report_init_codes<G, E>; }
+  return init ? k_report_rows<G, E, true, GM> : k_report_rows<G, E, false, GM>;
+}
+// the instance for a capacity: G lanes of E entries per row
+template <int GM> static ReportKern report_rows_kernel(int cap, bool init, bool codes_only) {
+  if (cap <= 8) return report_rows_at<1, 8, GM>(init, codes_only);
+  if (cap <= 16) return report_rows_at<1, 16, GM>(init, codes_only);
+  if (cap <= 32) return report_rows_at<2, 16, GM>(init, codes_only);
+  if (cap <= 64) return report_rows_at<4, 16, GM>(init, codes_only);
+  if (cap <= 128) return report_rows_at<8, 16, GM>(init, codes_only);
+  return report_rows_at<16, 16, GM>(init, codes_only);
+}
+template <int GM> static ReportKern report_slow_kernel(bool init) { return init ? k_report_slow<true, GM> : k_report_slow<false, GM>; }
+
 extern "C" {
 
 // ---------------------------------------------------------------------------
@@ -1086,6 +1102,23 @@ static int make_cnat(tsem_ctx* h, RowPassArgs& A) {
   TSEM_HIP(hipGetLastError());
   A.cnat = h->d_cnat;
   return TSEM_OK;
+}
+
+// a host array of n int32 copied to a new device buffer (the caller's scope frees it)
+static int upload_i32(tsem_ctx* h, int32_t*& d, const int32_t* src, int64_t n) {
+  TSEM_ALLOC(d, n);
+  if (n) TSEM_HIP(hipMemcpyAsync(d, src, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
+  return TSEM_OK;
+}
+// device scratch kept between calls, grown (not preserved) when a call needs more than `bytes`
+static hipError_t grow_scratch(void*& p, size_t& bytes, size_t need) {
+  if (p && bytes >= need) return hipSuccess;
+  if (p) (void)hipFree(p);
+  p = nullptr; bytes = 0;
+  const hipError_t e = hipMalloc(&p, need ? need : 1);
+  if (e == hipSuccess) bytes = need;
+  else p = nullptr;
+  return e;
 }
 
 // the counter of rows redone in the reference's order of additions (near-ties), zeroed when it is first needed
@@ -1114,12 +1147,16 @@ static void redrop_indices(tsem_ctx* h) {
   }
 }
 
+// Option "report_kernel": 1 (default) the streaming report kernels, 0 the generic row pass for everything.
+// The streaming kernels (k_report_rows, k_report_pack32, k_report_init_codes) read the popularity ids and stage the score table in
+// LDS; a caller-assigned z stays on the generic row pass.
+static bool streaming_ok(const tsem_ctx* h, int which, const RowPassArgs& A) {
+  return h->opt_report_kernel != 0 && which != TSEM_Z_USER && h->d_rid16 && h->d_col_of_id && A.lut_len > 0;
+}
 // The passes over the INITIAL z that work on the 2-byte score codes alone (k_report_init_codes, k_choose_init_codes): a row's best
 // hits are its largest codes — true when the score table is strictly increasing and no stored score is 0 (code 0 is their padding).
-// Option "report_kernel": 1 (default) streaming kernels incl. the codes-only ones; 2 streaming kernels WITHOUT the codes-only ones
-// (timing comparisons); 0 the generic row pass for everything.
 static bool codes_path_ok(const tsem_ctx* h) {
-  return h->opt_report_kernel == 1 && h->lut_increasing && !h->opt_reproducible && h->have_rowstats && !h->has_zero_score &&
+  return h->opt_report_kernel != 0 && h->lut_increasing && !h->opt_reproducible && h->have_rowstats && !h->has_zero_score &&
          h->d_rid16 && h->d_col_of_id;
 }
 
@@ -1180,7 +1217,9 @@ static int rowpass_args(tsem_ctx* h, int which, RowPassArgs& A) {
   if (A.pi) { if (int rc = make_cnat(h, A)) return rc; }
   return TSEM_OK;
 }
-int tsem_rowpass_grid(tsem_ctx* h) { return (int)std::min<int64_t>(8192, std::max<int64_t>(1, (h->N + 15) / 16)); }
+// workgroups of 256 threads (16 rows each) for a row pass over n rows, listed or all of them
+static int list_grid(int64_t n) { return (int)std::min<int64_t>(8192, std::max<int64_t>(1, (n + 15) / 16)); }
+int tsem_rowpass_grid(tsem_ctx* h) { return list_grid(h->N); }
 
 static int export_z_with(tsem_ctx* h, RowPassArgs& A, double* z) {
   double* d_z = nullptr;
@@ -1242,13 +1281,36 @@ int tsem_best_counts(tsem_ctx* h, int which, int32_t* nbest) {
   return TSEM_OK;
 }
 
-struct TiedRow {                                            // predicate of tsem_best_ties: rows with several best hits
+struct TiedRow {                                            // predicate of select_ties: rows with several best hits
   const int32_t* nb;
   __device__ bool operator()(const int32_t& i) const { return nb[i] > 1; }
 };
+// the rows with several best hits (d_nb[row] > 1) in row order -> d_rows, their number -> *n (rocPRIM's scratch: d_rep_tmp)
+static int select_ties(tsem_ctx* h, const int32_t* d_nb, int32_t* d_rows, unsigned long long* d_n, unsigned long long* n) {
+  size_t tb = 0;
+  TiedRow pred{d_nb};
+  rocprim::counting_iterator<int32_t> first(0);
+  TSEM_HIP(rocprim::select(nullptr, tb, first, d_rows, d_n, (size_t)h->N, pred, h->stream));
+  TSEM_HIP(grow_scratch(h->d_rep_tmp, h->rep_tmp_bytes, tb));
+  TSEM_HIP(rocprim::select(h->d_rep_tmp, tb, first, d_rows, d_n, (size_t)h->N, pred, h->stream));
+  TSEM_HIP(hipMemcpyAsync(n, d_n, 8, hipMemcpyDeviceToHost, h->stream));
+  TSEM_HIP(hipStreamSynchronize(h->stream));
+  return TSEM_OK;
+}
 __global__ void k_gather_i32(int64_t n, const int32_t* __restrict__ idx, const int32_t* __restrict__ src, int32_t* __restrict__ out) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = src[idx[i]];
+}
+// the device tie list of a report (tsem_report_ties, tsem_reassign_rows with rows == NULL): n rows in order and their best-hit counts
+static int install_ties(tsem_ctx* h, const int32_t* d_rows, const int32_t* d_nb, int64_t n) {
+  if (n) {
+    TSEM_ALLOC(h->d_tie_rows, n); TSEM_ALLOC(h->d_tie_cnt, n);
+    TSEM_HIP(hipMemcpyAsync(h->d_tie_rows, d_rows, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, h->stream));
+    k_gather_i32<<<cdiv64(n, 256), 256, 0, h->stream>>>(n, d_rows, d_nb, h->d_tie_cnt);
+    TSEM_HIP(hipStreamSynchronize(h->stream));
+  }
+  h->n_ties = n;
+  return TSEM_OK;
 }
 
 int tsem_best_ties(tsem_ctx* h, int which, int64_t cap, int32_t* rows, int32_t* counts, int64_t* n_out) {
@@ -1260,22 +1322,14 @@ int tsem_best_ties(tsem_ctx* h, int which, int64_t cap, int32_t* rows, int32_t* 
   if (int rc = rowpass_args(h, which, A)) return rc;
   int32_t *d_nb = nullptr, *d_rows = nullptr, *d_cnt = nullptr;
   unsigned long long* d_n = nullptr;
-  void* tmp = nullptr;
-  TSEM_SCOPED(d_nb); TSEM_SCOPED(d_rows); TSEM_SCOPED(d_cnt); TSEM_SCOPED(d_n); TSEM_SCOPED(tmp);
+  TSEM_SCOPED(d_nb); TSEM_SCOPED(d_rows); TSEM_SCOPED(d_cnt); TSEM_SCOPED(d_n);
   TSEM_ALLOC(d_nb, h->N); TSEM_ALLOC(d_rows, h->N); TSEM_ALLOC(d_n, 1);
   A.nbest = d_nb;
   IndicesGuard ig(h);
   if (int rc = with_indices(h, A)) return rc;
   if (int rc = launch_rowpass(h, RP_BEST, -1, tsem_rowpass_grid(h), 256, (size_t)A.lut_len * 8, A)) return rc;
-  size_t tb = 0;
-  TiedRow pred{d_nb};
-  rocprim::counting_iterator<int32_t> first(0);
-  TSEM_HIP(rocprim::select(nullptr, tb, first, d_rows, d_n, (size_t)h->N, pred, h->stream));
-  TSEM_HIP(hipMalloc(&tmp, tb ? tb : 1));
-  TSEM_HIP(rocprim::select(tmp, tb, first, d_rows, d_n, (size_t)h->N, pred, h->stream));
   unsigned long long n = 0;
-  TSEM_HIP(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, h->stream));
-  TSEM_HIP(hipStreamSynchronize(h->stream));
+  if (int rc = select_ties(h, d_nb, d_rows, d_n, &n)) return rc;
   *n_out = (int64_t)n;
   int rc = TSEM_OK;
   if ((int64_t)n > cap) {
@@ -1291,22 +1345,30 @@ int tsem_best_ties(tsem_ctx* h, int which, int64_t cap, int32_t* rows, int32_t* 
   return rc;
 }
 
-// option "reproducible": a second, zeroed buffer for the low pieces of the values a row pass sums (exact_split01);
-// rowpass_lo_end adds it to the sums and frees it
-static int rowpass_lo_begin(tsem_ctx* h, RowPassArgs& A, int64_t n, double** lo) {
-  *lo = nullptr;
-  if (!h->opt_reproducible || n <= 0) return TSEM_OK;
-  TSEM_ALLOC(*lo, n);
-  TSEM_HIP(hipMemsetAsync(*lo, 0, sizeof(double) * n, h->stream));
-  A.colsums_lo = *lo;
-  return TSEM_OK;
-}
-static int rowpass_lo_end(tsem_ctx* h, double* sums, double* lo, int64_t n) {
+// A row pass that sums into sums[0..n).  Option "reproducible": the low pieces of its values (exact_split01) go to a second, zeroed
+// buffer, added to the sums once the pass is done.
+static int rowpass_exact(tsem_ctx* h, RowPassArgs& A, int mode, int meth, int grid, int block, size_t lds, double* sums, int64_t n) {
+  double* lo = nullptr;
+  TSEM_SCOPED(lo);
+  if (h->opt_reproducible && n > 0) {
+    TSEM_ALLOC(lo, n);
+    TSEM_HIP(hipMemsetAsync(lo, 0, sizeof(double) * n, h->stream));
+    A.colsums_lo = lo;
+  }
+  if (int rc = launch_rowpass(h, mode, meth, grid, block, lds, A)) return rc;
   if (!lo) return TSEM_OK;
   k_add_lo<<<cdiv64(n, 256), 256, 0, h->stream>>>(n, sums, lo);
   TSEM_HIP(hipGetLastError());
   TSEM_HIP(hipStreamSynchronize(h->stream));
-  return TSEM_OK;                                          // (the caller's scope guard frees `lo`)
+  A.colsums_lo = nullptr;
+  return TSEM_OK;
+}
+// The hot slots of every column part in LDS (k_rowpass REASSIGN / REPORT: `copies` sums per slot) for `wgs` workgroups of 1024 threads
+// per CU; returns the pass's LDS bytes
+static size_t rowpass_hot_slots(tsem_ctx* h, RowPassArgs& A, int wgs, int copies) {
+  A.colmap = h->d_colmap; A.col_of_pc = h->d_col_of_pc; A.P = h->P; A.Kp = h->Kp;
+  A.Hs = std::max(0, std::min(h->Kp, (int)((TS_LDS_MAX / wgs - 8192 / wgs - 1024 - A.lut_len * 8) / 8 / h->P / copies)));
+  return (size_t)(copies * A.P * A.Hs + A.lut_len) * 8;
 }
 
 int tsem_reassign(tsem_ctx* h, int method, double thresh, int which, const int32_t* picks, double* colsums,
@@ -1346,37 +1408,26 @@ int tsem_reassign(tsem_ctx* h, int method, double thresh, int which, const int32
   TSEM_ALLOC(d_cs, h->K);
   TSEM_HIP(hipMemsetAsync(d_cs, 0, sizeof(double) * h->K, h->stream));
   if (mask) TSEM_ALLOC(d_mask, h->nnz);
-  if (method == TSEM_RA_CHOOSE && picks) {
-    TSEM_ALLOC(d_picks, h->N);
-    if (h->N) TSEM_HIP(hipMemcpyAsync(d_picks, picks, sizeof(int32_t) * h->N, hipMemcpyHostToDevice, h->stream));
-  }
+  if (method == TSEM_RA_CHOOSE && picks) { if (int rc = upload_i32(h, d_picks, picks, h->N)) return rc; }
   A.colsums = d_cs; A.zout = d_mask; A.picks = d_picks;
-  double* d_lo = nullptr;
-  TSEM_SCOPED(d_lo);                                    // (the low pieces of the exact sums: freed on every return path)
-  if (int rc = rowpass_lo_begin(h, A, h->K, &d_lo)) return rc;
   if (h->N && h->d_colmap && h->d_col_of_pc && h->P > 0) {
     // hot slots of every part in LDS.  `all` emits one value per stored entry, so it wants as many slots as fit: one
     // 1024-thread workgroup per CU with ~150 KB of accumulators.  The other modes emit at most a few values per ROW
     // and the pass is bound by the latency of its dependent loads (row pointers -> entries), not by atomics: two
-    // workgroups per CU (32 waves) with half the slots each (option "rowpass_wgs").
-    const int wgs = (method == TSEM_RA_ALL || h->opt_rowpass_wgs < 2) ? 1 : 2;
-    A.colmap = h->d_colmap; A.col_of_pc = h->d_col_of_pc; A.P = h->P; A.Kp = h->Kp;
-    A.Hs = std::max(0, std::min(h->Kp, (int)((TS_LDS_MAX / wgs - 8192 / wgs - 1024 - A.lut_len * 8) / 8 / h->P)));
-    if (int rc = launch_rowpass(h, RP_REASSIGN, method, h->n_cu * wgs, 1024, (size_t)(A.P * A.Hs + A.lut_len) * 8, A)) return rc;
+    // workgroups per CU (32 waves) with half the slots each.
+    const int wgs = method == TSEM_RA_ALL ? 1 : 2;
+    const size_t lds = rowpass_hot_slots(h, A, wgs, 1);
+    if (int rc = rowpass_exact(h, A, RP_REASSIGN, method, h->n_cu * wgs, 1024, lds, d_cs, h->K)) return rc;
   } else if (h->N) {
-    if (int rc = launch_rowpass(h, RP_REASSIGN, -1, tsem_rowpass_grid(h), 256, (size_t)A.lut_len * 8, A)) return rc;
+    if (int rc = rowpass_exact(h, A, RP_REASSIGN, -1, tsem_rowpass_grid(h), 256, (size_t)A.lut_len * 8, d_cs, h->K)) return rc;
   }
-  if (int rc = rowpass_lo_end(h, d_cs, d_lo, h->K)) return rc;
   TSEM_HIP(hipMemcpyAsync(colsums, d_cs, sizeof(double) * h->K, hipMemcpyDeviceToHost, h->stream));
   if (mask && h->nnz) TSEM_HIP(hipMemcpyAsync(mask, d_mask, sizeof(double) * h->nnz, hipMemcpyDeviceToHost, h->stream));
   TSEM_HIP(hipStreamSynchronize(h->stream));
   return TSEM_OK;
 }
 
-// One pass for the column sums output_report takes from one z (model.py:432-457): conf | exclude | average, and the rows
-// with several best hits (the only rows `choose` treats differently from `exclude`) compacted in row order.
-// packed report pass: a row with several best hits is a row the fp32 filter left to k_report_slow — the tied rows are picked from the
-// deferred list (a few thousand entries) instead of a select over all N best-hit counts (0.5 ms at 5e7 rows); sorted afterwards
+// the deferred rows of k_report_pack32 with several best hits (ties_of_deferred)
 __global__ void k_ties_of_deferred(const unsigned long long* __restrict__ nd, const int32_t* __restrict__ defer_rows, const int32_t* __restrict__ nbest,
                                    int32_t* __restrict__ out, unsigned long long* __restrict__ n_out) {
   const int64_t n = (int64_t)*nd;
@@ -1427,6 +1478,154 @@ static int ensure_report_chunks(tsem_ctx* h, int E) {
   return TSEM_OK;
 }
 
+// ---- tsem_report_colsums ------------------------------------------------------------------------------------------------------
+// [N] best-hit counts, [N] rows (the deferred ones, then the tied ones) and their counter: kept between reports (allocating and
+// freeing two N-sized vectors cost more than the pass's kernels)
+static int report_scratch(tsem_ctx* h) {
+  if (!h->d_rep_nb) { TSEM_ALLOC(h->d_rep_nb, h->N); TSEM_ALLOC(h->d_rep_rows, h->N); TSEM_ALLOC(h->d_rep_n, 1); }
+  return TSEM_OK;
+}
+// The streaming report kernels' arguments for the z of a row pass (A.pi == null: the initial z; else pi*theta | pi by id are written
+// to c2 [2 IDN]).  Rows they leave to k_report_slow go to the report scratch; outputs and LDS budgets are the caller's.
+static ReportArgs report_args(tsem_ctx* h, const RowPassArgs& A, double thresh, double* c2) {
+  ReportArgs R{};
+  R.N = h->N; R.nnz = h->nnz; R.K = h->K; R.IDN = h->Kpad; R.indptr = h->d_indptr; R.rid = h->d_rid16; R.raw = h->d_raw;
+  R.lut = h->d_lut; R.lut_len = A.lut_len; R.thresh = thresh; R.exact_n = A.exact_n;
+  R.defer_rows = h->d_rep_rows; R.defer_n = h->d_rep_n;
+  if (A.pi) {
+    k_cnat2_id<<<cdiv64(R.IDN, 256), 256, 0, h->stream>>>(R.IDN, h->d_col_of_id, A.pi, A.theta, c2);
+    R.cnat2 = c2;
+  }
+  return R;
+}
+// lanes per row x entries per lane of k_report_rows / k_report_init_codes: the smallest capacity that fewer than 0.5 % of the rows
+// exceed (row-length histogram of tsem_rowstats)
+static int report_capacity(const tsem_ctx* h) {
+  if (h->have_rowstats)
+    for (int q = 0; q < 6; ++q)
+      if ((double)h->len_gt[q] <= 0.005 * (double)h->N) return 8 << q;
+  return 256;
+}
+
+static double lut_max(const tsem_ctx* h) {
+  double m = 0.0;
+  for (double v : h->lut_host) m = std::max(m, v);
+  return m;
+}
+// k_report_pack32 serves the final z at 0.51 < conf_prob <= 0.99999 (at 1.0 a unique row's z = fl(n fl(1 / n)) may miss the threshold),
+// without the low pieces, with lut[0] = 0 and a finite score table; option report_dbg 8 keeps k_report_rows
+static bool packed_ok(const tsem_ctx* h, const ReportArgs& R) {
+  const double m = lut_max(h);
+  return R.cnat2 && !h->opt_reproducible && R.thresh > 0.51 && R.thresh <= 0.99999 && h->lut0_zero && m > 0.0 && std::isfinite(m) &&
+         (int)h->lut_host.size() == R.lut_len && !(h->opt_report_dbg & 8) && h->N < 0x7FFFFFFF;
+}
+
+// The final z on k_report_pack32 (tsem_report_pack.h): the chunk table, fp32 tables by id — in LDS, all of them up to ~34 000 slots —
+// and copies of the score table; then the winners per id (k_report_hist: the whole LDS for counters, the ids in windows).  The fp32
+// tables go to `tabs`, which the caller frees at its end (hipFree waits for the device).
+static int report_packed(tsem_ctx* h, const ReportArgs& R, DevTmp& tabs, PhaseTimer& pt) {
+  const int IDN = R.IDN;
+  // entries per lane: 16 amortise the per-chunk work (row map, scan, prefetch) over twice the entries; short rows fill 8 better
+  // (report_dbg 128 / 256 force 8 / 16)
+  const int E = (h->opt_report_dbg & 128) ? 8 : ((h->opt_report_dbg & 256) ? 16 : (h->nnz >= 24 * h->N ? 16 : 8));
+  pt.lap("report: by-id tables");
+  if (int rc = ensure_report_chunks(h, E)) return rc;
+  pt.lap("report: chunk table");
+  TSEM_TMP(tabs, sizeof(uint32_t) * ((size_t)IDN + 1) + sizeof(float) * (size_t)R.lut_len);
+  uint32_t* const t32 = tabs.as<uint32_t>();
+  float* const l32 = reinterpret_cast<float*>(t32 + IDN + 1);
+  const int lut_sq = std::ilogb(lut_max(h)) - 40;          // lut 2^-lut_sq: the largest score table entry in [2^40, 2^41)
+  k_rp32_tables<<<cdiv64(std::max(IDN + 1, R.lut_len), 256), 256, 0, h->stream>>>(IDN, R.cnat2, R.lut_len, R.lut, lut_sq, t32, l32);
+  constexpr int nwv = 16;
+  const int words = (TS_LDS_MAX - 1024) / 4 - 8 - (E + 1) * (E / 2);   // LDS words for the table of the ids and the copies of the score table
+  Rp32Args P;
+  P.N = h->N; P.IDN = IDN; P.lut_len = R.lut_len; P.indptr = h->d_indptr; P.rid = h->d_rid16; P.raw = h->d_raw;
+  P.HC = std::min(IDN, std::max(0, words - R.lut_len));
+  P.lut_rep = 0;
+  while (P.lut_rep < 5 && P.HC + 1 + (R.lut_len << (P.lut_rep + 1)) <= words) ++P.lut_rep;
+  P.t32 = t32; P.l32 = l32; P.thresh = (float)R.thresh; P.win = reinterpret_cast<uint32_t*>(R.nbest);
+  P.defer_rows = R.defer_rows; P.defer_n = R.defer_n; P.chunks = h->d_rep_chunks; P.nchunks = h->n_rep_chunks;
+  const size_t lds = (size_t)((E + 1) * (E / 2) + P.HC + 1 + (P.lut_len << P.lut_rep)) * 4;
+  void (*pk)(Rp32Args) = E == 16 ? (P.HC < IDN ? k_report_pack32<16, true> : k_report_pack32<16, false>)
+                                 : (P.HC < IDN ? k_report_pack32<8, true> : k_report_pack32<8, false>);
+  TSEM_HIP(hipFuncSetAttribute((const void*)pk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+  if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[0], h->stream));
+  pk<<<h->n_cu, nwv * 64, lds, h->stream>>>(P);
+  if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[1], h->stream));
+  TSEM_HIP(hipGetLastError());
+  pt.lap("report: k_report_pack32");
+  const int W = std::min(IDN, (TS_LDS_MAX - 1024) / 8);
+  TSEM_HIP(hipFuncSetAttribute((const void*)k_report_hist, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+  for (int id0 = 0; id0 < IDN; id0 += W)
+    k_report_hist<<<h->n_cu, 1024, (size_t)std::min(W, IDN - id0) * 8, h->stream>>>(h->N, P.win, id0, std::min(W, IDN - id0), R.g_n1, R.g_conf);
+  return TSEM_OK;
+}
+
+// k_report_rows at the capacity of the row lengths — or, for the initial z without a conf column, k_report_init_codes — one workgroup
+// per CU.  LDS: the final z wants pi*theta of as many ids as fit (8 B each) next to at most 3072 accumulator slots (16 B each, 24 with
+// the low pieces); the initial z has no pi*theta; the codes-only kernel holds two 32-bit counters per id and nothing else.
+static int report_streaming(tsem_ctx* h, ReportArgs& R, bool codes_only) {
+  const bool init = R.cnat2 == nullptr;
+  const int lds_avail = TS_LDS_MAX - 2048 - R.lut_len * 8;
+  const int slot_bytes = h->opt_reproducible ? 24 : 16;    // conf (f64) + two counters (+ the low pieces)
+  R.Hs = std::min(R.IDN, init ? lds_avail / slot_bytes : std::min(3072, lds_avail / slot_bytes / 4));
+  R.HC = init ? 0 : std::max(0, std::min(R.IDN, (lds_avail - R.Hs * slot_bytes) / 8));
+  if (codes_only) R.Hs = std::min(R.IDN, (TS_LDS_MAX - 2048) / 8);
+  const size_t lds = codes_only ? (size_t)R.Hs * 8 : (size_t)R.lut_len * 8 + (size_t)R.HC * 8 + (size_t)R.Hs * slot_bytes;
+  const ReportKern rk = report_rows_kernel<0>(report_capacity(h), init, codes_only);
+  TSEM_HIP(hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+  if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[0], h->stream));
+  rk<<<h->n_cu, rr_nt(init), lds, h->stream>>>(R);
+  if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[1], h->stream));
+  return TSEM_OK;
+}
+
+// The generic row pass k_rowpass<RP_REPORT> over the CSR: two workgroups per CU with the hot slots of every column part in LDS where
+// the matrix has its blocked layout, 16 lanes per row over all rows else (that pass leaves the last report's kernel statistics)
+static int report_generic(tsem_ctx* h, RowPassArgs& A, double* d_cs) {
+  const bool parts = h->d_colmap && h->d_col_of_pc && h->P > 0;
+  if (parts) { h->rep_timed = false; h->rep_kernel = 1; h->rep_deferred = 0; }
+  if (int rc = with_indices(h, A)) return rc;
+  const int64_t n = 3 * (int64_t)h->K;
+  if (!parts) return rowpass_exact(h, A, RP_REPORT, -1, tsem_rowpass_grid(h), 256, (size_t)A.lut_len * 8, d_cs, n);
+  const size_t lds = rowpass_hot_slots(h, A, 2, 3);
+  return rowpass_exact(h, A, RP_REPORT, -1, h->n_cu * 2, 1024, lds, d_cs, n);
+}
+
+// The tied rows after k_report_pack32: its fp32 filter decides rows with ONE best hit only, so they are among the rows it deferred — picked
+// from that list (a few thousand rows) instead of a select over all N best-hit counts (0.5 ms at 5e7 rows), then sorted.
+static int ties_of_deferred(tsem_ctx* h) {
+  unsigned long long nd = 0, nt = 0;
+  TSEM_HIP(hipMemcpyAsync(&nd, h->d_rep_n, 8, hipMemcpyDeviceToHost, h->stream));
+  TSEM_HIP(hipStreamSynchronize(h->stream));
+  h->rep_deferred = (int64_t)nd;
+  if (!nd) return TSEM_OK;
+  int32_t *d_unsorted = nullptr, *d_sorted = nullptr;
+  unsigned long long* d_nt = nullptr;
+  TSEM_SCOPED(d_unsorted); TSEM_SCOPED(d_sorted); TSEM_SCOPED(d_nt);
+  TSEM_ALLOC(d_unsorted, nd); TSEM_ALLOC(d_nt, 1);
+  TSEM_HIP(hipMemsetAsync(d_nt, 0, sizeof(unsigned long long), h->stream));
+  k_ties_of_deferred<<<256, 256, 0, h->stream>>>(h->d_rep_n, h->d_rep_rows, h->d_rep_nb, d_unsorted, d_nt);
+  TSEM_HIP(hipGetLastError());
+  TSEM_HIP(hipMemcpyAsync(&nt, d_nt, 8, hipMemcpyDeviceToHost, h->stream));
+  TSEM_HIP(hipStreamSynchronize(h->stream));
+  if (!nt) return TSEM_OK;
+  TSEM_ALLOC(d_sorted, nt);
+  size_t tb = 0;
+  TSEM_HIP(rocprim::radix_sort_keys(nullptr, tb, d_unsorted, d_sorted, (size_t)nt, 0, 32, h->stream));
+  TSEM_HIP(grow_scratch(h->d_rep_tmp, h->rep_tmp_bytes, tb));
+  TSEM_HIP(rocprim::radix_sort_keys(h->d_rep_tmp, tb, d_unsorted, d_sorted, (size_t)nt, 0, 32, h->stream));
+  return install_ties(h, d_sorted, h->d_rep_nb, (int64_t)nt);
+}
+// ... after the other passes: a select over the best-hit counts
+static int ties_of_counts(tsem_ctx* h) {
+  unsigned long long n = 0;
+  if (int rc = select_ties(h, h->d_rep_nb, h->d_rep_rows, h->d_rep_n, &n)) return rc;
+  return install_ties(h, h->d_rep_rows, h->d_rep_nb, (int64_t)n);
+}
+
+// One pass for the column sums output_report takes from one z (model.py:432-457): conf | exclude | average, and the rows
+// with several best hits (the only rows `choose` treats differently from `exclude`) compacted in row order.
 int tsem_report_colsums(tsem_ctx* h, int which, double thresh, double* out3K, int64_t* n_ties) {
   if (!h || !h->d_indptr || !out3K) return TSEM_ERR_ARG;
   if (int rc = ensure_device(h)) return rc;
@@ -1438,215 +1637,53 @@ int tsem_report_colsums(tsem_ctx* h, int which, double thresh, double* out3K, in
   if (int rc = rowpass_args(h, which, A)) return rc;
   dfree(h->d_tie_rows); dfree(h->d_tie_cnt); h->n_ties = 0;
   if (n_ties) *n_ties = 0;
-  const int K = h->K;
-  double* d_cs = nullptr;
-  TSEM_SCOPED(d_cs);
+  const int K = h->K, IDN = h->Kpad;
+  if (h->N == 0) {
+    for (int64_t j = 0; j < 3 * (int64_t)K; ++j) out3K[j] = 0.0;
+    return TSEM_OK;
+  }
+  double *d_cs = nullptr, *d_g = nullptr, *d_c2 = nullptr;
+  TSEM_SCOPED(d_cs); TSEM_SCOPED(d_g); TSEM_SCOPED(d_c2);
+  DevTmp tabs;                                             // (k_report_pack32's tables)
   TSEM_ALLOC(d_cs, 3 * (int64_t)K);
   TSEM_HIP(hipMemsetAsync(d_cs, 0, sizeof(double) * 3 * K, h->stream));
-  if (h->N) {
-    // per-row best-hit counts, the compacted tie list and the scan's scratch stay allocated between reports (two N-sized
-    // vectors: allocating and freeing them cost more than the pass's kernels)
-    if (!h->d_rep_nb) { TSEM_ALLOC(h->d_rep_nb, h->N); TSEM_ALLOC(h->d_rep_rows, h->N); TSEM_ALLOC(h->d_rep_n, 1); }
-    int32_t *const d_nb = h->d_rep_nb, *const d_rows = h->d_rep_rows;
-    unsigned long long* const d_n = h->d_rep_n;
-    A.thresh = thresh; A.colsums = d_cs; A.nbest = d_nb;
-    pt.lap("report: scratch");
-    if (h->opt_report_kernel != 0 && which != TSEM_Z_USER && h->d_rid16 && h->d_col_of_id && A.lut_len > 0) {
-      // the streaming report kernel (k_report_rows): lanes per row x entries per lane = the smallest capacity that
-      // fewer than 0.5 % of the rows exceed (row-length histogram of tsem_rowstats); the rest goes to k_report_slow
-      const int IDN = h->Kpad;
-      ReportArgs R;
-      R.N = h->N; R.nnz = h->nnz; R.K = K; R.IDN = IDN; R.indptr = h->d_indptr; R.rid = h->d_rid16; R.raw = h->d_raw;
-      R.lut = h->d_lut; R.lut_len = A.lut_len; R.cnat2 = nullptr; R.thresh = thresh; R.nbest = d_nb; R.exact_n = A.exact_n;
-      const bool init = A.pi == nullptr;
-      // thresh < 0: the caller wants no `conf` column.  The initial z then needs no arithmetic at all — the best hits of a row are its
-      // largest score codes (k_report_init_codes) — provided the score table is strictly increasing and no stored score is 0.
-      const bool codes_only = init && !want_conf && codes_path_ok(h);
-      double *d_g = nullptr, *d_c2 = nullptr;
-      TSEM_SCOPED(d_g); TSEM_SCOPED(d_c2);
-      const bool exact = h->opt_reproducible != 0;
-      TSEM_ALLOC(d_g, 6 * (int64_t)IDN);
-      TSEM_HIP(hipMemsetAsync(d_g, 0, sizeof(double) * 6 * IDN, h->stream));
-      if (!init) {
-        TSEM_ALLOC(d_c2, 2 * (int64_t)IDN);
-        k_cnat2_id<<<cdiv64(IDN, 256), 256, 0, h->stream>>>(IDN, h->d_col_of_id, A.pi, A.theta, d_c2);
-        R.cnat2 = d_c2;
-      }
-      R.g_conf = d_g; R.g_n1 = d_g + IDN; R.g_n2 = d_g + 2 * (int64_t)IDN; R.g_avgt = d_g + 3 * (int64_t)IDN;
-      if (exact) { R.g_conf_lo = d_g + 4 * (int64_t)IDN; R.g_avgt_lo = d_g + 5 * (int64_t)IDN; }
-      // the final z at conf_prob > 0.51: rows packed into the lanes without padding (tsem_report_pack.h)
-      int lut_sq = 0;                                        // lut 2^-lut_sq: the largest score table entry in [2^40, 2^41)
-      double lut_max = 0.0;
-      for (double v : h->lut_host) lut_max = std::max(lut_max, v);
-      if (lut_max > 0.0 && std::isfinite(lut_max)) lut_sq = std::ilogb(lut_max) - 40;
-      const bool packed = !init && !exact && thresh > 0.51 && thresh <= 0.99999 &&   // (at 1.0 a unique row's z = fl(n fl(1 / n)) may miss the threshold)
-                          h->lut0_zero && lut_max > 0.0 && std::isfinite(lut_max) &&
-                          (int)h->lut_host.size() == R.lut_len && !(h->opt_report_dbg & 8) && h->opt_report_lanes == 0 && h->N < 0x7FFFFFFF;
-      // LDS: one workgroup of rr_nt() threads per CU (or two, option rowpass_wgs).  The final z wants pi*theta of as many
-      // ids as fit (8 B each) next to a few thousand accumulator slots (16 B each); the initial z has no pi*theta.
-      const int wgs = h->opt_rowpass_wgs >= 2 && h->opt_report_wgs2 ? 2 : 1;
-      const int lds_avail = TS_LDS_MAX / wgs - 2048 - R.lut_len * 8;
-      const int slot_bytes = exact ? 24 : 16;                // conf (f64) + two counters (+ the low pieces)
-      R.Hs = std::min(IDN, init ? lds_avail / slot_bytes : std::min(3072, lds_avail / slot_bytes / 4));
-      R.HC = init ? 0 : std::max(0, std::min(IDN, (lds_avail - R.Hs * slot_bytes) / 8));
-      const int cw = h->opt_report_wgs2 ? 2 : 1;             // (codes-only kernel: 32 VGPRs, so two 1024-thread workgroups fit a CU with half the slots each)
-      if (codes_only) R.Hs = std::min(IDN, (TS_LDS_MAX / cw - 2048) / 8);   // two 32-bit counters per id, nothing else in LDS
-      int cap = 256;                                       // G x E
-      if (h->opt_report_lanes > 0) {
-        cap = (int)h->opt_report_lanes;
-      } else if (h->have_rowstats) {
-        for (int q = 0; q < 6; ++q)
-          if ((double)h->len_gt[q] <= 0.005 * (double)h->N) { cap = 8 << q; break; }
-      }
-      void (*rk)(ReportArgs) = nullptr;
-#define RK(G_, E_) (codes_only ? k_report_init_codes<G_, E_> : (init ? k_report_rows<G_, E_, true> : k_report_rows<G_, E_, false>))
-      if (cap <= 8) rk = RK(1, 8); else if (cap <= 16) rk = RK(1, 16); else if (cap <= 32) rk = RK(2, 16);
-      else if (cap <= 64) rk = RK(4, 16); else if (cap <= 128) rk = RK(8, 16); else rk = RK(16, 16);
-#undef RK
-      TSEM_HIP(hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
-      R.dbg = (int)h->opt_report_dbg;
-      R.defer_rows = d_rows; R.defer_n = d_n;               // (d_rows is the tie list later: the slow kernel is done with it by then)
-      TSEM_HIP(hipMemsetAsync(d_n, 0, sizeof(unsigned long long), h->stream));
-      h->rep_timed = h->opt_timing != 0; h->rep_kernel = packed ? 4 : (codes_only ? 3 : 2); h->rep_deferred = 0;
-      if (h->rep_timed) {
-        for (int q = 0; q < 2; ++q) if (!h->ev_rep[q]) TSEM_HIP(hipEventCreate(&h->ev_rep[q]));
-      }
-      if (packed) {
-        // tsem_report_pack.h: fp32 tables (by id), the per-row winner records, the chunk table; LDS = the table of as many ids as fit
-        // (all of them up to ~34 000 slots) + the score table + 16 B per lane of row slots
-        // entries per lane: 16 amortise the per-chunk work (row map, scan, prefetch) over twice the entries; short rows fill 8 better
-        const int pkE = (h->opt_report_dbg & 128) ? 8 : ((h->opt_report_dbg & 256) ? 16 : (h->nnz >= 24 * h->N ? 16 : 8));
-        pt.lap("report: by-id tables");
-        if (int rc = ensure_report_chunks(h, pkE)) return rc;
-        pt.lap("report: chunk table");
-        uint32_t* d_t32 = nullptr; float* d_l32 = nullptr;
-        TSEM_SCOPED(d_t32); TSEM_SCOPED(d_l32);
-        TSEM_ALLOC(d_t32, (int64_t)IDN + 1); TSEM_ALLOC(d_l32, R.lut_len);
-        k_rp32_tables<<<cdiv64(std::max(IDN + 1, R.lut_len), 256), 256, 0, h->stream>>>(IDN, d_c2, R.lut_len, R.lut, lut_sq, d_t32, d_l32);
-        constexpr int nwv = 16;
-        const int words = (TS_LDS_MAX - 1024) / 4 - 8 - (pkE + 1) * (pkE / 2);   // LDS words for the table of the ids and the copies of the score table
-        Rp32Args P;
-        P.N = h->N; P.IDN = IDN; P.lut_len = R.lut_len; P.indptr = h->d_indptr; P.rid = h->d_rid16; P.raw = h->d_raw;
-        P.HC = std::min(IDN, std::max(0, words - R.lut_len));
-        P.lut_rep = 0;
-        while (P.lut_rep < 5 && P.HC + 1 + (R.lut_len << (P.lut_rep + 1)) <= words) ++P.lut_rep;
-        P.t32 = d_t32; P.l32 = d_l32; P.thresh = (float)thresh; P.win = reinterpret_cast<uint32_t*>(d_nb); P.defer_rows = d_rows; P.defer_n = d_n;
-        P.chunks = h->d_rep_chunks; P.nchunks = h->n_rep_chunks; P.dbg = (int)h->opt_report_dbg;
-        const size_t lds = (size_t)((pkE + 1) * (pkE / 2) + P.HC + 1 + (P.lut_len << P.lut_rep)) * 4;
-        void (*pk)(Rp32Args) = pkE == 16 ? (P.HC < IDN ? k_report_pack32<16, true> : k_report_pack32<16, false>)
-                                         : (P.HC < IDN ? k_report_pack32<8, true> : k_report_pack32<8, false>);
-        TSEM_HIP(hipFuncSetAttribute((const void*)pk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
-        if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[0], h->stream));
-        pk<<<h->n_cu, nwv * 64, lds, h->stream>>>(P);
-        if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[1], h->stream));
-        TSEM_HIP(hipGetLastError());
-        pt.lap("report: k_report_pack32");
-        // the winners per id: the whole LDS for counters, the ids in windows
-        const int W = std::min(IDN, (TS_LDS_MAX - 1024) / 8);
-        TSEM_HIP(hipFuncSetAttribute((const void*)k_report_hist, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
-        for (int id0 = 0; id0 < IDN; id0 += W)
-          k_report_hist<<<h->n_cu, 1024, (size_t)std::min(W, IDN - id0) * 8, h->stream>>>(h->N, reinterpret_cast<const uint32_t*>(d_nb), id0, std::min(W, IDN - id0), R.g_n1, R.g_conf);
-      } else {
-        if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[0], h->stream));
-        if (codes_only) rk<<<h->n_cu * cw, 1024, (size_t)R.Hs * 8, h->stream>>>(R);
-        else rk<<<h->n_cu * wgs, rr_nt(init), (size_t)R.lut_len * 8 + (size_t)R.HC * 8 + (size_t)R.Hs * slot_bytes, h->stream>>>(R);
-        if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[1], h->stream));
-      }
-      TSEM_HIP(hipGetLastError());
-      pt.lap("report: pass (+ histogram)");
-      if (init) k_report_slow<true><<<h->n_cu * 2, 256, 0, h->stream>>>(R);
-      else k_report_slow<false><<<h->n_cu * 2, 256, 0, h->stream>>>(R);
-      TSEM_HIP(hipGetLastError());
-      k_report_finish<<<cdiv64(IDN, 256), 256, 0, h->stream>>>(IDN, K, h->d_col_of_id, R.g_conf, R.g_n1, R.g_n2, R.g_avgt, R.g_conf_lo, R.g_avgt_lo, d_cs);
-      TSEM_HIP(hipGetLastError());
-      if (packed) {
-        // the tied rows: among the deferred ones (the fp32 filter decides only rows with ONE best hit) — picked from the list, sorted
-        unsigned long long nd = 0, nt = 0;
-        TSEM_HIP(hipMemcpyAsync(&nd, d_n, 8, hipMemcpyDeviceToHost, h->stream));
-        TSEM_HIP(hipMemcpyAsync(out3K, d_cs, sizeof(double) * 3 * K, hipMemcpyDeviceToHost, h->stream));
-        TSEM_HIP(hipStreamSynchronize(h->stream));
-        h->rep_deferred = (int64_t)nd;
-        pt.lap("report: exact rows, by column");
-        if (nd) {
-          int32_t *d_unsorted = nullptr, *d_sorted = nullptr;
-          unsigned long long* d_nt = nullptr;
-          TSEM_SCOPED(d_unsorted); TSEM_SCOPED(d_sorted); TSEM_SCOPED(d_nt);
-          TSEM_ALLOC(d_unsorted, nd); TSEM_ALLOC(d_nt, 1);
-          TSEM_HIP(hipMemsetAsync(d_nt, 0, sizeof(unsigned long long), h->stream));
-          k_ties_of_deferred<<<256, 256, 0, h->stream>>>(d_n, d_rows, d_nb, d_unsorted, d_nt);
-          TSEM_HIP(hipGetLastError());
-          TSEM_HIP(hipMemcpyAsync(&nt, d_nt, 8, hipMemcpyDeviceToHost, h->stream));
-          TSEM_HIP(hipStreamSynchronize(h->stream));
-          if (nt) {
-            TSEM_ALLOC(d_sorted, nt);
-            size_t tb = 0;
-            TSEM_HIP(rocprim::radix_sort_keys(nullptr, tb, d_unsorted, d_sorted, (size_t)nt, 0, 32, h->stream));
-            if (h->rep_tmp_bytes < tb || !h->d_rep_tmp) {
-              if (h->d_rep_tmp) (void)hipFree(h->d_rep_tmp);
-              h->d_rep_tmp = nullptr; h->rep_tmp_bytes = 0;
-              TSEM_HIP(hipMalloc(&h->d_rep_tmp, tb ? tb : 1));
-              h->rep_tmp_bytes = tb;
-            }
-            TSEM_HIP(rocprim::radix_sort_keys(h->d_rep_tmp, tb, d_unsorted, d_sorted, (size_t)nt, 0, 32, h->stream));
-            TSEM_ALLOC(h->d_tie_rows, nt); TSEM_ALLOC(h->d_tie_cnt, nt);
-            TSEM_HIP(hipMemcpyAsync(h->d_tie_rows, d_sorted, sizeof(int32_t) * nt, hipMemcpyDeviceToDevice, h->stream));
-            k_gather_i32<<<cdiv64((int64_t)nt, 256), 256, 0, h->stream>>>((int64_t)nt, d_sorted, d_nb, h->d_tie_cnt);
-            TSEM_HIP(hipStreamSynchronize(h->stream));
-          }
-        }
-        pt.lap("report: tied rows");
-        h->n_ties = (int64_t)nt;
-        if (n_ties) *n_ties = (int64_t)nt;
-        return TSEM_OK;
-      }
-      TSEM_HIP(hipStreamSynchronize(h->stream));
-    } else if (h->d_colmap && h->d_col_of_pc && h->P > 0) {
-      h->rep_timed = false; h->rep_kernel = 1; h->rep_deferred = 0;
-      if (int rc = with_indices(h, A)) return rc;
-      const int wgs = h->opt_rowpass_wgs < 2 ? 1 : 2;
-      A.colmap = h->d_colmap; A.col_of_pc = h->d_col_of_pc; A.P = h->P; A.Kp = h->Kp;
-      A.Hs = std::max(0, std::min(h->Kp, (int)((TS_LDS_MAX / wgs - 8192 / wgs - 1024 - A.lut_len * 8) / 8 / h->P / 3)));
-      double* d_lo = nullptr;
-      TSEM_SCOPED(d_lo);                                    // (the low pieces of the exact sums: freed on every return path)
-      if (int rc = rowpass_lo_begin(h, A, 3 * (int64_t)K, &d_lo)) return rc;
-      if (int rc = launch_rowpass(h, RP_REPORT, -1, h->n_cu * wgs, 1024, (size_t)(3 * A.P * A.Hs + A.lut_len) * 8, A)) return rc;
-      if (int rc = rowpass_lo_end(h, d_cs, d_lo, 3 * (int64_t)K)) return rc;
-    } else {
-      if (int rc = with_indices(h, A)) return rc;
-      double* d_lo = nullptr;
-      TSEM_SCOPED(d_lo);                                    // (the low pieces of the exact sums: freed on every return path)
-      if (int rc = rowpass_lo_begin(h, A, 3 * (int64_t)K, &d_lo)) return rc;
-      if (int rc = launch_rowpass(h, RP_REPORT, -1, tsem_rowpass_grid(h), 256, (size_t)A.lut_len * 8, A)) return rc;
-      if (int rc = rowpass_lo_end(h, d_cs, d_lo, 3 * (int64_t)K)) return rc;
-    }
+  if (int rc = report_scratch(h)) return rc;
+  A.thresh = thresh; A.colsums = d_cs; A.nbest = h->d_rep_nb;
+  pt.lap("report: scratch");
+  bool packed = false;
+  if (streaming_ok(h, which, A)) {
+    // sums by popularity id — conf | n1 | n2 | the wider ties' shares (| the low pieces of conf and of the shares) — mapped to the
+    // columns by k_report_finish; the rows the pass leaves (too long, near-ties) go to k_report_slow
+    const bool init = A.pi == nullptr;
+    TSEM_ALLOC(d_g, 6 * (int64_t)IDN);
+    TSEM_HIP(hipMemsetAsync(d_g, 0, sizeof(double) * 6 * IDN, h->stream));
+    if (!init) TSEM_ALLOC(d_c2, 2 * (int64_t)IDN);
+    ReportArgs R = report_args(h, A, thresh, d_c2);
+    R.nbest = h->d_rep_nb;
+    R.g_conf = d_g; R.g_n1 = d_g + IDN; R.g_n2 = d_g + 2 * (int64_t)IDN; R.g_avgt = d_g + 3 * (int64_t)IDN;
+    if (h->opt_reproducible) { R.g_conf_lo = d_g + 4 * (int64_t)IDN; R.g_avgt_lo = d_g + 5 * (int64_t)IDN; }
+    // the initial z without a conf column needs no arithmetic at all: a row's best hits are its largest score codes
+    const bool codes_only = init && !want_conf && codes_path_ok(h);
+    packed = packed_ok(h, R);
+    TSEM_HIP(hipMemsetAsync(h->d_rep_n, 0, sizeof(unsigned long long), h->stream));
+    h->rep_timed = h->opt_timing != 0; h->rep_kernel = packed ? 4 : (codes_only ? 3 : 2); h->rep_deferred = 0;
+    if (h->rep_timed)
+      for (int q = 0; q < 2; ++q) if (!h->ev_rep[q]) TSEM_HIP(hipEventCreate(&h->ev_rep[q]));
+    if (int rc = packed ? report_packed(h, R, tabs, pt) : report_streaming(h, R, codes_only)) return rc;
     TSEM_HIP(hipGetLastError());
-    size_t tb = 0;
-    TiedRow pred{d_nb};
-    rocprim::counting_iterator<int32_t> first(0);
-    TSEM_HIP(rocprim::select(nullptr, tb, first, d_rows, d_n, (size_t)h->N, pred, h->stream));
-    if (h->rep_tmp_bytes < tb || !h->d_rep_tmp) {
-      if (h->d_rep_tmp) (void)hipFree(h->d_rep_tmp);
-      h->d_rep_tmp = nullptr; h->rep_tmp_bytes = 0;
-      TSEM_HIP(hipMalloc(&h->d_rep_tmp, tb ? tb : 1));
-      h->rep_tmp_bytes = tb;
-    }
-    void* const tmp = h->d_rep_tmp;
-    TSEM_HIP(rocprim::select(tmp, tb, first, d_rows, d_n, (size_t)h->N, pred, h->stream));
-    unsigned long long n = 0;
-    TSEM_HIP(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, h->stream));
-    TSEM_HIP(hipMemcpyAsync(out3K, d_cs, sizeof(double) * 3 * K, hipMemcpyDeviceToHost, h->stream));
-    TSEM_HIP(hipStreamSynchronize(h->stream));
-    if (n) {
-      TSEM_ALLOC(h->d_tie_rows, n); TSEM_ALLOC(h->d_tie_cnt, n);
-      TSEM_HIP(hipMemcpyAsync(h->d_tie_rows, d_rows, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, h->stream));
-      k_gather_i32<<<cdiv64((int64_t)n, 256), 256, 0, h->stream>>>((int64_t)n, d_rows, d_nb, h->d_tie_cnt);
-      TSEM_HIP(hipStreamSynchronize(h->stream));
-    }
-    h->n_ties = (int64_t)n;
-    if (n_ties) *n_ties = (int64_t)n;
-  } else {
-    for (int64_t j = 0; j < 3 * (int64_t)K; ++j) out3K[j] = 0.0;
+    pt.lap("report: pass (+ histogram)");
+    const ReportKern rs = report_slow_kernel<0>(init);
+    rs<<<h->n_cu * 2, 256, 0, h->stream>>>(R);
+    TSEM_HIP(hipGetLastError());
+    k_report_finish<<<cdiv64(IDN, 256), 256, 0, h->stream>>>(IDN, K, h->d_col_of_id, R.g_conf, R.g_n1, R.g_n2, R.g_avgt, R.g_conf_lo, R.g_avgt_lo, d_cs);
+    TSEM_HIP(hipGetLastError());
+  } else if (int rc = report_generic(h, A, d_cs)) {
+    return rc;
   }
+  TSEM_HIP(hipMemcpyAsync(out3K, d_cs, sizeof(double) * 3 * K, hipMemcpyDeviceToHost, h->stream));
+  if (int rc = packed ? ties_of_deferred(h) : ties_of_counts(h)) return rc;
+  pt.lap("report: tied rows");
+  if (n_ties) *n_ties = h->n_ties;
   return TSEM_OK;
 }
 
@@ -1680,14 +1717,8 @@ int tsem_reassign_rows(tsem_ctx* h, int method, double thresh, int which, const 
   TSEM_SCOPED(d_cs); TSEM_SCOPED(d_rows); TSEM_SCOPED(d_picks);
   TSEM_ALLOC(d_cs, h->K);
   TSEM_HIP(hipMemsetAsync(d_cs, 0, sizeof(double) * h->K, h->stream));
-  if (rows) {
-    TSEM_ALLOC(d_rows, n);
-    TSEM_HIP(hipMemcpyAsync(d_rows, rows, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
-  }
-  if (method == TSEM_RA_CHOOSE && picks) {
-    TSEM_ALLOC(d_picks, n);
-    TSEM_HIP(hipMemcpyAsync(d_picks, picks, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
-  }
+  if (rows) { if (int rc = upload_i32(h, d_rows, rows, n)) return rc; }
+  if (method == TSEM_RA_CHOOSE && picks) { if (int rc = upload_i32(h, d_picks, picks, n)) return rc; }
   // `choose` over the initial z: the picked best hit is the picks[i]-th entry with the row's largest score code — no score table,
   // no column ids (the popularity ids do), no floating point — under the premises of k_report_init_codes
   if (method == TSEM_RA_CHOOSE && which == TSEM_Z_INITIAL) {
@@ -1709,12 +1740,7 @@ int tsem_reassign_rows(tsem_ctx* h, int method, double thresh, int which, const 
   A.rowlist = rows ? d_rows : h->d_tie_rows; A.nlist = n;
   IndicesGuard ig(h);
   if (int rc = with_indices(h, A)) return rc;
-  const int grid = (int)std::min<int64_t>(8192, std::max<int64_t>(1, (n + 15) / 16));
-  double* d_lo = nullptr;
-  TSEM_SCOPED(d_lo);                                    // (the low pieces of the exact sums: freed on every return path)
-  if (int rc = rowpass_lo_begin(h, A, h->K, &d_lo)) return rc;
-  if (int rc = launch_rowpass(h, RP_REASSIGN, -1, grid, 256, (size_t)A.lut_len * 8, A)) return rc;
-  if (int rc = rowpass_lo_end(h, d_cs, d_lo, h->K)) return rc;
+  if (int rc = rowpass_exact(h, A, RP_REASSIGN, -1, list_grid(n), 256, (size_t)A.lut_len * 8, d_cs, h->K)) return rc;
   TSEM_HIP(hipMemcpyAsync(colsums, d_cs, sizeof(double) * h->K, hipMemcpyDeviceToHost, h->stream));
   TSEM_HIP(hipStreamSynchronize(h->stream));
   return TSEM_OK;
@@ -1741,8 +1767,8 @@ int tsem_rows_lookup(tsem_ctx* h, int which, int method, double thresh, int64_t 
   double *d_z = nullptr, *d_m = nullptr;
   uint32_t* d_bad = nullptr;
   TSEM_SCOPED(d_rows); TSEM_SCOPED(d_picks); TSEM_SCOPED(d_off); TSEM_SCOPED(d_z); TSEM_SCOPED(d_m); TSEM_SCOPED(d_bad);
-  TSEM_ALLOC(d_rows, n); TSEM_ALLOC(d_off, n + 1); TSEM_ALLOC(d_bad, 1);
-  TSEM_HIP(hipMemcpyAsync(d_rows, rows, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
+  if (int rc = upload_i32(h, d_rows, rows, n)) return rc;
+  TSEM_ALLOC(d_off, n + 1); TSEM_ALLOC(d_bad, 1);
   TSEM_HIP(hipMemcpyAsync(d_off, out_off, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, h->stream));
   TSEM_HIP(hipMemsetAsync(d_bad, 0, 4, h->stream));
   k_check_offsets<<<cdiv64(n, 256), 256, 0, h->stream>>>(n, d_rows, d_off, h->d_indptr, d_bad);   // every row's slice holds exactly its entries
@@ -1750,14 +1776,11 @@ int tsem_rows_lookup(tsem_ctx* h, int which, int method, double thresh, int64_t 
   TSEM_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, h->stream));
   TSEM_HIP(hipStreamSynchronize(h->stream));
   if (bad) TSEM_FAIL(TSEM_ERR_ARG, "tsem_rows_lookup: out_off does not follow the listed rows' lengths");
-  if (method == TSEM_RA_CHOOSE && picks) {
-    TSEM_ALLOC(d_picks, n);
-    TSEM_HIP(hipMemcpyAsync(d_picks, picks, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
-  }
+  if (method == TSEM_RA_CHOOSE && picks) { if (int rc = upload_i32(h, d_picks, picks, n)) return rc; }
   A.rowlist = d_rows; A.nlist = n; A.out_off = d_off;
   IndicesGuard ig(h);
   if (int rc = with_indices(h, A)) return rc;
-  const int grid = (int)std::min<int64_t>(8192, std::max<int64_t>(1, (n + 15) / 16));
+  const int grid = list_grid(n);
   if (z_out) {
     TSEM_ALLOC(d_z, total);
     A.zout = d_z;
@@ -1819,66 +1842,40 @@ int tsem_reassign_groups(tsem_ctx* h, int method, double thresh, int which, cons
   if (n_groups == 0 || K == 0) return TSEM_OK;
   const int64_t budget = h->opt_group_tile > 0 ? h->opt_group_tile : ((int64_t)1 << 30);
   const bool stream_ok = (method == TSEM_RA_EXCLUDE || method == TSEM_RA_AVERAGE || method == TSEM_RA_ALL || (method == TSEM_RA_CONF && thresh > 0.51)) &&
-                         h->opt_report_kernel != 0 && which != TSEM_Z_USER && h->d_rid16 && h->d_col_of_id && A.lut_len > 0 &&
-                         !h->opt_reproducible && h->N > 0;
+                         streaming_ok(h, which, A) && !h->opt_reproducible && h->N > 0;
   // the budget covers BOTH copies of a tile the streaming kernel needs (by column for the caller, by id for the kernel)
   const int tile = (int)std::max<int64_t>(1, std::min<int64_t>(n_groups, budget / (((int64_t)K + (stream_ok ? IDN : 0)) * 8)));
   // scratch kept between calls: the tile by column (what the caller gets) and, for the streaming kernel, the tile by id
   const size_t out_bytes = (size_t)tile * K * 8, id_bytes = stream_ok ? (size_t)tile * IDN * 8 : 0;
-  if (h->gtile_bytes < out_bytes + id_bytes || !h->d_gtile) {
-    if (h->d_gtile) (void)hipFree(h->d_gtile);
-    h->d_gtile = nullptr; h->gtile_bytes = 0;
-    if (hipMalloc(&h->d_gtile, out_bytes + id_bytes) != hipSuccess) TSEM_FAIL(TSEM_ERR_NOMEM, "hipMalloc failed (per-group tile)");
-    h->gtile_bytes = out_bytes + id_bytes;
-  }
+  if (grow_scratch(h->d_gtile, h->gtile_bytes, out_bytes + id_bytes) != hipSuccess) TSEM_FAIL(TSEM_ERR_NOMEM, "hipMalloc failed (per-group tile)");
   double* const d_out = static_cast<double*>(h->d_gtile);
   void* const d_id = static_cast<char*>(h->d_gtile) + out_bytes;
-  DevTmp t_picks, t_c2, t_lo;
-  if (method == TSEM_RA_CHOOSE && picks) {
-    TSEM_TMP(t_picks, sizeof(int32_t) * h->N);
-    if (h->N) TSEM_HIP(hipMemcpyAsync(t_picks.p, picks, sizeof(int32_t) * h->N, hipMemcpyHostToDevice, h->stream));
-  }
-  ReportArgs R;
-  void (*rk)(ReportArgs) = nullptr;
-  void (*rs)(ReportArgs) = nullptr;
+  int32_t* d_picks = nullptr;
+  double* d_c2 = nullptr;
+  TSEM_SCOPED(d_picks); TSEM_SCOPED(d_c2);
+  if (method == TSEM_RA_CHOOSE && picks) { if (int rc = upload_i32(h, d_picks, picks, h->N)) return rc; }
   const bool init = A.pi == nullptr;
   const int gm = method == TSEM_RA_EXCLUDE ? 1 : (method == TSEM_RA_AVERAGE ? 2 : (method == TSEM_RA_ALL ? 4 : 3));
+  const bool counts = gm == 1 || gm == 4;                  // the tile by id: 32-bit counters (`exclude`, `all`) or doubles
+  ReportArgs R{};
+  ReportKern rk = nullptr, rs = nullptr;
   size_t lds = 0;
   if (stream_ok) {
-    R.N = h->N; R.nnz = h->nnz; R.K = K; R.IDN = IDN; R.indptr = h->d_indptr; R.rid = h->d_rid16; R.raw = h->d_raw;
-    R.lut = h->d_lut; R.lut_len = A.lut_len; R.cnat2 = nullptr; R.thresh = method == TSEM_RA_CONF ? thresh : 0.9; R.nbest = nullptr;
-    R.g_conf = R.g_n1 = R.g_n2 = R.g_avgt = nullptr; R.dbg = 0; R.exact_n = A.exact_n;
-    if (!init) {
-      TSEM_TMP(t_c2, sizeof(double) * 2 * IDN);
-      k_cnat2_id<<<cdiv64(IDN, 256), 256, 0, h->stream>>>(IDN, h->d_col_of_id, A.pi, A.theta, t_c2.as<double>());
-      R.cnat2 = t_c2.as<double>();
-    }
-    const int lds_avail = TS_LDS_MAX - 2048 - R.lut_len * 8;
-    R.Hs = 0;
-    R.HC = init ? 0 : std::max(0, std::min(IDN, lds_avail / 8));
-    lds = (size_t)R.lut_len * 8 + (size_t)R.HC * 8;
-    int cap = 256;                                         // G x E: the smallest capacity that fewer than 0.5 % of the rows exceed
-    if (h->opt_report_lanes > 0) cap = (int)h->opt_report_lanes;
-    else if (h->have_rowstats)
-      for (int q = 0; q < 6; ++q)
-        if ((double)h->len_gt[q] <= 0.005 * (double)h->N) { cap = 8 << q; break; }
-#define RKG(G_, E_) (gm == 1 ? (init ? k_report_rows<G_, E_, true, 1> : k_report_rows<G_, E_, false, 1>) : \
-                     gm == 2 ? (init ? k_report_rows<G_, E_, true, 2> : k_report_rows<G_, E_, false, 2>) : \
-                     gm == 4 ? (init ? k_report_rows<G_, E_, true, 4> : k_report_rows<G_, E_, false, 4>) : \
-                               (init ? k_report_rows<G_, E_, true, 3> : k_report_rows<G_, E_, false, 3>))
-    if (cap <= 8) rk = RKG(1, 8); else if (cap <= 16) rk = RKG(1, 16); else if (cap <= 32) rk = RKG(2, 16);
-    else if (cap <= 64) rk = RKG(4, 16); else if (cap <= 128) rk = RKG(8, 16); else rk = RKG(16, 16);
-#undef RKG
-    rs = gm == 1 ? (init ? k_report_slow<true, 1> : k_report_slow<false, 1>) :
-         gm == 2 ? (init ? k_report_slow<true, 2> : k_report_slow<false, 2>) :
-         gm == 4 ? (init ? k_report_slow<true, 4> : k_report_slow<false, 4>) : (init ? k_report_slow<true, 3> : k_report_slow<false, 3>);
-    TSEM_HIP(hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
-    if (!h->d_rep_nb) { TSEM_ALLOC(h->d_rep_nb, h->N); TSEM_ALLOC(h->d_rep_rows, h->N); TSEM_ALLOC(h->d_rep_n, 1); }
     // (d_rep_rows / d_rep_n are only scratch here: the tie list of the last tsem_report_colsums lives in its own d_tie_rows / d_tie_cnt,
     //  which tsem_reassign_rows(rows = NULL) and `choose` still use after this call — ADVICE r4)
-    R.defer_rows = h->d_rep_rows; R.defer_n = h->d_rep_n; R.group = h->d_group;
-  } else if (h->opt_reproducible) {
-    TSEM_TMP(t_lo, out_bytes);
+    if (int rc = report_scratch(h)) return rc;
+    if (!init) TSEM_ALLOC(d_c2, 2 * (int64_t)IDN);
+    R = report_args(h, A, method == TSEM_RA_CONF ? thresh : 0.9, d_c2);
+    R.group = h->d_group;
+    // LDS: pi*theta of as many ids as fit, no accumulator slots
+    R.HC = init ? 0 : std::max(0, std::min(IDN, (TS_LDS_MAX - 2048 - R.lut_len * 8) / 8));
+    lds = (size_t)R.lut_len * 8 + (size_t)R.HC * 8;
+    const int cap = report_capacity(h);
+    rk = gm == 1 ? report_rows_kernel<1>(cap, init, false) : gm == 2 ? report_rows_kernel<2>(cap, init, false)
+       : gm == 4 ? report_rows_kernel<4>(cap, init, false) : report_rows_kernel<3>(cap, init, false);
+    rs = gm == 1 ? report_slow_kernel<1>(init) : gm == 2 ? report_slow_kernel<2>(init)
+       : gm == 4 ? report_slow_kernel<4>(init) : report_slow_kernel<3>(init);
+    TSEM_HIP(hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
   }
   for (int g0 = 0; g0 < n_groups; g0 += tile) {
     const int g1 = std::min(n_groups, g0 + tile);
@@ -1886,9 +1883,9 @@ int tsem_reassign_groups(tsem_ctx* h, int method, double thresh, int which, cons
     TSEM_HIP(hipMemsetAsync(d_out, 0, sizeof(double) * n_out, h->stream));
     if (stream_ok) {
       const int64_t n_id = (int64_t)(g1 - g0) * IDN;
-      TSEM_HIP(hipMemsetAsync(d_id, 0, ((gm == 1 || gm == 4) ? 4 : 8) * (size_t)n_id, h->stream));
+      TSEM_HIP(hipMemsetAsync(d_id, 0, (counts ? 4 : 8) * (size_t)n_id, h->stream));
       TSEM_HIP(hipMemsetAsync(R.defer_n, 0, sizeof(unsigned long long), h->stream));
-      R.g0 = g0; R.g1 = g1; R.t_cnt = (gm == 1 || gm == 4) ? static_cast<uint32_t*>(d_id) : nullptr; R.t_val = (gm == 1 || gm == 4) ? nullptr : static_cast<double*>(d_id);
+      R.g0 = g0; R.g1 = g1; R.t_cnt = counts ? static_cast<uint32_t*>(d_id) : nullptr; R.t_val = counts ? nullptr : static_cast<double*>(d_id);
       rk<<<h->n_cu, rr_nt(init), lds, h->stream>>>(R);
       TSEM_HIP(hipGetLastError());
       rs<<<h->n_cu * 2, 256, 0, h->stream>>>(R);
@@ -1901,10 +1898,8 @@ int tsem_reassign_groups(tsem_ctx* h, int method, double thresh, int which, cons
       TSEM_HIP(hipGetLastError());
     } else if (h->N) {
       if (int rc = with_indices(h, A)) return rc;
-      A.colsums = d_out; A.picks = t_picks.as<int32_t>(); A.group = h->d_group; A.g0 = g0; A.g1 = g1;
-      if (t_lo.p) { TSEM_HIP(hipMemsetAsync(t_lo.p, 0, sizeof(double) * n_out, h->stream)); A.colsums_lo = t_lo.as<double>(); }
-      if (int rc = launch_rowpass(h, RP_REASSIGN, -1, tsem_rowpass_grid(h), 256, (size_t)A.lut_len * 8, A)) return rc;
-      if (t_lo.p) { k_add_lo<<<cdiv64(n_out, 256), 256, 0, h->stream>>>(n_out, d_out, t_lo.as<double>()); TSEM_HIP(hipGetLastError()); }
+      A.colsums = d_out; A.picks = d_picks; A.group = h->d_group; A.g0 = g0; A.g1 = g1;
+      if (int rc = rowpass_exact(h, A, RP_REASSIGN, -1, tsem_rowpass_grid(h), 256, (size_t)A.lut_len * 8, d_out, n_out)) return rc;
     }
     TSEM_HIP(hipMemcpyAsync(out + (int64_t)g0 * K, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, h->stream));
     TSEM_HIP(hipStreamSynchronize(h->stream));

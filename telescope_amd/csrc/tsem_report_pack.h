@@ -161,7 +161,6 @@ struct Rp32Args {
                                                             // word is rewritten by k_report_slow with its count, after k_report_hist has run)
   int32_t* defer_rows; unsigned long long* defer_n;
   const RpChunk* chunks; int64_t nchunks;
-  int dbg;                                                  // timing experiments (wrong results): 16 no scan, 32 no stores, no decisions
 };
 
 // A row's (sum, largest, second largest, id of the largest) over its lanes: a segmented inclusive scan on the VALU — row_shr 1 / 2 / 4 / 8
@@ -305,7 +304,7 @@ __global__ __launch_bounds__(1024) void k_report_pack32(Rp32Args A) {
     v.w = (jw & 1u) ? wsel >> 16 : wsel & 0xFFFFu;
     const uint32_t q0 = __float_as_uint(r.q[0]), c0 = r.c[0], id0 = t.id[0][0] & 0xFFFFu;   // (what a unique row needs)
     const int gm = __builtin_amdgcn_readfirstlane(p.gmax);     // the longest row of the chunk, in lanes: steps beyond it are skipped
-    if (gm > 1 && !(A.dbg & 16)) {
+    if (gm > 1) {
       const int pos = p.pos, l15 = lane & 15, l31 = lane & 31;
       rp_scan_step<0x111, 0xF>(v, pos >= 1);
       if (gm > 2) rp_scan_step<0x112, 0xF>(v, pos >= 2);
@@ -337,7 +336,7 @@ __global__ __launch_bounds__(1024) void k_report_pack32(Rp32Args A) {
   // has a whole iteration to complete before anything younger is awaited.  The best-hit count of a decided row (1; 0 for an empty row)
   // is not stored: the host takes the tied rows from the deferred list (k_ties_of_deferred).
   auto emit = [&](const Out& o) {
-    if (!o.act || (A.dbg & 32)) return;
+    if (!o.act) return;
     rp_store_u32(&A.win[o.row], o.w);
     if (o.nb < 0) rp_store_u32(reinterpret_cast<uint32_t*>(&A.defer_rows[atomicAdd(A.defer_n, 1ull)]), (uint32_t)o.row);
   };

@@ -1,6 +1,6 @@
 """The report pass over the FINAL z on the bench workload: wall clock per call of tsem_report_colsums, the packed fp32 kernel
-(default) against the capacity kernel (report_dbg = 8) and the packed kernel's timing experiments (report_dbg 16 / 32 / 64: wrong
-results).   python tools/time_report_final.py [rows] [nnz_row] [cols] [dbg values ...]"""
+(default) against the capacity kernel (report_dbg = 8) and the packed kernel at 8 / 16 entries per lane (report_dbg 128 / 256).
+python tools/time_report_final.py [rows] [nnz_row] [cols] [dbg values out of 0 8 128 256 ...]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
@@ -12,7 +12,7 @@ from telescope_amd.likelihood import TelescopeLikelihood
 rows = int(sys.argv[1]) if len(sys.argv) > 1 else 50_000_000
 d = float(sys.argv[2]) if len(sys.argv) > 2 else 40.0
 cols = int(sys.argv[3]) if len(sys.argv) > 3 else 30000
-dbgs = [int(x) for x in sys.argv[4:]] or [0, 8]
+dbgs = [int(x) for x in sys.argv[4:]] or [0, 8, 128, 256]
 class O: em_epsilon = 0.0; max_iter = 5; pi_prior = 0; theta_prior = 200000
 eng = Engine(0)
 eng.generate(0, rows, cols, synthetic.poisson_cdf_u32(d), 42, 1, 0.05)

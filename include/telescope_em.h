@@ -115,7 +115,10 @@ int  tsem_set_stream(tsem_ctx* h, void* hip_stream); /* launch on this hipStream
  *                  of magnitude slower per entry (tsem_layout_info[24] / [26] say which form runs).
  *   "em_precision" 1: the EM pass in fp32 arithmetic (row sums, posteriors and column sums in fp32) — a
  *                  DIAGNOSTIC for the fp32-vs-fp64 tolerance sweep of BASELINE config 3, not a product path
- *   "fused_dbg", "fused_prof", "chunk_blocks"     timing experiments */
+ *   "fused_dbg"    test hooks, a sum of bits: 32 / 64 the fused EM / lnl pass behaves like a hand-off time-out; 8192 the lnl pass
+ *                  takes a logarithm per entry, 16384 looks log Q up where the arithmetic form applies, 32768 takes the log
+ *                  form whatever the parameters.  Any other bit: TSEM_ERR_ARG.
+ *   "fused_prof", "chunk_blocks"     timing experiments */
 int  tsem_set_option(tsem_ctx* h, const char* key, int64_t value);
 int  tsem_synchronize(tsem_ctx* h);
 

@@ -31,7 +31,7 @@ LIB_UNITS = ('tsem_host', 'tsem_setup', 'tsem_em', 'tsem_report', 'tsem_comm', '
 FZ_UNITS = tuple('tsem_fz_p%d' % p for p in range(1, 9))
 
 
-def build_library(force=False, verbose=False, extra_flags=(), out=None):
+def build_library(force=False, verbose=False, out=None):
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  Fourteen translation units — the six of
     LIB_UNITS and the eight that instantiate the fused kernel for one team size each (most of the build time) — are compiled
     in parallel and linked into one shared object."""
@@ -42,7 +42,7 @@ def build_library(force=False, verbose=False, extra_flags=(), out=None):
     target = out or LIB_PATH
     objdir = os.path.join(csrc, '_obj' + ('' if out is None else '_' + os.path.basename(out)))
     common = ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-ffp-contract=off',
-              '-I' + os.path.join(ROOT, 'include'), '-I' + csrc] + list(extra_flags)
+              '-I' + os.path.join(ROOT, 'include'), '-I' + csrc]
     link_stamp = os.path.join(objdir, '_link.flags')        # (a change of the compile flags alone must rebuild too)
 
     def unit_flags(src):

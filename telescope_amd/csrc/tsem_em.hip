@@ -661,7 +661,7 @@ static int launch_fused(tsem_ctx* h, int mode, hipEvent_t* pair, int bin = 0) {
   if (mode == 8) { A.ctab = h->d_ctab_prev; A.ctab2 = h->d_ctab; A.koff = bin * A.Kh; A.lnl_out = h->d_lnl_part + (size_t)bin * h->fz_grid; }
   A.wrow = h->d_amb_w; A.partial = h->d_fpartial; A.xchg = h->d_xchg; A.sorted = h->sorted_layout ? 1 : 0;
   A.sync = h->d_xflags;
-  A.prof = (mode == 0 || mode == 4 || mode == 5) ? h->d_prof : nullptr; A.prof_blocks = A.prof ? h->prof_steps : 0; A.dbg = (int)h->opt_dbg;
+  A.prof = (mode == 0 || mode == 4 || mode == 5) ? h->d_prof : nullptr; A.prof_blocks = A.prof ? h->prof_steps : 0; A.dbg = (int)(h->opt_dbg & (32 | 64));
   A.ctl = h->d_ctl;
   A.ebias = h->d_ebias; A.bin = bin; A.ovf = h->d_ovf; A.partial2 = h->d_fpartial2;
 

@@ -56,23 +56,14 @@ __host__ __device__ constexpr int fz_dt(int g) { return FZ_NT - 64 * fz_nxw(g); 
 __host__ __device__ constexpr int fz_cap(int g) { return fz_dt(g) * 4; }            // entries per register tile
 __host__ __device__ constexpr int fz_rmax(int g) { return 2 * 64 * fz_rp(g) * fz_nxw(g); }
 constexpr int FZ_MAX_P = 8;
-#ifndef FZ_GAP_STEPS
-#define FZ_GAP_STEPS 1
-#endif
-constexpr int FZ_GAP = FZ_GAP_STEPS;   // steps between a block's publish and the partner loads
+constexpr int FZ_GAP = 1;              // steps between a block's publish and the partner loads
 constexpr int FZ_NS = 5 + FZ_GAP;      // register sets: block k lives in set k % FZ_NS
 constexpr int FZ_DL = 2;               // prefetch distance (steps)
 constexpr int FZ_LAG = 3 + FZ_GAP;     // scatter lag (steps) = FZ_NS - FZ_DL
 // (y ring, fz_yr(GEO) deep: row sums of block k live from step k to its combine at k+3 — or, geometry 3, to its publish at k+1)
 constexpr int FZ_XS = 8;               // exchange slots per team (ring)
 constexpr unsigned FZ_SPIN_LIMIT = 2000000u;
-#ifndef FZ_SKIP_IDLE_WAVES
-#define FZ_SKIP_IDLE_WAVES 1
-#endif
 constexpr int FZ_PROF_SLOTS = 16;
-#ifndef FZ_LAG_CERR
-#define FZ_LAG_CERR 0
-#endif
 
 // sync words (uint32): [0..7] per-XCD tickets, [8] registered WGs, [9] error
 constexpr int FZ_SYNC_WORDS = 16;
@@ -140,8 +131,7 @@ struct FusedArgs {
   // (ensure_log_tables); codes below lq_c0 (t < 38: absent from alignment data, whose Q starts at e^46) take the exact branch.
   int lq_lin, lq_c0;
   double lq_a, lq_b;
-  int dbg;              // bit0: skip partner loads (timing experiments only; wrong results)
-                        // bit5 / bit6: behave like a hand-off time-out in the EM / lnl pass (tests of the recovery path)
+  int dbg;              // test hook, bit5 / bit6: behave like a hand-off time-out in the EM / lnl pass (tests of the recovery path)
   unsigned long long* prof;   // optional per-step timestamps of team 0 / member 0
   int prof_blocks;
 };
@@ -159,10 +149,7 @@ __device__ __forceinline__ uint32_t fz_ld_u32(const uint32_t* p) {
 typedef unsigned int fz_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int fz_u32x2 __attribute__((ext_vector_type(2)));
 constexpr int FZ_RSRC_FLAGS = 0x00027000;
-#ifndef FZ_STREAM_POLICY
-#define FZ_STREAM_POLICY 2
-#endif
-constexpr int FZ_STREAM = FZ_STREAM_POLICY;              // cache policy of the entry loads: nt (read once) keeps the
+constexpr int FZ_STREAM = 2;                             // cache policy of the entry loads: nt (read once) keeps the
                                                          // exchange ring and the tables in L2 (fp64 entries: -3.6 %)
 constexpr unsigned FZ_OOB = 0x7FFFFF00u;                 // beyond num_records of every resource used here
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t fz_rsrc(const void* base, uint64_t byte_off, unsigned bytes) {
@@ -327,14 +314,13 @@ __device__ __forceinline__ void fz_xchg(const FusedArgs& A, const FzX& X) {
   __amdgpu_buffer_rsrc_t xrsrc = fz_rsrc(xbase, 0, (unsigned)(FZ_XS * P * R * 8));
   __amdgpu_buffer_rsrc_t qrsrc = fz_rsrc(A.sb_q32, 0, (unsigned)((A.nb * P + 2) * 4));
   const bool offw = X.xw == 0;                                  // wave that also ferries the sub-block offsets
-  const bool nopart = (A.dbg & 1) != 0;                         // timing experiment: partner loads go out of range
   auto slot_of = [&](int64_t k, int q) -> unsigned long long* {
     return xbase + ((int64_t)(k & (FZ_XS - 1)) * P + q) * R;
   };
   auto tag_of = [&](int64_t k) -> unsigned long long {
     return (unsigned long long)((((k / FZ_XS) & 1) ^ 1));
   };
-  if (!(A.dbg & 16)) __builtin_amdgcn_s_setprio(3);   // few instructions, all on the critical path of the step
+  __builtin_amdgcn_s_setprio(3);   // few instructions, all on the critical path of the step
   struct Gen { u64x2 pv[NPART][FZ_RP]; double2 w[FZ_RP]; uint32_t wc[FZ_RP]; uint32_t off; double2 rpv[FZ_RP]; };
   Gen g1;
   g1.off = 0;
@@ -385,7 +371,7 @@ __device__ __forceinline__ void fz_xchg(const FusedArgs& A, const FzX& X) {
       // and put `s_waitcnt vmcnt(0)` between them — the exchange wave then sat behind the data waves' whole
       // burst in the middle of its issue sequence, every step (round-2 ISA review; r02 timelines "x:issued").
       // Lanes past the last row pair re-read row pair R-2: one more hit on a line the wave loads anyway.
-      __amdgpu_buffer_rsrc_t xr = fz_rsrc(xbase, 0, (kv && !nopart) ? (unsigned)(FZ_XS * P * R * 8) : 0u);
+      __amdgpu_buffer_rsrc_t xr = fz_rsrc(xbase, 0, kv ? (unsigned)(FZ_XS * P * R * 8) : 0u);
 #pragma unroll
       for (int j = 0; j < FZ_RP; ++j) {
         const int r = min(rlo + 2 * (lane + 64 * j), R - 2);
@@ -414,9 +400,6 @@ __device__ __forceinline__ void fz_xchg(const FusedArgs& A, const FzX& X) {
       return;
     }
     if (SPA) return;
-#ifdef FZ_EXPERIMENT
-    if (A.dbg & 2048) return;                             // timing experiment: no combine at all (s stays 0, members free-run)
-#endif
     // (Round 3 tried carrying this member's OWN sums in registers from the publish to the combine, zeroing y at the
     // publish: two LDS operations and one LDS wait less per step — and 2.3x the tag misses, code16 3.33 -> 3.37 ms, fp64
     // unchanged, with one or two steps of gap alike (profiles/r03_exchange_bounds.txt): what the combine costs is
@@ -428,7 +411,7 @@ __device__ __forceinline__ void fz_xchg(const FusedArgs& A, const FzX& X) {
       if (r < rhi) {
         u64x2 own;
         if (OWNREG) own = mine.v[j]; else own = *reinterpret_cast<const u64x2*>(&y[(k & (FZ_YR - 1)) * R + r]);
-        if (P > 1 && !nopart) {
+        if (P > 1) {
           unsigned spins = 0;
           for (;;) {                                    // normally true at once: published 2 steps ago
             bool ok = true;
@@ -450,7 +433,7 @@ __device__ __forceinline__ void fz_xchg(const FusedArgs& A, const FzX& X) {
         double ys0 = 0.0, ys1 = 0.0;
 #pragma unroll
         for (int q = 0; q < P; ++q) {                   // fixed order: every member computes the same bits
-          u64x2 v = (q == p || nopart) ? own : g.pv[q < p ? q : (q > 0 ? q - 1 : 0)][j];
+          u64x2 v = q == p ? own : g.pv[q < p ? q : (q > 0 ? q - 1 : 0)][j];
           if (P > 1) { v.x &= ~1ull; v.y &= ~1ull; }
           ys0 += __longlong_as_double((long long)v.x);
           ys1 += __longlong_as_double((long long)v.y);
@@ -476,13 +459,6 @@ __device__ __forceinline__ void fz_xchg(const FusedArgs& A, const FzX& X) {
     }
   };
   int64_t i = 0;
-  if (A.dbg & 8) {                                      // timing experiment: exchange waves only keep the barriers
-    for (; i < nsteps; ++i) {
-      if (offw && lane < 2) { const int64_t ko = i + FZ_DL + 2; if (ko >= 5 && ko < nblk) offs[(ko & 7) * 2 + lane] = A.sb_q32[(team + ko * T) * P + p + lane]; }
-      __syncthreads();
-    }
-    return;
-  }
   auto xstep = [&]() {
     const bool pr = A.prof && team == 0 && p == 0 && lane == 0 && offw && (int)i < A.prof_blocks;
     if (pr) A.prof[i * FZ_PROF_SLOTS + 6] = clock64();
@@ -554,12 +530,7 @@ __device__ __forceinline__ void fz_xchg(const FusedArgs& A, const FzX& X) {
       const int64_t kp = i - 1;
       const bool pv = kp >= 0 && kp < nblk;
       const unsigned long long tag = tag_of(kp);
-#ifdef FZ_EXPERIMENT
-      const bool xnp = (A.dbg & 1024) != 0;               // timing experiment: publish stores dropped
-#else
-      constexpr bool xnp = false;
-#endif
-      __amdgpu_buffer_rsrc_t xs = fz_rsrc(xbase, 0, (pv && !xnp) ? (unsigned)(FZ_XS * P * R * 8) : 0u);   // (an empty resource drops the store)
+      __amdgpu_buffer_rsrc_t xs = fz_rsrc(xbase, 0, pv ? (unsigned)(FZ_XS * P * R * 8) : 0u);   // (an empty resource drops the store)
 #pragma unroll
       for (int j = 0; j < FZ_RP; ++j) {
         const int r = min(rlo + 2 * (lane + 64 * j), R - 2);   // lanes past the last row pair store row pair R-2 again (same bytes)
@@ -739,9 +710,6 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
   if (sprof) { sprof[4] = wall_clock64(); sprof[7] = ((unsigned long long)xcc << 48) | ((unsigned long long)team << 32) | ((unsigned long long)p << 16) | (unsigned long long)nblk; }
 
   double lsum = 0.0;                                      // lnl mode: this thread's share of the sum
-#ifdef FZ_EXPERIMENT
-  const unsigned long long fz_t0 = clock64();
-#endif
   if (tid >= FZ_DT) {
     // ============================ exchange wave ===============================
     // dispatched on the member index so every register array is statically indexed
@@ -891,9 +859,6 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       z.rc = make_uint4(0xFFFFFFFFu, 0, 0, 0); z.v0 = z.v1 = make_double2(0.0, 0.0); z.cd = make_uint2(0, 0);
       r0 = r1 = r2 = r3 = r4 = r5 = z;
     }
-#if FZ_GAP_STEPS == 2
-    FzRegs r6 = r0;
-#endif
     int64_t i = 0;
     // step i (lnl pass): `rs` is the set of block i-LAG (scattered, then refilled with block i+2); `rp` the set of block i
     auto step_lnl = [&](FzRegs& rs, FzRegs& rp) {
@@ -932,7 +897,7 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       // step has a floor of LDS instruction ISSUE (~22 wave-instructions per data wave, ~8 clk each even with every lane
       // masked, profiles/HISTORY.md 9.2); idle waves used to pay it in full.  (Wave-uniform branch around LDS operations only: the
       // streaming loads below stay unconditional.)
-      const bool wave_idle = FZ_SKIP_IDLE_WAVES && GEO >= 2 && !LAG &&   // (only the short-row geometry leaves whole waves idle; elsewhere the branch costs 1.5 %; MODE 4: it costs registers the log1p needs)
+      const bool wave_idle = GEO >= 2 && !LAG &&   // (only the short-row geometry leaves whole waves idle; elsewhere the branch costs 1.5 %; MODE 4: it costs registers the log1p needs)
                              (__builtin_amdgcn_ballot_w64(!idle) | __builtin_amdgcn_ballot_w64(!idle2)) == 0ull;
       if (wave_idle) {
         rp.rc.x = 0xFFFFFFFFu;
@@ -948,22 +913,12 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
       if (!SPA) { s0 = sb[a0 >> 16]; s1 = sb[a1 >> 16]; s2 = sb[a2 >> 16]; s3 = sb[a3 >> 16]; }
       double2 q0 = rp.v0, q1 = rp.v1;
-#ifdef FZ_EXPERIMENT   // upper bounds (WRONG RESULTS): what conflict-free LDS accesses would buy, per kind of access
-      const uint32_t xm_l = (A.dbg & 128) ? 3u : 0xFFFFu, xm_c = (A.dbg & 256) ? 31u : 0xFFFFu;
-#else
-      constexpr uint32_t xm_l = 0xFFFFu, xm_c = 0xFFFFu;
-#endif
       if (FMT == 1) {                                     // Q from the score table: the same fp64 the fp64 layout stores
-#ifdef FZ_X_NOLUT   // upper bound (WRONG RESULTS): the step without its four score-table gathers (a conversion on the VALU instead)
-        q0 = make_double2((double)(rp.cd.x & 0xFFFFu), (double)(rp.cd.x >> 16));
-        q1 = make_double2((double)(rp.cd.y & 0xFFFFu), (double)(rp.cd.y >> 16));
-#else
-        q0 = make_double2(lutS[rp.cd.x & xm_l], lutS[(rp.cd.x >> 16) & xm_l]);
-        q1 = make_double2(lutS[rp.cd.y & xm_l], lutS[(rp.cd.y >> 16) & xm_l]);
-#endif
+        q0 = make_double2(lutS[rp.cd.x & 0xFFFFu], lutS[rp.cd.x >> 16]);
+        q1 = make_double2(lutS[rp.cd.y & 0xFFFFu], lutS[rp.cd.y >> 16]);
       }
       double c0 = 1.0, c1 = 1.0, c2 = 1.0, c3 = 1.0;           // (MODE 7 scatters Q * s: the column's pi*theta is applied by k_colreduce)
-      if (!SPB) { c0 = c[rp.rc.x & xm_c]; c1 = c[rp.rc.y & xm_c]; c2 = c[rp.rc.z & xm_c]; c3 = c[rp.rc.w & xm_c]; }
+      if (!SPB) { c0 = c[rp.rc.x & 0xFFFF]; c1 = c[rp.rc.y & 0xFFFF]; c2 = c[rp.rc.z & 0xFFFF]; c3 = c[rp.rc.w & 0xFFFF]; }
       // ---- phase 1 of block i: numerators stay in the set, partial row sums into y(i) ----
       const double m0 = q0.x * c0, m1 = q0.y * c1, m2 = q1.x * c2, m3 = q1.y * c3;
       rp.v0 = make_double2(m0, m1); rp.v1 = make_double2(m2, m3);
@@ -985,14 +940,8 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       // ---- phase 2 of block i-LAG: w*z into the part's column accumulators; ALWAYS four atomics, issued last ----
       if (!SPA) {
         const uint32_t dj = (uint32_t)(dum - acc) + (uint32_t)lane_id;   // the lane's dummy slot as an index into acc[]
-#ifdef FZ_EXPERIMENT
-        const bool xa = (A.dbg & 512) != 0;                // every lane its own slot: no conflicts, no shared addresses
-        const uint32_t j0 = (idle2 | xa) ? dj : (a0 & 0xFFFFu), j1 = (idle2 | xa) ? dj : (a1 & 0xFFFFu);
-        const uint32_t j2 = (idle2 | xa) ? dj : (a2 & 0xFFFFu), j3 = (idle2 | xa) ? dj : (a3 & 0xFFFFu);
-#else
         const uint32_t j0 = idle2 ? dj : (a0 & 0xFFFFu), j1 = idle2 ? dj : (a1 & 0xFFFFu);
         const uint32_t j2 = idle2 ? dj : (a2 & 0xFFFFu), j3 = idle2 ? dj : (a3 & 0xFFFFu);
-#endif
         if (EXACT) {
           // Exact accumulation (Demmel-Nguyen style pre-rounding on a per-slot grid): v = hi + lo + rest with hi a multiple of
           // 2^(E-30) and lo a multiple of 2^(E-60); the sums of the hi pieces (and of the lo pieces) of up to 2^23 contributions
@@ -1039,7 +988,7 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
         // left alone, the compiler sinks the arithmetic below the barrier (nothing but `lsum` at the very end needs it), keeps the
         // twelve gathered values alive into the next step and spills the streaming loads' destinations
         auto term = [&](double q, double cp, double rf, double m) {
-          lsum = fma((q * cp) * rf, fz_log1p_tab<FZ_LAG_CERR != 0>(m, logtab), lsum);
+          lsum = fma((q * cp) * rf, fz_log1p_tab<false>(m, logtab), lsum);
           asm volatile("" : "+v"(lsum));
           __builtin_amdgcn_sched_barrier(0);
         };
@@ -1080,7 +1029,6 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
     };
     load_blk(r0, offs[0], offs[1], 0);
     load_blk(r1, offs[2], offs[3], 1);
-#if FZ_GAP_STEPS == 1
     static_assert(FZ_NS == 6 && FZ_LAG == 4 && FZ_DL == 2, "ring unrolling below assumes 6 sets");
     while (i < nsteps) {                                  // block k lives in set k % 6; (i-4) % 6 == (i+2) % 6
       step(r2, r0); if (i >= nsteps) break;               // i % 6 == 0
@@ -1090,18 +1038,6 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       step(r0, r4); if (i >= nsteps) break;
       step(r1, r5);
     }
-#else
-    static_assert(FZ_NS == 7 && FZ_LAG == 5 && FZ_DL == 2, "ring unrolling below assumes 7 sets");
-    while (i < nsteps) {                                  // block k lives in set k % 7; (i-5) % 7 == (i+2) % 7
-      step(r2, r0); if (i >= nsteps) break;               // i % 7 == 0
-      step(r3, r1); if (i >= nsteps) break;
-      step(r4, r2); if (i >= nsteps) break;
-      step(r5, r3); if (i >= nsteps) break;
-      step(r6, r4); if (i >= nsteps) break;
-      step(r0, r5); if (i >= nsteps) break;
-      step(r1, r6);
-    }
-#endif
   }
   __syncthreads();
   if (sprof) sprof[5] = wall_clock64();
@@ -1118,12 +1054,6 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
     if (LNL1 || SPL) return;
   }
   if (SPA) return;                                        // the row factors are in A.rinv; no column sums from this pass
-#ifdef FZ_EXPERIMENT
-  if ((A.dbg & 4096) && A.prof && tid == 0) {             // per-member loop time (cycles) and blocks: prof[(team*P+p)*2 ..]
-    A.prof[(team * P + p) * 2] = clock64() - fz_t0;
-    A.prof[(team * P + p) * 2 + 1] = (unsigned long long)nblk;
-  }
-#endif
   double* out = A.partial + (int64_t)team * (P * Kp) + p * Kp;
   for (int t = tid; t < Kp; t += FZ_NT) out[t] = acc[t];
   if (MODE == 3) {

@@ -2,10 +2,5 @@
 #include "tsem_fused_inst.h"
 
 fz_fn tsem_fz_kernel_p7(int P, int mode, int fmt, int geo) {
-#ifdef TSEM_FAST_BUILD                                     // kernel experiments (tools/ab.sh): teams of 4 only
-  (void)P; (void)mode; (void)fmt; (void)geo;
-  return nullptr;
-#else
   return P == 7 ? fz_pick<7>(mode, fmt, geo) : nullptr;
-#endif
 }

@@ -182,7 +182,10 @@ int tsem_set_option(tsem_ctx* h, const char* key, int64_t v) {
   else if (k == "parts") h->opt_P = v;
   else if (k == "row_offset") h->row_offset = v;
   else if (k == "chunk_blocks") h->opt_chunk = v;
-  else if (k == "fused_dbg") h->opt_dbg = v;
+  else if (k == "fused_dbg") {                             // test hooks: 32 / 64 a hand-off time-out of the EM / lnl pass, 8192 / 16384 / 32768 a form of the lnl pass
+    if (v & ~(int64_t)(32 | 64 | 8192 | 16384 | 32768)) TSEM_FAIL(TSEM_ERR_ARG, "fused_dbg takes the bits 32, 64, 8192, 16384 and 32768 only");
+    h->opt_dbg = v;
+  }
   else if (k == "split") h->opt_split = v;
   else if (k == "value_format") h->opt_format = v;
   else if (k == "hot_split") h->opt_hot_split = v;

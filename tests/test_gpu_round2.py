@@ -214,6 +214,20 @@ def test_timeout_in_the_stepwise_api_leaves_parameters_untouched(gpu_device):
     assert np.allclose(eng.get_params(_lib.Z_CUR)[0], good._eng.get_params(_lib.Z_CUR)[0], rtol=1e-10, atol=0)
 
 
+def test_fused_dbg_takes_only_the_test_hook_bits(gpu_device):
+    """fused_dbg keeps the test hooks only: the time-out bits 32 / 64 and the lnl-form bits 8192 / 16384 / 32768.  The bits of the
+    removed timing experiments, which made the kernel return wrong sums, are refused."""
+    from telescope_amd import _lib
+    eng = _lib.Engine(0)
+    for bit in (1, 8, 16, 128, 256, 512, 1024, 2048, 4096):
+        with pytest.raises(_lib.EngineError) as ei:
+            eng.set_option('fused_dbg', bit)
+        assert ei.value.code == _lib.ERR_ARG
+    for bit in (32, 64, 8192, 16384, 32768):
+        eng.set_option('fused_dbg', bit)
+    eng.set_option('fused_dbg', 0)
+
+
 def test_two_engines_on_two_streams(gpu_device):
     """two handles on two streams of one GPU.  Their persistent kernels cannot both be
     resident; whichever way the hardware schedules them (one after the other, or a time-out followed by the

@@ -345,6 +345,22 @@ int  tsem_legacy_randint(uint32_t* key624, int32_t* pos, const int32_t* counts, 
 int  tsem_set_groups(tsem_ctx* h, const int32_t* group_of_row /* N, or NULL to drop */, int32_t n_groups);
 int  tsem_reassign_groups(tsem_ctx* h, int method, double thresh, int which, const int32_t* picks,
                           const int32_t* group_of_row /* N, or NULL: the map of tsem_set_groups */, int32_t n_groups, double* out);
+/* Per-barcode counts at droplet scale (model.py:611-625), where the dense n_groups x K matrix above is almost all zeros:
+ * reassign(method, thresh, which)[rows of group g, :].sum(0) for every group g of the row -> group map set with
+ * tsem_set_groups (a partition: each row in at most one group, -1 = none), as a SPARSE matrix kept on the device;
+ * *nnz = its stored entries.  Rows of a group are taken in ascending row order.  picks: as tsem_reassign_groups.
+ * Every (group, column) is added in ascending row order starting from 0 — what scipy's csr[rows].sum(0) does — so the
+ * result is bit-identical to summing tsem_reassign's matrix with scipy, for every method, and deterministic.  No global
+ * atomics: the entries of a tile of groups (option "group_tile_bytes" of device scratch for the tile's buffers, default 1 GB; the
+ * grouping cached per map, 16 B per row, the picks and the result are outside it) are sorted by
+ * (group, column) and one lane adds each (group, column)'s values; a (group, column) that holds a large share of the
+ * matrix's rows therefore runs at one lane's speed (real barcodes never do).  Single GPU only: a handle with a
+ * communicator attached is refused. */
+int  tsem_group_counts(tsem_ctx* h, int method, double thresh, int which, const int32_t* picks, int64_t* nnz);
+/* copy the last result out: group_ptr[n_groups + 1] (int64), cols[nnz] ascending within a group, vals[nnz] (fp64) */
+int  tsem_group_counts_copy(tsem_ctx* h, int64_t* group_ptr, int32_t* cols, double* vals);
+/* the last result's number of groups and stored entries: what the arrays of tsem_group_counts_copy must hold */
+int  tsem_group_counts_shape(tsem_ctx* h, int32_t* n_groups, int64_t* nnz);
 
 /* ---- csr_matrix_plus primitives on arbitrary fp64 CSR (sparse_plus.py) ---- */
 int  tsem_csr_norm_rows(int device, int64_t n_rows, const int64_t* indptr,

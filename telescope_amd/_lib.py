@@ -27,7 +27,7 @@ class EngineError(RuntimeError):
 
 
 # host / ABI, set-up, EM support, report / row passes, collectives, CSR primitives (telescope_amd/csrc/tsem_internal.h)
-LIB_UNITS = ('tsem_host', 'tsem_setup', 'tsem_em', 'tsem_report', 'tsem_comm', 'tsem_csr')
+LIB_UNITS = ('tsem_host', 'tsem_setup', 'tsem_em', 'tsem_report', 'tsem_comm', 'tsem_csr', 'tsem_cells')
 FZ_UNITS = tuple('tsem_fz_p%d' % p for p in range(1, 9))
 
 
@@ -218,6 +218,9 @@ def lib():
     L.tsem_rows_lookup.argtypes = [vp, C.c_int, C.c_int, dbl, i64, vp, vp, vp, vp, vp]
     L.tsem_reassign_groups.argtypes = [vp, C.c_int, dbl, C.c_int, vp, vp, C.c_int32, vp]
     L.tsem_set_groups.argtypes = [vp, vp, C.c_int32]
+    L.tsem_group_counts.argtypes = [vp, C.c_int, dbl, C.c_int, vp, C.POINTER(i64)]
+    L.tsem_group_counts_copy.argtypes = [vp, vp, vp, vp]
+    L.tsem_group_counts_shape.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
     L.tsem_csr_norm_rows.argtypes = [C.c_int, i64, vp, vp, vp]
     L.tsem_csr_binmax_rows.argtypes = [C.c_int, i64, i32, vp, vp, vp]
     L.tsem_csr_scale.argtypes = [C.c_int, C.c_int, i64, i32, vp, vp, vp]
@@ -573,6 +576,22 @@ class Engine(object):
         self._ck(self._L.tsem_reassign_groups(self._h, RA_CODE[method], float(thresh), which, ptr(picks), ptr(grp),
                                               int(n_groups), ptr(out)))
         return out
+
+    def group_counts(self, method, thresh, which, picks=None):
+        """Sparse per-group sums of the assignment over the map of `set_groups` (tsem_group_counts): (group_ptr int64 [n_groups + 1],
+        cols int32 [nnz], vals float64 [nnz]) — a CSR matrix with columns ascending within a group."""
+        n, _, _ = self.dims()
+        if picks is not None:
+            picks = np.ascontiguousarray(picks, dtype=np.int32)
+            if picks.shape != (n,):
+                raise ValueError('picks must have one entry per row')
+        nnz, n_groups = C.c_int64(), C.c_int32()
+        self._ck(self._L.tsem_group_counts(self._h, RA_CODE[method], float(thresh), which, ptr(picks), C.byref(nnz)))
+        self._ck(self._L.tsem_group_counts_shape(self._h, C.byref(n_groups), C.byref(nnz)))   # (the arrays are sized by the library)
+        gptr = np.empty(n_groups.value + 1, np.int64)
+        cols, vals = np.empty(nnz.value, np.int32), np.empty(nnz.value)
+        self._ck(self._L.tsem_group_counts_copy(self._h, ptr(gptr), ptr(cols), ptr(vals)))
+        return gptr, cols, vals
 
     # -- instrumentation --
     def kernel_stats(self, reset=False):

@@ -6,6 +6,12 @@ telescope/__main__.py:49-92).  Same option names and defaults, same log lines, s
 
     python -m telescope_amd assign <alignments.bam> <annotation.gtf> [...]
 
+    python -m telescope_amd sc assign <alignments.bam> <annotation.gtf> [--barcode_tag CB] [--use_every_reassign_mode] [...]
+    python -m telescope_amd sc resume <checkpoint.npz> [...]
+
+`sc` is single-cell mode (scTelescope, telescope/utils/model.py:567-629; scIDOptions, telescope_assign.py:203-370): per-barcode
+count matrices, built sparse on the device (`<exp_tag>-TE_counts[_<method>].tsv`, or `.mtx` with `--count_format mtx`).
+
 `assign` (telescope/telescope_assign.py:372-451) uses telescope_amd/loader.py, a pysam-free
 restatement of the reference's sequential loader; `--updated_sam` and `--ncpu > 1` are not offered.
 """
@@ -27,7 +33,16 @@ def format_minutes(seconds):
 def build_parser():
     ap = argparse.ArgumentParser(prog='telescope', description='Telescope EM reassignment on MI355X')
     sub = ap.add_subparsers(dest='command')
-    rs = sub.add_parser('resume', help='Resume from a checkpoint: EM + reports')
+    _resume_args(sub.add_parser('resume', help='Resume from a checkpoint: EM + reports'))
+    _assign_args(sub.add_parser('assign', help='Load alignments + annotation, checkpoint, EM, reports'))
+    sc = sub.add_parser('sc', help='Single-cell mode: per-barcode count matrices (scTelescope)')
+    scsub = sc.add_subparsers(dest='sc_command')
+    _sc_args(_assign_args(scsub.add_parser('assign', help='Load alignments (with cell barcodes) + annotation, checkpoint, EM, reports')), True)
+    _sc_args(_resume_args(scsub.add_parser('resume', help='Resume from a single-cell checkpoint: EM + reports')), False)
+    return ap
+
+
+def _resume_args(rs):
     g = rs.add_argument_group('Input Options')
     g.add_argument('checkpoint', help='Path to checkpoint file.')
     g = rs.add_argument_group('Reporting Options')
@@ -55,7 +70,10 @@ def build_parser():
     g.add_argument('--device', type=int, default=0, help='GPU index (single-process runs).')
     g.add_argument('--reproducible', action='store_true',
                    help='Exact, order-independent sums on the device: the same bits in every run (1.6-2.5x the time per EM iteration).')
-    asg = sub.add_parser('assign', help='Load alignments + annotation, checkpoint, EM, reports')
+    return rs
+
+
+def _assign_args(asg):
     g = asg.add_argument_group('Input Options')
     g.add_argument('samfile', help='Path to alignment file (BAM, collated by read name).  Read by a streaming '
                                    'pure-Python BAM parser (~50-100 k records/s, memory independent of the file size): '
@@ -98,7 +116,26 @@ def build_parser():
     g.add_argument('--device', type=int, default=0, help='GPU index (single-process runs).')
     g.add_argument('--reproducible', action='store_true',
                    help='Exact, order-independent sums on the device: the same bits in every run (1.6-2.5x the time per EM iteration).')
-    return ap
+    return asg
+
+
+def _sc_args(p, assign):
+    """The options scIDOptions adds to the bulk ones (telescope_assign.py:203-370), and the output format of the counts."""
+    groups = {g.title: g for g in p._action_groups}
+    if assign:
+        groups['Input Options'].add_argument('--barcode_tag', type=str, default='CB',
+                                             help='Name of the field in the BAM/SAM file containing the barcode for each read.')
+        groups['Input Options'].add_argument('--tempdir', help='(accepted for compatibility; no temporary files are written)')
+        groups['Run Modes'].add_argument('--annotation_class', default='intervaltree', choices=['intervaltree', 'htseq'],
+                                         help='(accepted for compatibility; the annotation is indexed by this engine)')
+    g = groups['Run Modes']
+    g.add_argument('--use_every_reassign_mode', action='store_true',
+                   help='Output count matrices generated using every reassign mode (conf, all, unique, exclude, choose, average).')
+    g = groups['Reporting Options']
+    g.add_argument('--count_format', default='tsv', choices=['tsv', 'mtx'],
+                   help='tsv: the dense cells x features table the reference writes; mtx: Matrix Market (cells x features) with '
+                        '-barcodes.tsv and -features.tsv beside it.')
+    return p
 
 
 class ResumeOptions(object):
@@ -193,19 +230,31 @@ def finish(comm):
         dist.destroy_process_group()
 
 
-def run_resume(args):
-    """telescope_resume.py:183-232."""
+def _refuse_sharded_sc(sc):
+    if sc and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise SystemExit('telescope sc: row-sharded runs (WORLD_SIZE > 1) are not supported; run single-cell assignment on one GPU')
+
+
+def run_resume(args, sc=False):
+    """telescope_resume.py:183-232.  sc=True: `sc resume` — a single-cell checkpoint (scTelescope) and its per-cell reports."""
+    _refuse_sharded_sc(sc)
     opts = ResumeOptions(args)
     configure_logging(opts)
     warm = None if opts.skip_em else warm_device(opts)       # (before the heavy imports below: they run while the device comes up)
     from .likelihood import TelescopeLikelihood
-    from .run_container import Telescope
+    from .run_container import Telescope, scTelescope
     lg.info('\n{}\n'.format(opts))
     total_time = time()
     lg.info('Loading Telescope object from file...')
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     # a rank of a row-sharded launch reads its own fragments only (VERDICT r4 missing #4: every rank used to read the whole file)
-    ts = Telescope.load_shard(opts.checkpoint, world, rank) if world > 1 else Telescope.load(opts.checkpoint)
+    if sc:
+        try:
+            ts = scTelescope.load(opts.checkpoint)
+        except ValueError as e:
+            raise SystemExit('telescope sc resume: %s' % e)
+    else:
+        ts = Telescope.load_shard(opts.checkpoint, world, rank) if world > 1 else Telescope.load(opts.checkpoint)
     ts.opts = opts
     ts.print_summary(lg.INFO)
     if opts.skip_em:
@@ -230,10 +279,11 @@ def run_resume(args):
     return 0
 
 
-def run_assign(args):
+def run_assign(args, sc=False):
     """telescope_assign.py:372-451.  Row-sharded (`torch.distributed.run ... -m telescope_amd assign`): rank 0 alone parses the
     annotation and the alignments and writes the checkpoint; the other ranks wait for it and read THEIR fragments from the file
     (Telescope.load_shard) — one BAM parse and one whole matrix in host memory per job, not per rank."""
+    _refuse_sharded_sc(sc)
     opts = ResumeOptions(args)
     configure_logging(opts)
     if opts.updated_sam or opts.ncpu != 1:
@@ -241,7 +291,7 @@ def run_assign(args):
     warm = None if opts.skip_em else warm_device(opts)       # (the device comes up while the BAM is parsed)
     from .likelihood import TelescopeLikelihood
     from .loader import Annotation
-    from .run_container import Telescope
+    from .run_container import Telescope, scTelescope
     lg.info('\n{}\n'.format(opts))
     total_time = time()
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
@@ -252,7 +302,7 @@ def run_assign(args):
     ts, status, failure = None, 0, None                      # status 1: nothing overlaps the annotation; 2: rank 0 failed (every rank must learn it)
     if rank == 0:
         try:
-            ts = Telescope(opts)
+            ts = scTelescope(opts) if sc else Telescope(opts)
             ts.run_info['version'] = opts.version
             lg.info('Loading annotation...')
             stime = time()
@@ -330,6 +380,10 @@ def main(argv=None):
         return run_resume(args)
     if args.command == 'assign':
         return run_assign(args)
+    if args.command == 'sc' and args.sc_command == 'resume':
+        return run_resume(args, sc=True)
+    if args.command == 'sc' and args.sc_command == 'assign':
+        return run_assign(args, sc=True)
     ap.print_help()
     return 2
 

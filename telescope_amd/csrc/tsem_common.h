@@ -202,6 +202,19 @@ struct tsem_ctx {
   int32_t n_groups = 0;
   void* d_gtile = nullptr; size_t gtile_bytes = 0;   // one tile of per-group sums (by column | by id), kept between calls
   int64_t opt_group_tile = 0;       // bytes of per-group output computed per pass over the matrix (0 = 1 GB)
+  // sparse per-group counts (tsem_group_counts, tsem_cells.hip): the group map's rows in group order, cached per map, and the last result
+  uint64_t groups_version = 0;      // bumped by every tsem_set_groups
+  uint64_t gc_version = ~0ull;      // the map version the cached grouping below was built from
+  uint32_t* d_gc_key = nullptr;     // [N] group of the i-th row in group order (n_groups: the rows in no group, last)
+  int32_t* d_gc_rows = nullptr;     // [N] the rows in group order, ascending within a group
+  int64_t* d_gc_eoff = nullptr;     // [N + 1] where the i-th row's entries start in group order
+  std::vector<int64_t> gc_rptr;     // host [n_groups + 1]: first row of every group in d_gc_rows
+  std::vector<int64_t> gc_gent;     // host [n_groups + 1]: first entry of every group (d_gc_eoff at gc_rptr)
+  int32_t gc_groups = 0;            // groups of the last result
+  int64_t gc_nnz = 0, gc_cap = 0;   // stored entries of the last result / capacity of its arrays
+  int32_t *d_gc_ogrp = nullptr, *d_gc_ocol = nullptr;   // [gc_cap] the last result: group, column, value per stored entry
+  double* d_gc_oval = nullptr;
+  int64_t* d_gc_gptr = nullptr;     // [gc_groups + 1] the last result's group pointer
   int32_t *d_rep_nb = nullptr, *d_rep_rows = nullptr;   // [N] scratch of tsem_report_colsums, kept between calls
   unsigned long long* d_rep_n = nullptr;
   struct RpChunk* d_rep_chunks = nullptr; int64_t n_rep_chunks = 0; int rep_chunk_E = 0;   // k_report_pack's packing of the rows into wave-sized chunks (tsem_report_pack.h)

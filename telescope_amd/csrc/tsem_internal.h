@@ -178,6 +178,11 @@ int tsem_twopass_attributes(tsem_ctx* h);                 // dynamic-LDS limits 
 int tsem_sum_parts(tsem_ctx* h, const double* a, int na, const double* b, int nb, double* out);   // out[0] = sum a + sum b, fixed order
 // tsem_report.hip
 int tsem_rowpass_grid(tsem_ctx* h);
+// reassign(method)[row, :] of a DEVICE row list into mask[off[i] ...] (the row pass of tsem_rows_lookup, no host copies; d_picks[i]
+// belongs to list row i).  It leaves the CSR column ids resident: the caller ends with tsem_redrop_indices once it has read them.
+int tsem_rows_mask_dev(tsem_ctx* h, int which, int method, double thresh, int64_t n, const int32_t* d_rows, const int32_t* d_picks,
+                       const int64_t* d_off, double* d_mask);
+void tsem_redrop_indices(tsem_ctx* h);
 // tsem_comm.hip
 bool tsem_comm_on(const tsem_ctx* h);
 int tsem_comm_allreduce_dev(tsem_comm* c, void* buf, size_t count, int dtype, hipStream_t s, std::string& err);

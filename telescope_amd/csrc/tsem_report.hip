@@ -1797,11 +1797,24 @@ int tsem_rows_lookup(tsem_ctx* h, int which, int method, double thresh, int64_t 
   return TSEM_OK;
 }
 
+int tsem_rows_mask_dev(tsem_ctx* h, int which, int method, double thresh, int64_t n, const int32_t* d_rows, const int32_t* d_picks,
+                       const int64_t* d_off, double* d_mask) {
+  if (n <= 0) return TSEM_OK;
+  RowPassArgs A;
+  if (int rc = rowpass_args(h, which, A)) return rc;
+  A.rowlist = d_rows; A.nlist = n; A.out_off = d_off;
+  A.zout = d_mask; A.method = method; A.thresh = thresh; A.picks = d_picks; A.colsums = nullptr;
+  if (int rc = with_indices(h, A)) return rc;
+  return launch_rowpass(h, RP_REASSIGN, -1, list_grid(n), 256, (size_t)A.lut_len * 8, A);
+}
+void tsem_redrop_indices(tsem_ctx* h) { redrop_indices(h); }
+
 // The row -> group map of the per-group sums (tsem_reassign_groups): copied to the device ONCE and kept until the next call / the
 // next matrix (-1 = the row belongs to no group); range-checked on the device.  group_of_row == NULL drops it.
 int tsem_set_groups(tsem_ctx* h, const int32_t* group_of_row, int32_t n_groups) {
   if (!h || !h->d_indptr || n_groups < 0) return TSEM_ERR_ARG;
   if (int rc = ensure_device(h)) return rc;
+  ++h->groups_version;                                     // (the grouping of tsem_group_counts follows the map)
   if (!group_of_row) { dfree(h->d_group); h->n_groups = 0; return TSEM_OK; }
   TSEM_ALLOC(h->d_group, h->N);
   h->n_groups = 0;

@@ -541,6 +541,33 @@ class TelescopeLikelihood(object):
             out = np.rint(out).astype(np.int64)
         return out
 
+    def reassign_cell_counts(self, method, cell_of_row, n_cells, thresh=0.9, initial=False):
+        """Per-cell count matrix of single-cell assignment (scTelescope.output_report, model.py:611-625) as a scipy CSR matrix
+        (n_cells x K, float64): row c is `reassign(method, thresh, initial)[rows with cell_of_row == c, :].sum(0)`, every column added
+        in ascending row order like scipy adds it — bit-identical to summing the device's own `reassign` matrix.  `cell_of_row[i]` in
+        [0, n_cells) or -1 (a row in no cell).  Built sparse on the device (tsem_group_counts); `choose` draws its picks like
+        `reassign('choose')`.  The map goes to the device once per content and serves every method asked of it.  One GPU only."""
+        import hashlib
+        if method not in REASSIGN_METHODS:
+            raise ValueError('Argument "method" should be one of (exclude, choose, average, conf, unique, all)')
+        if self.comm.world > 1:
+            raise NotImplementedError('reassign_cell_counts: row-sharded runs (WORLD_SIZE > 1) are not supported; run single-cell '
+                                      'assignment on one GPU')
+        cor = np.ascontiguousarray(cell_of_row, dtype=np.int32)
+        n_cells = int(n_cells)
+        if cor.shape != (self.N,):
+            raise ValueError('cell_of_row must have one entry per row')
+        if cor.size and (cor.min() < -1 or cor.max() >= n_cells):
+            raise ValueError('cell_of_row entries must lie in [-1, n_cells)')
+        which = self._which(initial)
+        picks = self._picks(which) if method == 'choose' else None
+        key = ('cells', hashlib.blake2b(cor.tobytes(), digest_size=16).hexdigest(), n_cells)
+        if getattr(self._eng, 'groups_token', None) != key:
+            self._eng.set_groups(cor, n_cells)
+            self._eng.groups_token = key
+        gptr, cols, vals = self._eng.group_counts(method, thresh, which, self._dense_picks(picks))
+        return sp.csr_matrix((vals, cols, gptr), shape=(n_cells, self.K))
+
     def _group_layers(self, group_rows, token=None):
         """Row -> group maps for `reassign_group_sums`, one per LAYER: within a layer every row belongs to at most one group; the
         k-th listing of a row (over all groups, duplicates inside a group included) goes to layer k.  Built once per grouping

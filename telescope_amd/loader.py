@@ -19,7 +19,8 @@ Host-side restatement of the reference's SEQUENTIAL loader so that
 This is loader glue, not the accelerated path: plain Python, BAM only (BGZF is a
 sequence of gzip members, so the stdlib `gzip` module reads it), name-collated
 input as the reference requires.  Not covered: `--updated_sam` BAM rewriting,
-`--ncpu > 1` (broken at the reference's HEAD), single-cell barcodes.
+`--ncpu > 1` (broken at the reference's HEAD).  Single-cell barcodes (scTelescope, model.py:245-247,311-316):
+`load_alignment(..., barcode_tag='CB')` keeps one Z-type tag of every mapped fragment's first read.
 
 Size: the BAM is STREAMED (one record at a time through a buffered gzip reader: memory does not grow with
 the file), the mappings are kept as four compact integer arrays (16 B per (fragment, locus) hit, like the
@@ -43,7 +44,7 @@ _B_SIZE = {'c': 1, 'C': 1, 's': 2, 'S': 2, 'i': 4, 'I': 4, 'f': 4}
 
 
 class Segment(object):
-    __slots__ = ('qname', 'flag', 'ref_id', 'pos', 'nref', 'npos', 'tlen', 'cigar', 'AS')
+    __slots__ = ('qname', 'flag', 'ref_id', 'pos', 'nref', 'npos', 'tlen', 'cigar', 'AS', 'bc')
 
     @property
     def is_paired(self): return bool(self.flag & 0x1)
@@ -68,8 +69,10 @@ class Segment(object):
         return out
 
 
-def read_bam(path):
-    """-> (reference names, iterator of Segment) from a BAM file, streamed."""
+def read_bam(path, barcode_tag=None):
+    """-> (reference names, iterator of Segment) from a BAM file, streamed.  `barcode_tag` (e.g. 'CB'): the value of that Z-type
+    tag goes to Segment.bc (None where the record has no such tag)."""
+    btag = barcode_tag.encode() if barcode_tag else None
     fh = io.BufferedReader(gzip.open(path, 'rb'), buffer_size=1 << 20)
 
     def need(n):
@@ -106,7 +109,7 @@ def read_bam(path):
                 s.qname = buf[p:p + l_rn - 1].decode(); p += l_rn
                 s.cigar = struct.unpack_from('<%dI' % n_cig, buf, p); p += 4 * n_cig
                 p += (l_seq + 1) // 2 + l_seq
-                s.AS = None
+                s.AS = s.bc = None
                 while p < bs:
                     tag = buf[p:p + 2]; typ = chr(buf[p + 2]); p += 3
                     if typ in _TAG_FMT:
@@ -117,7 +120,10 @@ def read_bam(path):
                     elif typ == 'A':
                         p += 1
                     elif typ in 'ZH':
-                        p = buf.index(b'\x00', p) + 1
+                        end = buf.index(b'\x00', p)
+                        if typ == 'Z' and tag == btag:
+                            s.bc = buf[p:end].decode()
+                        p = end + 1
                     elif typ == 'B':
                         sub = chr(buf[p]); (cnt,) = struct.unpack_from('<i', buf, p + 1)
                         p += 5 + cnt * _B_SIZE[sub]
@@ -260,12 +266,16 @@ CODE_DESC = OrderedDict([('SU', 'single_unmapped'), ('SM', 'single_mapped'), ('P
 
 
 def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_mode='threshold',
-                   overlap_threshold=0.2, stranded_mode='None'):
-    """-> dict(raw_scores uint16 CSR, read_index, feat_index, feature_length, run_info fields)."""
+                   overlap_threshold=0.2, stranded_mode='None', barcode_tag=None):
+    """-> dict(raw_scores uint16 CSR, read_index, feat_index, feature_length, run_info fields).  With `barcode_tag` (scTelescope,
+    model.py:245-247,311-316) also cell_of_row (int32 per row, -1 = no barcode) and barcodes (the cell names): the tag is read from
+    the first read of every mapped fragment; only fragments that become rows count; cells are ordered by the first appearance of
+    their barcode in BAM order among those fragments."""
     if overlap_mode != 'threshold':
         raise NotImplementedError('only overlap_mode "threshold" is implemented (as in the reference, '
                                   'model.py:899-903)')
-    refs, records = read_bam(samfile)
+    refs, records = read_bam(samfile, barcode_tag)
+    read_bc = {}                                         # fragment name -> barcode, in BAM order (model.py:245-247)
 
     def assign(pair):
         if pair.r1.is_reverse:
@@ -289,6 +299,8 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
         info[code] += 1
         if code in ('SU', 'PU'):
             continue
+        if barcode_tag and alns[0].r1.bc is not None:
+            read_bc[alns[0].r1.qname] = alns[0].r1.bc
         mapped = [a for a in alns if not a.is_unmapped]
         ambig = len(mapped) > 1
         for a in mapped:
@@ -348,6 +360,18 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
         info[desc] = info[cs]
     fields = ['total_fragments', 'pair_mapped', 'pair_mixed', 'single_mapped', 'unmapped', 'unique',
               'ambig', 'overlap_unique', 'overlap_ambig']
-    return dict(raw_scores=raw, read_index={names[int(old)]: new for new, old in enumerate(keep)},
-                feat_index=dict(fidx), feature_length=annotation.feature_length(),
-                run_info=OrderedDict((f, info[f]) for f in fields), score_range=(min_as, max_as))
+    out = dict(raw_scores=raw, read_index={names[int(old)]: new for new, old in enumerate(keep)},
+               feat_index=dict(fidx), feature_length=annotation.feature_length(),
+               run_info=OrderedDict((f, info[f]) for f in fields), score_range=(min_as, max_as))
+    if barcode_tag:
+        # model.py:311-316: barcodes -> rows, for the fragments that are rows (post-trim ids; the sequential loader never makes a row
+        # of a fragment that hits only `__no_feature`, so the reference's pre-trim map holds the same fragments)
+        cell_of_row = np.full(keep.size, -1, dtype=np.int32)
+        cells = OrderedDict()
+        for rid, bc in read_bc.items():
+            old = ridx.get(rid)
+            if old is None or remap[old] < 0:
+                continue
+            cell_of_row[remap[old]] = cells.setdefault(bc, len(cells))
+        out['cell_of_row'], out['barcodes'] = cell_of_row, list(cells)
+    return out

@@ -246,3 +246,144 @@ class Telescope(object):
             stats.to_csv(fh, sep='\t', index=False)
         with open(counts_filename, 'w') as fh:
             counts.to_csv(fh, sep='\t', index=False)
+
+
+# ---- single-cell mode (scTelescope, model.py:567-629) -----------------------------------------------------------------------------
+SC_METHODS = ('conf', 'all', 'unique', 'exclude', 'choose', 'average')   # model.py:618: the order fixes when `choose` draws
+
+
+def _float_repr(v):
+    return repr(float(v))
+
+
+def write_dense_counts(fh, csr, barcodes, features, block=None):
+    """`pd.DataFrame(csr.todense(), columns=features, index=barcodes).to_csv(fh, sep='\t')` (model.py:626-629), byte for byte, streamed
+    from the CSR: no dense array is built — a line starts as K copies of `0.0` and only the stored entries are formatted (repr, as
+    pandas writes float64: `3.0`, `0.3333333333333333`).  Lines go out in blocks of `block` cells (default: ~32 MB of text each)."""
+    csr = sp.csr_matrix(csr)
+    csr.sort_indices()
+    n_cells, k = csr.shape
+    if len(barcodes) != n_cells or len(features) != k:
+        raise ValueError('write_dense_counts: %d barcodes / %d features for a %s matrix' % (len(barcodes), len(features), csr.shape))
+    if block is None:
+        block = max(1, (32 << 20) // (4 * max(k, 1)))
+    fh.write('\t'.join([''] + [_csv_field(f) for f in features]) + '\n')
+    zeros = ['0.0'] * k
+    ip, ix, dv = csr.indptr, csr.indices, csr.data
+    for c0 in range(0, n_cells, block):
+        out = []
+        for c in range(c0, min(n_cells, c0 + block)):
+            vals = list(zeros)
+            for j, v in zip(ix[ip[c]:ip[c + 1]].tolist(), dv[ip[c]:ip[c + 1]].tolist()):
+                vals[j] = repr(v)
+            out.append(_csv_field(barcodes[c]) + '\t' + '\t'.join(vals) + '\n')
+        fh.write(''.join(out))
+
+
+def _csv_field(s):
+    """a field as pandas' csv writer quotes it with sep='\\t' (QUOTE_MINIMAL)"""
+    s = str(s)
+    if any(ch in s for ch in ('\t', '"', '\n', '\r')):
+        return '"' + s.replace('"', '""') + '"'
+    return s
+
+
+def write_mtx_counts(mtx_path, csr, barcodes, features):
+    """Matrix Market (cells x features, real general, full precision) at `mtx_path`; `<stem>-barcodes.tsv` and `<stem>-features.tsv`
+    beside it (one name per line), where <stem> is the path up to `-TE_counts`."""
+    import scipy.io
+    scipy.io.mmwrite(mtx_path, sp.coo_matrix(csr), field='real', precision=17)
+    cut = mtx_path.rfind('-TE_counts')
+    stem = mtx_path[:cut] if cut >= 0 else mtx_path[:mtx_path.rfind('.')]
+    for suffix, names in (('-barcodes.tsv', barcodes), ('-features.tsv', features)):
+        with open(stem + suffix, 'w') as fh:
+            fh.writelines('%s\n' % n for n in names)
+
+
+class scTelescope(Telescope):
+    """Single-cell run container: the bulk container plus the cell of every fragment (`cell_of_row`, -1 = no barcode) and the cell
+    names in first-appearance order (`barcodes`) — what the reference keeps as `barcode_read_indices` (model.py:311-316)."""
+
+    def __init__(self, opts=None):
+        super().__init__(opts)
+        self.cell_of_row = None
+        self.barcodes = []
+
+    def load_alignment(self, annotation):
+        from . import loader
+        o = self.opts
+        self.run_info['annotated_features'] = len(annotation.loci)
+        r = loader.load_alignment(o.samfile, annotation, o.no_feature_key, o.overlap_mode, o.overlap_threshold, o.stranded_mode,
+                                  barcode_tag=o.barcode_tag)
+        self.feature_length = r['feature_length']
+        self.read_index, self.feat_index = r['read_index'], r['feat_index']
+        self.raw_scores = r['raw_scores']
+        self.shape = self.raw_scores.shape
+        for k, v in r['run_info'].items():
+            self.run_info[k] = v
+        self.cell_of_row, self.barcodes = r['cell_of_row'], r['barcodes']
+
+    def save(self, filename):
+        """The bulk checkpoint's keys, byte for byte, plus `_barcode_list` (unicode, cell order) and `_read_barcode` (int32 per row,
+        -1 = none).  The bulk `load` and the reference's `Telescope.load` read named keys only and ignore them."""
+        feats = sorted(self.feat_index, key=self.feat_index.get)
+        raw = sp.csr_matrix(self.raw_scores)
+        np.savez(filename,
+                 _run_info=list(self.run_info.items()),
+                 _flen_list=[self.feature_length[f] for f in feats],
+                 _feat_list=feats,
+                 _read_list=sorted(self.read_index, key=self.read_index.get),
+                 _shape=self.shape,
+                 _raw_scores_data=raw.data, _raw_scores_indices=raw.indices,
+                 _raw_scores_indptr=raw.indptr, _raw_scores_shape=raw.shape,
+                 _barcode_list=np.array(list(self.barcodes), dtype=np.str_),
+                 _read_barcode=np.asarray(self.cell_of_row, dtype=np.int32))
+
+    @classmethod
+    def load(cls, filename):
+        obj = super(scTelescope, cls).load(filename)
+        z = np.load(filename)
+        if '_barcode_list' not in z.files or '_read_barcode' not in z.files:
+            raise ValueError('%s is not a single-cell checkpoint (no _barcode_list / _read_barcode): write one with '
+                             '`sc assign`' % filename)
+        obj.barcodes = [str(b) for b in z['_barcode_list']]
+        obj.cell_of_row = np.asarray(z['_read_barcode'], dtype=np.int32)
+        if obj.cell_of_row.shape != (obj.shape[0],) or (obj.cell_of_row.size and obj.cell_of_row.max() >= len(obj.barcodes)):
+            raise ValueError('%s: _read_barcode does not match the matrix / _barcode_list' % filename)
+        return obj
+
+    def output_report(self, tl, stats_filename, counts_filename, write=True):
+        """model.py:575-629: the stats TSV (transcript, transcript_length, final_prop, init_prop; sorted by final_prop, rounded; the
+        RunInfo line ENDS with a newline here) and one per-cell count matrix per method asked — `--reassign_mode`, or all six with
+        `--use_every_reassign_mode` (`<exp_tag>-TE_counts_<method>.tsv`, in the order conf, all, unique, exclude, choose, average).
+        The matrices are built sparse on the device (reassign_cell_counts) and written streamed (tsv) or as Matrix Market (mtx)."""
+        mode, prob = self.opts.reassign_mode, self.opts.conf_prob
+        every = bool(getattr(self.opts, 'use_every_reassign_mode', False))
+        fmt = getattr(self.opts, 'count_format', 'tsv')
+        names = sorted(self.feat_index, key=self.feat_index.get)
+        stats = pd.DataFrame(OrderedDict([
+            ('transcript', names),
+            ('transcript_length', [self.feature_length[f] for f in names]),
+            ('final_prop', tl.pi),
+            ('init_prop', tl.pi_init),
+        ]))
+        stats.sort_values('final_prop', ascending=False, inplace=True)
+        stats = stats.round(pd.Series([2, 3, 2, 3], index=['final_conf', 'final_prop', 'init_best_avg', 'init_prop']))
+        if write:
+            comment = ['## RunInfo'] + ['{}:{}'.format(k, v) for k, v in self.run_info.items()]
+            with open(stats_filename, 'w') as fh:
+                fh.write('\t'.join(comment) + '\n')
+                stats.to_csv(fh, sep='\t', index=False)
+        n_cells = len(self.barcodes)
+        for method in SC_METHODS:
+            if method != mode and not every:
+                continue
+            out = counts_filename[:counts_filename.rfind('.')] + '_' + method + '.tsv' if every else counts_filename
+            counts = tl.reassign_cell_counts(method, self.cell_of_row, n_cells, prob)
+            if not write:
+                continue
+            if fmt == 'mtx':
+                write_mtx_counts(out[:out.rfind('.')] + '.mtx', counts, self.barcodes, names)
+            else:
+                with open(out, 'w') as fh:
+                    write_dense_counts(fh, counts, self.barcodes, names)

@@ -328,6 +328,18 @@ int  tsem_reassign_rows(tsem_ctx* h, int method, double thresh, int which, const
  * list row i.  Either output may be NULL. */
 int  tsem_rows_lookup(tsem_ctx* h, int which, int method, double thresh, int64_t n, const int32_t* rows, const int32_t* picks,
                       const int64_t* out_off, double* z_out, double* mask_out);
+/* The tags Telescope.update_sam sets on a PRI alignment (model.py:479-521), for every stored entry of the rows [row_begin,
+ * row_end) — a tile of consecutive rows — in ONE row pass: out[k - indptr[row_begin]] for entry k (CSR order) =
+ *   mapq | XP << 8 | assigned << 16 | (z >= 0.2) << 17
+ * with z = the entry's posterior in `which`'s z (0 where the reference drops it from z's pattern; formed like tsem_rows_lookup's
+ * z_out), mapq = phred(z) (helpers.py:14-37: the number of phred_tab entries <= z, 255 for z >= 1), XP = int(round(z * 100)),
+ * assigned = reassign(method, thresh)[row, col] > 0.  phred_tab: n_tab < 256 non-decreasing thresholds in [0, 1) (entry q - 1:
+ * the least P where numpy's scalar expression reaches q, computed on the host).  picks[i] (choose) belongs to tile row i.  With option "drop_csr_indices" the column
+ * ids are rebuilt at the first tile and kept: call tsem_entry_tags_end after the last tile. */
+int  tsem_entry_tags(tsem_ctx* h, int which, int method, double thresh, const int32_t* picks, int64_t row_begin, int64_t row_end,
+                     const double* phred_tab, int32_t n_tab, uint32_t* out);
+/* end of a run of tsem_entry_tags tiles: column ids rebuilt for them go again where option "drop_csr_indices" drops them */
+int  tsem_entry_tags_end(tsem_ctx* h);
 /* The random picks of `choose` (sparse_plus.py:140-154: np.random.choice per row with several best hits) in numpy's
  * LEGACY stream, on the host: out[i] = the draw np.random.randint(0, counts[i]) would return, taken in order from the
  * MT19937 state (key624, *pos) = np.random.get_state()[1:3]; the state is advanced exactly as numpy advances it, so
@@ -410,6 +422,8 @@ int  tsem_debug_fused_startup(tsem_ctx* h, uint64_t* out4096);
 int64_t tsem_debug_subblock(tsem_ctx* h, int64_t block, int32_t part, uint32_t* out, int64_t cap);
 /* y[i] = the device log1p the lnl passes use (finite x >= 0), for accuracy tests against libm */
 int  tsem_debug_log1p(int device, int32_t n, const double* x, double* y);
+/* out[i] = the PHRED lookup of tsem_entry_tags for p[i] (the table as there), for tests against numpy */
+int  tsem_debug_phred(int device, int32_t n, const double* p, const double* phred_tab, int32_t n_tab, int32_t* out);
 /* GB/s of a pure streaming read (16-byte non-temporal loads, 8 in flight per thread) over a scratch buffer of `bytes`,
  * best of `reps` launches: the measured-stream peak quoted beside the nominal HBM peak */
 int  tsem_debug_stream_read(int device, int64_t bytes, int32_t reps, double* gbs);

@@ -216,6 +216,8 @@ def lib():
     L.tsem_reassign_rows.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp, vp, i64, vp]
     L.tsem_reassign.argtypes = [vp, C.c_int, dbl, C.c_int, vp, vp, vp]
     L.tsem_rows_lookup.argtypes = [vp, C.c_int, C.c_int, dbl, i64, vp, vp, vp, vp, vp]
+    L.tsem_entry_tags.argtypes = [vp, C.c_int, C.c_int, dbl, vp, i64, i64, vp, i32, vp]
+    L.tsem_entry_tags_end.argtypes = [vp]
     L.tsem_reassign_groups.argtypes = [vp, C.c_int, dbl, C.c_int, vp, vp, C.c_int32, vp]
     L.tsem_set_groups.argtypes = [vp, vp, C.c_int32]
     L.tsem_group_counts.argtypes = [vp, C.c_int, dbl, C.c_int, vp, C.POINTER(i64)]
@@ -234,6 +236,7 @@ def lib():
     L.tsem_debug_log1p.argtypes = [C.c_int, C.c_int32, vp, vp]
     L.tsem_debug_log1p_tab.argtypes = [C.c_int, C.c_int32, vp, vp]
     L.tsem_debug_log1p_of_log.argtypes = [C.c_int, C.c_int32, vp, vp, vp, vp, vp]
+    L.tsem_debug_phred.argtypes = [C.c_int, C.c_int32, vp, vp, C.c_int32, vp]
     L.tsem_debug_stream_read.argtypes = [C.c_int, i64, i32, C.POINTER(dbl)]
     L.tsem_debug_subblock.argtypes = [vp, C.c_int64, C.c_int32, vp, C.c_int64]
     for name in exported_symbols():
@@ -548,6 +551,18 @@ class Engine(object):
                                           ptr(z), ptr(m)))
         return z, m
 
+    def entry_tags(self, method, thresh, which, row_begin, row_end, phred_tab, picks=None, n_out=None):
+        """uint32 tag word of every stored entry of rows [row_begin, row_end) (tsem_entry_tags); `n_out` = their count."""
+        tab = np.ascontiguousarray(phred_tab, dtype=np.float64)
+        pk = None if picks is None else np.ascontiguousarray(picks, dtype=np.int32)
+        out = np.empty(int(n_out), dtype=np.uint32)
+        self._ck(self._L.tsem_entry_tags(self._h, which, RA_CODE[method], float(thresh), ptr(pk), int(row_begin), int(row_end),
+                                         ptr(tab), len(tab), ptr(out)))
+        return out
+
+    def entry_tags_end(self):
+        self._ck(self._L.tsem_entry_tags_end(self._h))
+
     def set_groups(self, group_of_row, n_groups):
         """Row -> group map of the per-group sums, copied to the device once (None drops it)."""
         self.groups_token = None          # whoever sets a map may tag it afterwards (TelescopeLikelihood: a digest of the grouping)
@@ -749,6 +764,17 @@ def debug_log1p(x, device=0, table=False):
     if rc != OK:
         raise EngineError('tsem_debug_log1p failed (%d)' % rc)
     return y
+
+
+def debug_phred(p, phred_tab, device=0):
+    """The tag pass's PHRED lookup (tsem_debug_phred) of every p."""
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    tab = np.ascontiguousarray(phred_tab, dtype=np.float64)
+    out = np.empty(len(p), dtype=np.int32)
+    rc = lib().tsem_debug_phred(device, len(p), ptr(p), ptr(tab), len(tab), ptr(out))
+    if rc != OK:
+        raise EngineError('tsem_debug_phred failed (%d)' % rc)
+    return out
 
 
 def debug_log1p_of_log(q, c, device=0):

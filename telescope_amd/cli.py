@@ -13,7 +13,8 @@ telescope/__main__.py:49-92).  Same option names and defaults, same log lines, s
 count matrices, built sparse on the device (`<exp_tag>-TE_counts[_<method>].tsv`, or `.mtx` with `--count_format mtx`).
 
 `assign` (telescope/telescope_assign.py:372-451) uses telescope_amd/loader.py, a pysam-free
-restatement of the reference's sequential loader; `--updated_sam` and `--ncpu > 1` are not offered.
+restatement of the reference's sequential loader; `--ncpu > 1` is not offered.  `--updated_sam` writes `<exp_tag>-updated.bam`
+(model.py:479-521) beside `<exp_tag>-other.bam` and `<exp_tag>-tmp_tele.bam` of the load, on one GPU.
 """
 import argparse
 import logging as lg
@@ -85,13 +86,15 @@ def _assign_args(asg):
     g.add_argument('--no_feature_key', default='__no_feature',
                    help='Used internally to represent alignments that do not overlap any feature.')
     g.add_argument('--ncpu', type=int, default=1, help='Only 1 is supported (sequential loader).')
+    g.add_argument('--tempdir', help='(accepted for compatibility; no temporary files are written)')
     g = asg.add_argument_group('Reporting Options')
     g.add_argument('--quiet', action='store_true', help='Silence (most) output.')
     g.add_argument('--debug', action='store_true', help='Print debug messages.')
     g.add_argument('--logfile', type=argparse.FileType('a'), help='Log output to this file.')
     g.add_argument('--outdir', default='.', help='Output directory.')
     g.add_argument('--exp_tag', default='telescope', help='Experiment tag')
-    g.add_argument('--updated_sam', action='store_true', help='(not available in this engine)')
+    g.add_argument('--updated_sam', action='store_true',
+                   help='Generate an updated alignment file (<exp_tag>-updated.bam); one GPU only.')
     g = asg.add_argument_group('Run Modes')
     g.add_argument('--reassign_mode', default='exclude',
                    choices=['exclude', 'choose', 'average', 'conf', 'unique'],
@@ -104,6 +107,8 @@ def _assign_args(asg):
                    help='Fraction of fragment that must be contained within a feature.')
     g.add_argument('--stranded_mode', default='None', choices=['None', 'RF', 'R', 'FR', 'F'],
                    help='Stranded library orientation.')
+    g.add_argument('--annotation_class', default='intervaltree', choices=['intervaltree', 'htseq'],
+                   help='(accepted for compatibility; the annotation is indexed by this engine)')
     g = asg.add_argument_group('Model Parameters')
     g.add_argument('--pi_prior', type=int, default=0, help='Prior on pi.')
     g.add_argument('--theta_prior', type=int, default=200000, help='Prior on theta.')
@@ -125,9 +130,6 @@ def _sc_args(p, assign):
     if assign:
         groups['Input Options'].add_argument('--barcode_tag', type=str, default='CB',
                                              help='Name of the field in the BAM/SAM file containing the barcode for each read.')
-        groups['Input Options'].add_argument('--tempdir', help='(accepted for compatibility; no temporary files are written)')
-        groups['Run Modes'].add_argument('--annotation_class', default='intervaltree', choices=['intervaltree', 'htseq'],
-                                         help='(accepted for compatibility; the annotation is indexed by this engine)')
     g = groups['Run Modes']
     g.add_argument('--use_every_reassign_mode', action='store_true',
                    help='Output count matrices generated using every reassign mode (conf, all, unique, exclude, choose, average).')
@@ -235,6 +237,11 @@ def _refuse_sharded_sc(sc):
         raise SystemExit('telescope sc: row-sharded runs (WORLD_SIZE > 1) are not supported; run single-cell assignment on one GPU')
 
 
+def _refuse_sharded_updated_sam(opts):
+    if opts.updated_sam and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise SystemExit('telescope assign: --updated_sam is not supported in row-sharded runs (WORLD_SIZE > 1); run it on one GPU')
+
+
 def run_resume(args, sc=False):
     """telescope_resume.py:183-232.  sc=True: `sc resume` — a single-cell checkpoint (scTelescope) and its per-cell reports."""
     _refuse_sharded_sc(sc)
@@ -286,8 +293,9 @@ def run_assign(args, sc=False):
     _refuse_sharded_sc(sc)
     opts = ResumeOptions(args)
     configure_logging(opts)
-    if opts.updated_sam or opts.ncpu != 1:
-        raise SystemExit('--updated_sam and --ncpu > 1 are not available in this engine')
+    if opts.ncpu != 1:
+        raise SystemExit('--ncpu > 1 is not available in this engine')
+    _refuse_sharded_updated_sam(opts)
     warm = None if opts.skip_em else warm_device(opts)       # (the device comes up while the BAM is parsed)
     from .likelihood import TelescopeLikelihood
     from .loader import Annotation
@@ -311,6 +319,8 @@ def run_assign(args, sc=False):
             lg.info('Loaded {} features.'.format(len(annot.loci)))
             lg.info('Loading alignments...')
             stime = time()
+            if opts.updated_sam:
+                os.makedirs(opts.outdir, exist_ok=True)          # (the load writes <exp_tag>-other.bam and -tmp_tele.bam there)
             ts.load_alignment(annot)
             lg.info('Loaded alignment in {}'.format(format_minutes(time() - stime)))
             ts.print_summary(lg.INFO)
@@ -368,6 +378,9 @@ def run_assign(args, sc=False):
     lg.info('Generating Report...')
     ts.output_report(ts_model, opts.outfile_path('run_stats.tsv'), opts.outfile_path('TE_counts.tsv'),
                      write=comm is None or comm.rank == 0)
+    if opts.updated_sam:                                     # telescope_assign.py:446-448 (one GPU: refused above otherwise)
+        lg.info('Creating updated SAM file...')
+        ts.update_sam(ts_model, opts.outfile_path('updated.bam'))
     finish(comm)
     lg.info('telescope assign complete (%s)' % format_minutes(time() - total_time))
     return 0

@@ -46,7 +46,26 @@ __device__ double np_row_sum(const NpRow& a, int64_t m, bool all) {
 // ============================================================================
 // CSR row passes: z export, best-hit counts, reassign (model.py:808-865)
 // ============================================================================
-enum { RP_EXPORT_Z = 0, RP_BEST = 1, RP_REASSIGN = 2, RP_REPORT = 3 };
+enum { RP_EXPORT_Z = 0, RP_BEST = 1, RP_REASSIGN = 2, RP_REPORT = 3, RP_TAGS = 4 };
+
+// ---- the tag word of update_sam (model.py:479-521) -----------------------------------------------------------------------------
+// The PHRED table: tab[i] = the smallest P in [0, 1) with int(round(-10 * np.log10(1 - P))) > i (helpers.py:14-37, numpy's scalar
+// expression, found on the host by bisection over the float64 bit patterns: telescope_amd/bam_out.py), ascending, padded to 256
+// entries with 2.0.  phred(P) = the number of entries <= P, and 255 for P >= 1 — no device log10, whose last bits would differ.
+constexpr int TS_PHRED_TAB = 256;
+__device__ __forceinline__ uint32_t ts_phred(const double* __restrict__ tab, double p) {
+  if (p >= 1.0) return 255u;
+  int c = 0;
+#pragma unroll
+  for (int b = TS_PHRED_TAB / 2; b > 0; b >>= 1) c += (tab[c + b - 1] <= p) ? b : 0;
+  return (uint32_t)c;
+}
+// mapq | XP << 8 | assigned << 16 | (z >= 0.2) << 17 — XP = int(round(prob * 100)): one rounded product (no contraction), then
+// round-half-even like Python's round
+__device__ __forceinline__ uint32_t ts_tag_word(const double* __restrict__ tab, double z, bool assigned) {
+  const uint32_t xp = (uint32_t)rint(__dmul_rn(z, 100.0));
+  return ts_phred(tab, z) | (xp << 8) | (assigned ? 1u << 16 : 0u) | (z >= 0.2 ? 1u << 17 : 0u);
+}
 
 // Option "reproducible": values in [0, 2) — posteriors, shares of a tie — cut into a multiple of 2^-26 and the rest on the 2^-53
 // grid: up to 2^26 of either add exactly in fp64, whatever order the atomics are served in; the two sums are added once at the end.
@@ -87,6 +106,11 @@ struct RowPassArgs {
   int32_t g0 = 0, g1 = 0x7FFFFFFF;
   const int32_t* rowlist; int64_t nlist;   // REASSIGN / EXPORT_Z: optional list of rows to visit (picks[] is then indexed by list position)
   const int64_t* out_off = nullptr;        // with a row list: zout is COMPACT — the entries of list row i go to zout[out_off[i] ...] (tsem_rows_lookup)
+  // TAGS: rows row0 .. row0 + nlist (a tile, no row list), entry k -> tags[k - tag_base] (tag_base = indptr[row0]); picks[] is
+  // indexed by tile row; the PHRED table (TS_PHRED_TAB doubles) is staged in LDS behind the score table
+  int64_t row0 = 0, tag_base = 0;
+  uint32_t* tags = nullptr;
+  const double* phred_tab = nullptr;
   // REPORT: conf, exclude and average in ONE pass -> colsums[0..K), [K..2K), [2K..3K); best-hit counts -> nbest
   // REASSIGN without groups: the Hs most popular slots of every column part are summed in LDS per
   // workgroup and flushed once (global fp64 atomics: 22 G/s, 2 G/s on a popular column)
@@ -107,8 +131,9 @@ template <int MODE, int METH = -1, bool FIX = false>
 __global__ __launch_bounds__(1024) void k_rowpass(RowPassArgs A) {
   const int method = METH >= 0 ? METH : A.method;
   extern __shared__ double rp_lds[];                       // [lut_len] score table | [P][Hs] hot slots (REASSIGN with A.Hs > 0)
-  double* const lutS = rp_lds;
+  double* const lutS = rp_lds;                             //                       | [TS_PHRED_TAB] PHRED table (TAGS)
   double* const hot = rp_lds + A.lut_len;
+  double* const ptab = rp_lds + A.lut_len;
   const int sub = threadIdx.x / RP_SUB, lane = threadIdx.x % RP_SUB, subs = blockDim.x / RP_SUB;
   const bool initial = (A.pi == nullptr);
   const int nhot1 = (MODE == RP_REASSIGN || MODE == RP_REPORT) ? A.P * A.Hs : 0;
@@ -117,9 +142,11 @@ __global__ __launch_bounds__(1024) void k_rowpass(RowPassArgs A) {
   // comes from LDS and pi*theta from one precomputed table, 3 instead of 5 vector-memory instructions per round
   for (int t = threadIdx.x; t < A.lut_len; t += blockDim.x) lutS[t] = A.lut[t];
   for (int t = threadIdx.x; t < nhot; t += blockDim.x) hot[t] = 0.0;
+  if (MODE == RP_TAGS)
+    for (int t = threadIdx.x; t < TS_PHRED_TAB; t += blockDim.x) ptab[t] = A.phred_tab[t];
   __syncthreads();
   const bool listed = (MODE == RP_REASSIGN || MODE == RP_EXPORT_Z) && A.rowlist;
-  const int64_t n_visit = listed ? A.nlist : A.N;
+  const int64_t n_visit = (listed || MODE == RP_TAGS) ? A.nlist : A.N;
   // FIX: the outer loop walks the flag words, 16 per group and step (one per lane), the inner loops their set bits
   const int64_t n_outer = FIX ? ((*A.flag_n != 0ull) ? (n_visit + 511) / 512 : 0) : n_visit;
   for (int64_t o = (int64_t)blockIdx.x * subs + sub; o < n_outer; o += (int64_t)gridDim.x * subs) {
@@ -132,9 +159,9 @@ __global__ __launch_bounds__(1024) void k_rowpass(RowPassArgs A) {
    while (bits) {
     const int64_t idx = FIX ? (o * 16 + wl) * 32 + (__ffs((int)bits) - 1) : o;
     bits &= bits - 1u;
-    const int64_t row = listed ? (int64_t)A.rowlist[idx] : idx;
+    const int64_t row = listed ? (int64_t)A.rowlist[idx] : (MODE == RP_TAGS ? A.row0 + idx : idx);
     const int64_t s = A.indptr[row], e = A.indptr[row + 1];
-    const int64_t zo = (listed && A.out_off) ? A.out_off[idx] - s : 0;      // where entry k of this row goes in zout: k + zo
+    const int64_t zo = (listed && A.out_off) ? A.out_off[idx] - s : (MODE == RP_TAGS ? -A.tag_base : 0);   // entry k goes to k + zo
     const bool amb = (e - s) > 1;
     // one value of report column m (0 for a plain reassign) for column `col`: popular columns in LDS, the rest global
     auto emit = [&](int m, int col, uint32_t cm, double val, int64_t grp_off) {
@@ -169,6 +196,7 @@ __global__ __launch_bounds__(1024) void k_rowpass(RowPassArgs A) {
       // same summation order as the long-row path below: lane-strided partial sums, then across lanes
       const double rs = recip0(sg_sum<RP_SUB>(((n[0] + n[1]) + n[2]) + n[3]));
       double r = A.zin ? 1.0 : rs;                          // the caller's z is used as is (model.py:837)
+      const double rz = r;                                  // TAGS: z as RP_EXPORT_Z forms it (the FIX launch re-sums for the decision only)
       int cnt = 0;
 #pragma unroll
       for (int i = 0; i < 4; ++i) cnt += inp[i] ? 1 : 0;
@@ -237,7 +265,7 @@ __global__ __launch_bounds__(1024) void k_rowpass(RowPassArgs A) {
         }
         continue;
       }
-      const int pick = (method == TSEM_RA_CHOOSE && A.picks && nb > 1) ? A.picks[A.rowlist ? idx : row] : 0;
+      const int pick = (method == TSEM_RA_CHOOSE && A.picks && nb > 1) ? A.picks[(A.rowlist || MODE == RP_TAGS) ? idx : row] : 0;
       const int64_t grp_off = A.group ? ((A.group[row] < A.g0 || A.group[row] >= A.g1) ? -1 : (int64_t)(A.group[row] - A.g0) * A.K) : 0;
       int base = 0;
 #pragma unroll
@@ -257,6 +285,10 @@ __global__ __launch_bounds__(1024) void k_rowpass(RowPassArgs A) {
           case TSEM_RA_CONF:    val = (inp[i] && z >= A.thresh) ? z * recip0(vsum) : 0.0; break;
           case TSEM_RA_UNIQUE:  val = (inp[i] && !amb) ? ceil(z) : 0.0; break;
           case TSEM_RA_ALL:     val = (inp[i] && z > 0.0) ? 1.0 : 0.0; break;
+        }
+        if (MODE == RP_TAGS) {
+          if (vld[i]) A.tags[k + zo] = ts_tag_word(ptab, inp[i] ? n[i] * rz : 0.0, val > 0.0);
+          continue;
         }
         if (vld[i]) {
           if (A.zout) A.zout[k + zo] = val;
@@ -280,6 +312,7 @@ __global__ __launch_bounds__(1024) void k_rowpass(RowPassArgs A) {
     nmx = sg_max<RP_SUB>(nmx);
     cnt = sg_sum_i<RP_SUB>(cnt);
     double r = A.zin ? 1.0 : recip0(y);
+    const double rz = r;                                    // TAGS: z as RP_EXPORT_Z forms it
     if (FIX) {                                              // a near-tie: the row sum in the reference's order (see near_band)
       double ex = 0.0;
       if (lane == 0) {
@@ -357,7 +390,7 @@ __global__ __launch_bounds__(1024) void k_rowpass(RowPassArgs A) {
       }
       continue;
     }
-    const int pick = (method == TSEM_RA_CHOOSE && A.picks && nb > 1) ? A.picks[A.rowlist ? idx : row] : 0;
+    const int pick = (method == TSEM_RA_CHOOSE && A.picks && nb > 1) ? A.picks[(A.rowlist || MODE == RP_TAGS) ? idx : row] : 0;
     const int64_t grp_off = A.group ? ((A.group[row] < A.g0 || A.group[row] >= A.g1) ? -1 : (int64_t)(A.group[row] - A.g0) * A.K) : 0;
     int base = 0;
     for (int64_t k0 = s; k0 < e; k0 += RP_SUB) {
@@ -379,6 +412,10 @@ __global__ __launch_bounds__(1024) void k_rowpass(RowPassArgs A) {
         case TSEM_RA_CONF:    val = (inpat && z >= A.thresh) ? z * recip0(vsum) : 0.0; break;
         case TSEM_RA_UNIQUE:  val = (inpat && !amb) ? ceil(z) : 0.0; break;
         case TSEM_RA_ALL:     val = (inpat && z > 0.0) ? 1.0 : 0.0; break;
+      }
+      if (MODE == RP_TAGS) {
+        if (valid) A.tags[k + zo] = ts_tag_word(ptab, inpat ? n * rz : 0.0, val > 0.0);
+        continue;
       }
       if (valid) {
         if (A.zout) A.zout[k + zo] = val;
@@ -1056,6 +1093,7 @@ template <bool FIX> static RowKern rowpass_kern(int mode, int meth) {
     case RP_EXPORT_Z: return k_rowpass<RP_EXPORT_Z, -1, false>;
     case RP_BEST:     return k_rowpass<RP_BEST, -1, FIX>;
     case RP_REPORT:   return k_rowpass<RP_REPORT, -1, FIX>;
+    case RP_TAGS:     return k_rowpass<RP_TAGS, -1, FIX>;
     default: break;
   }
   switch (meth) {
@@ -1171,7 +1209,7 @@ struct IndicesGuard {                                      // at the top of an e
 // caller-assigned z decide nothing with a row sum: one launch.
 static int launch_rowpass(tsem_ctx* h, int mode, int meth, int grid, int block, size_t lds, RowPassArgs& A) {
   const bool listed = (mode == RP_REASSIGN || mode == RP_EXPORT_Z) && A.rowlist;
-  const int64_t n_visit = listed ? A.nlist : A.N;
+  const int64_t n_visit = (listed || mode == RP_TAGS) ? A.nlist : A.N;
   if (n_visit <= 0) return TSEM_OK;
   const bool fix = mode != RP_EXPORT_Z && !A.zin;
   A.flag_bits = nullptr; A.flag_n = nullptr;
@@ -1808,6 +1846,86 @@ int tsem_rows_mask_dev(tsem_ctx* h, int which, int method, double thresh, int64_
   return launch_rowpass(h, RP_REASSIGN, -1, list_grid(n), 256, (size_t)A.lut_len * 8, A);
 }
 void tsem_redrop_indices(tsem_ctx* h) { redrop_indices(h); }
+
+// the caller's PHRED thresholds (non-decreasing, in [0, 1), at most TS_PHRED_TAB - 1 of them) padded with 2.0 for ts_phred
+static bool phred_table(const double* tab, int32_t n_tab, double* out) {
+  if (!tab || n_tab < 0 || n_tab >= TS_PHRED_TAB) return false;
+  for (int i = 0; i < n_tab; ++i)
+    if (!(tab[i] >= 0.0 && tab[i] < 1.0) || (i && !(tab[i] >= tab[i - 1]))) return false;
+  for (int i = 0; i < TS_PHRED_TAB; ++i) out[i] = i < n_tab ? tab[i] : 2.0;
+  return true;
+}
+
+// The tag word of every stored entry of rows [row_begin, row_end), in CSR order (RP_TAGS: z and the reassign decision of one
+// pass, model.py:479-521).  The CSR column ids a dropped-ids matrix needs are rebuilt once and KEPT across the tiles of an update
+// (no IndicesGuard here): tsem_entry_tags_end drops them again.
+int tsem_entry_tags(tsem_ctx* h, int which, int method, double thresh, const int32_t* picks, int64_t row_begin, int64_t row_end,
+                    const double* phred_tab, int32_t n_tab, uint32_t* out) {
+  if (!h || !h->d_indptr || row_begin < 0 || row_end < row_begin || row_end > h->N) return TSEM_ERR_ARG;
+  if (method < TSEM_RA_EXCLUDE || method > TSEM_RA_ALL) TSEM_FAIL(TSEM_ERR_ARG, "bad reassign method");
+  double tab[TS_PHRED_TAB];
+  if (!phred_table(phred_tab, n_tab, tab)) TSEM_FAIL(TSEM_ERR_ARG, "tsem_entry_tags: the PHRED table must be non-decreasing, in [0, 1), < 256 entries");
+  if (int rc = ensure_device(h)) return rc;
+  const int64_t n = row_end - row_begin;
+  if (n == 0) return TSEM_OK;
+  RowPassArgs A;
+  if (int rc = rowpass_args(h, which, A)) return rc;
+  int64_t e0 = 0, e1 = 0;
+  TSEM_HIP(hipMemcpyAsync(&e0, h->d_indptr + row_begin, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  TSEM_HIP(hipMemcpyAsync(&e1, h->d_indptr + row_end, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  TSEM_HIP(hipStreamSynchronize(h->stream));
+  if (e1 > e0 && !out) return TSEM_ERR_ARG;
+  uint32_t* d_tags = nullptr;
+  int32_t* d_picks = nullptr;
+  double* d_tab = nullptr;
+  TSEM_SCOPED(d_tags); TSEM_SCOPED(d_picks); TSEM_SCOPED(d_tab);
+  TSEM_ALLOC(d_tags, e1 - e0);
+  TSEM_ALLOC(d_tab, TS_PHRED_TAB);
+  TSEM_HIP(hipMemcpyAsync(d_tab, tab, sizeof(tab), hipMemcpyHostToDevice, h->stream));
+  if (method == TSEM_RA_CHOOSE && picks) { if (int rc = upload_i32(h, d_picks, picks, n)) return rc; }
+  A.method = method; A.thresh = thresh; A.picks = d_picks; A.colsums = nullptr; A.zout = nullptr;
+  A.row0 = row_begin; A.nlist = n; A.tag_base = e0; A.tags = d_tags; A.phred_tab = d_tab;
+  if (int rc = with_indices(h, A)) return rc;
+  if (int rc = launch_rowpass(h, RP_TAGS, -1, list_grid(n), 256, (size_t)(A.lut_len + TS_PHRED_TAB) * 8, A)) return rc;
+  if (e1 > e0) TSEM_HIP(hipMemcpyAsync(out, d_tags, sizeof(uint32_t) * (e1 - e0), hipMemcpyDeviceToHost, h->stream));
+  TSEM_HIP(hipStreamSynchronize(h->stream));
+  return TSEM_OK;
+}
+
+int tsem_entry_tags_end(tsem_ctx* h) {
+  if (!h) return TSEM_ERR_ARG;
+  redrop_indices(h);
+  return TSEM_OK;
+}
+
+__global__ void k_phred_probe(int n, const double* __restrict__ p, const double* __restrict__ tab, int32_t* __restrict__ out) {
+  __shared__ double t[TS_PHRED_TAB];
+  for (int i = threadIdx.x; i < TS_PHRED_TAB; i += blockDim.x) t[i] = tab[i];
+  __syncthreads();
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (int32_t)ts_phred(t, p[i]);
+}
+/* the PHRED lookup of the tag pass (ts_phred) on caller-supplied P (accuracy test hook) */
+int tsem_debug_phred(int device, int32_t n, const double* p, const double* phred_tab, int32_t n_tab, int32_t* out) {
+  double tab[TS_PHRED_TAB];
+  if (n < 0 || (n && (!p || !out)) || !phred_table(phred_tab, n_tab, tab)) return TSEM_ERR_ARG;
+  if (hipSetDevice(device) != hipSuccess) return TSEM_ERR_HIP;
+  double *dp = nullptr, *dt = nullptr;
+  int32_t* dq = nullptr;
+  if (hipMalloc((void**)&dp, 8 * (size_t)std::max(1, n)) != hipSuccess || hipMalloc((void**)&dt, sizeof(tab)) != hipSuccess ||
+      hipMalloc((void**)&dq, 4 * (size_t)std::max(1, n)) != hipSuccess) {
+    (void)hipFree(dp); (void)hipFree(dt);
+    return TSEM_ERR_NOMEM;
+  }
+  hipError_t e = hipMemcpy(dt, tab, sizeof(tab), hipMemcpyHostToDevice);
+  if (e == hipSuccess && n) e = hipMemcpy(dp, p, 8 * (size_t)n, hipMemcpyHostToDevice);
+  if (e == hipSuccess && n) {
+    k_phred_probe<<<(n + 255) / 256, 256>>>(n, dp, dt, dq);
+    e = hipMemcpy(out, dq, 4 * (size_t)n, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dp); (void)hipFree(dt); (void)hipFree(dq);
+  return e == hipSuccess ? TSEM_OK : TSEM_ERR_HIP;
+}
 
 // The row -> group map of the per-group sums (tsem_reassign_groups): copied to the device ONCE and kept until the next call / the
 // next matrix (-1 = the row belongs to no group); range-checked on the device.  group_of_row == NULL drops it.

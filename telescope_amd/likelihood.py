@@ -653,6 +653,76 @@ class TelescopeLikelihood(object):
         val[found] = m[pos[found]]
         return prob, val.astype(_MASK_DTYPE[method])
 
+    def entry_tags(self, row_begin, row_end, method='exclude', thresh=0.9, assignment=None):
+        """The tag word of every stored entry of rows [row_begin, row_end), CSR order (uint32, tsem_entry_tags): bits 0-7 the MAPQ
+        phred(z), 8-15 XP = int(round(z * 100)), 16 `reassign(method, thresh)[row, col] > 0`, 17 z >= 0.2 — what update_sam sets on
+        a PRI alignment (model.py:503-517), with z the last E-step's (0 outside z's pattern), as `lookup` returns it.  One device
+        pass, 4 B per entry.  `choose`: the picks of `assignment` (a `reassign('choose')` result) or a fresh draw, as in `lookup`.
+        With option "drop_csr_indices" the column ids are rebuilt for the call and dropped again after it (`entry_tag_tiles` keeps
+        them across its tiles)."""
+        from .bam_out import phred_table
+        if method not in REASSIGN_METHODS:
+            raise ValueError('Argument "method" should be one of (exclude, choose, average, conf, unique, all)')
+        if self.comm.world > 1:
+            raise NotImplementedError('entry_tags: row-sharded runs (WORLD_SIZE > 1) are not supported')
+        row_begin, row_end = int(row_begin), int(row_end)
+        if not 0 <= row_begin <= row_end <= self.N:
+            raise IndexError('rows [%d, %d) outside [0, %d)' % (row_begin, row_end, self.N))
+        which = self._which(False)
+        picks = None
+        if method == 'choose':
+            picks = assignment._args[3] if assignment is not None else self._picks(which)
+        try:
+            return self._entry_tags(row_begin, row_end, method, thresh, which, picks, phred_table())
+        finally:
+            self._eng.entry_tags_end()                           # (ids rebuilt for this call do not stay resident: entry_tag_tiles keeps them)
+
+    def _entry_tags(self, r0, r1, method, thresh, which, picks, tab):
+        pk = None
+        if picks is not None and len(picks[0]):                  # sparse (tied rows, picks) -> one pick per tile row
+            rows = np.asarray(picks[0], dtype=np.int64)
+            a, b = np.searchsorted(rows, r0), np.searchsorted(rows, r1)
+            if b > a:
+                pk = np.zeros(r1 - r0, np.int32)
+                pk[rows[a:b] - r0] = np.asarray(picks[1])[a:b]
+        ip = self._eng_indptr()
+        return self._eng.entry_tags(method, thresh, which, r0, r1, tab, pk, n_out=int(ip[r1] - ip[r0]))
+
+    def _eng_indptr(self):
+        if self._raw is not None:
+            return self._raw.indptr
+        if getattr(self, '_indptr', None) is None:               # a device-generated matrix: its row pointers only (N + 1)
+            self._indptr = np.empty(self.N + 1, np.int64)
+            self._eng._ck(self._eng._L.tsem_export_csr(self._eng._h, self._indptr.ctypes.data, None, None))
+        return self._indptr
+
+    def entry_tag_tiles(self, method='exclude', thresh=0.9, assignment=None, tile_bytes=256 << 20):
+        """Generator of (row_begin, row_end, words): `entry_tags` over the whole matrix in tiles of consecutive rows holding at most
+        `tile_bytes` of words (a row longer than that is a tile of its own), so that the host never holds more than a tile.
+        `choose` draws its picks once, when the generator starts, unless `assignment` carries them.  With option
+        "drop_csr_indices" the device rebuilds the column ids once for all tiles and drops them again when the generator ends."""
+        from .bam_out import phred_table
+        if method not in REASSIGN_METHODS:
+            raise ValueError('Argument "method" should be one of (exclude, choose, average, conf, unique, all)')
+        if self.comm.world > 1:
+            raise NotImplementedError('entry_tags: row-sharded runs (WORLD_SIZE > 1) are not supported')
+        which = self._which(False)
+        picks = None
+        if method == 'choose':
+            picks = assignment._args[3] if assignment is not None else self._picks(which)
+        tab = phred_table()
+        ip = self._eng_indptr()
+        cap = max(1, int(tile_bytes) // 4)
+        try:
+            r0 = 0
+            while r0 < self.N:
+                r1 = int(np.searchsorted(ip, ip[r0] + cap, side='right')) - 1
+                r1 = min(self.N, max(r1, r0 + 1))
+                yield r0, r1, self._entry_tags(r0, r1, method, thresh, which, picks, tab)
+                r0 = r1
+        finally:
+            self._eng.entry_tags_end()
+
     def reassign(self, method, thresh=0.9, initial=False):
         """model.py:808-865 — the assignment matrix.  Returned as an `Assignment`: `.sum(0)` (all the
         reference's `output_report` asks of it, model.py:435-457) is answered by one device pass over

@@ -5,7 +5,7 @@ Mirrors the caller contract of the reference's `Telescope` class
 path needs it: `load` / `save` (model.py:108-148, the `.npz` checkpoint schema),
 `get_random_seed` (model.py:150-153), `print_summary` (model.py:523-555) and
 `output_report` (model.py:420-477, the two TSVs incl. the header glued to the
-RunInfo comment).  BAM loading and `update_sam` are out of scope.
+RunInfo comment), and, with `--updated_sam`, the two BAMs of the load and `update_sam` (model.py:479-521).
 """
 import logging as lg
 from collections import Counter, OrderedDict
@@ -98,12 +98,23 @@ class Telescope(object):
         self.row_range = None            # (r0, r1): `raw_scores` holds only these fragments (load_shard); None = all of them
 
     # ---- alignment loading (model.py:155-173, via telescope_amd/loader.py) --------
+    @property
+    def other_bam(self):
+        return self.opts.outfile_path('other.bam')               # model.py:89-92
+
+    @property
+    def tmp_bam(self):
+        return self.opts.outfile_path('tmp_tele.bam')
+
+    def _updated_sam_paths(self):
+        return (self.other_bam, self.tmp_bam) if getattr(self.opts, 'updated_sam', False) else None
+
     def load_alignment(self, annotation):
         from . import loader
         o = self.opts
         self.run_info['annotated_features'] = len(annotation.loci)
         r = loader.load_alignment(o.samfile, annotation, o.no_feature_key, o.overlap_mode,
-                                  o.overlap_threshold, o.stranded_mode)
+                                  o.overlap_threshold, o.stranded_mode, updated_sam=self._updated_sam_paths())
         self.feature_length = r['feature_length']
         self.read_index, self.feat_index = r['read_index'], r['feat_index']
         self.raw_scores = r['raw_scores']
@@ -247,6 +258,75 @@ class Telescope(object):
         with open(counts_filename, 'w') as fh:
             counts.to_csv(fh, sep='\t', index=False)
 
+    # ---- updated alignment file (model.py:479-521) ---------------------------------------------------------------------------
+    def update_sam(self, tl, filename, command_line=None):
+        """model.py:479-521: the tmp BAM of the load, re-read fragment by fragment (the reference's bundling and pairing), written to
+        `filename` with the input's header plus one @PG line.  Unmapped pairs unchanged; a SEC pair gets flag 0x100, MAPQ 0 and
+        YC 248,248,248; a PRI pair MAPQ phred(z), XP int(round(z * 100)) and — assigned by reassign(reassign_mode, conf_prob) —
+        0x100 cleared and YC vermilion, else 0x100 set and YC yellow (z >= 0.2) or GPAL[2]; z = tl.z[row, ZF's column] (0 outside
+        z's pattern).  The tags come from the device (tsem_entry_tags) in tiles of consecutive rows: fragment rows rise in the tmp
+        BAM's order, so the tiles are visited once, in order; a name that comes back in a later bundle (an input that is not
+        collated) maps to an earlier row, whose tags are asked again for that one row.  `choose` draws its picks ONCE here, after
+        the report's draws, like the reference's fresh `tl.reassign` (model.py:483).  Single GPU: row-sharded runs are refused."""
+        import sys
+        from . import bam_out, loader
+        if getattr(tl, 'comm', None) is not None and tl.comm.world > 1:
+            raise NotImplementedError('update_sam: row-sharded runs (WORLD_SIZE > 1) are not supported')
+        mode, prob = self.opts.reassign_mode, self.opts.conf_prob
+        asg = tl.reassign(mode, prob)                            # (choose: the draw happens here, as in the reference)
+        raw = sp.csr_matrix(self.raw_scores)
+        indptr, indices = raw.indptr, raw.indices
+        tiles = tl.entry_tag_tiles(mode, prob, assignment=asg)
+        cur = (0, 0, None)                                       # the tile in hand: rows [r0, r1), their words
+        back = {}                                                # rows met again behind the tile in hand
+
+        def word(ridx, fidx):
+            nonlocal cur
+            r0, r1, w = cur
+            if ridx >= r1:
+                for cur in tiles:
+                    if ridx < cur[1]:
+                        break
+                r0, r1, w = cur
+                if not r0 <= ridx < r1:
+                    raise AssertionError('update_sam: row %d outside the matrix' % ridx)
+                base = indptr[r0]
+            elif ridx < r0:
+                if ridx not in back:
+                    back[ridx] = tl.entry_tags(ridx, ridx + 1, mode, prob, assignment=asg)
+                w, base = back[ridx], indptr[ridx]
+            else:
+                base = indptr[r0]
+            s, e = indptr[ridx], indptr[ridx + 1]
+            k = s + int(np.searchsorted(indices[s:e], fidx))
+            return int(w[k - base]) if k < e and indices[k] == fidx else 0
+
+        _, records, header = loader.read_bam(self.tmp_bam, raw=True)
+        text = bam_out.header_with_pg(header['text'], self.run_info.get('version', getattr(self.opts, 'version', '')),
+                                      ' '.join(sys.argv) if command_line is None else command_line)
+        try:
+            with bam_out.BamWriter(filename, header, text) as out:
+                for _code, pairs in loader._fragments(records):
+                    if not pairs:
+                        continue
+                    ridx = self.read_index[pairs[0].r1.qname]
+                    for p in pairs:
+                        recs = p.records()
+                        if p.is_unmapped:
+                            for r in recs:
+                                out.write(r)
+                            continue
+                        zt = bam_out.get_tag(recs[0], 'ZT')
+                        if zt is None:
+                            raise AssertionError('Missing ZT tag')
+                        w = 0
+                        if zt != 'SEC':
+                            w = word(ridx, self.feat_index[bam_out.get_tag(recs[0], 'ZF')])
+                        for r in bam_out.update_pair(recs, zt, w):
+                            out.write(r)
+        finally:
+            tiles.close()
+
 
 # ---- single-cell mode (scTelescope, model.py:567-629) -----------------------------------------------------------------------------
 SC_METHODS = ('conf', 'all', 'unique', 'exclude', 'choose', 'average')   # model.py:618: the order fixes when `choose` draws
@@ -314,7 +394,7 @@ class scTelescope(Telescope):
         o = self.opts
         self.run_info['annotated_features'] = len(annotation.loci)
         r = loader.load_alignment(o.samfile, annotation, o.no_feature_key, o.overlap_mode, o.overlap_threshold, o.stranded_mode,
-                                  barcode_tag=o.barcode_tag)
+                                  barcode_tag=o.barcode_tag, updated_sam=self._updated_sam_paths())
         self.feature_length = r['feature_length']
         self.read_index, self.feat_index = r['read_index'], r['feat_index']
         self.raw_scores = r['raw_scores']

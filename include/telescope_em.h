@@ -375,11 +375,20 @@ int  tsem_group_counts_copy(tsem_ctx* h, int64_t* group_ptr, int32_t* cols, doub
 int  tsem_group_counts_shape(tsem_ctx* h, int32_t* n_groups, int64_t* nnz);
 
 /* ---- csr_matrix_plus primitives on arbitrary fp64 CSR (sparse_plus.py) ---- */
+/* All three: indptr[n_rows + 1] is a HOST array and is checked on the host before the device is touched. TSEM_ERR_ARG (text in
+ * tsem_last_error(NULL)) for n_rows < 0, n_cols < 0, indptr NULL, indptr[0] != 0, any indptr[i + 1] < indptr[i], or data / out
+ * NULL with indptr[n_rows] > 0: with or without a GPU, and no kernel ever sees such row pointers.  data and out hold
+ * indptr[n_rows] values.  A failed launch or copy is TSEM_ERR_HIP; out is then not to be read. */
+/* norm(1) :46-52: out = data * recip0(row sum); a NaN in a row makes the row NaN, as in scipy. */
 int  tsem_csr_norm_rows(int device, int64_t n_rows, const int64_t* indptr,
-                        const double* data, double* out);            /* norm(1)  :46-52  */
+                        const double* data, double* out);
+/* binmax(1) :117-129: out = 1 where data equals the row maximum, else 0.  The maximum is numpy's: a row with fewer than n_cols
+ * entries includes an implicit 0, and a row that holds a NaN has the maximum NaN and marks nothing. */
 int  tsem_csr_binmax_rows(int device, int64_t n_rows, int32_t n_cols, const int64_t* indptr,
-                          const double* data, int8_t* out);          /* binmax(1):117-129 */
-/* mode 0: norm() :47-48   mode 1: scale() :94-95   mode 2: scale(1) :96-97 */
+                          const double* data, int8_t* out);
+/* mode 0: norm() :47-48   mode 1: scale() :94-95   mode 2: scale(1) :96-97; any other mode is TSEM_ERR_ARG.  The maxima of modes 1
+ * and 2 are numpy's, as above: an implicit 0 where the matrix (1) or the row (2) is not full, and NaN once a NaN is seen, so
+ * that the whole matrix (1) or row (2) comes out NaN. */
 int  tsem_csr_scale(int device, int mode, int64_t n_rows, int32_t n_cols, const int64_t* indptr,
                     const double* data, double* out);
 

@@ -807,13 +807,19 @@ def stream_read_gbs(device=0, nbytes=8 << 30, reps=3):
     return g.value
 
 
+def _csr_error(fn, rc):
+    e = EngineError('%s failed (%d): %s' % (fn, rc, lib().tsem_last_error(None).decode()))
+    e.code = rc
+    return e
+
+
 def csr_norm_rows(indptr, data, device=0):
     indptr = np.ascontiguousarray(indptr, dtype=np.int64)
     data = np.ascontiguousarray(data, dtype=np.float64)
     out = np.empty_like(data)
     rc = lib().tsem_csr_norm_rows(device, len(indptr) - 1, ptr(indptr), ptr(data), ptr(out))
     if rc != OK:
-        raise EngineError('tsem_csr_norm_rows failed (%d): %s' % (rc, lib().tsem_last_error(None).decode()))
+        raise _csr_error('tsem_csr_norm_rows', rc)
     return out
 
 
@@ -823,7 +829,7 @@ def csr_binmax_rows(indptr, data, n_cols, device=0):
     out = np.empty(len(data), np.int8)
     rc = lib().tsem_csr_binmax_rows(device, len(indptr) - 1, int(n_cols), ptr(indptr), ptr(data), ptr(out))
     if rc != OK:
-        raise EngineError('tsem_csr_binmax_rows failed (%d): %s' % (rc, lib().tsem_last_error(None).decode()))
+        raise _csr_error('tsem_csr_binmax_rows', rc)
     return out
 
 
@@ -834,5 +840,5 @@ def csr_scale(mode, indptr, data, n_cols, device=0):
     out = np.empty_like(data)
     rc = lib().tsem_csr_scale(device, int(mode), len(indptr) - 1, int(n_cols), ptr(indptr), ptr(data), ptr(out))
     if rc != OK:
-        raise EngineError('tsem_csr_scale failed (%d): %s' % (rc, lib().tsem_last_error(None).decode()))
+        raise _csr_error('tsem_csr_scale', rc)
     return out

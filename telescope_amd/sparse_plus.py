@@ -9,6 +9,12 @@ on the GPU through the C ABI (`tsem_csr_norm_rows`, `tsem_csr_scale`,
 `check_equal`, `save`/`load` are structural, `choose_random` only consumes the
 caller's legacy RNG stream and edits the pattern, `apply_func` calls the
 caller's Python function per stored element exactly like the reference.
+
+The values are scipy's (tests/test_gpu_csr_primitives.py): maxima include the implicit zeros of a row (matrix) that is not
+full and keep a NaN once they have seen one, as `np.maximum` does.  Known differences from the reference:
+ * every input dtype is computed in float64 and `norm` / `scale` return float64, also for float32 input, where scipy (and so
+   the reference) stays in float32; the values are those of the reference on the input cast to float64.  `binmax` returns int8.
+ * `scale()` of a matrix with a zero dimension, e.g. (0, 5), returns the empty matrix; scipy's `max()` raises ValueError there.
 """
 import numpy as np
 import scipy.sparse

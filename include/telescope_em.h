@@ -334,8 +334,14 @@ int  tsem_rows_lookup(tsem_ctx* h, int which, int method, double thresh, int64_t
  * with z = the entry's posterior in `which`'s z (0 where the reference drops it from z's pattern; formed like tsem_rows_lookup's
  * z_out), mapq = phred(z) (helpers.py:14-37: the number of phred_tab entries <= z, 255 for z >= 1), XP = int(round(z * 100)),
  * assigned = reassign(method, thresh)[row, col] > 0.  phred_tab: n_tab < 256 non-decreasing thresholds in [0, 1) (entry q - 1:
- * the least P where numpy's scalar expression reaches q, computed on the host).  picks[i] (choose) belongs to tile row i.  With option "drop_csr_indices" the column
- * ids are rebuilt at the first tile and kept: call tsem_entry_tags_end after the last tile. */
+ * the least P where numpy's scalar expression reaches q, computed on the host).  picks[i] (choose) belongs to tile row i.
+ * In a near-tie row (two different numerators within 2^-42 at the row's maximum, or a z that close to `thresh`: tsem_layout_info
+ * [31] counts them) the two halves of the word use two row sums: mapq, XP and the 0.2 bit are taken from the pass's own z — the
+ * numerator times the reciprocal of the row sum in the pass's order of additions, bit for bit what tsem_export_z and
+ * tsem_rows_lookup's z_out give — while `assigned` is decided with the row sum added in the reference's order (np.add.reduceat),
+ * as tsem_rows_lookup's mask_out is; the two z differ by summation order only, (len + 3) 2^-53 relative at most.
+ * With option "drop_csr_indices" the column ids are rebuilt at the first tile and kept: call tsem_entry_tags_end after the last
+ * tile. */
 int  tsem_entry_tags(tsem_ctx* h, int which, int method, double thresh, const int32_t* picks, int64_t row_begin, int64_t row_end,
                      const double* phred_tab, int32_t n_tab, uint32_t* out);
 /* end of a run of tsem_entry_tags tiles: column ids rebuilt for them go again where option "drop_csr_indices" drops them */

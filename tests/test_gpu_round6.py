@@ -8,42 +8,10 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from _rowpass_reference import near_tie_matrix as _near_tie_matrix   # (the builder lives with the other seeded inputs)
 from conftest import GOLD, ROOT, Opts
 
 pytestmark = pytest.mark.gpu
-
-
-def _near_tie_matrix(seed, n=6000, k=400, max_len=40, long_rows=0, scores=(3, 4)):
-    """A matrix whose rows are full of near-ties once the parameters below are set: columns come in PAIRS (2j, 2j + 1) whose
-    pi * theta differ by one to three ulp, a row takes both columns of a pair with the same score, so its two largest z values are
-    a few ulp apart — whether they round together hangs on the last bit of 1 / rowsum, i.e. on the ORDER the row is added in."""
-    rng = np.random.RandomState(seed)
-    lens = rng.randint(1, max_len // 2 + 1, n) * 2
-    lens[rng.rand(n) < 0.1] = 1
-    if long_rows:
-        lens[rng.choice(n, long_rows, replace=False)] = rng.choice([130, 258, 300, 398], long_rows)    # beyond the streaming kernel's 256 entries too
-    indptr = np.concatenate([[0], np.cumsum(lens)])
-    indices = np.empty(indptr[-1], np.int32)
-    data = np.empty(indptr[-1], np.uint16)
-    for i, l in enumerate(lens):
-        s = indptr[i]
-        if l == 1:
-            indices[s] = rng.randint(k); data[s] = rng.choice(scores)
-            continue
-        pairs = np.sort(rng.choice(k // 2, l // 2, replace=False))
-        indices[s:s + l] = np.repeat(2 * pairs, 2) + np.tile([0, 1], l // 2)
-        data[s:s + l] = np.repeat(rng.choice(scores, l // 2), 2)
-    raw = sp.csr_matrix((data, indices, indptr), shape=(n, k))
-    pi = rng.dirichlet(np.full(k, 2.0))
-    theta = rng.dirichlet(np.full(k, 2.0))
-    for j in range(0, k, 2):                                # pi * theta of a pair: equal, or one to three ulp apart
-        theta[j + 1] = theta[j]
-        p = pi[j]
-        for _ in range(int(rng.randint(0, 4))):
-            p = np.nextafter(p, 1.0)
-        pi[j + 1] = p
-    return raw, pi, theta
-
 
 @pytest.mark.parametrize('seed,kw', [(1, {}), (2, dict(max_len=8)), (3, dict(long_rows=40, n=3000)), (4, dict(scores=(1, 2), k=64, max_len=60)),
                                      (5, dict(max_len=250, n=1500, k=600))])

@@ -52,6 +52,9 @@ LAYOUTS = [{}, {'value_format': 1}, {'hot_split': 0}, {'drop_csr_indices': 1}]
 @pytest.mark.parametrize('layout', range(len(LAYOUTS)))
 @pytest.mark.parametrize('name', case_names(full_only=True))
 def test_updated_sam_entry_tags_equal_lookup(gpu_device, name, layout):
+    """the tag pass restated from `tl.lookup` — the same kernel in another mode, so this ties the two entry points together and
+    nothing more; the outside reference of the words (exact z, the oracle's assignment, the host quantiser, on all entries) lives
+    in tests/test_gpu_rowpass_entries.py"""
     from telescope_amd.likelihood import TelescopeLikelihood
     c = load_case(name)
     raw = case_matrix(c)

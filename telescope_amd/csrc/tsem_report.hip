@@ -19,6 +19,18 @@
 // The band covers the distance between any two orders of adding up to `len` positive terms (2 len 2^-53) with room to spare.
 constexpr double TS_NEAR_BAND = 0x1p-42;
 __device__ __forceinline__ double near_band(int64_t len) { return fmax(TS_NEAR_BAND, (double)len * 0x1p-50); }
+// is the entry with numerator n (largest of the row: nmx, lo = nmx (1 - band); z = n r; tb = thresh * band) one that the last bits of r
+// could decide?  uses_thresh: the output compares z with the threshold (`conf`)
+__device__ __forceinline__ bool near_tie(double n, double r, double nmx, double lo, bool uses_thresh, double thresh, double tb) {
+  return (n >= lo && n != nmx) || (uses_thresh && fabs(n * r - thresh) <= tb);
+}
+// z's pattern: the entries of a caller's z that are not NaN; every stored entry of the initial z; else the non-zero products
+// (model.py:713-714 drops exact zeros before the sum)
+__device__ __forceinline__ bool in_pattern(bool zin, bool initial, double n) { return zin ? !isnan(n) : (initial || n != 0.0); }
+// a wave ballot cut down to the caller's 16-lane group (bit i: lane i of the group); the whole group must be active
+__device__ __forceinline__ uint32_t group_ballot(bool p) {
+  return (uint32_t)(__ballot(p) >> ((threadIdx.x & 63) / RP_SUB * RP_SUB)) & 0xFFFFu;
+}
 // the m terms of z's pattern in a row — every stored entry (`all`, the initial z) or the non-zero products (model.py:713-714 drops
 // exact zeros before the sum) — added like np.add.reduceat adds them.  Term of the row's k-th stored entry: lut[raw[s + k]], times
 // tab[column] unless tab is null (the initial z); the column is a CSR column id (col32) or a popularity id + toff (col16).
@@ -41,6 +53,15 @@ __device__ double np_row_sum(const NpRow& a, int64_t m, bool all) {
   };
   Cur c{a, 0, all};
   return m > 0 ? np_reduceat_sum(c, m) : 0.0;
+}
+// 1 / that sum on every lane of the row's G-lane group: lane 0 forms it and counts the row
+template <int G> __device__ __forceinline__ double np_row_recip(const NpRow& a, int64_t m, bool all, int lane, unsigned long long* exact_n) {
+  double ex = 0.0;
+  if (lane == 0) {
+    ex = np_row_sum(a, m, all);
+    if (exact_n) atomicAdd(exact_n, 1ull);
+  }
+  return recip0(__shfl(ex, 0, G));
 }
 
 // ============================================================================
@@ -85,26 +106,26 @@ __global__ void k_add_lo(int64_t n, double* __restrict__ a, const double* __rest
 }
 
 struct RowPassArgs {
-  int64_t N;
-  int32_t K;
-  const int64_t* indptr;
-  const int32_t* indices;
-  const uint16_t* raw;
-  const double* lut;
-  const double* pi;      // null => initial (c == 1)
-  const double* theta;
-  const double* zin;     // non-null: the caller's z (TSEM_Z_USER), aligned to the CSR pattern, NaN = no entry; used as is
-  const double* cnat;    // pi[j] * theta[j] per column (natural order): ONE gather per entry of an ambiguous row instead of two
-  int lut_len;           // the score table is staged in LDS ([lut_len] doubles in front of the hot slots)
-  int method;
-  double thresh;
-  const int32_t* picks;
-  double* zout;          // EXPORT_Z / mask
-  int32_t* nbest;
-  double* colsums;
-  const int32_t* group;  // REASSIGN: optional row -> group map; colsums is then [g1 - g0][K], rows of other groups (or -1) are skipped
+  int64_t N = 0;
+  int32_t K = 0;
+  const int64_t* indptr = nullptr;
+  const int32_t* indices = nullptr;
+  const uint16_t* raw = nullptr;
+  const double* lut = nullptr;
+  const double* pi = nullptr;      // null => initial (c == 1)
+  const double* theta = nullptr;
+  const double* zin = nullptr;     // non-null: the caller's z (TSEM_Z_USER), aligned to the CSR pattern, NaN = no entry; used as is
+  const double* cnat = nullptr;    // pi[j] * theta[j] per column (natural order): ONE gather per entry of an ambiguous row instead of two
+  int lut_len = 0;           // the score table is staged in LDS ([lut_len] doubles in front of the hot slots)
+  int method = 0;
+  double thresh = 0.0;
+  const int32_t* picks = nullptr;
+  double* zout = nullptr;          // EXPORT_Z / mask
+  int32_t* nbest = nullptr;
+  double* colsums = nullptr;
+  const int32_t* group = nullptr;  // REASSIGN: optional row -> group map; colsums is then [g1 - g0][K], rows of other groups (or -1) are skipped
   int32_t g0 = 0, g1 = 0x7FFFFFFF;
-  const int32_t* rowlist; int64_t nlist;   // REASSIGN / EXPORT_Z: optional list of rows to visit (picks[] is then indexed by list position)
+  const int32_t* rowlist = nullptr; int64_t nlist = 0;   // REASSIGN / EXPORT_Z: optional list of rows to visit (picks[] is then indexed by list position)
   const int64_t* out_off = nullptr;        // with a row list: zout is COMPACT — the entries of list row i go to zout[out_off[i] ...] (tsem_rows_lookup)
   // TAGS: rows row0 .. row0 + nlist (a tile, no row list), entry k -> tags[k - tag_base] (tag_base = indptr[row0]); picks[] is
   // indexed by tile row; the PHRED table (TS_PHRED_TAB doubles) is staged in LDS behind the score table
@@ -114,7 +135,7 @@ struct RowPassArgs {
   // REPORT: conf, exclude and average in ONE pass -> colsums[0..K), [K..2K), [2K..3K); best-hit counts -> nbest
   // REASSIGN without groups: the Hs most popular slots of every column part are summed in LDS per
   // workgroup and flushed once (global fp64 atomics: 22 G/s, 2 G/s on a popular column)
-  const uint32_t* colmap; const int32_t* col_of_pc; int P, Kp, Hs;
+  const uint32_t* colmap = nullptr; const int32_t* col_of_pc = nullptr; int P = 0, Kp = 0, Hs = 0;
   double* colsums_lo = nullptr;   // option "reproducible": the low pieces of every value (same shape as colsums; no LDS slots then)
   unsigned long long* exact_n = nullptr;   // counts the rows redone in the reference's order of additions (near-ties)
   // near-ties of a pass (see near_band): the pass proper (FIX = false) sets bit `idx` of flag_bits for a visited row it must not
@@ -125,6 +146,59 @@ struct RowPassArgs {
   unsigned long long* flag_n = nullptr;    // [1] rows flagged by this pass
 };
 
+// How a lane of a row's 16-lane group gets at its entries k = s + lane, s + lane + RP_SUB, ... of the row [s, e) — the ONLY thing short
+// and long rows differ in.  each(f) calls f(k, valid, inp, n) in ascending k on ALL 16 lanes in lockstep, so that f may ballot: n
+// is the entry's numerator, inp whether it belongs to z's pattern (in_pattern); a lane past the row's end gets valid = inp = false and
+// n = 0.0.
+//   RowTile:  rows of up to 4 * RP_SUB = 64 entries (all of them, for alignment data): the numerators and the two flags are computed once and
+//             every each() replays them from registers, fully unrolled;
+//   RowSweep: rows of any length: every each() is a sweep with stride RP_SUB that computes them again.
+template <class Numer> struct RowTile {
+  static constexpr int NT = 4;
+  int64_t k0; double n[NT]; bool valid[NT], inp[NT];
+  __device__ __forceinline__ RowTile(const Numer& numer, bool zin, bool initial, int64_t s, int64_t e, int lane) : k0(s + lane) {
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+      valid[i] = k0 + i * RP_SUB < e;
+      n[i] = valid[i] ? numer(k0 + i * RP_SUB) : 0.0;
+      inp[i] = valid[i] && in_pattern(zin, initial, n[i]);
+    }
+  }
+  template <class F> __device__ __forceinline__ void each(F&& f) const {
+#pragma unroll
+    for (int i = 0; i < NT; ++i) f(k0 + i * RP_SUB, valid[i], inp[i], n[i]);
+  }
+};
+template <class Numer> struct RowSweep {
+  const Numer& numer; const bool zin, initial; const int64_t s, e; const int lane;
+  __device__ __forceinline__ RowSweep(const Numer& numer_, bool zin_, bool initial_, int64_t s_, int64_t e_, int lane_)
+      : numer(numer_), zin(zin_), initial(initial_), s(s_), e(e_), lane(lane_) {}
+  template <class F> __device__ __forceinline__ void each(F&& f) const {
+    for (int64_t k = s + lane; k - lane < e; k += RP_SUB) {   // (the same trip count on all 16 lanes)
+      const bool valid = k < e;
+      const double n = valid ? numer(k) : 0.0;
+      f(k, valid, valid && in_pattern(zin, initial, n), n);
+    }
+  }
+};
+// the value reassign(method) gives an entry (model.py:808-865): z its posterior, best: one of the row's nb best hits, the ord-th of them
+__device__ __forceinline__ double reassign_value(int method, bool inp, bool best, bool amb, double z, int nb, int ord, int pick,
+                                                 double thresh, double vsum) {
+  switch (method) {
+    case TSEM_RA_EXCLUDE: return (best && nb == 1) ? 1.0 : 0.0;
+    case TSEM_RA_CHOOSE:  return (best && ord == pick) ? 1.0 : 0.0;
+    case TSEM_RA_AVERAGE: return best ? 1.0 * recip0((double)nb) : 0.0;
+    case TSEM_RA_CONF:    return (inp && z >= thresh) ? z * recip0(vsum) : 0.0;
+    case TSEM_RA_UNIQUE:  return (inp && !amb) ? ceil(z) : 0.0;
+    case TSEM_RA_ALL:     return (inp && z > 0.0) ? 1.0 : 0.0;
+  }
+  return 0.0;
+}
+
+// The generic row pass: one 16-lane group per row, every per-entry output that is not a streaming report.  The row algorithm — row
+// sum over z's pattern, near-tie test (or, FIX, the sum in the reference's order), largest z, best hits, the outputs of MODE — is
+// written ONCE, as `row_body`, over an accessor (RowTile for rows of up to 64 entries, RowSweep for longer ones): both kinds of row
+// do the same arithmetic in the same order — per-lane partial sums in ascending k from 0.0, then sg_sum — by construction.
 // METH >= 0 fixes the reassign method at compile time (the per-entry switch and the reductions a method does not
 // need disappear: the pass is bound by instruction issue, ~300 per four rows); METH = -1 reads it from the arguments.
 template <int MODE, int METH = -1, bool FIX = false>
@@ -151,7 +225,7 @@ __global__ __launch_bounds__(1024) void k_rowpass(RowPassArgs A) {
   const int64_t n_outer = FIX ? ((*A.flag_n != 0ull) ? (n_visit + 511) / 512 : 0) : n_visit;
   for (int64_t o = (int64_t)blockIdx.x * subs + sub; o < n_outer; o += (int64_t)gridDim.x * subs) {
    const uint32_t my_word = FIX ? A.flag_bits[o * 16 + lane] : 0u;
-   uint32_t lanes = FIX ? (uint32_t)((__ballot(my_word != 0u) >> ((threadIdx.x & 63) / RP_SUB * RP_SUB)) & 0xFFFFull) : 1u;
+   uint32_t lanes = FIX ? group_ballot(my_word != 0u) : 1u;
    while (lanes) {
     const int wl = __ffs((int)lanes) - 1;
     lanes &= lanes - 1u;
@@ -181,250 +255,94 @@ __global__ __launch_bounds__(1024) void k_rowpass(RowPassArgs A) {
       double c = amb ? A.cnat[col] : A.pi[col];              // cnat[col] = pi[col] * theta[col]: the same product, formed once per column
       return q * c;
     };
-    if (e - s <= 4 * RP_SUB) {
-      // Rows of up to 64 entries (all of them, for alignment data): the numerators are computed once
-      // and stay in registers for the row sum, the row maximum, the tie count and the output value.
-      double n[4]; bool vld[4], inp[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int64_t k = s + lane + i * RP_SUB;
-        vld[i] = k < e;
-        n[i] = vld[i] ? numer(k) : 0.0;
-        inp[i] = vld[i] && (A.zin ? !isnan(n[i]) : (initial || n[i] != 0.0));
-        if (A.zin && !inp[i]) n[i] = 0.0;
-      }
-      // same summation order as the long-row path below: lane-strided partial sums, then across lanes
-      const double rs = recip0(sg_sum<RP_SUB>(((n[0] + n[1]) + n[2]) + n[3]));
-      double r = A.zin ? 1.0 : rs;                          // the caller's z is used as is (model.py:837)
-      const double rz = r;                                  // TAGS: z as RP_EXPORT_Z forms it (the FIX launch re-sums for the decision only)
+    auto row_body = [&](const auto& ent) {
+      // the row sum (a caller's z is used as is, model.py:837), the size of z's pattern and its largest numerator
+      double y = 0.0, nmx = -1.0;
       int cnt = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) cnt += inp[i] ? 1 : 0;
+      ent.each([&](int64_t, bool, bool inp, double n) {
+        y += (A.zin && !inp) ? 0.0 : n;
+        if (inp) { nmx = fmax(nmx, n); ++cnt; }
+      });
       cnt = sg_sum_i<RP_SUB>(cnt);
+      double r = A.zin ? 1.0 : recip0(sg_sum<RP_SUB>(y));
+      const double rz = r;                                  // TAGS: z as RP_EXPORT_Z forms it (the FIX launch re-sums for the decision only)
       if (FIX) {                                            // a near-tie: the row sum in the reference's order (see near_band)
-        double ex = 0.0;
-        if (lane == 0) {
-          const NpRow nr{A.lut, A.raw, A.indices, nullptr, initial ? nullptr : (amb ? A.cnat : A.pi), 0u, s};
-          ex = np_row_sum(nr, cnt, initial);
-          if (A.exact_n) atomicAdd(A.exact_n, 1ull);
-        }
-        r = recip0(__shfl(ex, 0, RP_SUB));
+        const NpRow nr{A.lut, A.raw, A.indices, nullptr, initial ? nullptr : (amb ? A.cnat : A.pi), 0u, s};
+        r = np_row_recip<RP_SUB>(nr, cnt, initial, lane, A.exact_n);
       } else if (MODE != RP_EXPORT_Z && !A.zin && A.flag_bits) {   // is it one?  Then it is left to the FIX launch
-        double nmx = -1.0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) if (inp[i]) nmx = fmax(nmx, n[i]);
         nmx = sg_max<RP_SUB>(nmx);
         const bool uses_thresh = MODE == RP_REPORT || method == TSEM_RA_CONF;
-        const double lo = nmx * (1.0 - TS_NEAR_BAND), tb = A.thresh * TS_NEAR_BAND;
+        const double band = near_band(e - s), lo = nmx * (1.0 - band), tb = A.thresh * band;
         int nf = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (inp[i] && ((n[i] >= lo && n[i] != nmx) || (uses_thresh && fabs(n[i] * r - A.thresh) <= tb))) nf = 1;
+        ent.each([&](int64_t, bool, bool inp, double n) {
+          if (inp && near_tie(n, r, nmx, lo, uses_thresh, A.thresh, tb)) nf = 1;
+        });
         if (sg_max_i<RP_SUB>(nf)) {
           if (lane == 0) { atomicOr(&A.flag_bits[idx >> 5], 1u << (idx & 31)); atomicAdd(A.flag_n, 1ull); }
-          continue;
+          return;
         }
       }
-      double zmax = -1.0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) if (inp[i]) zmax = fmax(zmax, n[i] * r);
-      zmax = sg_max<RP_SUB>(zmax);
-      if (MODE == RP_EXPORT_Z) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) if (vld[i]) A.zout[s + lane + i * RP_SUB + zo] = inp[i] ? n[i] * r : -1.0;
-        continue;
+      if (MODE == RP_EXPORT_Z) {                            // -1 marks an entry the reference drops from z's pattern
+        ent.each([&](int64_t k, bool valid, bool inp, double n) { if (valid) A.zout[k + zo] = inp ? n * r : -1.0; });
+        return;
       }
+      // the largest z and the number of best hits (binmax, sparse_plus.py:117-129: exact ==)
+      double zmax = -1.0;
+      ent.each([&](int64_t, bool, bool inp, double n) { if (inp) zmax = fmax(zmax, n * r); });
+      zmax = sg_max<RP_SUB>(zmax);
       int nb = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) nb += (inp[i] && (n[i] * r) == zmax) ? 1 : 0;
+      ent.each([&](int64_t, bool, bool inp, double n) { nb += (inp && (n * r) == zmax) ? 1 : 0; });
       nb = sg_sum_i<RP_SUB>(nb);
       if (MODE == RP_BEST) {
         if (lane == 0) A.nbest[row] = cnt ? nb : 0;
-        continue;
+        return;
       }
-      double vsum = 0.0;
+      double vsum = 0.0;                                    // conf renormalises the z values at or above the threshold
       if (method == TSEM_RA_CONF || MODE == RP_REPORT) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) if (inp[i] && n[i] * r >= A.thresh) vsum += n[i] * r;
+        ent.each([&](int64_t, bool, bool inp, double n) { if (inp && n * r >= A.thresh) vsum += n * r; });
         vsum = sg_sum<RP_SUB>(vsum);
       }
       if (MODE == RP_REPORT) {                              // conf | exclude | average of model.py:839-856 from one set of numerators
         if (lane == 0 && A.nbest) A.nbest[row] = cnt ? nb : 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const double z = n[i] * r;
-          const bool best = inp[i] && (z == zmax);
-          const double vc = (inp[i] && z >= A.thresh) ? z * recip0(vsum) : 0.0;
-          if (vld[i] && (best || vc != 0.0)) {
-            const int col = A.indices[s + lane + i * RP_SUB];
+        ent.each([&](int64_t k, bool, bool inp, double n) {
+          const double z = n * r;
+          const bool best = inp && (z == zmax);
+          const double vc = (inp && z >= A.thresh) ? z * recip0(vsum) : 0.0;
+          if (best || vc != 0.0) {
+            const int col = A.indices[k];
             const uint32_t cm = nhot1 ? A.colmap[col] : 0xFFFFFFFFu;
             if (vc != 0.0) emit(0, col, cm, vc, 0);
             if (best && nb == 1) emit(1, col, cm, 1.0, 0);
             if (best) emit(2, col, cm, 1.0 * recip0((double)nb), 0);
           }
-        }
-        continue;
+        });
+        return;
       }
+      // REASSIGN | TAGS: the entry's value; `choose` keeps the pick-th best hit in CSR order, its ordinal counted by ballot
       const int pick = (method == TSEM_RA_CHOOSE && A.picks && nb > 1) ? A.picks[(A.rowlist || MODE == RP_TAGS) ? idx : row] : 0;
       const int64_t grp_off = A.group ? ((A.group[row] < A.g0 || A.group[row] >= A.g1) ? -1 : (int64_t)(A.group[row] - A.g0) * A.K) : 0;
       int base = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int64_t k = s + lane + i * RP_SUB;
-        const double z = n[i] * r;
-        const bool best = inp[i] && (z == zmax);
-        const unsigned long long bal = __ballot(best);
-        const unsigned grp = (unsigned)((bal >> ((threadIdx.x & 63) / RP_SUB * RP_SUB)) & 0xFFFFull);
+      ent.each([&](int64_t k, bool valid, bool inp, double n) {
+        const double z = n * r;
+        const bool best = inp && (z == zmax);
+        const uint32_t grp = group_ballot(best);
         const int ord = base + __popc(grp & ((1u << lane) - 1u));
         base += __popc(grp);
-        double val = 0.0;
-        switch (method) {
-          case TSEM_RA_EXCLUDE: val = (best && nb == 1) ? 1.0 : 0.0; break;
-          case TSEM_RA_CHOOSE:  val = (best && ord == pick) ? 1.0 : 0.0; break;
-          case TSEM_RA_AVERAGE: val = best ? 1.0 * recip0((double)nb) : 0.0; break;
-          case TSEM_RA_CONF:    val = (inp[i] && z >= A.thresh) ? z * recip0(vsum) : 0.0; break;
-          case TSEM_RA_UNIQUE:  val = (inp[i] && !amb) ? ceil(z) : 0.0; break;
-          case TSEM_RA_ALL:     val = (inp[i] && z > 0.0) ? 1.0 : 0.0; break;
-        }
+        const double val = reassign_value(method, inp, best, amb, z, nb, ord, pick, A.thresh, vsum);
+        if (!valid) return;
         if (MODE == RP_TAGS) {
-          if (vld[i]) A.tags[k + zo] = ts_tag_word(ptab, inp[i] ? n[i] * rz : 0.0, val > 0.0);
-          continue;
+          A.tags[k + zo] = ts_tag_word(ptab, inp ? n * rz : 0.0, val > 0.0);
+          return;
         }
-        if (vld[i]) {
-          if (A.zout) A.zout[k + zo] = val;
-          if (val != 0.0 && grp_off >= 0 && A.colsums) {
-            const int col = A.indices[k];
-            emit(0, col, nhot1 ? A.colmap[col] : 0xFFFFFFFFu, val, grp_off);
-          }
-        }
-      }
-      continue;
-    }
-    // sweep 1: row sum (and the largest numerator of z's pattern)
-    double y = 0.0, nmx = -1.0;
-    int cnt = 0;
-    for (int64_t k = s + lane; k < e; k += RP_SUB) {
-      const double v = numer(k);
-      y += (A.zin && isnan(v)) ? 0.0 : v;
-      if (A.zin ? !isnan(v) : (initial || v != 0.0)) { nmx = fmax(nmx, v); ++cnt; }
-    }
-    y = sg_sum<RP_SUB>(y);
-    nmx = sg_max<RP_SUB>(nmx);
-    cnt = sg_sum_i<RP_SUB>(cnt);
-    double r = A.zin ? 1.0 : recip0(y);
-    const double rz = r;                                    // TAGS: z as RP_EXPORT_Z forms it
-    if (FIX) {                                              // a near-tie: the row sum in the reference's order (see near_band)
-      double ex = 0.0;
-      if (lane == 0) {
-        const NpRow nr{A.lut, A.raw, A.indices, nullptr, initial ? nullptr : (amb ? A.cnat : A.pi), 0u, s};
-        ex = np_row_sum(nr, cnt, initial);
-        if (A.exact_n) atomicAdd(A.exact_n, 1ull);
-      }
-      r = recip0(__shfl(ex, 0, RP_SUB));
-    } else if (MODE != RP_EXPORT_Z && !A.zin && A.flag_bits) {     // is it one?  Then it is left to the FIX launch
-      const bool uses_thresh = MODE == RP_REPORT || method == TSEM_RA_CONF;
-      const double band = near_band(e - s), lo = nmx * (1.0 - band), tb = A.thresh * band;
-      int nf = 0;
-      for (int64_t k = s + lane; k < e; k += RP_SUB) {
-        const double v = numer(k);
-        if ((initial || v != 0.0) && ((v >= lo && v != nmx) || (uses_thresh && fabs(v * r - A.thresh) <= tb))) nf = 1;
-      }
-      if (sg_max_i<RP_SUB>(nf)) {
-        if (lane == 0) { atomicOr(&A.flag_bits[idx >> 5], 1u << (idx & 31)); atomicAdd(A.flag_n, 1ull); }
-        continue;
-      }
-    }
-    // sweep 2: row max over z's pattern
-    double zmax = -1.0;
-    for (int64_t k = s + lane; k < e; k += RP_SUB) {
-      double n = numer(k);
-      bool inpat = A.zin ? !isnan(n) : (initial || (n != 0.0));
-      if (inpat) zmax = fmax(zmax, n * r);
-    }
-    zmax = sg_max<RP_SUB>(zmax);
-    if (MODE == RP_EXPORT_Z) {
-      for (int64_t k = s + lane; k < e; k += RP_SUB) {
-        double n = numer(k);
-        bool inpat = A.zin ? !isnan(n) : (initial || (n != 0.0));
-        A.zout[k + zo] = inpat ? n * r : -1.0;   // -1 marks an entry the reference drops from z's pattern
-      }
-      continue;
-    }
-    // sweep 3: number of best hits (binmax, sparse_plus.py:117-129)
-    int nb = 0;
-    for (int64_t k = s + lane; k < e; k += RP_SUB) {
-      double n = numer(k);
-      bool inpat = A.zin ? !isnan(n) : (initial || (n != 0.0));
-      if (inpat && (n * r) == zmax) ++nb;
-    }
-    nb = sg_sum_i<RP_SUB>(nb);
-    if (MODE == RP_BEST) {
-      if (lane == 0) A.nbest[row] = cnt ? nb : 0;
-      continue;
-    }
-    // ---- reassign ----
-    double vsum = 0.0;
-    if (method == TSEM_RA_CONF || MODE == RP_REPORT) {
-      for (int64_t k = s + lane; k < e; k += RP_SUB) {
-        double n = numer(k);
-        double z = n * r;
-        if ((A.zin ? !isnan(n) : (initial || n != 0.0)) && z >= A.thresh) vsum += z;
-      }
-      vsum = sg_sum<RP_SUB>(vsum);
-    }
-    if (MODE == RP_REPORT) {
-      if (lane == 0 && A.nbest) A.nbest[row] = cnt ? nb : 0;
-      for (int64_t k = s + lane; k < e; k += RP_SUB) {
-        const double n = numer(k);
-        const bool inpat = A.zin ? !isnan(n) : (initial || n != 0.0);
-        const double z = n * r;
-        const bool best = inpat && (z == zmax);
-        const double vc = (inpat && z >= A.thresh) ? z * recip0(vsum) : 0.0;
-        if (best || vc != 0.0) {
-          const int col = A.indices[k];
-          const uint32_t cm = nhot1 ? A.colmap[col] : 0xFFFFFFFFu;
-          if (vc != 0.0) emit(0, col, cm, vc, 0);
-          if (best && nb == 1) emit(1, col, cm, 1.0, 0);
-          if (best) emit(2, col, cm, 1.0 * recip0((double)nb), 0);
-        }
-      }
-      continue;
-    }
-    const int pick = (method == TSEM_RA_CHOOSE && A.picks && nb > 1) ? A.picks[(A.rowlist || MODE == RP_TAGS) ? idx : row] : 0;
-    const int64_t grp_off = A.group ? ((A.group[row] < A.g0 || A.group[row] >= A.g1) ? -1 : (int64_t)(A.group[row] - A.g0) * A.K) : 0;
-    int base = 0;
-    for (int64_t k0 = s; k0 < e; k0 += RP_SUB) {
-      int64_t k = k0 + lane;
-      bool valid = k < e;
-      double n = valid ? numer(k) : 0.0;
-      bool inpat = valid && (A.zin ? !isnan(n) : (initial || n != 0.0));
-      double z = n * r;
-      bool best = inpat && (z == zmax);
-      unsigned long long bal = __ballot(best);
-      unsigned grp = (unsigned)((bal >> ((threadIdx.x & 63) / RP_SUB * RP_SUB)) & 0xFFFFull);
-      int ord = base + __popc(grp & ((1u << lane) - 1u));
-      base += __popc(grp);
-      double val = 0.0;
-      switch (method) {
-        case TSEM_RA_EXCLUDE: val = (best && nb == 1) ? 1.0 : 0.0; break;
-        case TSEM_RA_CHOOSE:  val = (best && ord == pick) ? 1.0 : 0.0; break;
-        case TSEM_RA_AVERAGE: val = best ? 1.0 * recip0((double)nb) : 0.0; break;
-        case TSEM_RA_CONF:    val = (inpat && z >= A.thresh) ? z * recip0(vsum) : 0.0; break;
-        case TSEM_RA_UNIQUE:  val = (inpat && !amb) ? ceil(z) : 0.0; break;
-        case TSEM_RA_ALL:     val = (inpat && z > 0.0) ? 1.0 : 0.0; break;
-      }
-      if (MODE == RP_TAGS) {
-        if (valid) A.tags[k + zo] = ts_tag_word(ptab, inpat ? n * rz : 0.0, val > 0.0);
-        continue;
-      }
-      if (valid) {
         if (A.zout) A.zout[k + zo] = val;
         if (val != 0.0 && grp_off >= 0 && A.colsums) {
           const int col = A.indices[k];
           emit(0, col, nhot1 ? A.colmap[col] : 0xFFFFFFFFu, val, grp_off);
         }
-      }
-    }
+      });
+    };
+    if (e - s <= 4 * RP_SUB) row_body(RowTile<decltype(numer)>(numer, A.zin != nullptr, initial, s, e, lane));
+    else row_body(RowSweep<decltype(numer)>(numer, A.zin != nullptr, initial, s, e, lane));
    }
    }
   }
@@ -954,16 +872,11 @@ __global__ __launch_bounds__(256) void k_report_slow(ReportArgs A) {
       int nf = rcode < 0 ? 1 : 0;
       for (int k = gl; k < len; k += G) {
         const double n = numer(k);
-        if ((INIT || n != 0.0) && ((n >= lo && n != nmx) || fabs(n * r - A.thresh) <= tb)) nf = 1;
+        if ((INIT || n != 0.0) && near_tie(n, r, nmx, lo, true, A.thresh, tb)) nf = 1;
       }
       if (sg_max_i<G>(nf)) {
-        double ex = 0.0;
-        if (gl == 0) {
-          const NpRow nr{A.lut, A.raw, nullptr, A.rid, INIT ? nullptr : A.cnat2, coff, s};
-          ex = np_row_sum(nr, cnt, INIT);
-          if (A.exact_n) atomicAdd(A.exact_n, 1ull);
-        }
-        r = recip0(__shfl(ex, 0, G));
+        const NpRow nr{A.lut, A.raw, nullptr, A.rid, INIT ? nullptr : A.cnat2, coff, s};
+        r = np_row_recip<G>(nr, cnt, INIT, gl, A.exact_n);
       }
     }
     double zmax = -1.0, vs = 0.0;
@@ -1240,8 +1153,7 @@ static int launch_rowpass(tsem_ctx* h, int mode, int meth, int grid, int block, 
 static int rowpass_args(tsem_ctx* h, int which, RowPassArgs& A) {
   if (int rc = exact_counter(h, &A.exact_n)) return rc;
   A.N = h->N; A.K = h->K; A.indptr = h->d_indptr; A.indices = h->d_indices; A.raw = h->d_raw; A.lut = h->d_lut;
-  A.method = 0; A.thresh = 0; A.picks = nullptr; A.zout = nullptr; A.nbest = nullptr; A.colsums = nullptr; A.group = nullptr; A.rowlist = nullptr; A.nlist = 0; A.colmap = nullptr; A.col_of_pc = nullptr; A.P = 0; A.Kp = 0; A.Hs = 0;
-  A.zin = nullptr; A.cnat = nullptr; A.lut_len = h->lut_len <= 2048 ? h->lut_len : 0;   // (larger tables stay in global memory)
+  A.lut_len = h->lut_len <= 2048 ? h->lut_len : 0;   // (larger tables stay in global memory)
   if (which == TSEM_Z_USER) {
     if (!h->d_user_z) TSEM_FAIL(TSEM_ERR_ARG, "TSEM_Z_USER without tsem_set_user_z");
     A.pi = h->d_pi; A.theta = h->d_theta; A.zin = h->d_user_z;

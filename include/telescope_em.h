@@ -401,7 +401,8 @@ int  tsem_csr_scale(int device, int mode, int64_t n_rows, int32_t n_cols, const 
 /* ---- instrumentation ------------------------------------------------------ */
 /* HIP-event time (ms) and number of TIMED launches of the dominant EM kernel(s) since the
  * last call with reset=1 (option "kernel_timing" = n times every n-th pass, 0 none; default 1);
- * algorithmic bytes one EM pass reads.  */
+ * algorithmic bytes one EM pass reads, as stored: per entry 6 (score codes), 11 (fp64 values behind the 3-byte index) or 12, plus
+ * 2 per row.  */
 int  tsem_kernel_stats(tsem_ctx* h, int reset, double* em_ms, int64_t* em_launches,
                        int64_t* algo_bytes_per_pass);
 /* The last tsem_report_colsums of the handle: HIP-event time (ms) of its dominant kernel — the pass over the stored entries — when
@@ -417,7 +418,7 @@ int  tsem_report_stats(tsem_ctx* h, double* kernel_ms, int64_t* algo_bytes, int6
 int  tsem_phase_times(tsem_ctx* h, int reset, double* ms6, int64_t* n_iter);
 /* Free / total bytes of the device's memory (hipMemGetInfo; h may be NULL, then `device` is asked) and, with a handle, the bytes its
  * matrix keeps resident: resident5 = { CSR row pointers + scores | CSR column ids (0 after option "drop_csr_indices") | popularity
- * ids | blocked layout | per-row arrays }.  What a capacity plan needs: 14 B per stored entry by default (score codes), 10 after
+ * ids | blocked layout (its index at 3 or 4 B per padded entry, see tsem_layout_info_n [32]) | per-row arrays }.  What a capacity plan needs: 14 B per stored entry by default (score codes), 10 after
  * the drop, + ~20 B per row. */
 int  tsem_device_memory(tsem_ctx* h, int device, int64_t* free_bytes, int64_t* total_bytes, int64_t* resident5);
 /* Facts about the resident layout, 32 values (the Python binding names them: _lib.Engine.layout_info).  Of the later ones: [23] the
@@ -428,13 +429,23 @@ int  tsem_device_memory(tsem_ctx* h, int device, int64_t* free_bytes, int64_t* t
  * additions (scipy's `sum(axis=1)` = np.add.reduceat: a0 + pairwise(a1 ..)) since the matrix was loaded — the rows where two z values,
  * or a z value and conf_prob, are closer than the rounding of 1 / rowsum could decide (sparse_plus.py:99-129 compares with `==`). */
 int  tsem_layout_info(tsem_ctx* h, int64_t* info32);
+/* The same with the caller's buffer length: the first min(n, TSEM_LAYOUT_INFO_N) values.  Appended behind the 32 above: [32] bytes of
+ * index per stored entry of the blocked layout — 3 where the fused kernel reads fp64 entries of a non-split layout (a 13-bit column
+ * slot and an 11-bit row slot per entry, four entries in 12 bytes), 4 (local row << 16 | local column) everywhere else. */
+#define TSEM_LAYOUT_INFO_N 33
+int  tsem_layout_info_n(tsem_ctx* h, int64_t* info, int32_t n);
 /* per-block shader-clock stamps of team 0 / member 0 of the fused kernel (option "fused_prof") */
 int  tsem_debug_fused_prof(tsem_ctx* h, uint64_t* out512);
 /* the same option's start-up timeline: per workgroup b (up to 512), out[8 b ..] = 100 MHz wall clock at entry / tickets counted /
  * LDS zeroed / tables loaded / loop start / loop end / exit, and (team << 32 | member << 16 | blocks) */
 int  tsem_debug_fused_startup(tsem_ctx* h, uint64_t* out4096);
-/* the packed local row / local column words of one sub-block of the blocked layout (layout studies) */
+/* the local row << 16 | local column words of one sub-block of the blocked layout (layout studies); a layout that stores the 3-byte
+ * index (tsem_layout_info_n [32] == 3) is decoded on the host: the same words either way */
 int64_t tsem_debug_subblock(tsem_ctx* h, int64_t block, int32_t part, uint32_t* out, int64_t cap);
+/* host only, no device: four local row << 16 | local column words (rows < 2048, columns < 8192; TSEM_ERR_ARG otherwise) packed into
+ * the 12 bytes of a quad of the 3-byte index — entry k is the 24-bit little-endian number row << 13 | column at bytes 3k .. 3k+2 —
+ * and unpacked again into back4, both with the inline functions the fill kernels and the fused kernel use */
+int  tsem_debug_idx24(const uint32_t* rc4, uint8_t* out12, uint32_t* back4);
 /* y[i] = the device log1p the lnl passes use (finite x >= 0), for accuracy tests against libm */
 int  tsem_debug_log1p(int device, int32_t n, const double* x, double* y);
 /* out[i] = the PHRED lookup of tsem_entry_tags for p[i] (the table as there), for tests against numpy */

@@ -231,6 +231,7 @@ def lib():
     L.tsem_phase_times.argtypes = [vp, C.c_int, vp, C.POINTER(i64)]
     L.tsem_device_memory.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64), vp]
     L.tsem_layout_info.argtypes = [vp, vp]
+    L.tsem_layout_info_n.argtypes = [vp, vp, i32]
     L.tsem_debug_fused_prof.argtypes = [vp, vp]
     L.tsem_debug_fused_startup.argtypes = [vp, vp]
     L.tsem_debug_log1p.argtypes = [C.c_int, C.c_int32, vp, vp]
@@ -239,6 +240,7 @@ def lib():
     L.tsem_debug_phred.argtypes = [C.c_int, C.c_int32, vp, vp, C.c_int32, vp]
     L.tsem_debug_stream_read.argtypes = [C.c_int, i64, i32, C.POINTER(dbl)]
     L.tsem_debug_subblock.argtypes = [vp, C.c_int64, C.c_int32, vp, C.c_int64]
+    L.tsem_debug_idx24.argtypes = [vp, vp, vp]
     for name in exported_symbols():
         fn = getattr(L, name)
         if name not in ('tsem_destroy', 'tsem_last_error', 'tsem_comm_destroy', 'tsem_comm_last_error',
@@ -658,11 +660,11 @@ class Engine(object):
         return out[:n]
 
     def layout_info(self):
-        info = np.zeros(32, np.int64)
-        self._ck(self._L.tsem_layout_info(self._h, ptr(info)))
+        info = np.zeros(33, np.int64)
+        self._ck(self._L.tsem_layout_info_n(self._h, ptr(info), info.size))
         return dict(zip(('P', 'Kp', 'R', 'nb', 'N_amb', 'N_uni', 'nnz_amb', 'nnz_pad', 'twin_cols',
                          'G1', 'G2', 'fused', 'slow_path', 'max_subblock', 'value_bytes', 'hot_cols',
-                         'lds_bytes', 'row_order', 'geometry', 'fallbacks', 'bin_repeats', 'reproducible', 'exact_single', 'lnl_fused', 'split', 'single_part_rows', 'row_pass_em', 'lnl_tables', 'lnl_linear', 'lnl_mid_entries', 'lnl_mid_limit', 'near_tie_rows'), info.tolist()))
+                         'lds_bytes', 'row_order', 'geometry', 'fallbacks', 'bin_repeats', 'reproducible', 'exact_single', 'lnl_fused', 'split', 'single_part_rows', 'row_pass_em', 'lnl_tables', 'lnl_linear', 'lnl_mid_entries', 'lnl_mid_limit', 'near_tie_rows', 'index_bytes'), info.tolist()))
 
 
 def legacy_randint(counts):

@@ -173,7 +173,8 @@ struct tsem_ctx {
   int hot_extra = 0;                // spare slots per part reserved for them
   int n_hot_cols = 0;               // columns that were split
   int64_t opt_format = 0;           // 0 auto (codes when the fused kernel runs and the table fits LDS), 1 fp64, 2 codes
-  uint32_t* d_prc = nullptr;        // [nnz_pad]  lrow<<16 | lcol
+  uint32_t* d_prc = nullptr;        // [nnz_pad]  lrow<<16 | lcol — or, idx24, 3 bytes per entry (tsem_idx24.h)
+  bool idx24 = false;               // d_prc holds the 3-byte packed index: fused kernel, non-split layout, fp64 entries (set by every layout build)
   double* d_ypart = nullptr;        // [P][N_amb_pad] partial row sums
   int G1 = 1, G2 = 1, T1 = 512, T2 = 1024;
   double* d_partial = nullptr;      // [G2][Kpad]

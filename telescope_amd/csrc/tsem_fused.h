@@ -25,9 +25,10 @@
 //     distance 2 steps, so every stored entry is read from HBM exactly once and the
 //     memory pipe never drains (data-path ceiling of this schedule: 6.2 TB/s,
 //     tools/ubench/ring.hip);
-//   * entries are 4 B (local row, local column) + either the fp64 Q value (FMT 0) or
+//   * entries are an index (local row, local column) + either the fp64 Q value (FMT 0, 2) or
 //     its 2-byte score code, looked up in an LDS copy of the score table (FMT 1): the
-//     same fp64 number at half the HBM bytes;
+//     same fp64 number at half the HBM bytes.  The index is 3 B next to fp64 values (11 B
+//     per entry: the pass is bound by the bytes it reads; tsem_idx24.h) and 4 B elsewhere;
 //   * a sub-block is stored in row order, so the row sums are reduced in registers and
 //     across lanes (fz_row_sums) and only the end of each run of equal rows issues an
 //     LDS atomic: ds_add_f64 costs 3x a gather (profiles/r01_lds_ubench.log).
@@ -35,6 +36,7 @@
 // their size and the block round-robin all derive from tickets taken at run
 // time; every wait is bounded and reports through an error word.
 #pragma once
+#include "tsem_idx24.h"
 
 constexpr int FZ_NT = 1024;            // threads per workgroup
 // Geometry (GEO): the exchange waves keep (P-1) partner values per row pair in registers, so larger
@@ -80,7 +82,7 @@ struct FusedArgs {
   const double* lut;        // FMT 1: the score table, copied to LDS [lut_len]
   int lut_len;
   const uint16_t* wcode;    // FMT 1: [N_amb_pad] row weight as a code, w_i = lut[max code of the row]
-  const uint32_t* prc;
+  const uint32_t* prc;      // entry index: 3 B per entry where fz_idx24(MODE, FMT), else one lrow << 16 | lcol word
   const double* ctab;
   const double* ctab2;  // lnl mode: pi*theta of the CURRENT params (ctab then holds the previous ones); MODE 4: of the PREVIOUS params
   double* lnl_out;      // lnl mode: one partial sum per workgroup [grid]
@@ -148,6 +150,7 @@ __device__ __forceinline__ uint32_t fz_ld_u32(const uint32_t* p) {
 // memory pipe twice per step (measured: 6.09 -> 5.04 ms per pass, profiles/HISTORY.md 4.1).
 typedef unsigned int fz_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int fz_u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int fz_u32x3 __attribute__((ext_vector_type(3)));
 constexpr int FZ_RSRC_FLAGS = 0x00027000;
 constexpr int FZ_STREAM = 2;                             // cache policy of the entry loads: nt (read once) keeps the
                                                          // exchange ring and the tables in L2 (fp64 entries: -3.6 %)
@@ -279,11 +282,28 @@ __device__ __forceinline__ double fz_logq_of(double q, const double* __restrict_
   return lqS[min(idx, (unsigned)(lq_n - 1))];              // (Q = 0, the padding: some finite entry; its z is 0)
 }
 
-struct FzRegs {            // 4 entries per thread: 12 VGPRs (FMT 1: 6 until phase 1 turns the codes into numerators)
-  uint4 rc;
+struct FzRegs {            // 4 entries per thread: 12 VGPRs (packed index: 11; FMT 1: 6 until phase 1 turns the codes into numerators)
+  uint4 rc;                // packed index: the quad's three words in x, y, z (w is never read: no register)
   double2 v0, v1;
   uint2 cd;
 };
+// Which instantiations read the packed 3-byte index (tsem_idx24.h): fp64 entries on the non-split layout.  The layout build stores
+// it under the same condition (tsem_setup.hip, h->idx24): the width is a property of the instantiation, never a run-time branch.
+// (MODE 4 exists for score codes only; the split layout's parts of up to 15 424 columns do not fit 13 bits.)
+__host__ __device__ constexpr bool fz_idx24(int mode, int fmt) {
+  return fmt != 1 && (mode == 0 || mode == 1 || mode == 2 || mode == 3 || mode == 9);
+}
+// Row slot / column slot of entry K of a register set.  The packed index is unpacked HERE, at each use (phase 1, and again in
+// phase 2 four steps later), from the three words the load left: unpacked at the load, the issue would wait for the data.
+constexpr uint32_t FZ_IDLE = 0xFFFFFFFFu;                  // rc.x of a set that holds nothing (packed: row slot 2047, which no layout has)
+template <bool I24, int K> __device__ __forceinline__ uint32_t fz_row(const uint4& rc) {
+  if constexpr (I24) return ts_idx24_row<K>(rc.x, rc.y, rc.z);
+  else return (K == 0 ? rc.x : (K == 1 ? rc.y : (K == 2 ? rc.z : rc.w))) >> 16;
+}
+template <bool I24, int K> __device__ __forceinline__ uint32_t fz_col(const uint4& rc) {
+  if constexpr (I24) return ts_idx24_col<K>(rc.x, rc.y, rc.z);
+  else return (K == 0 ? rc.x : (K == 1 ? rc.y : (K == 2 ? rc.z : rc.w))) & 0xFFFFu;
+}
 
 struct FzX {                 // context handed to the exchange wave
   const double* lut;
@@ -571,6 +591,7 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
   constexpr bool LAG = MODE == 4;                  // EM pass + the log-likelihood of the previous iteration
   constexpr bool LNL1 = MODE == 1 || MODE == 9;    // the dedicated log-likelihood pass; MODE 9: log tables in LDS (score table in LDS: FMT 1, 2)
   constexpr bool SPA = MODE == 5, SPB = MODE == 7, SPL = MODE == 8;   // split layout (see FusedArgs): ONE table of Kp entries, or two of Kh
+  constexpr bool I24 = fz_idx24(MODE, FMT);        // 3-byte packed entry index (else 4 B)
   const int KT = SPL ? A.Kh : Kp;                  // entries per LDS table
   double* c = reinterpret_cast<double*>(smem);
   double* acc = (SPA || SPB) ? c : c + KT;         // (MODE 5 has no accumulators, MODE 7 no pi*theta table)
@@ -734,8 +755,13 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
     auto load_blk = [&](FzRegs& rr, uint32_t oq0v, uint32_t oq1v, int64_t k) {
       const uint32_t oq0 = __builtin_amdgcn_readfirstlane(oq0v);
       const uint32_t nq = (k >= 0 && k < nblk) ? __builtin_amdgcn_readfirstlane(oq1v) - oq0 : 0u;
-      fz_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(fz_rsrc(A.prc, (uint64_t)oq0 * 16, nq * 16), (unsigned)tid * 16, 0, FZ_STREAM);
-      rr.rc = make_uint4(t.x, t.y, t.z, t.w);
+      if constexpr (I24) {                                // the quad's index: 12 bytes, one load
+        fz_u32x3 t = __builtin_amdgcn_raw_buffer_load_b96(fz_rsrc(A.prc, (uint64_t)oq0 * 12, nq * 12), (unsigned)tid * 12, 0, FZ_STREAM);
+        rr.rc = make_uint4(t.x, t.y, t.z, 0u);
+      } else {
+        fz_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(fz_rsrc(A.prc, (uint64_t)oq0 * 16, nq * 16), (unsigned)tid * 16, 0, FZ_STREAM);
+        rr.rc = make_uint4(t.x, t.y, t.z, t.w);
+      }
       if (FMT == 1) {
         fz_u32x2 cd = __builtin_amdgcn_raw_buffer_load_b64(fz_rsrc(A.pcode, (uint64_t)oq0 * 8, nq * 8), (unsigned)tid * 8, 0, FZ_STREAM);
         rr.cd = make_uint2(cd.x, cd.y);
@@ -753,8 +779,8 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
     auto phase1 = [&](FzRegs& rr, int64_t k) {
       const bool idle = FMT == 1 ? (rr.cd.x | rr.cd.y) == 0u
                                  : (rr.v0.x == 0.0) & (rr.v0.y == 0.0) & (rr.v1.x == 0.0) & (rr.v1.y == 0.0);
-      if (SPL) { if (idle) rr.rc.x = 0xFFFFFFFFu; return; }    // (the row factors come from pass A: nothing to sum)
-      if (__builtin_amdgcn_ballot_w64(!idle) == 0) { rr.rc.x = 0xFFFFFFFFu; return; }   // whole wave idle
+      if (SPL) { if (idle) rr.rc.x = FZ_IDLE; return; }    // (the row factors come from pass A: nothing to sum)
+      if (__builtin_amdgcn_ballot_w64(!idle) == 0) { rr.rc.x = FZ_IDLE; return; }   // whole wave idle
       double* yb = y + (k & (FZ_YR - 1)) * R;
       double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0;
       if (!idle) {
@@ -763,37 +789,37 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
           q0 = make_double2(lutS[rr.cd.x & 0xFFFFu], lutS[rr.cd.x >> 16]);
           q1 = make_double2(lutS[rr.cd.y & 0xFFFFu], lutS[rr.cd.y >> 16]);
         }
-        m0 = q0.x * c[rr.rc.x & 0xFFFF]; m1 = q0.y * c[rr.rc.y & 0xFFFF];
-        m2 = q1.x * c[rr.rc.z & 0xFFFF]; m3 = q1.y * c[rr.rc.w & 0xFFFF];
+        m0 = q0.x * c[fz_col<I24, 0>(rr.rc)]; m1 = q0.y * c[fz_col<I24, 1>(rr.rc)];
+        m2 = q1.x * c[fz_col<I24, 2>(rr.rc)]; m3 = q1.y * c[fz_col<I24, 3>(rr.rc)];
         // EM: the set keeps the numerators for phase 2.  lnl: phase 2 needs Q itself (twice) — the fp64
         // layout has it in the set already, the code layout looks it up again (2 registers per set
         // instead of 8: with four log1p expansions in flight the lnl kernel would spill otherwise)
         if (!lnl) { rr.v0 = make_double2(m0, m1); rr.v1 = make_double2(m2, m3); }
       }
       if (A.sorted) {
-        fz_row_sums(yb, idle, rr.rc.x >> 16, rr.rc.y >> 16, rr.rc.z >> 16, rr.rc.w >> 16, m0, m1, m2, m3);
+        fz_row_sums(yb, idle, fz_row<I24, 0>(rr.rc), fz_row<I24, 1>(rr.rc), fz_row<I24, 2>(rr.rc), fz_row<I24, 3>(rr.rc), m0, m1, m2, m3);
       } else if (!idle) {                                  // strand-transposed order: neighbouring entries never share a row
-        lds_add(&yb[rr.rc.x >> 16], m0); lds_add(&yb[rr.rc.y >> 16], m1);
-        lds_add(&yb[rr.rc.z >> 16], m2); lds_add(&yb[rr.rc.w >> 16], m3);
+        lds_add(&yb[fz_row<I24, 0>(rr.rc)], m0); lds_add(&yb[fz_row<I24, 1>(rr.rc)], m1);
+        lds_add(&yb[fz_row<I24, 2>(rr.rc)], m2); lds_add(&yb[fz_row<I24, 3>(rr.rc)], m3);
       }
-      if (idle) rr.rc.x = 0xFFFFFFFFu;
+      if (idle) rr.rc.x = FZ_IDLE;
     };
     // phase 2: scatter w * z into the part's column accumulators
     auto phase2 = [&](FzRegs& rr, int64_t k) {
-      if (rr.rc.x == 0xFFFFFFFFu) return;
+      if (rr.rc.x == FZ_IDLE) return;
       const double* sb = s + (k & 1) * R;
       if (lnl) {                                          // z = (Q c_prev) * recip0(rowsum);  acc[] holds c_cur
-        auto term = [&](double q, uint32_t rc) {
+        auto term = [&](double q, uint32_t row, uint32_t col) {
           if (SPL) {                                      // only the entries whose column lies in this launch's half
-            const uint32_t j = (rc & 0xFFFFu) - (uint32_t)A.koff;
+            const uint32_t j = col - (uint32_t)A.koff;
             if (j < (uint32_t)KT) {
-              const double z = (q * c[j]) * sb[rc >> 16];
+              const double z = (q * c[j]) * sb[row];
               if (z != 0.0) lsum += z * fz_log1p_tab(q * acc[j], logtab);
             }
             return;
           }
-          const double z = (q * c[rc & 0xFFFF]) * sb[rc >> 16];
-          if (z != 0.0) lsum += z * fz_log1p_tab(q * acc[rc & 0xFFFF], logtab);
+          const double z = (q * c[col]) * sb[row];
+          if (z != 0.0) lsum += z * fz_log1p_tab(q * acc[col], logtab);
         };
         if constexpr (LT) {
           // log tables: acc[] holds log(pi*theta) of the current parameters, lqS[] log Q: an addition instead of a logarithm per
@@ -801,9 +827,8 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
           // the compiler moves no load: term by term it was four round trips) — then their arithmetic: all four entries with score
           // codes, two and two with fp64 entries (whose six register sets of 12 leave no room for four: 56 VGPRs spilled).
           const double* const cg = A.ctab2 + p * Kp;     // pi*theta of the current parameters in global memory (the rare range only)
-          auto pair = [&](double qa, double qb, double la, double lb, uint32_t rca, uint32_t rcb) {
-            const uint32_t ja = rca & 0xFFFF, jb = rcb & 0xFFFF;
-            const double za = (qa * c[ja]) * sb[rca >> 16], zb = (qb * c[jb]) * sb[rcb >> 16];
+          auto pair = [&](double qa, double qb, double la, double lb, uint32_t ia, uint32_t ib, uint32_t ja, uint32_t jb) {
+            const double za = (qa * c[ja]) * sb[ia], zb = (qb * c[jb]) * sb[ib];
             const double La = la + acc[ja], Lb = lb + acc[jb];
             __builtin_amdgcn_sched_barrier(0);
             lsum = fma(za, fz_log1p_of_log<true>(La, [&]() { return qa * cg[ja]; }, logtab, false, za != 0.0), lsum);   // (always finite; padding has z = 0)
@@ -811,10 +836,10 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
           };
           if (FMT == 1) {
             const uint32_t k0 = rr.cd.x & 0xFFFFu, k1 = rr.cd.x >> 16, k2 = rr.cd.y & 0xFFFFu, k3 = rr.cd.y >> 16;
-            const uint32_t j0 = rr.rc.x & 0xFFFF, j1 = rr.rc.y & 0xFFFF, j2 = rr.rc.z & 0xFFFF, j3 = rr.rc.w & 0xFFFF;
+            const uint32_t j0 = fz_col<I24, 0>(rr.rc), j1 = fz_col<I24, 1>(rr.rc), j2 = fz_col<I24, 2>(rr.rc), j3 = fz_col<I24, 3>(rr.rc);
             const double q0 = lutS[k0], q1 = lutS[k1], q2 = lutS[k2], q3 = lutS[k3];
-            const double z0 = (q0 * c[j0]) * sb[rr.rc.x >> 16], z1 = (q1 * c[j1]) * sb[rr.rc.y >> 16];
-            const double z2 = (q2 * c[j2]) * sb[rr.rc.z >> 16], z3 = (q3 * c[j3]) * sb[rr.rc.w >> 16];
+            const double z0 = (q0 * c[j0]) * sb[fz_row<I24, 0>(rr.rc)], z1 = (q1 * c[j1]) * sb[fz_row<I24, 1>(rr.rc)];
+            const double z2 = (q2 * c[j2]) * sb[fz_row<I24, 2>(rr.rc)], z3 = (q3 * c[j3]) * sb[fz_row<I24, 3>(rr.rc)];
             const bool lin = A.lq_lin != 0;                // (a kernel argument: wave-uniform)
             double l0, l1, l2, l3;
             bool f0 = false, f1 = false, f2 = false, f3 = false;
@@ -831,32 +856,33 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
             lsum = fma(z3, fz_log1p_of_log<true>(L3, [&]() { return q3 * cg[j3]; }, logtab, f3, z3 != 0.0), lsum);
           } else {
             pair(rr.v0.x, rr.v0.y, fz_logq_of(rr.v0.x, lqS, A.lq_n, A.lq_shift, A.lq_base), fz_logq_of(rr.v0.y, lqS, A.lq_n, A.lq_shift, A.lq_base),
-                 rr.rc.x, rr.rc.y);
+                 fz_row<I24, 0>(rr.rc), fz_row<I24, 1>(rr.rc), fz_col<I24, 0>(rr.rc), fz_col<I24, 1>(rr.rc));
             pair(rr.v1.x, rr.v1.y, fz_logq_of(rr.v1.x, lqS, A.lq_n, A.lq_shift, A.lq_base), fz_logq_of(rr.v1.y, lqS, A.lq_n, A.lq_shift, A.lq_base),
-                 rr.rc.z, rr.rc.w);
+                 fz_row<I24, 2>(rr.rc), fz_row<I24, 3>(rr.rc), fz_col<I24, 2>(rr.rc), fz_col<I24, 3>(rr.rc));
           }
           return;
         }
         if (FMT == 1) {
-          term(lutS[rr.cd.x & 0xFFFFu], rr.rc.x); term(lutS[rr.cd.x >> 16], rr.rc.y);
-          term(lutS[rr.cd.y & 0xFFFFu], rr.rc.z); term(lutS[rr.cd.y >> 16], rr.rc.w);
+          term(lutS[rr.cd.x & 0xFFFFu], fz_row<I24, 0>(rr.rc), fz_col<I24, 0>(rr.rc)); term(lutS[rr.cd.x >> 16], fz_row<I24, 1>(rr.rc), fz_col<I24, 1>(rr.rc));
+          term(lutS[rr.cd.y & 0xFFFFu], fz_row<I24, 2>(rr.rc), fz_col<I24, 2>(rr.rc)); term(lutS[rr.cd.y >> 16], fz_row<I24, 3>(rr.rc), fz_col<I24, 3>(rr.rc));
         } else {
-          term(rr.v0.x, rr.rc.x); term(rr.v0.y, rr.rc.y); term(rr.v1.x, rr.rc.z); term(rr.v1.y, rr.rc.w);
+          term(rr.v0.x, fz_row<I24, 0>(rr.rc), fz_col<I24, 0>(rr.rc)); term(rr.v0.y, fz_row<I24, 1>(rr.rc), fz_col<I24, 1>(rr.rc));
+          term(rr.v1.x, fz_row<I24, 2>(rr.rc), fz_col<I24, 2>(rr.rc)); term(rr.v1.y, fz_row<I24, 3>(rr.rc), fz_col<I24, 3>(rr.rc));
         }
         return;
       }
       // all four gathers first: an LDS atomic may alias a later LDS read as far as the compiler knows,
       // so `add(acc, v * s[..])` four times in a row serialises gather -> wait -> atomic -> gather ...
-      const double s0 = sb[rr.rc.x >> 16], s1 = sb[rr.rc.y >> 16], s2 = sb[rr.rc.z >> 16], s3 = sb[rr.rc.w >> 16];
-      lds_add(&acc[rr.rc.x & 0xFFFF], rr.v0.x * s0);
-      lds_add(&acc[rr.rc.y & 0xFFFF], rr.v0.y * s1);
-      lds_add(&acc[rr.rc.z & 0xFFFF], rr.v1.x * s2);
-      lds_add(&acc[rr.rc.w & 0xFFFF], rr.v1.y * s3);
+      const double s0 = sb[fz_row<I24, 0>(rr.rc)], s1 = sb[fz_row<I24, 1>(rr.rc)], s2 = sb[fz_row<I24, 2>(rr.rc)], s3 = sb[fz_row<I24, 3>(rr.rc)];
+      lds_add(&acc[fz_col<I24, 0>(rr.rc)], rr.v0.x * s0);
+      lds_add(&acc[fz_col<I24, 1>(rr.rc)], rr.v0.y * s1);
+      lds_add(&acc[fz_col<I24, 2>(rr.rc)], rr.v1.x * s2);
+      lds_add(&acc[fz_col<I24, 3>(rr.rc)], rr.v1.y * s3);
     };
     FzRegs r0, r1, r2, r3, r4, r5;
     {
       FzRegs z;                                           // sets that hold no block yet are idle
-      z.rc = make_uint4(0xFFFFFFFFu, 0, 0, 0); z.v0 = z.v1 = make_double2(0.0, 0.0); z.cd = make_uint2(0, 0);
+      z.rc = make_uint4(FZ_IDLE, 0, 0, 0); z.v0 = z.v1 = make_double2(0.0, 0.0); z.cd = make_uint2(0, 0);
       r0 = r1 = r2 = r3 = r4 = r5 = z;
     }
     int64_t i = 0;
@@ -888,7 +914,7 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       // (codes), 2.20 / 2.24 / 2.25 (fp64 entries); 40 per row 3.35 / 3.37 / 3.51 — nothing, then slower.  profiles/r04_ab_delay.txt)
       const int64_t k2 = i - FZ_LAG;
       const uint32_t on0 = offs[((i + FZ_DL + 1) & 7) * 2], on1 = offs[((i + FZ_DL + 1) & 7) * 2 + 1];   // burst of the NEXT step
-      const bool idle2 = rs.rc.x == 0xFFFFFFFFu;
+      const bool idle2 = rs.rc.x == FZ_IDLE;
       // (padding has code 0 / value 0 -> numerator 0: no branch needed around the products)
       const bool idle = FMT == 1 ? (rp.cd.x | rp.cd.y) == 0u
                                  : (rp.v0.x == 0.0) & (rp.v0.y == 0.0) & (rp.v1.x == 0.0) & (rp.v1.y == 0.0);
@@ -900,25 +926,26 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       const bool wave_idle = GEO >= 2 && !LAG &&   // (only the short-row geometry leaves whole waves idle; elsewhere the branch costs 1.5 %; MODE 4: it costs registers the log1p needs)
                              (__builtin_amdgcn_ballot_w64(!idle) | __builtin_amdgcn_ballot_w64(!idle2)) == 0ull;
       if (wave_idle) {
-        rp.rc.x = 0xFFFFFFFFu;
+        rp.rc.x = FZ_IDLE;
         if (pr) { A.prof[i * FZ_PROF_SLOTS + 1] = clock64(); A.prof[i * FZ_PROF_SLOTS + 3] = clock64(); }
       } else {
       // ---- gathers ----
-      const uint32_t a0 = idle2 ? 0u : rs.rc.x, a1 = rs.rc.y, a2 = rs.rc.z, a3 = rs.rc.w;
+      // (the mark cleared, an idle set decodes to valid slots: its other words are zeros, or a padding quad's last row and column 0)
+      const uint4 a = make_uint4(idle2 ? 0u : rs.rc.x, rs.rc.y, rs.rc.z, rs.rc.w);
       const double* sb = s + (k2 & 1) * R;
       // (Row order: gathering only the outer two row factors of a lane when no lane of the wave spans three rows
       // — two LDS reads less per lane — was tried twice: with the select at the top (a second LDS round trip) 4.20 ->
       // 4.30 ms, with the select deferred to phase 2 3.57 -> 3.73 ms (codes) / 4.09 -> 4.19 ms: the ballot, the
       // compares and the selects cost more issue slots than the two broadcast reads they save.)
       double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-      if (!SPA) { s0 = sb[a0 >> 16]; s1 = sb[a1 >> 16]; s2 = sb[a2 >> 16]; s3 = sb[a3 >> 16]; }
+      if (!SPA) { s0 = sb[fz_row<I24, 0>(a)]; s1 = sb[fz_row<I24, 1>(a)]; s2 = sb[fz_row<I24, 2>(a)]; s3 = sb[fz_row<I24, 3>(a)]; }
       double2 q0 = rp.v0, q1 = rp.v1;
       if (FMT == 1) {                                     // Q from the score table: the same fp64 the fp64 layout stores
         q0 = make_double2(lutS[rp.cd.x & 0xFFFFu], lutS[rp.cd.x >> 16]);
         q1 = make_double2(lutS[rp.cd.y & 0xFFFFu], lutS[rp.cd.y >> 16]);
       }
       double c0 = 1.0, c1 = 1.0, c2 = 1.0, c3 = 1.0;           // (MODE 7 scatters Q * s: the column's pi*theta is applied by k_colreduce)
-      if (!SPB) { c0 = c[rp.rc.x & 0xFFFF]; c1 = c[rp.rc.y & 0xFFFF]; c2 = c[rp.rc.z & 0xFFFF]; c3 = c[rp.rc.w & 0xFFFF]; }
+      if (!SPB) { c0 = c[fz_col<I24, 0>(rp.rc)]; c1 = c[fz_col<I24, 1>(rp.rc)]; c2 = c[fz_col<I24, 2>(rp.rc)]; c3 = c[fz_col<I24, 3>(rp.rc)]; }
       // ---- phase 1 of block i: numerators stay in the set, partial row sums into y(i) ----
       const double m0 = q0.x * c0, m1 = q0.y * c1, m2 = q1.x * c2, m3 = q1.y * c3;
       rp.v0 = make_double2(m0, m1); rp.v1 = make_double2(m2, m3);
@@ -927,21 +954,21 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       if (SPB) {
         // no row sums in the scatter pass
       } else if (A.sorted) {
-        fz_row_sums(yb, idle, rp.rc.x >> 16, rp.rc.y >> 16, rp.rc.z >> 16, rp.rc.w >> 16, m0, m1, m2, m3);
+        fz_row_sums(yb, idle, fz_row<I24, 0>(rp.rc), fz_row<I24, 1>(rp.rc), fz_row<I24, 2>(rp.rc), fz_row<I24, 3>(rp.rc), m0, m1, m2, m3);
       } else {                                            // strand-transposed order: neighbouring entries never share a row
         double* d = dum + lane_id;
-        lds_add(idle ? d : &yb[rp.rc.x >> 16], m0); lds_add(idle ? d : &yb[rp.rc.y >> 16], m1);
-        lds_add(idle ? d : &yb[rp.rc.z >> 16], m2); lds_add(idle ? d : &yb[rp.rc.w >> 16], m3);
+        lds_add(idle ? d : &yb[fz_row<I24, 0>(rp.rc)], m0); lds_add(idle ? d : &yb[fz_row<I24, 1>(rp.rc)], m1);
+        lds_add(idle ? d : &yb[fz_row<I24, 2>(rp.rc)], m2); lds_add(idle ? d : &yb[fz_row<I24, 3>(rp.rc)], m3);
       }
-      if (idle) rp.rc.x = 0xFFFFFFFFu;
+      if (idle) rp.rc.x = FZ_IDLE;
       if (pr) A.prof[i * FZ_PROF_SLOTS + 3] = clock64();
       asm volatile("" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       // ---- phase 2 of block i-LAG: w*z into the part's column accumulators; ALWAYS four atomics, issued last ----
       if (!SPA) {
         const uint32_t dj = (uint32_t)(dum - acc) + (uint32_t)lane_id;   // the lane's dummy slot as an index into acc[]
-        const uint32_t j0 = idle2 ? dj : (a0 & 0xFFFFu), j1 = idle2 ? dj : (a1 & 0xFFFFu);
-        const uint32_t j2 = idle2 ? dj : (a2 & 0xFFFFu), j3 = idle2 ? dj : (a3 & 0xFFFFu);
+        const uint32_t j0 = idle2 ? dj : fz_col<I24, 0>(a), j1 = idle2 ? dj : fz_col<I24, 1>(a);
+        const uint32_t j2 = idle2 ? dj : fz_col<I24, 2>(a), j3 = idle2 ? dj : fz_col<I24, 3>(a);
         if (EXACT) {
           // Exact accumulation (Demmel-Nguyen style pre-rounding on a per-slot grid): v = hi + lo + rest with hi a multiple of
           // 2^(E-30) and lo a multiple of 2^(E-60); the sums of the hi pieces (and of the lo pieces) of up to 2^23 contributions
@@ -983,7 +1010,7 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
         // pipe behind the stream; score codes are looked up again instead of keeping Q alive across the row sums.  `idle` lanes
         // have marked rc.x by now: their Q is 0, and lane-private garbage in rc.x >> 16 must not index LDS -> masked.
         const double* rb = rpS + (i & 1) * R;
-        const uint32_t e0 = idle ? 0u : rp.rc.x, e1 = rp.rc.y, e2 = rp.rc.z, e3 = rp.rc.w;
+        const uint4 e = make_uint4(idle ? 0u : rp.rc.x, rp.rc.y, rp.rc.z, rp.rc.w);
         // all gathers of the four entries first (one LDS round trip), then the four evaluations, each PINNED where it is written:
         // left alone, the compiler sinks the arithmetic below the barrier (nothing but `lsum` at the very end needs it), keeps the
         // twelve gathered values alive into the next step and spills the streaming loads' destinations
@@ -994,16 +1021,16 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
         };
         if (FMT == 1) {
           const double g0 = lutS[rp.cd.x & 0xFFFFu], g1 = lutS[rp.cd.x >> 16], g2 = lutS[rp.cd.y & 0xFFFFu], g3 = lutS[rp.cd.y >> 16];
-          const double p0 = cprev[e0 & 0xFFFF], p1 = cprev[e1 & 0xFFFF], p2 = cprev[e2 & 0xFFFF], p3 = cprev[e3 & 0xFFFF];
-          const double f0 = rb[e0 >> 16], f1 = rb[e1 >> 16], f2 = rb[e2 >> 16], f3 = rb[e3 >> 16];
+          const double p0 = cprev[fz_col<I24, 0>(e)], p1 = cprev[fz_col<I24, 1>(e)], p2 = cprev[fz_col<I24, 2>(e)], p3 = cprev[fz_col<I24, 3>(e)];
+          const double f0 = rb[fz_row<I24, 0>(e)], f1 = rb[fz_row<I24, 1>(e)], f2 = rb[fz_row<I24, 2>(e)], f3 = rb[fz_row<I24, 3>(e)];
           term(g0, p0, f0, m0); term(g1, p1, f1, m1); term(g2, p2, f2, m2); term(g3, p3, f3, m3);
         } else {                                          // fp64 entries keep Q alive (8 VGPRs): two entries per round trip
           {
-            const double p0 = cprev[e0 & 0xFFFF], p1 = cprev[e1 & 0xFFFF], f0 = rb[e0 >> 16], f1 = rb[e1 >> 16];
+            const double p0 = cprev[fz_col<I24, 0>(e)], p1 = cprev[fz_col<I24, 1>(e)], f0 = rb[fz_row<I24, 0>(e)], f1 = rb[fz_row<I24, 1>(e)];
             term(q0.x, p0, f0, m0); term(q0.y, p1, f1, m1);
           }
           {
-            const double p2 = cprev[e2 & 0xFFFF], p3 = cprev[e3 & 0xFFFF], f2 = rb[e2 >> 16], f3 = rb[e3 >> 16];
+            const double p2 = cprev[fz_col<I24, 2>(e)], p3 = cprev[fz_col<I24, 3>(e)], f2 = rb[fz_row<I24, 2>(e)], f3 = rb[fz_row<I24, 3>(e)];
             term(q1.x, p2, f2, m2); term(q1.y, p3, f3, m3);
           }
         }

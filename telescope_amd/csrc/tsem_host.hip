@@ -478,7 +478,7 @@ int tsem_kernel_stats(tsem_ctx* h, int reset, double* em_ms, int64_t* em_launche
   // one EM pass must read every stored entry of the ambiguous rows once:
   // 4 B packed local row/col + the value AS STORED (8 B fp64 Q, or a 2 B score code) per entry,
   // + 2 B row weight code per row
-  if (algo_bytes) *algo_bytes = h->nnz_amb * (h->fmt_code ? 6 : 12) + h->N_amb * 2;
+  if (algo_bytes) *algo_bytes = h->nnz_amb * (h->fmt_code ? 6 : (h->idx24 ? 11 : 12)) + h->N_amb * 2;
   if (reset) { h->em_ms_acc = 0; h->em_launches = 0; h->em_timed = 0; }
   return TSEM_OK;
 }
@@ -512,7 +512,7 @@ int tsem_device_memory(tsem_ctx* h, int device, int64_t* free_bytes, int64_t* to
     resident5[0] = h->d_indptr ? 8 * (h->N + 1) + (h->d_raw ? 2 * nz : 0) : 0;
     resident5[1] = h->d_indices ? 4 * nz : 0;
     resident5[2] = h->d_rid16 ? 2 * nz : 0;
-    resident5[3] = (h->d_prc ? 4 * h->nnz_pad : 0) + (h->d_pcode ? 2 * h->nnz_pad : 0) + (h->d_pval ? 8 * h->nnz_pad : 0) +
+    resident5[3] = (h->d_prc ? (h->idx24 ? 3 : 4) * h->nnz_pad : 0) + (h->d_pcode ? 2 * h->nnz_pad : 0) + (h->d_pval ? 8 * h->nnz_pad : 0) +
                    (h->d_sb_off ? 12 * (h->nb * h->P + 2) : 0);
     resident5[4] = (h->d_row_code ? 3 * h->N : 0) + (h->d_amb_row ? 6 * h->N_amb : 0) + (h->d_slot_row ? 6 * h->N_amb_pad : 0) +
                    (h->d_uni_col ? 6 * h->N_uni : 0) + (h->d_amb_w ? 8 * h->N_amb_pad : 0) + (h->d_rinv ? 8 * h->N_amb_pad : 0) +
@@ -655,18 +655,47 @@ int tsem_debug_stream_read(int device, int64_t bytes, int32_t reps, double* gbs)
   return TSEM_OK;
 }
 
-/* debug: the packed (local row << 16 | local column) words of sub-block (block, part); returns their number */
+/* debug: the (local row << 16 | local column) words of sub-block (block, part), whatever index width the layout stores; returns their number */
 int64_t tsem_debug_subblock(tsem_ctx* h, int64_t block, int32_t part, uint32_t* out, int64_t cap) {
   if (!h || !h->d_prc || !h->d_sb_off || block < 0 || block >= h->nb || part < 0 || part >= h->P) return TSEM_ERR_ARG;
   int64_t o[2];
   if (hipMemcpy(o, h->d_sb_off + block * h->P + part, 16, hipMemcpyDeviceToHost) != hipSuccess) return TSEM_ERR_HIP;
   const int64_t n = std::min(cap, o[1] - o[0]);
+  if (h->idx24) {                                          // 3 bytes per entry: whole quads through the shared unpack (sub-blocks are multiples of 64 entries)
+    const int64_t nq = (n + 3) / 4;
+    std::vector<uint8_t> raw((size_t)std::max<int64_t>(1, nq * 12));
+    if (nq > 0 && hipMemcpy(raw.data(), reinterpret_cast<const uint8_t*>(h->d_prc) + o[0] * 3, (size_t)nq * 12, hipMemcpyDeviceToHost) != hipSuccess) return TSEM_ERR_HIP;
+    for (int64_t q = 0; q < nq; ++q) {
+      uint32_t rc[4];
+      ts_idx24_unpack_quad(raw.data() + q * 12, rc);
+      for (int k = 0; k < 4 && q * 4 + k < n; ++k) out[q * 4 + k] = rc[k];
+    }
+    return n;
+  }
   if (n > 0 && hipMemcpy(out, h->d_prc + o[0], sizeof(uint32_t) * n, hipMemcpyDeviceToHost) != hipSuccess) return TSEM_ERR_HIP;
   return n;
 }
 
+/* host only: four lrow << 16 | lcol words through the packed 3-byte index of tsem_idx24.h — the 12 bytes of the quad, and the words
+ * unpacked from them again (rows < 2048, columns < 8192) */
+int tsem_debug_idx24(const uint32_t* rc4, uint8_t* out12, uint32_t* back4) {
+  if (!rc4 || !out12 || !back4) return TSEM_ERR_ARG;
+  for (int k = 0; k < 4; ++k)
+    if ((rc4[k] >> 16) >= (uint32_t)TS_IDX24_MAX_R || (rc4[k] & 0xFFFFu) >= (uint32_t)TS_IDX24_MAX_KP) return TSEM_ERR_ARG;
+  ts_idx24_pack_quad(rc4, out12);
+  ts_idx24_unpack_quad(out12, back4);
+  return TSEM_OK;
+}
+
+/* the 32 values every caller's buffer has room for; values appended since come through tsem_layout_info_n */
 int tsem_layout_info(tsem_ctx* h, int64_t* info) {
-  if (!h || !info) return TSEM_ERR_ARG;
+  return tsem_layout_info_n(h, info, 32);
+}
+
+int tsem_layout_info_n(tsem_ctx* h, int64_t* out, int32_t n) {
+  if (!h || !out || n < 0) return TSEM_ERR_ARG;
+  int64_t info[TSEM_LAYOUT_INFO_N] = {};
+  info[32] = h->idx24 ? 3 : 4;                             // bytes of index per stored entry (3: the packed index of tsem_idx24.h)
   info[0] = h->P; info[1] = h->Kp; info[2] = h->R; info[3] = h->nb;
   info[4] = h->N_amb; info[5] = h->N_uni; info[6] = h->nnz_amb; info[7] = h->nnz_pad;
   info[8] = h->n_twin_cols; info[9] = h->G1; info[10] = h->G2; info[11] = h->use_fused ? 1 : 0;
@@ -695,6 +724,7 @@ int tsem_layout_info(tsem_ctx* h, int64_t* info) {
     unsigned long long m = 0;
     if (hipMemcpyAsync(&m, h->d_exact_n, 8, hipMemcpyDeviceToHost, h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess) info[31] = (int64_t)m;
   }
+  for (int i = 0; i < std::min<int>(n, TSEM_LAYOUT_INFO_N); ++i) out[i] = info[i];
   return TSEM_OK;
 }
 

@@ -376,10 +376,17 @@ __global__ __launch_bounds__(256) void k_sb_count(int64_t N_amb, int R, int P, c
   if (threadIdx.x < P) sb_cnt[b * P + threadIdx.x] = cnt[threadIdx.x];
 }
 
+// The index of entry `pos` of the blocked layout: the 3-byte packed form (tsem_idx24.h) where the fused kernel reads fp64 entries
+// of a non-split layout (h->idx24), one lrow << 16 | lcol word everywhere else.  Wave-uniform choice (a kernel argument).
+__device__ __forceinline__ void sb_store_index(uint32_t* __restrict__ prc, int64_t pos, uint32_t lrow, uint32_t lcol, int idx24) {
+  if (idx24) ts_idx24_store(reinterpret_cast<uint8_t*>(prc), pos, lrow, lcol);
+  else prc[pos] = (lrow << 16) | lcol;
+}
+
 __global__ __launch_bounds__(256) void k_sb_fill(int64_t N_amb, int R, int P, const int32_t* __restrict__ amb_row,
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, const uint16_t* __restrict__ raw,
     const double* __restrict__ lut, const uint32_t* __restrict__ colmap, const int64_t* __restrict__ sb_off,
-    double* __restrict__ pval, uint16_t* __restrict__ pcode, uint32_t* __restrict__ prc) {
+    double* __restrict__ pval, uint16_t* __restrict__ pcode, uint32_t* __restrict__ prc, int idx24) {
   __shared__ uint32_t cur[64];
   if (threadIdx.x < 64) cur[threadIdx.x] = 0;
   __syncthreads();
@@ -402,7 +409,7 @@ __global__ __launch_bounds__(256) void k_sb_fill(int64_t N_amb, int R, int P, co
       int64_t pos = base + (int64_t)(t % TS_STRANDS) * L + t / TS_STRANDS;
       if (pcode) pcode[pos] = raw[k];
       else pval[pos] = lut[raw[k]];
-      prc[pos] = ((uint32_t)lr << 16) | ((cm & CM_SM) + (t & ((1u << ((cm >> CM_LS) & 7u)) - 1u)));   // hot column: deal over its slots
+      sb_store_index(prc, pos, (uint32_t)lr, (cm & CM_SM) + (t & ((1u << ((cm >> CM_LS) & 7u)) - 1u)), idx24);   // hot column: deal over its slots
     }
   }
 }
@@ -424,7 +431,8 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
     double* __restrict__ pval, uint16_t* __restrict__ pcode, uint32_t* __restrict__ prc,
     const int64_t* __restrict__ bstart, const unsigned long long* __restrict__ pc,
     const uint16_t* __restrict__ rid /* popularity ids (slot * P + part) instead of the column-map gather, or null */,
-    uint32_t magicP /* ceil(2^32 / P) */, int nsplit /* ids below this may be split columns */, const uint8_t* __restrict__ lgtab) {
+    uint32_t magicP /* ceil(2^32 / P) */, int nsplit /* ids below this may be split columns */, const uint8_t* __restrict__ lgtab,
+    int idx24 /* store the 3-byte packed index (sb_store_index) */) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fl_lds[];
   uint32_t* const cnt = reinterpret_cast<uint32_t*>(fl_lds);                   // [row slot][part]: counts, then write cursors
   int64_t* const rstart = reinterpret_cast<int64_t*>(cnt + ((R * P + 1) & ~1));   // [row slot] first entry of the row in the CSR
@@ -512,7 +520,7 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
       const int64_t pos = sbase[p] + t;
       if (pcode) pcode[pos] = (uint16_t)code;
       else pval[pos] = lut[code];
-      prc[pos] = ((uint32_t)lr << 16) | ((cm & CM_SM) + (t & ((1u << ((cm >> CM_LS) & 7u)) - 1u)));   // hot column: deal over its slots
+      sb_store_index(prc, pos, (uint32_t)lr, (cm & CM_SM) + (t & ((1u << ((cm >> CM_LS) & 7u)) - 1u)), idx24);   // hot column: deal over its slots
     }
   };
   auto cm_of_id = [&](uint32_t id) -> uint32_t {           // the ids k_row_partcounts wrote: a coalesced 2-byte read instead of a gather
@@ -560,7 +568,7 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
   for (int p = 0; p < P; ++p) {                            // padding: value 0 (written here: the buffers of this path are not zero-filled), row = last row
     const int64_t base = sbase[p], end = sb_off[b * P + p + 1];
     for (int64_t pos = base + total[p] + threadIdx.x; pos < end; pos += blockDim.x) {
-      prc[pos] = lastrow[p] << 16;
+      sb_store_index(prc, pos, lastrow[p], 0u, idx24);
       if (pcode) pcode[pos] = (uint16_t)0; else pval[pos] = 0.0;
     }
   }
@@ -1109,7 +1117,7 @@ int tsem_build_layout(tsem_ctx* h) {
     TSEM_HIP(hipMemcpy(h->d_col_of_pc, cpc.data(), sizeof(int32_t) * h->Kpad, hipMemcpyHostToDevice));
     h->nb = 0; h->N_amb_pad = 1; h->nnz_pad = 0; h->max_subblock = 0; h->n_hot_cols = 0;
     h->nnz_amb = h->nnz - h->N_uni;
-    h->fmt_code = h->fmt_wcode = false; h->sorted_layout = false;
+    h->fmt_code = h->fmt_wcode = false; h->sorted_layout = false; h->idx24 = false;
     h->G1 = h->G2 = 1;
     return TSEM_OK;
   }
@@ -1316,6 +1324,9 @@ int tsem_build_layout(tsem_ctx* h) {
     h->use_fused = false;
   }
   if (h->use_fused && (R > fz_rmax(h->geo) || (R & 1) || fz_lds_bytes(h, false) > (size_t)TS_LDS_MAX - 1024)) h->use_fused = false;
+  // the packed index has 13 bits of column slot and 11 of row slot: every non-split fused layout fits by construction (Kp <= TS_MAX_KP,
+  // R <= fz_rmax); one that did not would keep the 32-bit index and the two-pass kernels that read it
+  if (h->use_fused && !h->split && (Kp > TS_IDX24_MAX_KP || R > TS_IDX24_MAX_R)) h->use_fused = false;
   h->fmt_code = h->use_fused && fz_wants_codes(h) && fz_lds_bytes(h, true) <= (size_t)TS_LDS_MAX - 1024;
   h->fmt_wcode = h->use_fused && !h->fmt_code && h->lut_len > 0 && h->lut_len <= 2048 &&
                  fz_lds_bytes(h, true) <= (size_t)TS_LDS_MAX - 1024;
@@ -1328,8 +1339,12 @@ int tsem_build_layout(tsem_ctx* h) {
   // (zero-filled for the strand-transposed fill only, whose padding is whatever it does not write; the row-order fill writes
   //  every position, padding included — 12-24 GB of memsets, ~3 ms at 2e9 entries, went away with that)
   const bool will_sort = h->use_fused && R * P <= FILL_MAX_RP && (h->opt_sorted >= 0 ? h->opt_sorted != 0 : true) && nb > 0;
-  TSEM_ALLOC(h->d_prc, off);
-  if (!will_sort) TSEM_HIP(hipMemsetAsync(h->d_prc, 0, sizeof(uint32_t) * std::max<int64_t>(1, off), h->stream));
+  // fp64 entries under the fused kernel, non-split: 3 B of index per entry (the instantiations of fz_idx24(), tsem_fused.h).  Decided
+  // HERE for every build of the layout, the rebuild of the two-pass fall-back included (use_fused is false then: 4 B again).
+  h->idx24 = h->use_fused && !h->split && !h->fmt_code;
+  const int64_t prc_words = h->idx24 ? (off * 3 + 3) / 4 : off;   // (sub-blocks are padded to 64 entries: a multiple of 192 B each)
+  TSEM_ALLOC(h->d_prc, prc_words);
+  if (!will_sort) TSEM_HIP(hipMemsetAsync(h->d_prc, 0, sizeof(uint32_t) * std::max<int64_t>(1, prc_words), h->stream));
   if (h->fmt_code) {
     TSEM_ALLOC(h->d_pcode, off);
     if (!will_sort) TSEM_HIP(hipMemsetAsync(h->d_pcode, 0, sizeof(uint16_t) * std::max<int64_t>(1, off), h->stream));   // code 0 -> Q = 0
@@ -1375,7 +1390,7 @@ int tsem_build_layout(tsem_ctx* h) {
     const uint32_t magicP = (uint32_t)((0x100000000ull + (uint64_t)P - 1) / (uint64_t)P);
     k_sb_fill_sorted<<<(unsigned)nb, 256, fill_lds_bytes(R, P), h->stream>>>(na, R, P, h->d_slot_row, h->d_indptr, h->d_indices, h->d_raw, h->d_lut,
                                                          h->d_colmap, h->d_sb_off, h->d_pval, h->d_pcode, h->d_prc,
-                                                         d_pc ? d_bs : nullptr, d_pc, rid_fill, magicP, nsplit, d_lgtab);
+                                                         d_pc ? d_bs : nullptr, d_pc, rid_fill, magicP, nsplit, d_lgtab, h->idx24 ? 1 : 0);
     TSEM_HIP(hipGetLastError());
     if (deconflict) {
       const int64_t n_win = off / 64;
@@ -1396,7 +1411,7 @@ int tsem_build_layout(tsem_ctx* h) {
     if (rid_fill && h->d_col_of_id && (h->opt_drop_indices == 1 || (h->opt_drop_indices < 0 && h->nnz >= 4000000000ll))) dfree(h->d_indices);
   } else if (nb) {
     k_sb_fill<<<(unsigned)nb, 256, 0, h->stream>>>(na, R, P, h->d_slot_row, h->d_indptr, h->d_indices, h->d_raw, h->d_lut,
-                                                  h->d_colmap, h->d_sb_off, h->d_pval, h->d_pcode, h->d_prc);
+                                                  h->d_colmap, h->d_sb_off, h->d_pval, h->d_pcode, h->d_prc, h->idx24 ? 1 : 0);
     TSEM_HIP(hipGetLastError());
   }
   TSEM_HIP(hipStreamSynchronize(h->stream));

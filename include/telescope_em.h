@@ -379,6 +379,30 @@ int  tsem_group_counts(tsem_ctx* h, int method, double thresh, int which, const 
 int  tsem_group_counts_copy(tsem_ctx* h, int64_t* group_ptr, int32_t* cols, double* vals);
 /* the last result's number of groups and stored entries: what the arrays of tsem_group_counts_copy must hold */
 int  tsem_group_counts_shape(tsem_ctx* h, int32_t* n_groups, int64_t* nnz);
+/* Single-cell `individual` pooling: ONE EM fit per group (cell) of the map set with tsem_set_groups — a partition: each row in at
+ * most one group, -1 = none — instead of one fit of the pool (model.py:762-806 per cell; the reference fits the pool only,
+ * model.py:570-625).  The fit of cell c is TelescopeLikelihood(raw[rows of c]) with the score scale of the whole matrix: the cell's
+ * own weights, total_wt / ambig_wt, prior weights prior x (the cell's largest weight) (model.py:690-697) and pisum0 (:699); all K
+ * columns count: a column the cell never touches has the closed-form value prior_wt / (total + prior_wt K) and takes part in
+ * diff_est (model.py:781).  Priors as given to tsem_set_model; needs tsem_rowstats and the score table.  Every cell is fitted by one
+ * workgroup from its first iteration to its last, all cells in one call; column sums are taken in ascending row order (scipy's), so
+ * the result is deterministic and exact twins inside a cell keep bit-identical pi / theta.  A cell stops after the same iteration
+ * whatever else is in the batch.  A cell without rows is not fitted: n_iter 0, converged 0, lnl NaN.
+ * Installs the per-cell final z — the last E-step's (model.py:795), NaN outside z's pattern and for rows in no cell — as the
+ * TSEM_Z_USER buffer: every report entry point reads it with which = TSEM_Z_USER.  Leaves the pooled state (pi, theta,
+ * TSEM_Z_PREV/CUR, lnl) untouched.  The compacted per-cell layout (18 B per stored entry of the cells' rows, 38 B while it is
+ * built, cached per group map) must fit the device: TSEM_ERR_NOMEM with a message otherwise.  Single GPU only: a handle with a
+ * communicator attached is refused. */
+int  tsem_cell_em(tsem_ctx* h, double epsilon, int32_t max_iter, int32_t use_likelihood);
+/* the last fit's number of cells and the sum of the cells' distinct columns Kc: what the arrays of tsem_cell_em_copy must hold */
+int  tsem_cell_em_shape(tsem_ctx* h, int32_t* n_cells, int64_t* n_cols /* sum of Kc */);
+/* copy the last fit out: cell c's distinct columns are cols[col_ptr[c] .. col_ptr[c + 1]) (ascending) with pi / theta (model.py:
+ * 733-740) and pi_init / theta_init (model.py:776-778) beside them; rest[4 c ..] = pi, theta, pi_init, theta_init of every column the
+ * cell does not touch; n_iter, converged, lnl (model.py:800-806) per cell */
+int  tsem_cell_em_copy(tsem_ctx* h, int64_t* col_ptr /* n_cells+1 */, int32_t* cols,
+                      double* pi, double* theta, double* pi_init, double* theta_init, /* n_cols each */
+                      double* rest /* n_cells x 4: the four values of the untouched columns */,
+                      int32_t* n_iter, int32_t* converged, double* lnl /* n_cells each */);
 
 /* ---- csr_matrix_plus primitives on arbitrary fp64 CSR (sparse_plus.py) ---- */
 /* All three: indptr[n_rows + 1] is a HOST array and is checked on the host before the device is touched. TSEM_ERR_ARG (text in

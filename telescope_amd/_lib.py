@@ -26,13 +26,14 @@ class EngineError(RuntimeError):
     code = 0
 
 
-# host / ABI, set-up, EM support, report / row passes, collectives, CSR primitives (telescope_amd/csrc/tsem_internal.h)
-LIB_UNITS = ('tsem_host', 'tsem_setup', 'tsem_em', 'tsem_report', 'tsem_comm', 'tsem_csr', 'tsem_cells')
+# host / ABI, set-up, EM support, report / row passes, collectives, CSR primitives, per-cell counts, per-cell fits
+# (telescope_amd/csrc/tsem_internal.h)
+LIB_UNITS = ('tsem_host', 'tsem_setup', 'tsem_em', 'tsem_report', 'tsem_comm', 'tsem_csr', 'tsem_cells', 'tsem_cellem')
 FZ_UNITS = tuple('tsem_fz_p%d' % p for p in range(1, 9))
 
 
 def build_library(force=False, verbose=False, out=None):
-    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  Fourteen translation units — the six of
+    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  Sixteen translation units — the eight of
     LIB_UNITS and the eight that instantiate the fused kernel for one team size each (most of the build time) — are compiled
     in parallel and linked into one shared object."""
     from concurrent.futures import ThreadPoolExecutor
@@ -223,6 +224,9 @@ def lib():
     L.tsem_group_counts.argtypes = [vp, C.c_int, dbl, C.c_int, vp, C.POINTER(i64)]
     L.tsem_group_counts_copy.argtypes = [vp, vp, vp, vp]
     L.tsem_group_counts_shape.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
+    L.tsem_cell_em.argtypes = [vp, dbl, i32, i32]
+    L.tsem_cell_em_shape.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
+    L.tsem_cell_em_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tsem_csr_norm_rows.argtypes = [C.c_int, i64, vp, vp, vp]
     L.tsem_csr_binmax_rows.argtypes = [C.c_int, i64, i32, vp, vp, vp]
     L.tsem_csr_scale.argtypes = [C.c_int, C.c_int, i64, i32, vp, vp, vp]
@@ -609,6 +613,20 @@ class Engine(object):
         cols, vals = np.empty(nnz.value, np.int32), np.empty(nnz.value)
         self._ck(self._L.tsem_group_counts_copy(self._h, ptr(gptr), ptr(cols), ptr(vals)))
         return gptr, cols, vals
+
+    def cell_em(self, epsilon, max_iter, use_likelihood=False):
+        """One EM fit per group of the map of `set_groups` (tsem_cell_em); the per-cell final z becomes the Z_USER buffer.  Returns
+        the arrays of tsem_cell_em_copy as a dict."""
+        self._ck(self._L.tsem_cell_em(self._h, float(epsilon), int(max_iter), int(bool(use_likelihood))))
+        n_cells, n_cols = C.c_int32(), C.c_int64()
+        self._ck(self._L.tsem_cell_em_shape(self._h, C.byref(n_cells), C.byref(n_cols)))
+        g, nc = n_cells.value, n_cols.value
+        r = dict(col_ptr=np.empty(g + 1, np.int64), cols=np.empty(nc, np.int32), pi=np.empty(nc), theta=np.empty(nc),
+                 pi_init=np.empty(nc), theta_init=np.empty(nc), rest=np.empty((g, 4)), n_iter=np.empty(g, np.int32),
+                 converged=np.empty(g, np.int32), lnl=np.empty(g))
+        self._ck(self._L.tsem_cell_em_copy(self._h, *[ptr(r[k]) for k in ('col_ptr', 'cols', 'pi', 'theta', 'pi_init', 'theta_init',
+                                                                         'rest', 'n_iter', 'converged', 'lnl')]))
+        return r
 
     # -- instrumentation --
     def kernel_stats(self, reset=False):

@@ -133,6 +133,10 @@ def _sc_args(p, assign):
     g = groups['Run Modes']
     g.add_argument('--use_every_reassign_mode', action='store_true',
                    help='Output count matrices generated using every reassign mode (conf, all, unique, exclude, choose, average).')
+    g.add_argument('--pooling_mode', default='pseudobulk', choices=['pseudobulk', 'individual'],
+                   help='pseudobulk (default): one model fitted to the pool of all cells, as the reference does.  individual: after '
+                        'the pooled fit, one model per cell (all cells in one device call); the count matrices come from the per-cell '
+                        'posteriors and <exp_tag>-cell_stats.tsv lists every cell\'s fit.')
     g = groups['Reporting Options']
     g.add_argument('--count_format', default='tsv', choices=['tsv', 'mtx'],
                    help='tsv: the dense cells x features table the reference writes; mtx: Matrix Market (cells x features) with '
@@ -153,7 +157,7 @@ class ResumeOptions(object):
     def __str__(self):
         keys = ('checkpoint', 'samfile', 'gtffile', 'attribute', 'quiet', 'debug', 'outdir', 'exp_tag',
                 'reassign_mode', 'conf_prob', 'overlap_mode', 'overlap_threshold', 'stranded_mode',
-                'pi_prior', 'theta_prior', 'em_epsilon', 'max_iter', 'use_likelihood', 'skip_em')
+                'pi_prior', 'theta_prior', 'em_epsilon', 'max_iter', 'use_likelihood', 'skip_em', 'pooling_mode')
         lines = ['{:34}{}'.format('Version:', self.version)]
         lines += ['    {:30}{}'.format(k + ':', getattr(self, k)) for k in keys if hasattr(self, k)]
         return '\n'.join(lines)
@@ -242,6 +246,16 @@ def _refuse_sharded_updated_sam(opts):
         raise SystemExit('telescope assign: --updated_sam is not supported in row-sharded runs (WORLD_SIZE > 1); run it on one GPU')
 
 
+def pooling_mode(opts):
+    return getattr(opts, 'pooling_mode', 'pseudobulk')
+
+
+def _refuse_individual_updated_sam(opts):
+    if pooling_mode(opts) == 'individual' and getattr(opts, 'updated_sam', False):
+        raise SystemExit('telescope sc assign: --pooling_mode individual with --updated_sam is not supported (the tags of the '
+                         'updated file come from the pooled posteriors); run the two separately')
+
+
 def run_resume(args, sc=False):
     """telescope_resume.py:183-232.  sc=True: `sc resume` — a single-cell checkpoint (scTelescope) and its per-cell reports."""
     _refuse_sharded_sc(sc)
@@ -296,6 +310,7 @@ def run_assign(args, sc=False):
     if opts.ncpu != 1:
         raise SystemExit('--ncpu > 1 is not available in this engine')
     _refuse_sharded_updated_sam(opts)
+    _refuse_individual_updated_sam(opts)
     warm = None if opts.skip_em else warm_device(opts)       # (the device comes up while the BAM is parsed)
     from .likelihood import TelescopeLikelihood
     from .loader import Annotation

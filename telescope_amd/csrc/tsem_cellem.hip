@@ -1,0 +1,489 @@
+// libtelescope_em.so, per-cell EM unit: the reference's mixture model (model.py:631-806) fitted once PER GROUP of rows — one fit per
+// barcode of a single-cell run — for every group of the map set with tsem_set_groups, in one go.
+//
+// The fit of cell c is `TelescopeLikelihood(raw[rows_c])` with the score scale of the whole matrix: the cell's own weights, totals,
+// prior weights and pisum0, the full K columns.  Thousands of small, independent problems: every cell is fitted by ONE workgroup
+// (or one wave) from its first iteration to its last.  No workgroup ever waits for another: no flags, no grid barriers, the only
+// loops are over rows, entries, columns and — bounded by max_iter — iterations.
+//
+// Layout (set-up, once per group map; tsem_cells.hip's cached grouping gives every cell's rows in ascending order):
+//   row-ordered view     the entries of the cells' rows in group order: per entry its CELL-LOCAL column number (4 B) and score code
+//                        (2 B), per row its class and weight code (4 B);
+//   compacted columns    the sorted distinct columns of every cell (cols, col_ptr): only these Kc columns have state; the K - Kc
+//                        columns a cell never touches share one closed-form value per parameter (`rest`);
+//   column-ordered view  the entries stably radix-sorted by (cell, column): per compacted column the positions of its entries in the
+//                        row-ordered view, ascending row order (4 B per entry).
+//   scratch              8 B per entry: what the row pass leaves for the column pass.
+// Order of sums: a column's sum is taken by ONE lane over the column-ordered view, in ascending row order from 0 — scipy's order
+// (model.py:729, `.sum(0)`) — so it depends on the column's entries alone: two runs give the same bits, and two columns of a cell
+// with the same rows and scores (twins) get bit-identical pi and theta.  No atomics anywhere.  Block-wide scalars (weights' totals,
+// diff, lnl) are reduced in a fixed tree.
+//
+// Numerators are formed as the reference forms them, both terms (model.py:718-720): (Q Y)(pi theta) + (Q (1 - Y)) pi — so that a NaN
+// theta (a cell without ambiguous rows at theta_prior = 0) spreads exactly as it does there.
+#include "tsem_internal.h"
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+
+namespace {
+
+// device memory of the set-up per stored entry of the grouped rows: kept — local column 4, code 2, column view 4, scratch 8 (18 B, +
+// 4 B per row, + 60 B per compacted column); while it runs — two 8-byte keys and a second 4-byte position on top (38 B)
+constexpr int64_t CE_BYTES_KEPT = 18, CE_BYTES_PEAK = 38;
+// cell classes: tables of Kc columns x 5 (pi, theta, their previous values, pisum0) in LDS
+constexpr int CE_KC_WAVE = 256, CE_ENT_WAVE = 4096;        // a wave per cell: 10 KiB of tables
+constexpr int CE_KC_SMALL = 1024;                          // 256 threads, up to 40 KiB
+constexpr int CE_KC_LARGE = 3840;                          // 512 threads, up to 150 KiB; beyond: the tables in a global workspace
+constexpr int CE_RED = 16;                                 // doubles of LDS in front of the tables (block reductions)
+
+int ce_bits_for(uint64_t v) { int b = 1; while (b < 64 && (v >> b) != 0) ++b; return b; }
+
+struct CeArgs {
+  int32_t K, max_iter, use_lnl;
+  double eps, pi_prior, theta_prior;
+  const int32_t* cells;            // the cells of this launch (largest first)
+  const int64_t* rptr;             // [G + 1] first row of every cell in group order
+  const int64_t* eoff;             // [M + 1] first entry of every row of the group order
+  const int32_t* rows;             // [M] the CSR row of every row of the group order
+  const uint32_t* rinfo;           // [M] row class << 16 | weight code
+  const int64_t* indptr;
+  const int32_t* lcol;             // [E] cell-local column of every entry (row-ordered view)
+  const uint16_t* code;            // [E] its score code
+  const double* lut;
+  const int64_t* col_ptr;          // [G + 1] first compacted column of every cell
+  const uint32_t* cptr;            // [n_cols + 1] first entry of every compacted column in the column-ordered view
+  const uint32_t* cpos;            // [E] column-ordered view: positions in the row-ordered view
+  double* scratch;                 // [E]
+  double* user_z;                  // [nnz] the final z at every entry's own CSR position
+  double *pi, *theta, *pi_init, *theta_init, *ws_pi_prev, *ws_theta_prev, *ws_pisum0;   // [n_cols]
+  double* rest;                    // [G][4] pi, theta, pi_init, theta_init of the columns a cell never touches
+  int32_t *n_iter, *converged;     // [G]
+  double* lnl;                     // [G]
+};
+
+template <int T>
+__device__ __forceinline__ double ce_sum(double v, double* red) {   // the same value in every thread, fixed order
+  v = sg_sum<64>(v);
+  if (T == 64) return v;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+#pragma unroll
+  for (int i = 0; i < T / 64; ++i) t += red[i];
+  return t;
+}
+template <int T>
+__device__ __forceinline__ double ce_max(double v, double* red) {
+  v = sg_max<64>(v);
+  if (T == 64) return v;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = red[0];
+#pragma unroll
+  for (int i = 1; i < T / 64; ++i) t = fmax(t, red[i]);
+  return t;
+}
+__device__ __forceinline__ double ce_recip0(double v) {    // sparse_plus.py:16-22
+  const double r = 1.0 / v;
+  return isinf(r) ? 0.0 : r;
+}
+// model.py:718-720 for one entry: (Q Y)(pi theta) + (Q (1 - Y)) pi
+__device__ __forceinline__ double ce_numer(double q, double y, double p, double t) { return (q * y) * (p * t) + (q * (1.0 - y)) * p; }
+
+__global__ void k_ce_fill_nan(int64_t n, double* __restrict__ z) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) z[i] = __longlong_as_double(0x7FF8000000000000ll);
+}
+
+// One cell per workgroup of T threads.  LDS: the five column tables sit in LDS; otherwise in the cell's slices of the global arrays.
+template <int T, bool LDS>
+__global__ __launch_bounds__(T) void k_cell_em(CeArgs A) {
+  extern __shared__ double ce_sm[];
+  const int c = A.cells[blockIdx.x];
+  const int tid = threadIdx.x;
+  const int64_t r0 = A.rptr[c], r1 = A.rptr[c + 1];
+  const int64_t c0 = A.col_ptr[c];
+  const int Kc = (int)(A.col_ptr[c + 1] - c0);
+  const int K = A.K;
+  double* red = ce_sm;
+  double *pi, *th, *pp, *tp, *ps0;
+  if constexpr (LDS) { pi = ce_sm + CE_RED; th = pi + Kc; pp = th + Kc; tp = pp + Kc; ps0 = tp + Kc; }
+  else { pi = A.pi + c0; th = A.theta + c0; pp = A.ws_pi_prev + c0; tp = A.ws_theta_prev + c0; ps0 = A.ws_pisum0 + c0; }
+  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  if (r1 == r0) {                                           // a cell without rows is not fitted
+    if (tid == 0) {
+      A.n_iter[c] = 0; A.converged[c] = 0; A.lnl[c] = nan;
+      A.rest[4 * (int64_t)c] = 1.0 / K; A.rest[4 * (int64_t)c + 1] = 1.0 / K; A.rest[4 * (int64_t)c + 2] = nan; A.rest[4 * (int64_t)c + 3] = nan;
+    }
+    return;
+  }
+  // ---- the cell's weights (model.py:690-697) and pisum0 (model.py:699) ----
+  double tw = 0.0, aw = 0.0, wm = 0.0;
+  for (int64_t i = r0 + tid; i < r1; i += T) {
+    const uint32_t info = A.rinfo[i];
+    const int cls = (int)(info >> 16);
+    const double w = cls ? A.lut[info & 0xFFFFu] : 0.0, y = cls == 2 ? 1.0 : 0.0;
+    tw += w; aw += w * y; wm = fmax(wm, w);
+    for (int64_t e = A.eoff[i]; e < A.eoff[i + 1]; ++e) A.scratch[e] = A.lut[A.code[e]] * (1.0 - y);
+  }
+  tw = ce_sum<T>(tw, red); aw = ce_sum<T>(aw, red); wm = ce_max<T>(wm, red);
+  __syncthreads();
+  const double inv_k = 1.0 / K;
+  for (int lc = tid; lc < Kc; lc += T) {
+    double s = 0.0;
+    for (uint32_t p = A.cptr[c0 + lc]; p < A.cptr[c0 + lc + 1]; ++p) s += A.scratch[A.cpos[p]];
+    ps0[lc] = s; pi[lc] = inv_k; th[lc] = inv_k;
+  }
+  const double ppw = A.pi_prior * wm, tpw = A.theta_prior * wm;
+  const double den_th = aw + tpw * K, den_pi = tw + ppw * K;
+  double rest_pi = inv_k, rest_th = inv_k, rest_pi_prev = inv_k, rest_th_prev = inv_k, rest_pi_init = nan, rest_th_init = nan;
+  int it = 0;
+  bool conv = false;
+  double lnl_prev = INFINITY;
+
+  // calculate_lnl(z(previous parameters), current parameters) (model.py:744-760); WRITE: z goes to its CSR positions as well
+  auto lnl_pass = [&](auto write) -> double {
+    double part = 0.0;
+    for (int64_t i = r0 + tid; i < r1; i += T) {
+      const uint32_t info = A.rinfo[i];
+      const double y = (info >> 16) == 2 ? 1.0 : 0.0;
+      const int64_t a = A.eoff[i], b = A.eoff[i + 1];
+      double sum = 0.0;
+      for (int64_t e = a; e < b; ++e) { const int lc = A.lcol[e]; sum += ce_numer(A.lut[A.code[e]], y, pp[lc], tp[lc]); }
+      const double rinv = ce_recip0(sum);
+      const int64_t zo = decltype(write)::value ? A.indptr[A.rows[i]] - a : 0;
+      for (int64_t e = a; e < b; ++e) {
+        const int lc = A.lcol[e];
+        const double q = A.lut[A.code[e]];
+        const double n = ce_numer(q, y, pp[lc], tp[lc]);
+        const bool inp = n != 0.0;
+        const double z = n * rinv;
+        if constexpr (decltype(write)::value) A.user_z[zo + e] = inp ? z : nan;
+        const double m = ce_numer(q, y, pi[lc], th[lc]);
+        if (inp && m != 0.0) part += z * log1p(m);
+      }
+    }
+    return ce_sum<T>(part, red);
+  };
+
+  do {
+    // ---- previous <- current ----
+    __syncthreads();
+    for (int lc = tid; lc < Kc; lc += T) { pp[lc] = pi[lc]; tp[lc] = th[lc]; }
+    rest_pi_prev = rest_pi; rest_th_prev = rest_th;
+    __syncthreads();
+    // ---- E-step (model.py:702-722), a lane per row: every entry's z w Y for the column pass ----
+    for (int64_t i = r0 + tid; i < r1; i += T) {
+      const uint32_t info = A.rinfo[i];
+      const int cls = (int)(info >> 16);
+      const double w = cls ? A.lut[info & 0xFFFFu] : 0.0, y = cls == 2 ? 1.0 : 0.0;
+      const int64_t a = A.eoff[i], b = A.eoff[i + 1];
+      double sum = 0.0;
+      for (int64_t e = a; e < b; ++e) { const int lc = A.lcol[e]; sum += ce_numer(A.lut[A.code[e]], y, pp[lc], tp[lc]); }
+      const double rinv = ce_recip0(sum);
+      for (int64_t e = a; e < b; ++e) {
+        const int lc = A.lcol[e];
+        const double n = ce_numer(A.lut[A.code[e]], y, pp[lc], tp[lc]);
+        A.scratch[e] = n != 0.0 ? ((n * rinv) * w) * y : 0.0;          // products that are exactly zero leave z's pattern
+      }
+    }
+    __syncthreads();
+    // ---- M-step (model.py:724-742), a lane per column of the cell, ascending row order ----
+    double dpart = 0.0;
+    for (int lc = tid; lc < Kc; lc += T) {
+      double s = 0.0;
+      for (uint32_t p = A.cptr[c0 + lc]; p < A.cptr[c0 + lc + 1]; ++p) s += A.scratch[A.cpos[p]];
+      const double thn = (s + tpw) / den_th;
+      const double pin = ((ps0[lc] + s) + ppw) / den_pi;
+      dpart += fabs(pin - pp[lc]);
+      pi[lc] = pin; th[lc] = thn;
+      if (it == 0) { A.pi_init[c0 + lc] = pin; A.theta_init[c0 + lc] = thn; }
+    }
+    rest_th = (0.0 + tpw) / den_th;
+    rest_pi = ((0.0 + 0.0) + ppw) / den_pi;
+    if (it == 0) { rest_pi_init = rest_pi; rest_th_init = rest_th; }
+    ++it;
+    const double diff = ce_sum<T>(dpart, red) + (K > Kc ? (double)(K - Kc) * fabs(rest_pi - rest_pi_prev) : 0.0);   // model.py:781, all K columns
+    __syncthreads();
+    if (A.use_lnl) {                                        // model.py:783-789
+      const double lnl = lnl_pass(std::false_type());
+      conv = fabs(lnl - lnl_prev) < A.eps;
+      lnl_prev = lnl;
+    } else {
+      conv = diff < A.eps;
+    }
+  } while (!conv && it < A.max_iter);
+
+  // ---- the final z — the last E-step's, from the parameters before the last M-step (model.py:795) — and the lnl (model.py:800-801;
+  // under use_likelihood the same sum as the last iteration's) ----
+  const double lnl = lnl_pass(std::true_type());
+  if constexpr (LDS) {
+    for (int lc = tid; lc < Kc; lc += T) { A.pi[c0 + lc] = pi[lc]; A.theta[c0 + lc] = th[lc]; }
+  }
+  if (tid == 0) {
+    A.n_iter[c] = it; A.converged[c] = conv ? 1 : 0; A.lnl[c] = lnl;
+    double* r = A.rest + 4 * (int64_t)c;
+    r[0] = rest_pi; r[1] = rest_th; r[2] = rest_pi_init; r[3] = rest_th_init;
+  }
+  (void)rest_th_prev;
+}
+
+// ---- set-up kernels -----------------------------------------------------------------------------------------------------------
+// per row of the group order: class and weight code; per entry: key (cell << cbits | column) and score code (a lane per row)
+__global__ void k_ce_rows(int64_t M, const int32_t* __restrict__ rows, const uint32_t* __restrict__ gkey, const int64_t* __restrict__ eoff,
+                          const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, const uint16_t* __restrict__ raw,
+                          const uint8_t* __restrict__ cls, const uint16_t* __restrict__ wcode, int cbits, uint32_t* __restrict__ rinfo,
+                          uint64_t* __restrict__ key, uint16_t* __restrict__ code) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= M) return;
+  const int32_t row = rows[i];
+  rinfo[i] = (uint32_t)cls[row] << 16 | wcode[row];
+  const uint64_t hi = (uint64_t)gkey[i] << cbits;
+  const int64_t s = indptr[row], len = indptr[row + 1] - s, o = eoff[i];
+  for (int64_t k = 0; k < len; ++k) { key[o + k] = hi | (uint32_t)indices[s + k]; code[o + k] = raw[s + k]; }
+}
+__global__ void k_ce_heads(int64_t n, const uint64_t* __restrict__ key, uint32_t* __restrict__ head) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) head[i] = (i == 0 || key[i] != key[i - 1]) ? 1u : 0u;
+}
+// first compacted column of every cell: the runs before the cell's first entry (the entries are sorted by cell first)
+__global__ void k_ce_colptr(int64_t G1, int64_t E, int64_t n_runs, const int64_t* __restrict__ gent, const uint32_t* __restrict__ hscan,
+                            int64_t* __restrict__ col_ptr) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= G1) return;
+  const int64_t e = gent[g];
+  col_ptr[g] = e < E ? (int64_t)hscan[e] - 1 : n_runs;
+}
+// per entry of the column-ordered view: its run = compacted column; heads write the column's start and id; every entry's local column
+__global__ void k_ce_columns(int64_t E, int64_t n_runs, const uint64_t* __restrict__ key, const uint32_t* __restrict__ hscan,
+                             const uint32_t* __restrict__ cpos, const int64_t* __restrict__ col_ptr, int cbits, uint32_t* __restrict__ cptr,
+                             int32_t* __restrict__ cols, int32_t* __restrict__ lcol) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p == 0) cptr[n_runs] = (uint32_t)E;
+  if (p >= E) return;
+  const uint64_t k = key[p];
+  const int64_t r = (int64_t)hscan[p] - 1;
+  if (p == 0 || k != key[p - 1]) { cptr[r] = (uint32_t)p; cols[r] = (int32_t)(k & ((1ull << cbits) - 1ull)); }
+  lcol[cpos[p]] = (int32_t)(r - col_ptr[k >> cbits]);
+}
+
+struct CeIdsGuard {                                        // CSR column ids rebuilt for the set-up go again afterwards
+  tsem_ctx* h; bool had;
+  explicit CeIdsGuard(tsem_ctx* c) : h(c), had(c->d_indices != nullptr) {}
+  ~CeIdsGuard() { if (!had) tsem_redrop_indices(h); }
+};
+
+void ce_free_layout(tsem_ctx* h) {
+  dfree(h->d_ce_rptr); dfree(h->d_ce_rinfo); dfree(h->d_ce_lcol); dfree(h->d_ce_code); dfree(h->d_ce_cpos); dfree(h->d_ce_cptr);
+  dfree(h->d_ce_colptr); dfree(h->d_ce_cols); dfree(h->d_ce_scratch);
+  h->ce_colptr.clear(); h->ce_version = ~0ull; h->ce_ncols = 0; h->ce_cells = 0;
+}
+void ce_free_result(tsem_ctx* h) {
+  dfree(h->d_ce_pi); dfree(h->d_ce_theta); dfree(h->d_ce_pi_init); dfree(h->d_ce_theta_init); dfree(h->d_ce_ws0); dfree(h->d_ce_ws1);
+  dfree(h->d_ce_ws2); dfree(h->d_ce_rest); dfree(h->d_ce_niter); dfree(h->d_ce_conv); dfree(h->d_ce_lnl); dfree(h->d_ce_list);
+  h->ce_fitted = false;
+}
+
+// the compacted, column-ordered copy of the grouped rows (see the top of this file), cached per group map
+int ce_build_layout(tsem_ctx* h) {
+  if (int rc = tsem_build_grouping(h)) return rc;
+  if (h->ce_version == h->groups_version && h->d_ce_colptr) return TSEM_OK;
+  ce_free_layout(h);
+  ce_free_result(h);
+  const int32_t G = h->n_groups;
+  const int64_t M = G ? h->gc_rptr[G] : 0, E = G ? h->gc_gent[G] : 0;
+  if (E >= ((int64_t)1 << 31))
+    TSEM_FAIL(TSEM_ERR_NOMEM, "tsem_cell_em: " + std::to_string(E) + " stored entries in cells: the per-cell layout holds fewer than 2^31 (tiling it is not supported)");
+  size_t free_b = 0, total_b = 0;
+  TSEM_HIP(hipMemGetInfo(&free_b, &total_b));
+  const int64_t need = CE_BYTES_PEAK * E + 4 * M + (64ll << 20);
+  if ((int64_t)free_b < need)
+    TSEM_FAIL(TSEM_ERR_NOMEM, "tsem_cell_em: the per-cell layout needs " + std::to_string(need) + " B of device memory (" +
+              std::to_string(CE_BYTES_KEPT) + " B per stored entry kept, " + std::to_string(CE_BYTES_PEAK) + " while it is built); " +
+              std::to_string(free_b) + " B are free (tiling it is not supported)");
+  if (int rc = tsem_ensure_indices(h)) return rc;
+  CeIdsGuard ig(h);
+  PhaseTimer pt(h->stream);
+  const int cbits = ce_bits_for((uint64_t)std::max(0, h->K - 1)), gbits = ce_bits_for((uint64_t)G);
+  TSEM_ALLOC(h->d_ce_rptr, 2 * ((int64_t)G + 1));           // row pointer | entry pointer of every cell
+  TSEM_ALLOC(h->d_ce_rinfo, M);
+  TSEM_ALLOC(h->d_ce_lcol, E);
+  TSEM_ALLOC(h->d_ce_code, E);
+  TSEM_ALLOC(h->d_ce_cpos, E);
+  TSEM_ALLOC(h->d_ce_colptr, (int64_t)G + 1);
+  TSEM_ALLOC(h->d_ce_scratch, E);
+  int64_t* d_gent = h->d_ce_rptr + G + 1;
+  TSEM_HIP(hipMemcpyAsync(h->d_ce_rptr, h->gc_rptr.data(), 8 * ((size_t)G + 1), hipMemcpyHostToDevice, h->stream));
+  TSEM_HIP(hipMemcpyAsync(d_gent, h->gc_gent.data(), 8 * ((size_t)G + 1), hipMemcpyHostToDevice, h->stream));
+  int64_t n_runs = 0;
+  DevTmp key, key2, hscan, tmp;
+  TSEM_TMP(key, 8 * E); TSEM_TMP(key2, 8 * E); TSEM_TMP(hscan, 4 * E);
+  if (M > 0) {                                              // (rows without entries too: their class is what the fit reads)
+    k_ce_rows<<<cdiv64(M, 256), 256, 0, h->stream>>>(M, h->d_gc_rows, h->d_gc_key, h->d_gc_eoff, h->d_indptr, h->d_indices, h->d_raw,
+                                                    h->d_row_cls, h->d_row_code, cbits, h->d_ce_rinfo, key.as<uint64_t>(), h->d_ce_code);
+    TSEM_HIP(hipGetLastError());
+  }
+  if (E > 0) {
+    rocprim::counting_iterator<uint32_t> iota(0);
+    size_t sb = 0, sc = 0;
+    TSEM_HIP(rocprim::radix_sort_pairs(nullptr, sb, key.as<uint64_t>(), key2.as<uint64_t>(), iota, h->d_ce_cpos, (size_t)E, 0,
+                                       std::min(64, cbits + gbits), h->stream));
+    TSEM_HIP(rocprim::inclusive_scan(nullptr, sc, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)E, rocprim::plus<uint32_t>(), h->stream));
+    TSEM_TMP(tmp, std::max(sb, sc));
+    // stable: equal (cell, column) keys keep the row-ordered view's order — ascending rows
+    TSEM_HIP(rocprim::radix_sort_pairs(tmp.p, sb, key.as<uint64_t>(), key2.as<uint64_t>(), iota, h->d_ce_cpos, (size_t)E, 0,
+                                       std::min(64, cbits + gbits), h->stream));
+    uint32_t* head = reinterpret_cast<uint32_t*>(key.p);    // (the unsorted keys are done with)
+    k_ce_heads<<<cdiv64(E, 256), 256, 0, h->stream>>>(E, key2.as<uint64_t>(), head);
+    TSEM_HIP(hipGetLastError());
+    TSEM_HIP(rocprim::inclusive_scan(tmp.p, sc, head, hscan.as<uint32_t>(), (size_t)E, rocprim::plus<uint32_t>(), h->stream));
+    uint32_t nr = 0;
+    TSEM_HIP(hipMemcpyAsync(&nr, hscan.as<uint32_t>() + E - 1, 4, hipMemcpyDeviceToHost, h->stream));
+    TSEM_HIP(hipStreamSynchronize(h->stream));
+    n_runs = nr;
+    TSEM_ALLOC(h->d_ce_cptr, n_runs + 1);
+    TSEM_ALLOC(h->d_ce_cols, n_runs);
+    k_ce_colptr<<<cdiv64((int64_t)G + 1, 256), 256, 0, h->stream>>>((int64_t)G + 1, E, n_runs, d_gent, hscan.as<uint32_t>(), h->d_ce_colptr);
+    TSEM_HIP(hipGetLastError());
+    k_ce_columns<<<cdiv64(E, 256), 256, 0, h->stream>>>(E, n_runs, key2.as<uint64_t>(), hscan.as<uint32_t>(), h->d_ce_cpos, h->d_ce_colptr,
+                                                       cbits, h->d_ce_cptr, h->d_ce_cols, h->d_ce_lcol);
+    TSEM_HIP(hipGetLastError());
+    h->ce_colptr.assign((size_t)G + 1, 0);
+    TSEM_HIP(hipMemcpyAsync(h->ce_colptr.data(), h->d_ce_colptr, 8 * ((size_t)G + 1), hipMemcpyDeviceToHost, h->stream));
+    TSEM_HIP(hipStreamSynchronize(h->stream));
+  } else {
+    TSEM_ALLOC(h->d_ce_cptr, 1);
+    TSEM_ALLOC(h->d_ce_cols, 1);
+    TSEM_HIP(hipMemsetAsync(h->d_ce_cptr, 0, 4, h->stream));
+    TSEM_HIP(hipMemsetAsync(h->d_ce_colptr, 0, 8 * ((size_t)G + 1), h->stream));
+    h->ce_colptr.assign((size_t)G + 1, 0);
+    TSEM_HIP(hipStreamSynchronize(h->stream));
+  }
+  h->ce_ncols = n_runs;
+  h->ce_cells = G;
+  h->ce_version = h->groups_version;
+  pt.lap("cell_em: layout");
+  return TSEM_OK;
+}
+
+template <int T, bool LDS>
+int ce_launch(tsem_ctx* h, CeArgs A, const int32_t* d_list, int n, int kc_max) {
+  if (n <= 0) return TSEM_OK;
+  const size_t lds = 8 * ((size_t)CE_RED + (LDS ? 5 * (size_t)kc_max : 0));
+  if (lds > 48 * 1024)
+    TSEM_HIP(hipFuncSetAttribute((const void*)k_cell_em<T, LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+  A.cells = d_list;
+  k_cell_em<T, LDS><<<n, T, lds, h->stream>>>(A);
+  TSEM_HIP(hipGetLastError());
+  return TSEM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void tsem_cellem_free(tsem_ctx* h) { ce_free_layout(h); ce_free_result(h); }
+
+// One EM fit per group of rows (model.py:762-806 on raw[rows of the group], max_score of the whole matrix): see the top of this file.
+int tsem_cell_em(tsem_ctx* h, double epsilon, int32_t max_iter, int32_t use_likelihood) {
+  if (!h || !h->d_indptr) return TSEM_ERR_ARG;
+  if (int rc = ensure_device(h)) return rc;
+  if (tsem_comm_on(h)) TSEM_FAIL(TSEM_ERR_ARG, "tsem_cell_em: row-sharded per-cell fits are not supported (one GPU per run)");
+  if (!h->have_rowstats || !h->d_row_cls || !h->d_row_code) TSEM_FAIL(TSEM_ERR_ARG, "tsem_cell_em: no row statistics (tsem_rowstats)");
+  if (!h->d_lut || h->lut_len <= 0) TSEM_FAIL(TSEM_ERR_ARG, "tsem_cell_em: no score table (tsem_set_lut)");
+  if (!h->have_model) TSEM_FAIL(TSEM_ERR_ARG, "tsem_cell_em: no model (tsem_set_model gives the priors)");
+  if (!h->d_group && h->N) TSEM_FAIL(TSEM_ERR_ARG, "tsem_cell_em: no group map (tsem_set_groups)");
+  if (h->K <= 0) TSEM_FAIL(TSEM_ERR_ARG, "tsem_cell_em: the matrix has no columns");
+  h->ce_fitted = false;
+  if (int rc = ce_build_layout(h)) return rc;
+  PhaseTimer pt(h->stream);
+  const int32_t G = h->n_groups;
+  const int64_t nc = h->ce_ncols;
+  if (!h->d_ce_pi) {
+    TSEM_ALLOC(h->d_ce_pi, nc); TSEM_ALLOC(h->d_ce_theta, nc); TSEM_ALLOC(h->d_ce_pi_init, nc); TSEM_ALLOC(h->d_ce_theta_init, nc);
+    TSEM_ALLOC(h->d_ce_ws0, nc); TSEM_ALLOC(h->d_ce_ws1, nc); TSEM_ALLOC(h->d_ce_ws2, nc);
+    TSEM_ALLOC(h->d_ce_rest, 4 * (int64_t)G); TSEM_ALLOC(h->d_ce_niter, G); TSEM_ALLOC(h->d_ce_conv, G); TSEM_ALLOC(h->d_ce_lnl, G);
+    TSEM_ALLOC(h->d_ce_list, G);
+  }
+  TSEM_ALLOC(h->d_user_z, h->nnz);
+  if (h->nnz) {
+    k_ce_fill_nan<<<cdiv64(h->nnz, 256), 256, 0, h->stream>>>(h->nnz, h->d_user_z);   // rows in no cell have no entries
+    TSEM_HIP(hipGetLastError());
+  }
+  // the cells by class, each class largest first (by entries; ties in cell order)
+  std::vector<int32_t> cls[4];
+  int kc_max[4] = {0, 0, 0, 0};
+  for (int32_t c = 0; c < G; ++c) {
+    const int64_t kc = h->ce_colptr[c + 1] - h->ce_colptr[c], ne = h->gc_gent[c + 1] - h->gc_gent[c];
+    const int k = (kc <= CE_KC_WAVE && ne <= CE_ENT_WAVE) ? 0 : kc <= CE_KC_SMALL ? 1 : kc <= CE_KC_LARGE ? 2 : 3;
+    cls[k].push_back(c);
+    kc_max[k] = std::max<int>(kc_max[k], (int)kc);
+  }
+  std::vector<int32_t> list;
+  list.reserve((size_t)G);
+  int first[5] = {0, 0, 0, 0, 0};
+  for (int k = 0; k < 4; ++k) {
+    std::stable_sort(cls[k].begin(), cls[k].end(), [&](int32_t a, int32_t b) {
+      return h->gc_gent[a + 1] - h->gc_gent[a] > h->gc_gent[b + 1] - h->gc_gent[b];
+    });
+    list.insert(list.end(), cls[k].begin(), cls[k].end());
+    first[k + 1] = (int)list.size();
+  }
+  if (G) TSEM_HIP(hipMemcpyAsync(h->d_ce_list, list.data(), 4 * (size_t)G, hipMemcpyHostToDevice, h->stream));
+  CeArgs A{};
+  A.K = h->K; A.max_iter = max_iter; A.use_lnl = use_likelihood ? 1 : 0;
+  A.eps = epsilon; A.pi_prior = h->pi_prior; A.theta_prior = h->theta_prior;
+  A.rptr = h->d_ce_rptr; A.eoff = h->d_gc_eoff; A.rows = h->d_gc_rows; A.rinfo = h->d_ce_rinfo; A.indptr = h->d_indptr;
+  A.lcol = h->d_ce_lcol; A.code = h->d_ce_code; A.lut = h->d_lut; A.col_ptr = h->d_ce_colptr; A.cptr = h->d_ce_cptr; A.cpos = h->d_ce_cpos;
+  A.scratch = h->d_ce_scratch; A.user_z = h->d_user_z;
+  A.pi = h->d_ce_pi; A.theta = h->d_ce_theta; A.pi_init = h->d_ce_pi_init; A.theta_init = h->d_ce_theta_init;
+  A.ws_pi_prev = h->d_ce_ws0; A.ws_theta_prev = h->d_ce_ws1; A.ws_pisum0 = h->d_ce_ws2;
+  A.rest = h->d_ce_rest; A.n_iter = h->d_ce_niter; A.converged = h->d_ce_conv; A.lnl = h->d_ce_lnl;
+  if (int rc = ce_launch<64, true>(h, A, h->d_ce_list + first[0], first[1] - first[0], kc_max[0])) return rc;
+  if (int rc = ce_launch<256, true>(h, A, h->d_ce_list + first[1], first[2] - first[1], kc_max[1])) return rc;
+  if (int rc = ce_launch<512, true>(h, A, h->d_ce_list + first[2], first[3] - first[2], kc_max[2])) return rc;
+  if (int rc = ce_launch<512, false>(h, A, h->d_ce_list + first[3], first[4] - first[3], kc_max[3])) return rc;
+  TSEM_HIP(hipStreamSynchronize(h->stream));
+  for (int k = 0; k < 4; ++k) h->ce_class_n[k] = first[k + 1] - first[k];
+  h->ce_fitted = true;
+  pt.lap("cell_em: fit");
+  return TSEM_OK;
+}
+
+int tsem_cell_em_shape(tsem_ctx* h, int32_t* n_cells, int64_t* n_cols) {
+  if (!h || !n_cells || !n_cols) return TSEM_ERR_ARG;
+  if (!h->ce_fitted) TSEM_FAIL(TSEM_ERR_ARG, "tsem_cell_em_shape: no result (tsem_cell_em)");
+  *n_cells = h->ce_cells;
+  *n_cols = h->ce_ncols;
+  return TSEM_OK;
+}
+
+int tsem_cell_em_copy(tsem_ctx* h, int64_t* col_ptr, int32_t* cols, double* pi, double* theta, double* pi_init, double* theta_init,
+                      double* rest, int32_t* n_iter, int32_t* converged, double* lnl) {
+  if (!h || !col_ptr) return TSEM_ERR_ARG;
+  if (!h->ce_fitted) TSEM_FAIL(TSEM_ERR_ARG, "tsem_cell_em_copy: no result (tsem_cell_em)");
+  const size_t nc = (size_t)h->ce_ncols, G = (size_t)h->ce_cells;
+  if ((nc && (!cols || !pi || !theta || !pi_init || !theta_init)) || (G && (!rest || !n_iter || !converged || !lnl))) return TSEM_ERR_ARG;
+  if (int rc = ensure_device(h)) return rc;
+  std::copy(h->ce_colptr.begin(), h->ce_colptr.end(), col_ptr);
+  if (nc) {
+    TSEM_HIP(hipMemcpyAsync(cols, h->d_ce_cols, 4 * nc, hipMemcpyDeviceToHost, h->stream));
+    TSEM_HIP(hipMemcpyAsync(pi, h->d_ce_pi, 8 * nc, hipMemcpyDeviceToHost, h->stream));
+    TSEM_HIP(hipMemcpyAsync(theta, h->d_ce_theta, 8 * nc, hipMemcpyDeviceToHost, h->stream));
+    TSEM_HIP(hipMemcpyAsync(pi_init, h->d_ce_pi_init, 8 * nc, hipMemcpyDeviceToHost, h->stream));
+    TSEM_HIP(hipMemcpyAsync(theta_init, h->d_ce_theta_init, 8 * nc, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (G) {
+    TSEM_HIP(hipMemcpyAsync(rest, h->d_ce_rest, 32 * G, hipMemcpyDeviceToHost, h->stream));
+    TSEM_HIP(hipMemcpyAsync(n_iter, h->d_ce_niter, 4 * G, hipMemcpyDeviceToHost, h->stream));
+    TSEM_HIP(hipMemcpyAsync(converged, h->d_ce_conv, 4 * G, hipMemcpyDeviceToHost, h->stream));
+    TSEM_HIP(hipMemcpyAsync(lnl, h->d_ce_lnl, 8 * G, hipMemcpyDeviceToHost, h->stream));
+  }
+  TSEM_HIP(hipStreamSynchronize(h->stream));
+  return TSEM_OK;
+}
+
+}  // extern "C"

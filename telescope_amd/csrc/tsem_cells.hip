@@ -238,6 +238,8 @@ int run_tile(tsem_ctx* h, const TileBufs& B, int method, double thresh, int whic
 
 extern "C" {
 
+int tsem_build_grouping(tsem_ctx* h) { return build_grouping(h); }   // (the per-cell fits start from the same grouping)
+
 // scTelescope.output_report's per-barcode counts (model.py:611-625) as a sparse matrix: see the top of this file.
 int tsem_group_counts(tsem_ctx* h, int method, double thresh, int which, const int32_t* picks, int64_t* nnz) {
   if (!h || !h->d_indptr || !nnz) return TSEM_ERR_ARG;

@@ -216,6 +216,27 @@ struct tsem_ctx {
   int32_t *d_gc_ogrp = nullptr, *d_gc_ocol = nullptr;   // [gc_cap] the last result: group, column, value per stored entry
   double* d_gc_oval = nullptr;
   int64_t* d_gc_gptr = nullptr;     // [gc_groups + 1] the last result's group pointer
+  // per-cell EM fits (tsem_cell_em, tsem_cellem.hip): the compacted, column-ordered copy of the grouped rows, cached per map, and the last fit
+  uint64_t ce_version = ~0ull;      // the map version the layout below was built from
+  int64_t* d_ce_rptr = nullptr;     // [2 (n_groups + 1)] first row | first entry of every cell in group order
+  uint32_t* d_ce_rinfo = nullptr;   // [rows in cells] row class << 16 | weight code, group order
+  int32_t* d_ce_lcol = nullptr;     // [entries in cells] cell-local column of every entry, row-ordered view
+  uint16_t* d_ce_code = nullptr;    // [entries in cells] its score code
+  uint32_t* d_ce_cpos = nullptr;    // [entries in cells] column-ordered view: positions in the row-ordered view
+  uint32_t* d_ce_cptr = nullptr;    // [ce_ncols + 1] first entry of every compacted column in the column-ordered view
+  int64_t* d_ce_colptr = nullptr;   // [n_groups + 1] first compacted column of every cell
+  int32_t* d_ce_cols = nullptr;     // [ce_ncols] the compacted columns: sorted distinct columns of every cell
+  double* d_ce_scratch = nullptr;   // [entries in cells] what the row pass leaves for the column pass
+  std::vector<int64_t> ce_colptr;   // host copy of d_ce_colptr
+  int64_t ce_ncols = 0;             // sum of the cells' distinct columns
+  int32_t ce_cells = 0;             // cells of the layout
+  double *d_ce_pi = nullptr, *d_ce_theta = nullptr, *d_ce_pi_init = nullptr, *d_ce_theta_init = nullptr;   // [ce_ncols] the last fit
+  double *d_ce_ws0 = nullptr, *d_ce_ws1 = nullptr, *d_ce_ws2 = nullptr;   // [ce_ncols] previous pi / theta, pisum0 of the cells whose tables do not fit LDS
+  double* d_ce_rest = nullptr;      // [ce_cells][4] pi, theta, pi_init, theta_init of the columns a cell never touches
+  int32_t *d_ce_niter = nullptr, *d_ce_conv = nullptr, *d_ce_list = nullptr;   // [ce_cells] iterations, converged, launch order
+  double* d_ce_lnl = nullptr;       // [ce_cells]
+  int32_t ce_class_n[4] = {0, 0, 0, 0};   // cells per class of the last fit: wave | 256 threads | 512 threads | global workspace
+  bool ce_fitted = false;
   int32_t *d_rep_nb = nullptr, *d_rep_rows = nullptr;   // [N] scratch of tsem_report_colsums, kept between calls
   unsigned long long* d_rep_n = nullptr;
   struct RpChunk* d_rep_chunks = nullptr; int64_t n_rep_chunks = 0; int rep_chunk_E = 0;   // k_report_pack's packing of the rows into wave-sized chunks (tsem_report_pack.h)

@@ -115,6 +115,7 @@ void tsem_free_matrix(tsem_ctx* h) {
   dfree(h->d_group); h->n_groups = 0;
   dfree(h->d_gc_key); dfree(h->d_gc_rows); dfree(h->d_gc_eoff); h->gc_version = ~0ull; h->gc_rptr.clear(); h->gc_gent.clear();
   dfree(h->d_gc_ogrp); dfree(h->d_gc_ocol); dfree(h->d_gc_oval); dfree(h->d_gc_gptr); h->gc_nnz = h->gc_cap = 0; h->gc_groups = 0;
+  tsem_cellem_free(h);
   if (h->d_gtile) { (void)hipFree(h->d_gtile); h->d_gtile = nullptr; h->gtile_bytes = 0; }
   if (h->d_rep_tmp) { (void)hipFree(h->d_rep_tmp); h->d_rep_tmp = nullptr; h->rep_tmp_bytes = 0; }
   h->first_pending = false;

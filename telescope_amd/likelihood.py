@@ -115,6 +115,43 @@ class Assignment(object):
         return self.tocsr().toarray()
 
 
+class CellFits(object):
+    """What `TelescopeLikelihood.em_cells` returns: one EM fit per cell (tsem_cell_em).  Cell c touches the columns
+    `cols[col_ptr[c]:col_ptr[c + 1]]` (ascending); `pi`, `theta`, `pi_init`, `theta_init` hold its parameters there, `rest[c]` the
+    four values every other column of the cell has (the closed form of a column without fragments).  `n_iter`, `converged`, `lnl`
+    per cell; a cell without rows is not fitted (`n_iter` 0, not converged, `lnl` NaN)."""
+    FIELDS = ('col_ptr', 'cols', 'pi', 'theta', 'pi_init', 'theta_init', 'rest', 'n_iter', 'converged', 'lnl')
+
+    def __init__(self, K, col_ptr, cols, pi, theta, pi_init, theta_init, rest, n_iter, converged, lnl):
+        self.K = int(K)
+        self.col_ptr, self.cols = np.asarray(col_ptr, dtype=np.int64), np.asarray(cols, dtype=np.int32)
+        self.pi, self.theta = np.asarray(pi, dtype=np.float64), np.asarray(theta, dtype=np.float64)
+        self.pi_init, self.theta_init = np.asarray(pi_init, dtype=np.float64), np.asarray(theta_init, dtype=np.float64)
+        self.rest = np.asarray(rest, dtype=np.float64).reshape(-1, 4)
+        self.n_iter = np.asarray(n_iter, dtype=np.int32)
+        self.converged = np.asarray(converged).astype(bool)
+        self.lnl = np.asarray(lnl, dtype=np.float64)
+        self.n_cells = len(self.col_ptr) - 1
+        if not (len(self.rest) == len(self.n_iter) == len(self.converged) == len(self.lnl) == self.n_cells):
+            raise ValueError('CellFits: per-cell arrays of different lengths')
+        n_cols = int(self.col_ptr[-1]) if self.n_cells >= 0 and len(self.col_ptr) else 0
+        if any(len(a) != n_cols for a in (self.cols, self.pi, self.theta, self.pi_init, self.theta_init)):
+            raise ValueError('CellFits: per-column arrays do not match col_ptr')
+
+    def dense(self, c):
+        """(pi, theta, pi_init, theta_init) of cell c as full K-vectors."""
+        c = int(c)
+        if not 0 <= c < self.n_cells:
+            raise IndexError('cell %d outside [0, %d)' % (c, self.n_cells))
+        a, b = int(self.col_ptr[c]), int(self.col_ptr[c + 1])
+        out = []
+        for j, src in enumerate((self.pi, self.theta, self.pi_init, self.theta_init)):
+            v = np.full(self.K, self.rest[c, j])
+            v[self.cols[a:b]] = src[a:b]
+            out.append(v)
+        return tuple(out)
+
+
 class TelescopeLikelihood(object):
     """EM model over a fragments x loci score matrix (model.py:631-865)."""
 
@@ -217,6 +254,7 @@ class TelescopeLikelihood(object):
         self._z = None
         self._z_which = None
         self._report_cache = {}
+        self._cells_z = False                                        # the device's Z_USER buffer holds the z of em_cells
         self.n_iter, self.converged = 0, False
 
     # ---- lazily materialised compat attributes --------------------------------
@@ -417,6 +455,70 @@ class TelescopeLikelihood(object):
         self.comm.allreduce_device(self._eng, self.K, 1)
         return float(self._eng.read_reduce(self.K, 1)[0])
 
+    # ---- per-cell fits (single-cell `--pooling_mode individual`) ----------------------------------
+    def _check_cells(self, cell_of_row, n_cells, what):
+        if self.comm.world > 1:
+            raise NotImplementedError('%s: row-sharded runs (WORLD_SIZE > 1) are not supported; run single-cell '
+                                      'assignment on one GPU' % what)
+        cor = np.ascontiguousarray(cell_of_row, dtype=np.int32)
+        n_cells = int(n_cells)
+        if cor.shape != (self.N,):
+            raise ValueError('cell_of_row must have one entry per row')
+        if cor.size and (cor.min() < -1 or cor.max() >= n_cells):
+            raise ValueError('cell_of_row entries must lie in [-1, n_cells)')
+        return cor, n_cells
+
+    def _set_cells(self, cor, n_cells):
+        """The row -> cell map on the device, once per content: the per-cell fit and the per-cell counts share it."""
+        import hashlib
+        key = ('cells', hashlib.blake2b(cor.tobytes(), digest_size=16).hexdigest(), n_cells)
+        if getattr(self._eng, 'groups_token', None) != key:
+            self._eng.set_groups(cor, n_cells)
+            self._eng.groups_token = key
+
+    def em_cells(self, cell_of_row, n_cells, use_likelihood=False, loglev=lg.WARNING):
+        """One EM fit PER CELL instead of one fit of the pool: cell c's model is `TelescopeLikelihood(raw[rows of c])` with the score
+        scale of the whole matrix (model.py:762-806 on the cell's rows; its own weights, totals, prior weights and pisum0; all K
+        columns) — all cells in one device call (tsem_cell_em), each fitted by one workgroup, deterministic.  `cell_of_row[i]` in
+        [0, n_cells) or -1 (a row in no cell), as for `reassign_cell_counts`.  Returns a `CellFits`.
+
+        Afterwards `tl.z` is the per-cell posterior matrix (rows in no cell have no entries) and `reassign`, `reassign_colsums`,
+        `reassign_cell_counts`, `reassign_group_sums` and `lookup` read it; `select_z('pooled')` switches back to the pooled fit's z
+        and `select_z('cells')` to this one, without refitting.  `pi`, `theta`, `lnl`, `n_iter` stay the pooled fit's.  One GPU only."""
+        cor, n_cells = self._check_cells(cell_of_row, n_cells, 'em_cells')
+        self._set_cells(cor, n_cells)
+        r = self._eng.cell_em(self.epsilon, self.max_iter, use_likelihood)
+        fits = CellFits(self.K, *[r[k] for k in CellFits.FIELDS])
+        self._pooled_which = self._z_which if self._z_which != Z_USER else getattr(self, '_pooled_which', None)
+        self._cells_z = True
+        self._z, self._z_which = None, Z_USER
+        self._report_cache = {}
+        fitted = fits.n_iter > 0
+        if fitted.any():
+            it = fits.n_iter[fitted]
+            lg.log(loglev, 'Per-cell EM: {:d} cells fitted, {:d} converged; iterations min {:d} / median {:g} / max {:d}.'.format(
+                int(fitted.sum()), int(fits.converged[fitted].sum()), int(it.min()), float(np.median(it)), int(it.max())))
+        else:
+            lg.log(loglev, 'Per-cell EM: no cell has fragments.')
+        return fits
+
+    def select_z(self, which):
+        """Which posteriors `tl.z` and the report methods read: 'pooled' — the pooled fit's (`em()`) — or 'cells' — the per-cell
+        fits' (`em_cells()`).  Nothing is refitted."""
+        if which == 'cells':
+            if not getattr(self, '_cells_z', False):
+                raise ValueError("select_z('cells'): no per-cell posteriors on the device (em_cells(), and no z assigned since)")
+            new = Z_USER
+        elif which == 'pooled':
+            new = getattr(self, '_pooled_which', None) if self._z_which == Z_USER else self._z_which
+            if new is None:
+                raise ValueError("select_z('pooled'): no pooled posteriors yet (em())")
+        else:
+            raise ValueError("select_z: 'pooled' or 'cells'")
+        if new != self._z_which:
+            self._z, self._z_which = None, new
+            self._report_cache = {}
+
     # ---- reassign -------------------------------------------------------------------------
     def _which(self, initial):
         if initial:
@@ -427,6 +529,7 @@ class TelescopeLikelihood(object):
             if not getattr(self, '_user_z_loaded', False):   # a caller assigned tl.z: the device reads it as is
                 self._eng.set_user_z(self._align(self._z, fill=np.nan))
                 self._user_z_loaded = True
+                self._cells_z = False                            # (the buffer em_cells filled is replaced)
             return Z_USER
         return self._z_which
 
@@ -547,24 +650,12 @@ class TelescopeLikelihood(object):
         in ascending row order like scipy adds it — bit-identical to summing the device's own `reassign` matrix.  `cell_of_row[i]` in
         [0, n_cells) or -1 (a row in no cell).  Built sparse on the device (tsem_group_counts); `choose` draws its picks like
         `reassign('choose')`.  The map goes to the device once per content and serves every method asked of it.  One GPU only."""
-        import hashlib
         if method not in REASSIGN_METHODS:
             raise ValueError('Argument "method" should be one of (exclude, choose, average, conf, unique, all)')
-        if self.comm.world > 1:
-            raise NotImplementedError('reassign_cell_counts: row-sharded runs (WORLD_SIZE > 1) are not supported; run single-cell '
-                                      'assignment on one GPU')
-        cor = np.ascontiguousarray(cell_of_row, dtype=np.int32)
-        n_cells = int(n_cells)
-        if cor.shape != (self.N,):
-            raise ValueError('cell_of_row must have one entry per row')
-        if cor.size and (cor.min() < -1 or cor.max() >= n_cells):
-            raise ValueError('cell_of_row entries must lie in [-1, n_cells)')
+        cor, n_cells = self._check_cells(cell_of_row, n_cells, 'reassign_cell_counts')
         which = self._which(initial)
         picks = self._picks(which) if method == 'choose' else None
-        key = ('cells', hashlib.blake2b(cor.tobytes(), digest_size=16).hexdigest(), n_cells)
-        if getattr(self._eng, 'groups_token', None) != key:
-            self._eng.set_groups(cor, n_cells)
-            self._eng.groups_token = key
+        self._set_cells(cor, n_cells)
         gptr, cols, vals = self._eng.group_counts(method, thresh, which, self._dense_picks(picks))
         return sp.csr_matrix((vals, cols, gptr), shape=(n_cells, self.K))
 

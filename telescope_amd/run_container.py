@@ -455,6 +455,12 @@ class scTelescope(Telescope):
                 fh.write('\t'.join(comment) + '\n')
                 stats.to_csv(fh, sep='\t', index=False)
         n_cells = len(self.barcodes)
+        if getattr(self.opts, 'pooling_mode', 'pseudobulk') == 'individual':
+            # one model per cell: from here on tl's z is the per-cell posteriors, and the counts below come from them
+            fits = tl.em_cells(self.cell_of_row, n_cells, bool(getattr(self.opts, 'use_likelihood', False)), loglev=lg.INFO)
+            if write:
+                self.write_cell_stats(tl, fits, stats_filename.replace('run_stats.tsv', 'cell_stats.tsv')
+                                      if stats_filename.endswith('run_stats.tsv') else stats_filename + '.cell_stats.tsv')
         for method in SC_METHODS:
             if method != mode and not every:
                 continue
@@ -467,3 +473,18 @@ class scTelescope(Telescope):
             else:
                 with open(out, 'w') as fh:
                     write_dense_counts(fh, counts, self.barcodes, names)
+
+    def write_cell_stats(self, tl, fits, filename):
+        """`<exp_tag>-cell_stats.tsv` of `--pooling_mode individual`: one line per barcode — its fragments, how many of them are
+        ambiguous, the features it touches, and its fit's iterations, convergence and log-likelihood."""
+        cor = np.asarray(self.cell_of_row)
+        n_cells = len(self.barcodes)
+        in_cell = cor >= 0
+        frags = np.bincount(cor[in_cell], minlength=n_cells)
+        amb = np.bincount(cor[in_cell], weights=np.asarray(tl.Y).ravel()[in_cell], minlength=n_cells).astype(np.int64)
+        with open(filename, 'w') as fh:
+            fh.write('barcode\tfragments\tambiguous\tcolumns\titerations\tconverged\tlnl\n')
+            for c in range(n_cells):
+                fh.write('%s\t%d\t%d\t%d\t%d\t%s\t%s\n' % (_csv_field(self.barcodes[c]), frags[c], amb[c],
+                                                            fits.col_ptr[c + 1] - fits.col_ptr[c], fits.n_iter[c],
+                                                            bool(fits.converged[c]), _float_repr(fits.lnl[c])))

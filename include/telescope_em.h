@@ -455,8 +455,10 @@ int  tsem_device_memory(tsem_ctx* h, int device, int64_t* free_bytes, int64_t* t
 int  tsem_layout_info(tsem_ctx* h, int64_t* info32);
 /* The same with the caller's buffer length: the first min(n, TSEM_LAYOUT_INFO_N) values.  Appended behind the 32 above: [32] bytes of
  * index per stored entry of the blocked layout — 3 where the fused kernel reads fp64 entries of a non-split layout (a 13-bit column
- * slot and an 11-bit row slot per entry, four entries in 12 bytes), 4 (local row << 16 | local column) everywhere else. */
-#define TSEM_LAYOUT_INFO_N 33
+ * slot and an 11-bit row slot per entry, four entries in 12 bytes), 4 (local row << 16 | local column) everywhere else; [33]-[36] the
+ * cells the last tsem_cell_em fitted per kernel class — a wave per cell | 256 threads | 512 threads, tables in LDS | 512 threads,
+ * tables in a global workspace — all 0 before a fit. */
+#define TSEM_LAYOUT_INFO_N 37
 int  tsem_layout_info_n(tsem_ctx* h, int64_t* info, int32_t n);
 /* per-block shader-clock stamps of team 0 / member 0 of the fused kernel (option "fused_prof") */
 int  tsem_debug_fused_prof(tsem_ctx* h, uint64_t* out512);

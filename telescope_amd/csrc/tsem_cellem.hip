@@ -285,6 +285,7 @@ void ce_free_result(tsem_ctx* h) {
   dfree(h->d_ce_pi); dfree(h->d_ce_theta); dfree(h->d_ce_pi_init); dfree(h->d_ce_theta_init); dfree(h->d_ce_ws0); dfree(h->d_ce_ws1);
   dfree(h->d_ce_ws2); dfree(h->d_ce_rest); dfree(h->d_ce_niter); dfree(h->d_ce_conv); dfree(h->d_ce_lnl); dfree(h->d_ce_list);
   h->ce_fitted = false;
+  for (int k = 0; k < 4; ++k) h->ce_class_n[k] = 0;
 }
 
 // the compacted, column-ordered copy of the grouped rows (see the top of this file), cached per group map
@@ -304,8 +305,8 @@ int ce_build_layout(tsem_ctx* h) {
     TSEM_FAIL(TSEM_ERR_NOMEM, "tsem_cell_em: the per-cell layout needs " + std::to_string(need) + " B of device memory (" +
               std::to_string(CE_BYTES_KEPT) + " B per stored entry kept, " + std::to_string(CE_BYTES_PEAK) + " while it is built); " +
               std::to_string(free_b) + " B are free (tiling it is not supported)");
+  CeIdsGuard ig(h);                                         // (before the ids come back: it has to see that they were dropped)
   if (int rc = tsem_ensure_indices(h)) return rc;
-  CeIdsGuard ig(h);
   PhaseTimer pt(h->stream);
   const int cbits = ce_bits_for((uint64_t)std::max(0, h->K - 1)), gbits = ce_bits_for((uint64_t)G);
   TSEM_ALLOC(h->d_ce_rptr, 2 * ((int64_t)G + 1));           // row pointer | entry pointer of every cell

@@ -1,6 +1,6 @@
 """Reference for the per-cell EM fits (`TelescopeLikelihood.em_cells`): the oracle, run once per cell on the cell's rows with the
-score scale of the whole matrix, and what the tests derive from its results.  Shared by tests/test_gpu_cell_em.py and
-tests/test_cell_em_host.py; every reference is computed once per shape and never changed."""
+score scale of the whole matrix, and what the tests derive from its results.  Shared by tests/test_gpu_cell_em.py,
+tests/test_gpu_cell_em_edges.py and tests/test_cell_em_host.py; every reference is computed once per shape and never changed."""
 import functools
 import warnings
 
@@ -54,7 +54,7 @@ class CellRef(object):
                     self.fits.append(None)
                     continue
                 om = OracleModel(self.raw[rows], pi_prior, theta_prior, max_score=gmax)
-                om.em(epsilon, max_iter, use_likelihood)
+                om.trace = om.em(epsilon, max_iter, use_likelihood)    # [(diff, lnl or None)] per iteration
                 self.fits.append(om)
 
     @functools.lru_cache(maxsize=None)
@@ -132,6 +132,164 @@ def shape_case(seed):
     n, k, n_cells, theta_prior, pi_prior, use_lnl = SHAPES[seed]
     raw, cor = random_matrix(seed, n, k, n_cells)
     return raw, cor, n_cells, CellRef(raw, cor, n_cells, pi_prior, theta_prior, use_likelihood=use_lnl)
+
+
+def boundary_matrix(seed, K, cells):
+    """A matrix whose cells have exactly the compacted column count and the entry count asked for: `cells` = [(Kc, entries), ...]
+    with Kc <= entries.  Per cell: Kc distinct columns of K; the entries laid cyclically over them; cut into rows of 1-8 entries
+    (30 % of the rows forced to one entry, lengths capped by Kc, so a row never meets a column twice); indices sorted per row, scores
+    100-399; the rows of all cells shuffled together.  Returns (raw, cell_of_row, [sorted columns of every cell])."""
+    rng = np.random.RandomState(seed)
+    lens, idx, cell, cols_of = [], [], [], []
+    for c, (kc, ne) in enumerate(cells):
+        assert 1 <= kc <= K and ne >= kc, (c, kc, ne)
+        cols = rng.choice(K, kc, replace=False)
+        seq = cols[np.arange(ne) % kc]
+        o = 0
+        while o < ne:
+            l = 1 if rng.rand() < 0.3 else int(rng.randint(1, 9))
+            l = min(l, kc, ne - o)
+            idx.append(np.sort(seq[o:o + l])); lens.append(l); cell.append(c)
+            o += l
+        cols_of.append(np.sort(cols).astype(np.int32))
+    perm = rng.permutation(len(lens))
+    indptr = np.concatenate([[0], np.cumsum(np.asarray(lens)[perm])])
+    indices = np.concatenate([idx[i] for i in perm]).astype(np.int32)
+    raw = sp.csr_matrix((rng.randint(100, 400, indptr[-1]).astype(np.uint16), indices, indptr), shape=(len(lens), K))
+    return raw, np.asarray(cell, np.int32)[perm], cols_of
+
+
+# Boundary case B: a cell on either side of every class threshold of the device unit (Kc 256 / 1024 / 3840 columns, 4096 entries
+# for the wave class), the largest LDS launch the unit can make (Kc = 3840), and three tiny cells.  Classes: wave 4 (cells 0, 7, 8,
+# 9), 256 threads 3 (1, 2, 3), 512 threads 2 (4, 5), global workspace 1 (6).  Seed 21, checked on the CPU
+# (tests/test_cell_em_host.py::test_boundary_case_is_decided_by_no_rounding): every cell is fitted without a NaN, in 2-100
+# iterations (four cells run into max_iter under the first parameter set), 5 and 22 of 10016 rows are undecided, and no
+# iteration's stop test lies within 1e-6 relative of epsilon — so no other seed was needed.
+B_SEED, B_K = 21, 4000
+B_CELLS = ((256, 4096), (257, 4096), (256, 4097), (1024, 3000), (1025, 3000), (3840, 8000), (3841, 8000), (1, 1), (1, 40), (2, 2))
+B_CLASSES = (4, 3, 2, 1)
+B_PARAMS = ((0, 200000, False), (1, 5, True))              # (pi_prior, theta_prior, use_likelihood)
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_case():
+    return boundary_matrix(B_SEED, B_K, B_CELLS)
+
+
+def _boundary_named():
+    raw, cor, _ = boundary_case()
+    return raw, cor, len(B_CELLS)
+
+
+# the two cells around the largest LDS launch alone (engine options are tested on them)
+LARGE_CELLS = ((3840, 8000), (3841, 8000))
+
+
+@functools.lru_cache(maxsize=None)
+def large_case():
+    raw, cor, _ = boundary_matrix(22, B_K, LARGE_CELLS)
+    return raw, cor, len(LARGE_CELLS)
+
+
+def empty_rows(raw, rows):
+    """`raw` with the stored entries of `rows` removed (the rows stay)."""
+    raw = sp.csr_matrix(raw)
+    lens = np.diff(raw.indptr)
+    keep = np.ones(raw.shape[0], bool)
+    keep[rows] = False
+    ek = np.repeat(keep, lens)
+    indptr = np.concatenate([[0], np.cumsum(lens * keep)])
+    return sp.csr_matrix((raw.data[ek], raw.indices[ek], indptr), shape=raw.shape)
+
+
+@functools.lru_cache(maxsize=None)
+def empty_rows_case():
+    """300 x 40, six random cells; five rows lose their entries: three stay in their (otherwise normal) cells, the other two
+    become cell 6, a cell of rows without entries only (Kc = 0)."""
+    raw, cor = random_matrix(7, 300, 40, 6)
+    rows = np.flatnonzero(cor >= 0)[[0, 10, 20, 30, 40]]
+    raw = empty_rows(raw, rows)
+    cor = cor.copy()
+    cor[rows[3:]] = 6
+    return raw, cor, 7
+
+
+@functools.lru_cache(maxsize=None)
+def full_columns_case():
+    """cell 0 touches every column (Kc == K: no `rest` column exists)"""
+    raw, cor, _ = boundary_matrix(3, 64, [(64, 500), (3, 7)])
+    return raw, cor, 2
+
+
+@functools.lru_cache(maxsize=None)
+def tiny_k_case(K):
+    raw, cor, _ = boundary_matrix(5, K, {2: [(2, 30), (1, 4)], 1: [(1, 5), (1, 1)]}[K])
+    return raw, cor, 2
+
+
+NAMED = {'B': _boundary_named, 'large': large_case, 'empty_rows': empty_rows_case, 'full_columns': full_columns_case,
+         'K2': functools.partial(tiny_k_case, 2), 'K1': functools.partial(tiny_k_case, 1),
+         'shape1': lambda: shape_case(1)[:3]}
+
+
+@functools.lru_cache(maxsize=None)
+def cell_ref(key,pi_prior, theta_prior, use_likelihood=False, max_iter=MAX_ITER):
+    """The oracle's fits of a named matrix (NAMED), once per session."""
+    raw, cor, n_cells = NAMED[key]()
+    return CellRef(raw, cor, n_cells, pi_prior, theta_prior, max_iter=max_iter, use_likelihood=use_likelihood)
+
+
+def stop_margin(ref, epsilon=EPSILON):
+    """The smallest relative distance |x - epsilon| / epsilon of any iteration's stop test x (diff, or the step of lnl) of any cell:
+    iteration counts are compared for equality and must not hinge on a rounding."""
+    worst = np.inf
+    for om in ref.fits:
+        if om is None:
+            continue
+        lnl_prev = np.inf
+        for diff, lnl in om.trace:
+            x = diff if lnl is None else abs(lnl - lnl_prev)
+            if lnl is not None:
+                lnl_prev = lnl
+            if np.isfinite(x):
+                worst = min(worst, abs(x - epsilon) / epsilon)
+    return worst
+
+
+def _check_fits(fits, ref, label):
+    """n_iter / converged equal; pi, theta, pi_init, theta_init (full K) and lnl at RTOL; a cell without rows is not fitted."""
+    assert fits.n_cells == ref.n_cells
+    for c, om in enumerate(ref.fits):
+        if om is None:
+            assert fits.n_iter[c] == 0 and not fits.converged[c] and np.isnan(fits.lnl[c]), (label, c)
+            assert fits.col_ptr[c + 1] == fits.col_ptr[c]
+            continue
+        assert fits.n_iter[c] == om.n_iter and bool(fits.converged[c]) == bool(om.converged), \
+            (label, c, int(fits.n_iter[c]), om.n_iter, bool(fits.converged[c]), om.converged)
+        cols = fits.cols[fits.col_ptr[c]:fits.col_ptr[c + 1]]
+        assert np.array_equal(cols, np.unique(ref.raw[ref.rows[c]].indices)), (label, c)
+        for got, want, name in zip(fits.dense(c), (om.pi, om.theta, om.pi_init, om.theta_init), ('pi', 'theta', 'pi_init', 'theta_init')):
+            assert np.allclose(got, want, rtol=RTOL, atol=0, equal_nan=True), (label, c, name, np.nanmax(np.abs(got - want)))
+        assert np.isclose(fits.lnl[c], om.lnl, rtol=RTOL, atol=0, equal_nan=True), (label, c, fits.lnl[c], om.lnl)
+
+
+def _check_z(tl, ref, label):
+    """Same pattern, stored entries at RTOL; rows in no cell have no entries.  A cell whose oracle z is NaN (theta = NaN spreads
+    through 0 * NaN, model.py:718-720) has no entries on the device: NaN is the device's mark for `not in z's pattern`."""
+    got = sp.csr_matrix(tl.z); got.sort_indices()
+    want = ref.z()
+    nan_rows = np.zeros(ref.N, bool)
+    if want.nnz:
+        nan_rows[np.unique(sp.coo_matrix(want).row[np.isnan(want.data)])] = True
+    glen, wlen = np.diff(got.indptr), np.diff(want.indptr)
+    assert np.all(glen[ref.cor < 0] == 0), label
+    assert np.all(glen[nan_rows] == 0), label
+    keep = ~nan_rows
+    assert np.array_equal(glen[keep], wlen[keep]), label
+    w = want[np.flatnonzero(keep)]
+    g = got[np.flatnonzero(keep)]
+    assert np.array_equal(g.indices, w.indices), label
+    assert np.allclose(g.data, w.data, rtol=RTOL, atol=0), (label, np.max(np.abs(g.data - w.data)))
 
 
 def selector(cor, n_cells):

@@ -137,6 +137,44 @@ def test_header_declares_and_library_lists_the_unit():
         assert name in _lib.exported_symbols()
 
 
+def test_boundary_matrix_gives_every_cell_its_columns_and_entries():
+    cells = [(5, 5), (1, 9), (7, 40), (64, 64)]
+    raw, cor, cols = R.boundary_matrix(11, 64, cells)
+    assert raw.has_canonical_format and raw.shape[1] == 64 and raw.nnz == sum(ne for _, ne in cells)
+    lens = np.diff(raw.indptr)
+    assert lens.min() >= 1 and lens.max() <= 8 and raw.data.min() >= 100 and raw.data.max() <= 399
+    for c, (kc, ne) in enumerate(cells):
+        sub = raw[cor == c]
+        assert sub.nnz == ne and len(cols[c]) == kc and np.array_equal(np.unique(sub.indices), cols[c]), c
+        assert np.diff(sub.indptr).max() <= kc
+    assert np.any(np.diff(cor) < 0)                          # (the cells' rows are shuffled together)
+    again = R.boundary_matrix(11, 64, cells)
+    assert np.array_equal(again[0].data, raw.data) and np.array_equal(again[1], cor)
+
+
+def test_boundary_case_is_decided_by_no_rounding():
+    """What tests/test_gpu_cell_em_edges.py relies on in case B, from the oracle alone: every cell has the column and entry counts
+    that put it where the case says; every cell is fitted without a NaN, in 2 to 100 iterations; the rows the oracle cannot decide
+    stay under the 0.5 % cap of the count comparison; and no iteration's stop test — diff, or the step of lnl — lies within 1e-6
+    relative of epsilon, so that iteration counts can be compared for equality."""
+    raw, cor, cols = R.boundary_case()
+    assert raw.shape[1] == R.B_K
+    want = [0, 0, 0, 0]
+    for c, (kc, ne) in enumerate(R.B_CELLS):
+        sub = raw[cor == c]
+        assert sub.nnz == ne and np.array_equal(np.unique(sub.indices), cols[c]) and len(cols[c]) == kc, c
+        want[0 if (kc <= 256 and ne <= 4096) else 1 if kc <= 1024 else 2 if kc <= 3840 else 3] += 1
+    assert tuple(want) == R.B_CLASSES
+    for params in R.B_PARAMS:
+        ref = R.cell_ref('B', *params)
+        for c, om in enumerate(ref.fits):
+            assert om is not None and 2 <= om.n_iter <= R.MAX_ITER, (params, c)
+            assert not np.any(np.isnan(om.pi)) and not np.any(np.isnan(om.theta)) and not np.isnan(om.lnl), (params, c)
+        assert len(ref.undecided_rows()) <= 0.005 * ref.fitted_rows(), params
+        assert R.stop_margin(ref) > 1e-6, (params, R.stop_margin(ref))
+    assert R.stop_margin(R.cell_ref('large', 0, 200000)) > 1e-6
+
+
 @pytest.mark.parametrize('pi_prior,theta_prior,use_likelihood', [(0, 200000, False), (0, 0, False), (1, 5, True)])
 def test_closed_form_of_untouched_columns_equals_the_oracle(pi_prior, theta_prior, use_likelihood):
     """The fit on a cell's compacted columns — one closed-form value for the K - Kc columns the cell never touches, which count in

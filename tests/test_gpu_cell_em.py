@@ -15,7 +15,7 @@ import scipy.sparse as sp
 
 from conftest import Opts
 import _cell_em_reference as R
-from _cell_em_reference import ALL_METHODS, INT_METHODS, RTOL
+from _cell_em_reference import ALL_METHODS, INT_METHODS, RTOL, _check_fits, _check_z
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
@@ -55,42 +55,6 @@ def _same_bits(a, b):
     return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
 
 
-def _check_fits(fits, ref, label):
-    """n_iter / converged equal; pi, theta, pi_init, theta_init (full K) and lnl at RTOL; a cell without rows is not fitted."""
-    assert fits.n_cells == ref.n_cells
-    for c, om in enumerate(ref.fits):
-        if om is None:
-            assert fits.n_iter[c] == 0 and not fits.converged[c] and np.isnan(fits.lnl[c]), (label, c)
-            assert fits.col_ptr[c + 1] == fits.col_ptr[c]
-            continue
-        assert fits.n_iter[c] == om.n_iter and bool(fits.converged[c]) == bool(om.converged), \
-            (label, c, int(fits.n_iter[c]), om.n_iter, bool(fits.converged[c]), om.converged)
-        cols = fits.cols[fits.col_ptr[c]:fits.col_ptr[c + 1]]
-        assert np.array_equal(cols, np.unique(ref.raw[ref.rows[c]].indices)), (label, c)
-        for got, want, name in zip(fits.dense(c), (om.pi, om.theta, om.pi_init, om.theta_init), ('pi', 'theta', 'pi_init', 'theta_init')):
-            assert np.allclose(got, want, rtol=RTOL, atol=0, equal_nan=True), (label, c, name, np.nanmax(np.abs(got - want)))
-        assert np.isclose(fits.lnl[c], om.lnl, rtol=RTOL, atol=0, equal_nan=True), (label, c, fits.lnl[c], om.lnl)
-
-
-def _check_z(tl, ref, label):
-    """Same pattern, stored entries at RTOL; rows in no cell have no entries.  A cell whose oracle z is NaN (theta = NaN spreads
-    through 0 * NaN, model.py:718-720) has no entries on the device: NaN is the device's mark for `not in z's pattern`."""
-    got = sp.csr_matrix(tl.z); got.sort_indices()
-    want = ref.z()
-    nan_rows = np.zeros(ref.N, bool)
-    if want.nnz:
-        nan_rows[np.unique(sp.coo_matrix(want).row[np.isnan(want.data)])] = True
-    glen, wlen = np.diff(got.indptr), np.diff(want.indptr)
-    assert np.all(glen[ref.cor < 0] == 0), label
-    assert np.all(glen[nan_rows] == 0), label
-    keep = ~nan_rows
-    assert np.array_equal(glen[keep], wlen[keep]), label
-    w = want[np.flatnonzero(keep)]
-    g = got[np.flatnonzero(keep)]
-    assert np.array_equal(g.indices, w.indices), label
-    assert np.allclose(g.data, w.data, rtol=RTOL, atol=0), (label, np.max(np.abs(g.data - w.data)))
-
-
 @pytest.mark.parametrize('seed', SEEDS)
 def test_fits_equal_the_oracle_per_cell(gpu_device, seed):
     tl, fits, _ = _device_case(seed)
@@ -100,12 +64,32 @@ def test_fits_equal_the_oracle_per_cell(gpu_device, seed):
 
 
 def test_every_class_is_exercised(gpu_device):
-    """The shapes reach all four cell classes: a wave per cell, 256 threads, 512 threads (LDS), global workspace."""
+    """The shapes reach all four cell classes: a wave per cell, 256 threads, 512 threads (LDS), global workspace — by the cells'
+    column counts, and by the counts per class the unit itself reports for each shape's fit (`layout_info`: every cell of the map is
+    classed, one without rows as a wave cell)."""
     kc = {seed: np.diff(_device_case(seed)[1].col_ptr) for seed in SEEDS}
     assert kc[2].max() <= 256
     assert 256 < kc[4].min() and kc[4].max() <= 1024
     assert 1024 < kc[6].min() and kc[6].max() <= 3840
     assert kc[5].min() > 3840
+    names = ('cell_em_wave', 'cell_em_256', 'cell_em_512', 'cell_em_global')
+    got = {}
+    for seed in SEEDS:
+        info = _device_case(seed)[0]._eng.layout_info()
+        got[seed] = tuple(info[n] for n in names)
+    assert got[2] == (200, 0, 0, 0) and got[3] == (25, 0, 0, 0), got
+    assert got[4] == (0, 30, 0, 0) and got[6] == (0, 0, 4, 0) and got[5] == (0, 0, 0, 3), got
+    raw, cor, n_cells, ref = R.shape_case(1)                 # shape 1 by the documented rule, from the matrix alone
+    want = [0, 0, 0, 0]
+    for rows in ref.rows:
+        sub = raw[rows]
+        k, e = len(np.unique(sub.indices)), sub.nnz
+        want[0 if (k <= 256 and e <= 4096) else 1 if k <= 1024 else 2 if k <= 3840 else 3] += 1
+    assert got[1] == tuple(want) and want[0] > 0 and want[1] > 0 and want[2] == want[3] == 0, (got[1], want)
+    from telescope_amd import _lib
+    fresh = _lib.Engine(gpu_device)
+    assert all(fresh.layout_info()[n] == 0 for n in names)   # 0 before a fit
+    fresh.close()
 
 
 @pytest.mark.parametrize('seed', SEEDS)

@@ -21,10 +21,7 @@
 //
 // Numerators are formed as the reference forms them, both terms (model.py:718-720): (Q Y)(pi theta) + (Q (1 - Y)) pi — so that a NaN
 // theta (a cell without ambiguous rows at theta_prior = 0) spreads exactly as it does there.
-#include "tsem_internal.h"
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
+#include "tsem_runs.h"
 
 namespace {
 
@@ -36,8 +33,6 @@ constexpr int CE_KC_WAVE = 256, CE_ENT_WAVE = 4096;        // a wave per cell: 1
 constexpr int CE_KC_SMALL = 1024;                          // 256 threads, up to 40 KiB
 constexpr int CE_KC_LARGE = 3840;                          // 512 threads, up to 150 KiB; beyond: the tables in a global workspace
 constexpr int CE_RED = 16;                                 // doubles of LDS in front of the tables (block reductions)
-
-int ce_bits_for(uint64_t v) { int b = 1; while (b < 64 && (v >> b) != 0) ++b; return b; }
 
 struct CeArgs {
   int32_t K, max_iter, use_lnl;
@@ -245,10 +240,6 @@ __global__ void k_ce_rows(int64_t M, const int32_t* __restrict__ rows, const uin
   const int64_t s = indptr[row], len = indptr[row + 1] - s, o = eoff[i];
   for (int64_t k = 0; k < len; ++k) { key[o + k] = hi | (uint32_t)indices[s + k]; code[o + k] = raw[s + k]; }
 }
-__global__ void k_ce_heads(int64_t n, const uint64_t* __restrict__ key, uint32_t* __restrict__ head) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) head[i] = (i == 0 || key[i] != key[i - 1]) ? 1u : 0u;
-}
 // first compacted column of every cell: the runs before the cell's first entry (the entries are sorted by cell first)
 __global__ void k_ce_colptr(int64_t G1, int64_t E, int64_t n_runs, const int64_t* __restrict__ gent, const uint32_t* __restrict__ hscan,
                             int64_t* __restrict__ col_ptr) {
@@ -269,12 +260,6 @@ __global__ void k_ce_columns(int64_t E, int64_t n_runs, const uint64_t* __restri
   if (p == 0 || k != key[p - 1]) { cptr[r] = (uint32_t)p; cols[r] = (int32_t)(k & ((1ull << cbits) - 1ull)); }
   lcol[cpos[p]] = (int32_t)(r - col_ptr[k >> cbits]);
 }
-
-struct CeIdsGuard {                                        // CSR column ids rebuilt for the set-up go again afterwards
-  tsem_ctx* h; bool had;
-  explicit CeIdsGuard(tsem_ctx* c) : h(c), had(c->d_indices != nullptr) {}
-  ~CeIdsGuard() { if (!had) tsem_redrop_indices(h); }
-};
 
 void ce_free_layout(tsem_ctx* h) {
   dfree(h->d_ce_rptr); dfree(h->d_ce_rinfo); dfree(h->d_ce_lcol); dfree(h->d_ce_code); dfree(h->d_ce_cpos); dfree(h->d_ce_cptr);
@@ -305,10 +290,10 @@ int ce_build_layout(tsem_ctx* h) {
     TSEM_FAIL(TSEM_ERR_NOMEM, "tsem_cell_em: the per-cell layout needs " + std::to_string(need) + " B of device memory (" +
               std::to_string(CE_BYTES_KEPT) + " B per stored entry kept, " + std::to_string(CE_BYTES_PEAK) + " while it is built); " +
               std::to_string(free_b) + " B are free (tiling it is not supported)");
-  CeIdsGuard ig(h);                                         // (before the ids come back: it has to see that they were dropped)
-  if (int rc = tsem_ensure_indices(h)) return rc;
+  CsrIds ids(h);
+  if (int rc = ids.acquire()) return rc;
   PhaseTimer pt(h->stream);
-  const int cbits = ce_bits_for((uint64_t)std::max(0, h->K - 1)), gbits = ce_bits_for((uint64_t)G);
+  const int cbits = bits_for((uint64_t)std::max(0, h->K - 1)), gbits = bits_for((uint64_t)G);
   TSEM_ALLOC(h->d_ce_rptr, 2 * ((int64_t)G + 1));           // row pointer | entry pointer of every cell
   TSEM_ALLOC(h->d_ce_rinfo, M);
   TSEM_ALLOC(h->d_ce_lcol, E);
@@ -329,20 +314,14 @@ int ce_build_layout(tsem_ctx* h) {
   }
   if (E > 0) {
     rocprim::counting_iterator<uint32_t> iota(0);
-    size_t sb = 0, sc = 0;
-    TSEM_HIP(rocprim::radix_sort_pairs(nullptr, sb, key.as<uint64_t>(), key2.as<uint64_t>(), iota, h->d_ce_cpos, (size_t)E, 0,
-                                       std::min(64, cbits + gbits), h->stream));
-    TSEM_HIP(rocprim::inclusive_scan(nullptr, sc, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)E, rocprim::plus<uint32_t>(), h->stream));
-    TSEM_TMP(tmp, std::max(sb, sc));
-    // stable: equal (cell, column) keys keep the row-ordered view's order — ascending rows
-    TSEM_HIP(rocprim::radix_sort_pairs(tmp.p, sb, key.as<uint64_t>(), key2.as<uint64_t>(), iota, h->d_ce_cpos, (size_t)E, 0,
-                                       std::min(64, cbits + gbits), h->stream));
-    uint32_t* head = reinterpret_cast<uint32_t*>(key.p);    // (the unsorted keys are done with)
-    k_ce_heads<<<cdiv64(E, 256), 256, 0, h->stream>>>(E, key2.as<uint64_t>(), head);
-    TSEM_HIP(hipGetLastError());
-    TSEM_HIP(rocprim::inclusive_scan(tmp.p, sc, head, hscan.as<uint32_t>(), (size_t)E, rocprim::plus<uint32_t>(), h->stream));
+    const int kbits = std::min(64, cbits + gbits);
+    size_t tb = 0;
+    if (int rc = sorted_runs_tmp_bytes(h, iota, h->d_ce_cpos, E, kbits, &tb)) return rc;
+    TSEM_TMP(tmp, tb);
+    // stable: equal (cell, column) keys keep the row-ordered view's order — ascending rows; the heads reuse the unsorted keys' buffer
     uint32_t nr = 0;
-    TSEM_HIP(hipMemcpyAsync(&nr, hscan.as<uint32_t>() + E - 1, 4, hipMemcpyDeviceToHost, h->stream));
+    if (int rc = sorted_runs(h, tmp.p, tb, key.as<uint64_t>(), key2.as<uint64_t>(), iota, h->d_ce_cpos, E, kbits, key.as<uint32_t>(),
+                             hscan.as<uint32_t>(), &nr)) return rc;
     TSEM_HIP(hipStreamSynchronize(h->stream));
     n_runs = nr;
     TSEM_ALLOC(h->d_ce_cptr, n_runs + 1);

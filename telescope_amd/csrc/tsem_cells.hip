@@ -12,10 +12,7 @@
 // between the pieces (the pieces' lanes continue from them) and compacted after its last piece.  The result is bit-identical to summing
 // the device's own `reassign` matrix with scipy, for every method, and deterministic.  Limit: a (group, column) run is summed by one
 // lane — a group that holds a large share of the matrix's rows in one column runs at one lane's speed.  Real barcodes never do.
-#include "tsem_internal.h"
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
+#include "tsem_runs.h"
 
 namespace {
 
@@ -23,8 +20,6 @@ namespace {
 // buffers; outside it stay the grouping cached per map (16 B per row), the caller's picks (4 B per row, `choose`), the result (16 B per
 // stored entry) and, after option "drop_csr_indices", the CSR column ids rebuilt for the call (4 B per entry of the matrix)
 constexpr int64_t GC_BYTES_PER_ENTRY = 96;
-
-int bits_for(uint64_t v) { int b = 1; while (b < 64 && (v >> b) != 0) ++b; return b; }   // bits to hold 0..v (at least 1)
 
 __global__ void k_gc_keys(int64_t N, const int32_t* __restrict__ grp, int32_t n_groups, uint32_t* __restrict__ key) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -70,10 +65,6 @@ __global__ void k_gc_entry_keys(int64_t n, int64_t r0, const int32_t* __restrict
   const int64_t s = indptr[row], len = indptr[row + 1] - s, o = off[i];
   for (int64_t k = 0; k < len; ++k) key[o + k] = hi | (uint32_t)indices[s + k];
 }
-__global__ void k_gc_heads(int64_t n, const uint64_t* __restrict__ key, uint32_t* __restrict__ head) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) head[i] = (i == 0 || key[i] != key[i - 1]) ? 1u : 0u;
-}
 // run r = the entries [start[r], start[r + 1]) — found from the inclusive scan of the heads: head i starts run hscan[i] - 1
 __global__ void k_gc_starts(int64_t n, const uint32_t* __restrict__ head, const uint32_t* __restrict__ hscan, uint32_t* __restrict__ start) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -112,11 +103,6 @@ __global__ void k_gc_scatter(int64_t n, const uint32_t* __restrict__ keep, const
   const int64_t o = base + kscan[r] - 1;
   ogrp[o] = rgrp[r]; ocol[o] = rcol[r]; oval[o] = rval[r];
 }
-struct IdsGuard {                                          // CSR column ids rebuilt for this call go again afterwards
-  tsem_ctx* h; bool had;
-  explicit IdsGuard(tsem_ctx* c) : h(c), had(c->d_indices != nullptr) {}
-  ~IdsGuard() { if (!had) tsem_redrop_indices(h); }
-};
 
 // the rows of every group in ascending order, their entry offsets, and per group its first row and entry (host copies)
 int build_grouping(tsem_ctx* h) {
@@ -201,7 +187,7 @@ int keep_runs(tsem_ctx* h, const TileBufs& B, int64_t n_runs) {
   return TSEM_OK;
 }
 
-int run_tile(tsem_ctx* h, const TileBufs& B, int method, double thresh, int which, const int32_t* d_picks, int64_t r0, int64_t r1,
+int run_tile(tsem_ctx* h, CsrIds& ids, const TileBufs& B, int method, double thresh, int which, const int32_t* d_picks, int64_t r0, int64_t r1,
              int64_t ne, int32_t g0, int32_t g1, double* carry) {
   const int64_t n = r1 - r0;
   if (n <= 0 || ne <= 0) return TSEM_OK;
@@ -210,20 +196,14 @@ int run_tile(tsem_ctx* h, const TileBufs& B, int method, double thresh, int whic
   k_gc_tile_rows<<<cdiv64(n + 1, 256), 256, 0, h->stream>>>(n, r0, h->d_gc_rows, h->d_gc_eoff, d_picks, B.off,
                                                             method == TSEM_RA_CHOOSE ? B.lpicks : nullptr);
   TSEM_HIP(hipGetLastError());
-  // stage A: reassign(method) of every entry, in the tile's entry order (ensures the CSR column ids)
-  if (int rc = tsem_rows_mask_dev(h, which, method, thresh, n, h->d_gc_rows + r0, method == TSEM_RA_CHOOSE ? B.lpicks : nullptr,
+  // stage A: reassign(method) of every entry, in the tile's entry order (acquires the CSR column ids)
+  if (int rc = tsem_rows_mask_dev(h, ids, which, method, thresh, n, h->d_gc_rows + r0, method == TSEM_RA_CHOOSE ? B.lpicks : nullptr,
                                   B.off, B.val)) return rc;
   k_gc_entry_keys<<<cdiv64(n, 256), 256, 0, h->stream>>>(n, r0, h->d_gc_rows, h->d_gc_key, B.off, h->d_indptr, h->d_indices, g0,
                                                          cbits, B.key);
   TSEM_HIP(hipGetLastError());
-  size_t tb = B.sort_bytes;
-  TSEM_HIP(rocprim::radix_sort_pairs(B.sort_tmp, tb, B.key, B.key2, B.val, B.val2, (size_t)ne, 0, kbits, h->stream));
-  k_gc_heads<<<cdiv64(ne, 256), 256, 0, h->stream>>>(ne, B.key2, B.head);
-  TSEM_HIP(hipGetLastError());
-  tb = B.sort_bytes;
-  TSEM_HIP(rocprim::inclusive_scan(B.sort_tmp, tb, B.head, B.hscan, (size_t)ne, rocprim::plus<uint32_t>(), h->stream));
   uint32_t n_runs = 0;
-  TSEM_HIP(hipMemcpyAsync(&n_runs, B.hscan + ne - 1, 4, hipMemcpyDeviceToHost, h->stream));
+  if (int rc = sorted_runs(h, B.sort_tmp, B.sort_bytes, B.key, B.key2, B.val, B.val2, ne, kbits, B.head, B.hscan, &n_runs)) return rc;
   k_gc_starts<<<cdiv64(ne, 256), 256, 0, h->stream>>>(ne, B.head, B.hscan, B.start);
   TSEM_HIP(hipGetLastError());
   TSEM_HIP(hipStreamSynchronize(h->stream));
@@ -252,7 +232,7 @@ int tsem_group_counts(tsem_ctx* h, int method, double thresh, int which, const i
   const int32_t G = h->n_groups;
   const int K = h->K;
   if (int rc = build_grouping(h)) return rc;
-  IdsGuard ig(h);
+  CsrIds ids(h);                                           // (acquired by the first tile's row pass: no tile, no rebuild)
   const int64_t budget = h->opt_group_tile > 0 ? h->opt_group_tile : ((int64_t)1 << 30);
   // entries (and rows) per tile: at least one row of the widest possible length, at most 2^31 (32-bit run positions)
   int64_t cap = std::min<int64_t>(std::max<int64_t>(budget / GC_BYTES_PER_ENTRY, (int64_t)K + 1), (int64_t)1 << 30);
@@ -268,11 +248,7 @@ int tsem_group_counts(tsem_ctx* h, int method, double thresh, int which, const i
   TileBufs B{};
   if (total > 0) {
     const int cbits = bits_for((uint64_t)std::max(0, K - 1));
-    size_t sb = 0, sc = 0;
-    TSEM_HIP(rocprim::radix_sort_pairs(nullptr, sb, (uint64_t*)nullptr, (uint64_t*)nullptr, (double*)nullptr, (double*)nullptr, (size_t)cap,
-                                       0, std::min(64, cbits + 32), h->stream));
-    TSEM_HIP(rocprim::inclusive_scan(nullptr, sc, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)cap, rocprim::plus<uint32_t>(), h->stream));
-    B.sort_bytes = std::max(sb, sc);
+    if (int rc = sorted_runs_tmp_bytes(h, (double*)nullptr, (double*)nullptr, cap, std::min(64, cbits + 32), &B.sort_bytes)) return rc;
     const size_t a = 256;                                  // (every array 256-byte aligned)
     auto up = [&](size_t x) { return (x + a - 1) / a * a; };
     const size_t c1 = (size_t)cap + 1;
@@ -304,7 +280,7 @@ int tsem_group_counts(tsem_ctx* h, int method, double thresh, int which, const i
       for (int64_t a = 0; a < nr;) {
         int64_t b = a + 1;                                 // (one row never exceeds cap: cap > K)
         while (b < nr && b - a < cap && eoff_slice[b + 1] - eoff_slice[a] <= cap) ++b;
-        if (int rc = run_tile(h, B, method, thresh, which, d_picks, r0 + a, r0 + b, eoff_slice[b] - eoff_slice[a], g, g + 1,
+        if (int rc = run_tile(h, ids, B, method, thresh, which, d_picks, r0 + a, r0 + b, eoff_slice[b] - eoff_slice[a], g, g + 1,
                               carry_t.as<double>())) return rc;
         a = b;
       }
@@ -316,7 +292,7 @@ int tsem_group_counts(tsem_ctx* h, int method, double thresh, int which, const i
     }
     int32_t g1 = g + 1;
     while (g1 < G && h->gc_gent[g1 + 1] - e0 <= cap && h->gc_rptr[g1 + 1] - r0 <= cap) ++g1;
-    if (int rc = run_tile(h, B, method, thresh, which, d_picks, r0, h->gc_rptr[g1], h->gc_gent[g1] - e0, g, g1, nullptr)) return rc;
+    if (int rc = run_tile(h, ids, B, method, thresh, which, d_picks, r0, h->gc_rptr[g1], h->gc_gent[g1] - e0, g, g1, nullptr)) return rc;
     g = g1;
   }
   TSEM_ALLOC(h->d_gc_gptr, (int64_t)G + 1);

@@ -69,7 +69,7 @@ struct tsem_ctx {
   int32_t* d_indices = nullptr;
   uint16_t* d_raw = nullptr;
   int64_t opt_drop_indices = -1;    // option "drop_csr_indices": free the CSR column ids (4 B per entry) once the blocked layout and the 2-byte popularity ids
-                                    // exist — col = col_of_id[rid16], rebuilt on demand (tsem_ensure_indices) for the generic row passes, z export, a
+                                    // exist — col = col_of_id[rid16], rebuilt for the span of a call (CsrIds, tsem_internal.h) by the generic row passes, z export, a
                                     // layout rebuild.  -1 auto: from 4e9 stored entries on; 0 never; 1 always
   double* d_lut = nullptr;
   int lut_len = 0;

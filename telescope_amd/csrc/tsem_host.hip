@@ -454,7 +454,8 @@ int tsem_export_csr(tsem_ctx* h, int64_t* indptr, int32_t* indices, uint16_t* ra
   if (int rc = ensure_device(h)) return rc;
   TSEM_HIP(hipStreamSynchronize(h->stream));
   if (indptr) TSEM_HIP(hipMemcpy(indptr, h->d_indptr, sizeof(int64_t) * (h->N + 1), hipMemcpyDeviceToHost));
-  if (indices && h->nnz) { if (int rc = tsem_ensure_indices(h)) return rc; }
+  CsrIds ids(h); ids.keep();                               // (a debugging export: they stay resident until the next layout drops them)
+  if (indices && h->nnz) { if (int rc = ids.acquire()) return rc; }
   if (indices && h->nnz) TSEM_HIP(hipMemcpy(indices, h->d_indices, sizeof(int32_t) * h->nnz, hipMemcpyDeviceToHost));
   if (raw && h->nnz) TSEM_HIP(hipMemcpy(raw, h->d_raw, sizeof(uint16_t) * h->nnz, hipMemcpyDeviceToHost));
   return TSEM_OK;

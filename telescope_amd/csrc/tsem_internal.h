@@ -162,6 +162,7 @@ static inline size_t fz_lds_bytes(const tsem_ctx* h, bool codes) {
 }
 
 // ---- host functions shared between the units (defined in the unit named) ---------------------------------------------
+class CsrIds;
 extern "C" {
 // tsem_host.hip
 void tsem_free_layout(tsem_ctx* h);
@@ -173,7 +174,8 @@ int tsem_bin_reset(tsem_ctx* h);                           // option "reproducib
 int tsem_make_ctabs(tsem_ctx* h);                          // the permuted pi * theta tables (current and previous) from the parameters
 void tsem_report_preload(void);                            // the same for the report unit (build_layout, behind the fill)
 void tsem_setup_preload(void);                             // load the set-up unit's code object now (behind a kernel that is running anyway)
-int tsem_ensure_indices(tsem_ctx* h);                      // the CSR column ids, rebuilt from the popularity ids if option "drop_csr_indices" freed them
+int tsem_ensure_indices(tsem_ctx* h);                      // the CSR column ids, rebuilt from the popularity ids if option "drop_csr_indices" freed
+void tsem_redrop_indices(tsem_ctx* h);                     // them | dropped again where the option says so: both for CsrIds (below) alone
 // tsem_em.hip
 int tsem_take_fused_error(tsem_ctx* h, uint32_t* word);
 int tsem_twopass_attributes(tsem_ctx* h);                 // dynamic-LDS limits of the two-pass kernels
@@ -181,10 +183,9 @@ int tsem_sum_parts(tsem_ctx* h, const double* a, int na, const double* b, int nb
 // tsem_report.hip
 int tsem_rowpass_grid(tsem_ctx* h);
 // reassign(method)[row, :] of a DEVICE row list into mask[off[i] ...] (the row pass of tsem_rows_lookup, no host copies; d_picks[i]
-// belongs to list row i).  It leaves the CSR column ids resident: the caller ends with tsem_redrop_indices once it has read them.
-int tsem_rows_mask_dev(tsem_ctx* h, int which, int method, double thresh, int64_t n, const int32_t* d_rows, const int32_t* d_picks,
-                       const int64_t* d_off, double* d_mask);
-void tsem_redrop_indices(tsem_ctx* h);
+// belongs to list row i).  The CSR column ids are acquired in the caller's scope `ids`, which reads them after the pass as well.
+int tsem_rows_mask_dev(tsem_ctx* h, CsrIds& ids, int which, int method, double thresh, int64_t n, const int32_t* d_rows,
+                       const int32_t* d_picks, const int64_t* d_off, double* d_mask);
 // tsem_cells.hip
 int tsem_build_grouping(tsem_ctx* h);                      // d_gc_rows / d_gc_key / d_gc_eoff, gc_rptr / gc_gent for the current group map (cached)
 // tsem_cellem.hip
@@ -194,3 +195,18 @@ bool tsem_comm_on(const tsem_ctx* h);
 int tsem_comm_allreduce_dev(tsem_comm* c, void* buf, size_t count, int dtype, hipStream_t s, std::string& err);
 int tsem_comm_allreduce_red(tsem_ctx* h, int64_t offset, int64_t count);
 }  // extern "C"
+
+// Option "drop_csr_indices" frees h->d_indices once the blocked layout exists (tsem_setup.hip).  A pass that reads them obtains them
+// through a scope of this type only: the constructor notes whether they are resident, acquire() rebuilds them if not (a path that never
+// acquires never rebuilds) and the destructor drops again what the scope had to bring back, the stream synchronised first, on every
+// return path.  A scope that found them resident does nothing at its end: no synchronisation on such a matrix, and scopes nest.
+class CsrIds {
+  tsem_ctx* h; bool had;
+ public:
+  explicit CsrIds(tsem_ctx* c) : h(c), had(c && c->d_indices != nullptr) {}   // (a null handle: the entry point's argument check follows)
+  ~CsrIds() { if (h && !had) tsem_redrop_indices(h); }
+  int acquire() { return tsem_ensure_indices(h); }
+  template <typename Args> int acquire(Args& A) { const int rc = acquire(); A.indices = h->d_indices; return rc; }   // (RowPassArgs)
+  void keep() { had = true; }                                      // the ids are meant to outlive the scope: every use says why
+  static void drop_kept(tsem_ctx* c) { tsem_redrop_indices(c); }   // ... and the end of that (tsem_entry_tags_end)
+};

@@ -1081,22 +1081,8 @@ static int exact_counter(tsem_ctx* h, unsigned long long** out) {
   *out = h->d_exact_n;
   return TSEM_OK;
 }
-// The kernels that read the CSR column ids — k_rowpass<*>, k_group_unique, k_mstep_rows, k_lnl_rows — call this right before they are
-// launched; the streaming passes (k_report_rows, k_report_init_codes, k_choose_init_codes, the group tiles) never do, so that a
-// matrix whose ids were dropped (option "drop_csr_indices") stays at 10 B per entry through a report.
-static int with_indices(tsem_ctx* h, RowPassArgs& A) {
-  if (int rc = tsem_ensure_indices(h)) return rc;
-  A.indices = h->d_indices;
-  return TSEM_OK;
-}
-// ... and this afterwards: ids that were rebuilt for one generic pass go again where the option drops them (the passes that need them
-// are the exception on such a matrix: a rebuild is one 6 B-per-entry sweep)
-static void redrop_indices(tsem_ctx* h) {
-  if (h->d_indices && h->d_rid16 && h->d_col_of_id && (h->opt_drop_indices == 1 || (h->opt_drop_indices < 0 && h->nnz >= 4000000000ll))) {
-    (void)hipStreamSynchronize(h->stream);
-    dfree(h->d_indices);
-  }
-}
+// k_rowpass<*>, k_group_unique, k_mstep_rows and k_lnl_rows read the CSR column ids: acquired (CsrIds) right before their launch.  The
+// streaming passes never do: a matrix whose ids were dropped (option "drop_csr_indices") stays at 10 B per entry through a report.
 
 // Option "report_kernel": 1 (default) the streaming report kernels, 0 the generic row pass for everything.
 // The streaming kernels (k_report_rows, k_report_pack32, k_report_init_codes) read the popularity ids and stage the score table in
@@ -1110,12 +1096,6 @@ static bool codes_path_ok(const tsem_ctx* h) {
   return h->opt_report_kernel != 0 && h->lut_increasing && !h->opt_reproducible && h->have_rowstats && !h->has_zero_score &&
          h->d_rid16 && h->d_col_of_id;
 }
-
-struct IndicesGuard {                                      // at the top of an entry point: ids this call had to rebuild do not outlive it
-  tsem_ctx* h; bool had;
-  explicit IndicesGuard(tsem_ctx* c) : h(c), had(c && c->d_indices != nullptr) {}
-  ~IndicesGuard() { if (h && !had) redrop_indices(h); }
-};
 
 // One generic row pass = the pass proper + the FIX launch over the rows it flagged as near-ties (RowPassArgs::flag_bits).  `meth`
 // >= 0 picks the instantiation with the reassign method fixed at compile time (-1: read from A.method).  z export and a
@@ -1171,12 +1151,12 @@ static int rowpass_args(tsem_ctx* h, int which, RowPassArgs& A) {
 static int list_grid(int64_t n) { return (int)std::min<int64_t>(8192, std::max<int64_t>(1, (n + 15) / 16)); }
 int tsem_rowpass_grid(tsem_ctx* h) { return list_grid(h->N); }
 
-static int export_z_with(tsem_ctx* h, RowPassArgs& A, double* z) {
+static int export_z_with(tsem_ctx* h, CsrIds& ids, RowPassArgs& A, double* z) {
   double* d_z = nullptr;
   TSEM_SCOPED(d_z);
   TSEM_ALLOC(d_z, h->nnz);
   A.zout = d_z;
-  if (int rc = with_indices(h, A)) return rc;
+  if (int rc = ids.acquire(A)) return rc;
   if (int rc = launch_rowpass(h, RP_EXPORT_Z, -1, tsem_rowpass_grid(h), 256, (size_t)A.lut_len * 8, A)) return rc;
   if (h->nnz) TSEM_HIP(hipMemcpyAsync(z, d_z, sizeof(double) * h->nnz, hipMemcpyDeviceToHost, h->stream));
   TSEM_HIP(hipStreamSynchronize(h->stream));
@@ -1186,10 +1166,10 @@ static int export_z_with(tsem_ctx* h, RowPassArgs& A, double* z) {
 int tsem_export_z(tsem_ctx* h, int which, double* z) {
   if (!h || !h->d_indptr || !z) return TSEM_ERR_ARG;
   if (int rc = ensure_device(h)) return rc;
-  IndicesGuard ig(h);
+  CsrIds ids(h);
   RowPassArgs A;
   if (int rc = rowpass_args(h, which, A)) return rc;
-  return export_z_with(h, A, z);
+  return export_z_with(h, ids, A, z);
 }
 
 int tsem_set_user_z(tsem_ctx* h, const double* z) {
@@ -1206,12 +1186,12 @@ int tsem_estep(tsem_ctx* h, const double* pi, const double* theta, double* z) {
   if (int rc = ensure_device(h)) return rc;
   TSEM_HIP(hipMemcpyAsync(h->d_tmp_pi, pi, sizeof(double) * h->K, hipMemcpyHostToDevice, h->stream));
   TSEM_HIP(hipMemcpyAsync(h->d_tmp_theta, theta, sizeof(double) * h->K, hipMemcpyHostToDevice, h->stream));
-  IndicesGuard ig(h);
+  CsrIds ids(h);
   RowPassArgs A;
   if (int rc = rowpass_args(h, TSEM_Z_CUR, A)) return rc;
   A.pi = h->d_tmp_pi; A.theta = h->d_tmp_theta;
   if (int rc = make_cnat(h, A)) return rc;
-  return export_z_with(h, A, z);
+  return export_z_with(h, ids, A, z);
 }
 
 int tsem_best_counts(tsem_ctx* h, int which, int32_t* nbest) {
@@ -1223,8 +1203,8 @@ int tsem_best_counts(tsem_ctx* h, int which, int32_t* nbest) {
   TSEM_SCOPED(d_nb);
   TSEM_ALLOC(d_nb, h->N);
   A.nbest = d_nb;
-  IndicesGuard ig(h);
-  if (int rc = with_indices(h, A)) return rc;
+  CsrIds ids(h);
+  if (int rc = ids.acquire(A)) return rc;
   if (int rc = launch_rowpass(h, RP_BEST, -1, tsem_rowpass_grid(h), 256, (size_t)A.lut_len * 8, A)) return rc;
   if (h->N) TSEM_HIP(hipMemcpyAsync(nbest, d_nb, sizeof(int32_t) * h->N, hipMemcpyDeviceToHost, h->stream));
   TSEM_HIP(hipStreamSynchronize(h->stream));
@@ -1275,8 +1255,8 @@ int tsem_best_ties(tsem_ctx* h, int which, int64_t cap, int32_t* rows, int32_t* 
   TSEM_SCOPED(d_nb); TSEM_SCOPED(d_rows); TSEM_SCOPED(d_cnt); TSEM_SCOPED(d_n);
   TSEM_ALLOC(d_nb, h->N); TSEM_ALLOC(d_rows, h->N); TSEM_ALLOC(d_n, 1);
   A.nbest = d_nb;
-  IndicesGuard ig(h);
-  if (int rc = with_indices(h, A)) return rc;
+  CsrIds ids(h);
+  if (int rc = ids.acquire(A)) return rc;
   if (int rc = launch_rowpass(h, RP_BEST, -1, tsem_rowpass_grid(h), 256, (size_t)A.lut_len * 8, A)) return rc;
   unsigned long long n = 0;
   if (int rc = select_ties(h, d_nb, d_rows, d_n, &n)) return rc;
@@ -1350,8 +1330,8 @@ int tsem_reassign(tsem_ctx* h, int method, double thresh, int which, const int32
     }
   }
   A.method = method; A.thresh = thresh;
-  IndicesGuard ig(h);
-  if (int rc = with_indices(h, A)) return rc;
+  CsrIds ids(h);
+  if (int rc = ids.acquire(A)) return rc;
   double *d_cs = nullptr, *d_mask = nullptr;
   int32_t* d_picks = nullptr;
   TSEM_SCOPED(d_cs); TSEM_SCOPED(d_mask); TSEM_SCOPED(d_picks);
@@ -1532,10 +1512,10 @@ static int report_streaming(tsem_ctx* h, ReportArgs& R, bool codes_only) {
 
 // The generic row pass k_rowpass<RP_REPORT> over the CSR: two workgroups per CU with the hot slots of every column part in LDS where
 // the matrix has its blocked layout, 16 lanes per row over all rows else (that pass leaves the last report's kernel statistics)
-static int report_generic(tsem_ctx* h, RowPassArgs& A, double* d_cs) {
+static int report_generic(tsem_ctx* h, CsrIds& ids, RowPassArgs& A, double* d_cs) {
   const bool parts = h->d_colmap && h->d_col_of_pc && h->P > 0;
   if (parts) { h->rep_timed = false; h->rep_kernel = 1; h->rep_deferred = 0; }
-  if (int rc = with_indices(h, A)) return rc;
+  if (int rc = ids.acquire(A)) return rc;
   const int64_t n = 3 * (int64_t)h->K;
   if (!parts) return rowpass_exact(h, A, RP_REPORT, -1, tsem_rowpass_grid(h), 256, (size_t)A.lut_len * 8, d_cs, n);
   const size_t lds = rowpass_hot_slots(h, A, 2, 3);
@@ -1582,7 +1562,7 @@ int tsem_report_colsums(tsem_ctx* h, int which, double thresh, double* out3K, in
   const bool want_conf = !(thresh < 0.0);                  // thresh < 0: no `conf` column wanted (its third of out3K stays 0)
   PhaseTimer pt(h->stream);                                // (TSEM_TRACE=1)
   if (!want_conf) thresh = 0.9;                            // (what the paths that compute it anyway use)
-  IndicesGuard ig(h);
+  CsrIds ids(h);
   RowPassArgs A;
   if (int rc = rowpass_args(h, which, A)) return rc;
   dfree(h->d_tie_rows); dfree(h->d_tie_cnt); h->n_ties = 0;
@@ -1627,7 +1607,7 @@ int tsem_report_colsums(tsem_ctx* h, int which, double thresh, double* out3K, in
     TSEM_HIP(hipGetLastError());
     k_report_finish<<<cdiv64(IDN, 256), 256, 0, h->stream>>>(IDN, K, h->d_col_of_id, R.g_conf, R.g_n1, R.g_n2, R.g_avgt, R.g_conf_lo, R.g_avgt_lo, d_cs);
     TSEM_HIP(hipGetLastError());
-  } else if (int rc = report_generic(h, A, d_cs)) {
+  } else if (int rc = report_generic(h, ids, A, d_cs)) {
     return rc;
   }
   TSEM_HIP(hipMemcpyAsync(out3K, d_cs, sizeof(double) * 3 * K, hipMemcpyDeviceToHost, h->stream));
@@ -1688,8 +1668,8 @@ int tsem_reassign_rows(tsem_ctx* h, int method, double thresh, int which, const 
   if (int rc = rowpass_args(h, which, A)) return rc;
   A.method = method; A.thresh = thresh; A.colsums = d_cs; A.picks = d_picks;
   A.rowlist = rows ? d_rows : h->d_tie_rows; A.nlist = n;
-  IndicesGuard ig(h);
-  if (int rc = with_indices(h, A)) return rc;
+  CsrIds ids(h);
+  if (int rc = ids.acquire(A)) return rc;
   if (int rc = rowpass_exact(h, A, RP_REASSIGN, -1, list_grid(n), 256, (size_t)A.lut_len * 8, d_cs, h->K)) return rc;
   TSEM_HIP(hipMemcpyAsync(colsums, d_cs, sizeof(double) * h->K, hipMemcpyDeviceToHost, h->stream));
   TSEM_HIP(hipStreamSynchronize(h->stream));
@@ -1728,8 +1708,8 @@ int tsem_rows_lookup(tsem_ctx* h, int which, int method, double thresh, int64_t 
   if (bad) TSEM_FAIL(TSEM_ERR_ARG, "tsem_rows_lookup: out_off does not follow the listed rows' lengths");
   if (method == TSEM_RA_CHOOSE && picks) { if (int rc = upload_i32(h, d_picks, picks, n)) return rc; }
   A.rowlist = d_rows; A.nlist = n; A.out_off = d_off;
-  IndicesGuard ig(h);
-  if (int rc = with_indices(h, A)) return rc;
+  CsrIds ids(h);
+  if (int rc = ids.acquire(A)) return rc;
   const int grid = list_grid(n);
   if (z_out) {
     TSEM_ALLOC(d_z, total);
@@ -1747,17 +1727,16 @@ int tsem_rows_lookup(tsem_ctx* h, int which, int method, double thresh, int64_t 
   return TSEM_OK;
 }
 
-int tsem_rows_mask_dev(tsem_ctx* h, int which, int method, double thresh, int64_t n, const int32_t* d_rows, const int32_t* d_picks,
-                       const int64_t* d_off, double* d_mask) {
+int tsem_rows_mask_dev(tsem_ctx* h, CsrIds& ids, int which, int method, double thresh, int64_t n, const int32_t* d_rows,
+                       const int32_t* d_picks, const int64_t* d_off, double* d_mask) {
   if (n <= 0) return TSEM_OK;
   RowPassArgs A;
   if (int rc = rowpass_args(h, which, A)) return rc;
   A.rowlist = d_rows; A.nlist = n; A.out_off = d_off;
   A.zout = d_mask; A.method = method; A.thresh = thresh; A.picks = d_picks; A.colsums = nullptr;
-  if (int rc = with_indices(h, A)) return rc;
+  if (int rc = ids.acquire(A)) return rc;
   return launch_rowpass(h, RP_REASSIGN, -1, list_grid(n), 256, (size_t)A.lut_len * 8, A);
 }
-void tsem_redrop_indices(tsem_ctx* h) { redrop_indices(h); }
 
 // the caller's PHRED thresholds (non-decreasing, in [0, 1), at most TS_PHRED_TAB - 1 of them) padded with 2.0 for ts_phred
 static bool phred_table(const double* tab, int32_t n_tab, double* out) {
@@ -1770,7 +1749,7 @@ static bool phred_table(const double* tab, int32_t n_tab, double* out) {
 
 // The tag word of every stored entry of rows [row_begin, row_end), in CSR order (RP_TAGS: z and the reassign decision of one
 // pass, model.py:479-521).  The CSR column ids a dropped-ids matrix needs are rebuilt once and KEPT across the tiles of an update
-// (no IndicesGuard here): tsem_entry_tags_end drops them again.
+// (CsrIds::keep): tsem_entry_tags_end drops them again.
 int tsem_entry_tags(tsem_ctx* h, int which, int method, double thresh, const int32_t* picks, int64_t row_begin, int64_t row_end,
                     const double* phred_tab, int32_t n_tab, uint32_t* out) {
   if (!h || !h->d_indptr || row_begin < 0 || row_end < row_begin || row_end > h->N) return TSEM_ERR_ARG;
@@ -1797,7 +1776,9 @@ int tsem_entry_tags(tsem_ctx* h, int which, int method, double thresh, const int
   if (method == TSEM_RA_CHOOSE && picks) { if (int rc = upload_i32(h, d_picks, picks, n)) return rc; }
   A.method = method; A.thresh = thresh; A.picks = d_picks; A.colsums = nullptr; A.zout = nullptr;
   A.row0 = row_begin; A.nlist = n; A.tag_base = e0; A.tags = d_tags; A.phred_tab = d_tab;
-  if (int rc = with_indices(h, A)) return rc;
+  CsrIds ids(h);
+  if (int rc = ids.acquire(A)) return rc;
+  ids.keep();                                              // (one rebuild serves every tile of an update: tsem_entry_tags_end drops them)
   if (int rc = launch_rowpass(h, RP_TAGS, -1, list_grid(n), 256, (size_t)(A.lut_len + TS_PHRED_TAB) * 8, A)) return rc;
   if (e1 > e0) TSEM_HIP(hipMemcpyAsync(out, d_tags, sizeof(uint32_t) * (e1 - e0), hipMemcpyDeviceToHost, h->stream));
   TSEM_HIP(hipStreamSynchronize(h->stream));
@@ -1806,7 +1787,7 @@ int tsem_entry_tags(tsem_ctx* h, int which, int method, double thresh, const int
 
 int tsem_entry_tags_end(tsem_ctx* h) {
   if (!h) return TSEM_ERR_ARG;
-  redrop_indices(h);
+  CsrIds::drop_kept(h);
   return TSEM_OK;
 }
 
@@ -1877,7 +1858,7 @@ int tsem_reassign_groups(tsem_ctx* h, int method, double thresh, int which, cons
   if (int rc = ensure_device(h)) return rc;
   if (group_of_row) { if (int rc = tsem_set_groups(h, group_of_row, n_groups)) return rc; }
   else if (!h->d_group || h->n_groups != n_groups) TSEM_FAIL(TSEM_ERR_ARG, "tsem_reassign_groups: no group map (tsem_set_groups) for this number of groups");
-  IndicesGuard ig(h);
+  CsrIds ids(h);
   RowPassArgs A;
   if (int rc = rowpass_args(h, which, A)) return rc;
   A.method = method; A.thresh = thresh;
@@ -1936,11 +1917,11 @@ int tsem_reassign_groups(tsem_ctx* h, int method, double thresh, int which, cons
       k_group_finish<<<cdiv64(n_id, 256), 256, 0, h->stream>>>(n_id, IDN, K, h->d_col_of_id, R.t_cnt, R.t_val, d_out);
       TSEM_HIP(hipGetLastError());
     } else if (h->N && method == TSEM_RA_UNIQUE && which != TSEM_Z_USER && !h->opt_reproducible) {
-      if (int rc = with_indices(h, A)) return rc;
+      if (int rc = ids.acquire(A)) return rc;
       k_group_unique<<<cdiv64(h->N, 256), 256, 0, h->stream>>>(h->N, h->d_indptr, h->d_indices, h->d_raw, h->d_lut, A.pi, h->d_group, g0, g1, K, d_out);
       TSEM_HIP(hipGetLastError());
     } else if (h->N) {
-      if (int rc = with_indices(h, A)) return rc;
+      if (int rc = ids.acquire(A)) return rc;
       A.colsums = d_out; A.picks = d_picks; A.group = h->d_group; A.g0 = g0; A.g1 = g1;
       if (int rc = rowpass_exact(h, A, RP_REASSIGN, -1, tsem_rowpass_grid(h), 256, (size_t)A.lut_len * 8, d_out, n_out)) return rc;
     }
@@ -1962,8 +1943,8 @@ int tsem_mstep(tsem_ctx* h, const double* z, double* pi_hat, double* theta_hat) 
   if (h->nnz) TSEM_HIP(hipMemcpyAsync(d_z, z, sizeof(double) * h->nnz, hipMemcpyHostToDevice, h->stream));
   TSEM_HIP(hipMemsetAsync(d_cs, 0, sizeof(double) * h->K, h->stream));
   A.colsums = d_cs;
-  IndicesGuard ig(h);
-  if (int rc = with_indices(h, A)) return rc;
+  CsrIds ids(h);
+  if (int rc = ids.acquire(A)) return rc;
   if (h->N) k_mstep_rows<<<tsem_rowpass_grid(h), 256, 0, h->stream>>>(A, d_z);
   if (tsem_comm_on(h)) {                                         // row-sharded: thetasum over all ranks (model.py:731)
     if (int rc = tsem_comm_allreduce_dev(h->comm, d_cs, (size_t)h->K, 0, h->stream, h->err)) return rc;
@@ -1990,8 +1971,8 @@ int tsem_calc_lnl(tsem_ctx* h, const double* z, const double* pi, const double* 
   TSEM_HIP(hipMemcpyAsync(h->d_tmp_pi, pi, sizeof(double) * h->K, hipMemcpyHostToDevice, h->stream));
   TSEM_HIP(hipMemcpyAsync(h->d_tmp_theta, theta, sizeof(double) * h->K, hipMemcpyHostToDevice, h->stream));
   A.pi = h->d_tmp_pi; A.theta = h->d_tmp_theta;
-  IndicesGuard ig(h);
-  if (int rc = with_indices(h, A)) return rc;
+  CsrIds ids(h);
+  if (int rc = ids.acquire(A)) return rc;
   int grid = std::min(4096, tsem_rowpass_grid(h));
   if (h->N) k_lnl_rows<<<grid, 256, 0, h->stream>>>(A, d_z, h->d_lnl_part);
   if (int rc = tsem_sum_parts(h, h->d_lnl_part, h->N ? grid : 0, h->d_lnl_part, 0, h->d_lnl_part + 8000)) return rc;

@@ -777,6 +777,8 @@ void tsem_setup_preload(void) {
   (void)hipFuncGetAttributes(&a, (const void*)k_class_flags);
 }
 
+// The CSR column ids under option "drop_csr_indices" — for CsrIds (tsem_internal.h): rebuilt as col_of_id[rid16], one 6 B-per-entry sweep
+static bool drops_indices(const tsem_ctx* h) { return h->opt_drop_indices == 1 || (h->opt_drop_indices < 0 && h->nnz >= 4000000000ll); }
 int tsem_ensure_indices(tsem_ctx* h) {
   if (h->d_indices || !h->d_indptr || h->nnz == 0) return TSEM_OK;
   if (!h->d_rid16 || !h->d_col_of_id) TSEM_FAIL(TSEM_ERR_ARG, "the CSR column ids were dropped and there are no popularity ids to rebuild them from");
@@ -786,6 +788,10 @@ int tsem_ensure_indices(tsem_ctx* h) {
       h->nnz, h->d_rid16, h->d_col_of_id, h->d_indices);
   TSEM_HIP(hipGetLastError());
   return TSEM_OK;
+}
+void tsem_redrop_indices(tsem_ctx* h) {                    // ... and dropped again where the option says so
+  if (!h->d_indices || !h->d_rid16 || !h->d_col_of_id || !drops_indices(h)) return;
+  (void)hipStreamSynchronize(h->stream); dfree(h->d_indices);
 }
 
 // option "reproducible": the slots' bounds as a run finds them: 2^E > the largest fragment weight >= every contribution w * z
@@ -936,7 +942,8 @@ int tsem_rowstats(tsem_ctx* h, double* stats3, double* pisum0, uint64_t* col_cou
   if (!h || !h->d_indptr) return TSEM_ERR_ARG;
   if (!h->d_lut || h->lut_len <= 0) TSEM_FAIL(TSEM_ERR_ARG, "no score table: call tsem_set_lut after tsem_generate");
   if (int rc = ensure_device(h)) return rc;
-  if (int rc = tsem_ensure_indices(h)) return rc;
+  CsrIds ids(h); ids.keep();                               // (tsem_build_layout, which follows the statistics, reads them and drops them again)
+  if (int rc = ids.acquire()) return rc;
   const int64_t N = h->N;
   const int K = h->K;
   PhaseTimer pt(h->stream);
@@ -1101,7 +1108,8 @@ int tsem_build_layout(tsem_ctx* h) {
   PhaseTimer pt(h->stream);
   const int K = h->K;
   const int64_t na = h->N_amb;
-  if (int rc = tsem_ensure_indices(h)) return rc;          // (a rebuild after option "drop_csr_indices": from the ids of the layout about to go)
+  CsrIds ids(h); ids.keep();                               // (the popularity ids go with the old layout: the fill below drops the column ids once it has made the new ones)
+  if (int rc = ids.acquire()) return rc;                   // (a rebuild after option "drop_csr_indices": from the ids of the layout about to go)
   TSEM_HIP(hipStreamSynchronize(h->stream));
   tsem_free_layout(h);
   h->nnz_amb = 0;
@@ -1408,7 +1416,7 @@ int tsem_build_layout(tsem_ctx* h) {
     TSEM_HIP(hipStreamSynchronize(h->stream));
     // option "drop_csr_indices": the fill was the last reader of the CSR column ids (the report pass and this layout carry 2-byte
     // popularity ids; col = col_of_id[id]): 10 instead of 14 B per stored entry stay resident.
-    if (rid_fill && h->d_col_of_id && (h->opt_drop_indices == 1 || (h->opt_drop_indices < 0 && h->nnz >= 4000000000ll))) dfree(h->d_indices);
+    if (rid_fill && h->d_col_of_id && drops_indices(h)) dfree(h->d_indices);
   } else if (nb) {
     k_sb_fill<<<(unsigned)nb, 256, 0, h->stream>>>(na, R, P, h->d_slot_row, h->d_indptr, h->d_indices, h->d_raw, h->d_lut,
                                                   h->d_colmap, h->d_sb_off, h->d_pval, h->d_pcode, h->d_prc, h->idx24 ? 1 : 0);

@@ -113,6 +113,9 @@ int  tsem_set_stream(tsem_ctx* h, void* hip_stream); /* launch on this hipStream
  *                  (tests; needs "parts" >= 5), 0 forbids it (the two-pass kernels then take over at K > 61 440).  K <= 491 520:
  *                  the two-pass kernels (64 column parts).  Beyond: plain CSR row passes with global fp64 atomics — any K, an order
  *                  of magnitude slower per entry (tsem_layout_info[24] / [26] say which form runs).
+ *   "boot_hot_columns", "boot_batch"  tsem_bootstrap (below): how many of the most popular columns get workgroup-private LDS accumulators
+ *                  (-1, default: as many as 32 KiB of LDS hold for the batch, 4096 / batch; 0 none: every sum is a global fp64 atomic;
+ *                  at most 5120 / batch) and how many replicates share one sweep over the matrix (0, default: 8, the most)
  *   "em_precision" 1: the EM pass in fp32 arithmetic (row sums, posteriors and column sums in fp32) — a
  *                  DIAGNOSTIC for the fp32-vs-fp64 tolerance sweep of BASELINE config 3, not a product path
  *   "fused_dbg"    test hooks, a sum of bits: 32 / 64 the fused EM / lnl pass behaves like a hand-off time-out; 8192 the lnl pass
@@ -403,6 +406,37 @@ int  tsem_cell_em_copy(tsem_ctx* h, int64_t* col_ptr /* n_cells+1 */, int32_t* c
                       double* pi, double* theta, double* pi_init, double* theta_init, /* n_cols each */
                       double* rest /* n_cells x 4: the four values of the untouched columns */,
                       int32_t* n_iter, int32_t* converged, double* lnl /* n_cells each */);
+
+/* ---- bootstrap replicates of the EM fit ---------------------------------------------------------------------------------------
+ * Replicate b gives every row i a multiplicity m_i in 0..255; its fit is, by definition, the reference's fit of the matrix in which
+ * row i appears m_i times (model.py:762-806 on raw[np.repeat(arange(N), m_b)]) with the score scale of the whole matrix, as for the
+ * per-cell fits: its own W_tot = sum m w, W_amb = sum m w Y, prior weights prior x (the largest w of a row with m > 0), pisum0 =
+ * sum over unique rows of m Q; all K columns, dense, from pi = theta = 1 / K.  Only the parameter stop test (diff_est < epsilon,
+ * model.py:792) is offered.  `mult` NULL: Poisson(1) draws of the counter hash, m = #{n : T[n] <= hash3(seed ^ SALT_BOOT, global
+ * row, b) >> 32} with T = floor(2^32 P(X <= n)) (at most 14; telescope_amd/synthetic.py bootstrap_multiplicities gives the same
+ * numbers on the host), evaluated on the fly; else a HOST array [n_rep x N] that is copied to the device (TSEM_ERR_NOMEM with a
+ * message if results, workspace and multiplicities do not fit).  Priors as given to tsem_set_model, whose twin classes are used
+ * as well: a call before it is TSEM_ERR_ARG.
+ * Replicates are fitted in batches of up to 8 that share every sweep over the CSR (scores, column ids through the same scope as
+ * every other row pass: option "drop_csr_indices" keeps working); each stops on its own — diff_est < epsilon or max_iter — and is
+ * frozen by the update kernel from then on, whatever else is in the batch and however often the host looks.  After its last
+ * iteration: lnl (model.py:795-801, the z of the parameters before the last M-step against those after it) and counts[j] =
+ * sum_i m_i A[i, j] with A = reassign(method, thresh) of that z (model.py:837-862; TSEM_RA_CHOOSE is refused).  A replicate with
+ * sum m = 0 is not fitted: n_iter 0, not converged, NaN pi / theta / counts / lnl.  One whose parameters turn NaN (no ambiguous
+ * fragment at theta_prior = 0) runs to max_iter unconverged, like the reference, and has NaN counts and lnl.
+ * Column sums are unordered fp64 atomics (LDS for the most popular columns, options "boot_hot_columns" / "boot_batch"): results
+ * agree from run to run to rounding, not bit for bit, so a handle with option "reproducible" is refused, as is a row-sharded
+ * one (TSEM_ERR_ARG with a message).  Columns that are twins only inside a replicate (the rows that tell them apart drew 0) are not
+ * recognised; ties between them may fall differently from the reference's.  The pooled state, every z buffer, the per-cell fits and
+ * the blocked layout are left untouched. */
+int  tsem_bootstrap(tsem_ctx* h, int32_t n_rep, uint64_t seed, const uint8_t* mult /* NULL | n_rep x N */,
+                    int32_t method, double thresh, double epsilon, int32_t max_iter);
+/* copy the last call's results out (tsem_dims gives K, the caller knows n_rep) */
+int  tsem_bootstrap_copy(tsem_ctx* h, double* pi, double* theta, double* counts /* n_rep x K each, any may be NULL */,
+                         int64_t* n_frags /* sum of m_i */, int32_t* n_iter, int32_t* converged, double* lnl /* n_rep each, any may be NULL */,
+                         int32_t* info2 /* replicates per batch and hot columns used; may be NULL */);
+/* the default multiplicities of replicate `rep` for the handle's rows [row_begin, row_end), computed on the device */
+int  tsem_bootstrap_mult(tsem_ctx* h, uint64_t seed, int32_t rep, int64_t row_begin, int64_t row_end, uint8_t* out);
 
 /* ---- csr_matrix_plus primitives on arbitrary fp64 CSR (sparse_plus.py) ---- */
 /* All three: indptr[n_rows + 1] is a HOST array and is checked on the host before the device is touched. TSEM_ERR_ARG (text in

@@ -26,14 +26,14 @@ class EngineError(RuntimeError):
     code = 0
 
 
-# host / ABI, set-up, EM support, report / row passes, collectives, CSR primitives, per-cell counts, per-cell fits
+# host / ABI, set-up, EM support, report / row passes, collectives, CSR primitives, per-cell counts, per-cell fits, bootstrap
 # (telescope_amd/csrc/tsem_internal.h)
-LIB_UNITS = ('tsem_host', 'tsem_setup', 'tsem_em', 'tsem_report', 'tsem_comm', 'tsem_csr', 'tsem_cells', 'tsem_cellem')
+LIB_UNITS = ('tsem_host', 'tsem_setup', 'tsem_em', 'tsem_report', 'tsem_comm', 'tsem_csr', 'tsem_cells', 'tsem_cellem', 'tsem_boot')
 FZ_UNITS = tuple('tsem_fz_p%d' % p for p in range(1, 9))
 
 
 def build_library(force=False, verbose=False, out=None):
-    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  Sixteen translation units — the eight of
+    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  Seventeen translation units — the nine of
     LIB_UNITS and the eight that instantiate the fused kernel for one team size each (most of the build time) — are compiled
     in parallel and linked into one shared object."""
     from concurrent.futures import ThreadPoolExecutor
@@ -227,6 +227,9 @@ def lib():
     L.tsem_cell_em.argtypes = [vp, dbl, i32, i32]
     L.tsem_cell_em_shape.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
     L.tsem_cell_em_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tsem_bootstrap.argtypes = [vp, i32, u64, vp, i32, dbl, dbl, i32]
+    L.tsem_bootstrap_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tsem_bootstrap_mult.argtypes = [vp, u64, i32, i64, i64, vp]
     L.tsem_csr_norm_rows.argtypes = [C.c_int, i64, vp, vp, vp]
     L.tsem_csr_binmax_rows.argtypes = [C.c_int, i64, i32, vp, vp, vp]
     L.tsem_csr_scale.argtypes = [C.c_int, C.c_int, i64, i32, vp, vp, vp]
@@ -627,6 +630,26 @@ class Engine(object):
         self._ck(self._L.tsem_cell_em_copy(self._h, *[ptr(r[k]) for k in ('col_ptr', 'cols', 'pi', 'theta', 'pi_init', 'theta_init',
                                                                          'rest', 'n_iter', 'converged', 'lnl')]))
         return r
+
+    def bootstrap(self, n_rep, seed, mult, method, thresh, epsilon, max_iter, n_cols):
+        """`n_rep` bootstrap refits (tsem_bootstrap); `mult` None (the device draws Poisson(1) multiplicities from `seed`) or a
+        uint8 [n_rep x N] array.  Returns the arrays of tsem_bootstrap_copy as a dict, `info` = (batch, hot columns)."""
+        if mult is not None:
+            mult = np.ascontiguousarray(mult, dtype=np.uint8)
+        self._ck(self._L.tsem_bootstrap(self._h, int(n_rep), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(mult), RA_CODE[method], float(thresh),
+                                        float(epsilon), int(max_iter)))
+        b, k = int(n_rep), int(n_cols)
+        r = dict(pi=np.empty((b, k)), theta=np.empty((b, k)), counts=np.empty((b, k)), n_frags=np.empty(b, np.int64),
+                 n_iter=np.empty(b, np.int32), converged=np.empty(b, np.int32), lnl=np.empty(b), info=np.zeros(2, np.int32))
+        self._ck(self._L.tsem_bootstrap_copy(self._h, *[ptr(r[key]) for key in ('pi', 'theta', 'counts', 'n_frags', 'n_iter', 'converged',
+                                                                               'lnl', 'info')]))
+        return r
+
+    def bootstrap_mult(self, seed, rep, row_begin, row_end):
+        """The multiplicities the device draws for replicate `rep`, rows [row_begin, row_end) (tsem_bootstrap_mult)."""
+        out = np.empty(max(0, int(row_end) - int(row_begin)), np.uint8)
+        self._ck(self._L.tsem_bootstrap_mult(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(rep), int(row_begin), int(row_end), ptr(out)))
+        return out
 
     # -- instrumentation --
     def kernel_stats(self, reset=False):

@@ -1,6 +1,7 @@
 """`telescope resume` on the MI355X engine (reference: telescope/telescope_resume.py:28-232,
 telescope/__main__.py:49-92).  Same option names and defaults, same log lines, same output files:
-`<outdir>/<exp_tag>-run_stats.tsv` and `<outdir>/<exp_tag>-TE_counts.tsv`.
+`<outdir>/<exp_tag>-run_stats.tsv` and `<outdir>/<exp_tag>-TE_counts.tsv`; `--bootstrap N` (not in the reference) adds
+`<outdir>/<exp_tag>-bootstrap.tsv`.
 
     python -m telescope_amd resume <checkpoint.npz> [--reassign_mode exclude] [--outdir .] ...
 
@@ -34,8 +35,8 @@ def format_minutes(seconds):
 def build_parser():
     ap = argparse.ArgumentParser(prog='telescope', description='Telescope EM reassignment on MI355X')
     sub = ap.add_subparsers(dest='command')
-    _resume_args(sub.add_parser('resume', help='Resume from a checkpoint: EM + reports'))
-    _assign_args(sub.add_parser('assign', help='Load alignments + annotation, checkpoint, EM, reports'))
+    _bootstrap_args(_resume_args(sub.add_parser('resume', help='Resume from a checkpoint: EM + reports')))
+    _bootstrap_args(_assign_args(sub.add_parser('assign', help='Load alignments + annotation, checkpoint, EM, reports')))
     sc = sub.add_parser('sc', help='Single-cell mode: per-barcode count matrices (scTelescope)')
     scsub = sc.add_subparsers(dest='sc_command')
     _sc_args(_assign_args(scsub.add_parser('assign', help='Load alignments (with cell barcodes) + annotation, checkpoint, EM, reports')), True)
@@ -122,6 +123,16 @@ def _assign_args(asg):
     g.add_argument('--reproducible', action='store_true',
                    help='Exact, order-independent sums on the device: the same bits in every run (1.6-2.5x the time per EM iteration).')
     return asg
+
+
+def _bootstrap_args(p):
+    """Bulk `assign` / `resume` only: bootstrap replicates of the fit (TelescopeLikelihood.bootstrap)."""
+    g = {g.title: g for g in p._action_groups}['Run Modes']
+    g.add_argument('--bootstrap', type=int, default=0, metavar='N',
+                   help='After the report, refit the model on N Poisson resamples of the fragments (on the device) and write '
+                        '<exp_tag>-bootstrap.tsv: mean, sd and 95 %% bounds of every count and final_prop.  Default 0: none.')
+    g.add_argument('--bootstrap_seed', type=int, default=0, metavar='S', help='Seed of the resampling (default 0).')
+    return p
 
 
 def _sc_args(p, assign):
@@ -256,9 +267,42 @@ def _refuse_individual_updated_sam(opts):
                          'updated file come from the pooled posteriors); run the two separately')
 
 
+def _refuse_bootstrap(args):
+    """--bootstrap with what the device's bootstrap does not offer: refused before anything is read or written."""
+    n = getattr(args, 'bootstrap', 0)
+    if not n:
+        return
+    if n < 0:
+        raise SystemExit('telescope: --bootstrap takes a number of replicates >= 0')
+    if args.reassign_mode == 'choose':
+        raise SystemExit('telescope: --bootstrap with --reassign_mode choose is not supported (choose draws one random hit per '
+                         'fragment from numpy\'s stream); use exclude, average, conf or unique')
+    if args.use_likelihood:
+        raise SystemExit('telescope: --bootstrap with --use_likelihood is not supported (the replicates stop on the parameter '
+                         'test only)')
+    if args.reproducible:
+        raise SystemExit('telescope: --bootstrap with --reproducible is not supported (the replicates\' column sums are unordered '
+                         'atomics: they agree from run to run to rounding, not bit for bit)')
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise SystemExit('telescope: --bootstrap is not supported in row-sharded runs (WORLD_SIZE > 1); run it on one GPU')
+
+
+def run_bootstrap(ts, ts_model, opts):
+    """--bootstrap N: the replicates, and <exp_tag>-bootstrap.tsv beside the ordinary report."""
+    n = getattr(opts, 'bootstrap', 0)
+    if not n:
+        return
+    lg.info('Bootstrap: %d replicates, seed %d' % (n, opts.bootstrap_seed))
+    stime = time()
+    fits = ts_model.bootstrap(n, opts.bootstrap_seed, method=opts.reassign_mode, thresh=opts.conf_prob, loglev=lg.INFO)
+    ts.output_bootstrap(ts_model, fits, opts.outfile_path('bootstrap.tsv'))
+    lg.info('Bootstrap completed in %s' % format_minutes(time() - stime))
+
+
 def run_resume(args, sc=False):
     """telescope_resume.py:183-232.  sc=True: `sc resume` — a single-cell checkpoint (scTelescope) and its per-cell reports."""
     _refuse_sharded_sc(sc)
+    _refuse_bootstrap(args)
     opts = ResumeOptions(args)
     configure_logging(opts)
     warm = None if opts.skip_em else warm_device(opts)       # (before the heavy imports below: they run while the device comes up)
@@ -295,6 +339,7 @@ def run_resume(args, sc=False):
     os.makedirs(opts.outdir, exist_ok=True)
     ts.output_report(ts_model, opts.outfile_path('run_stats.tsv'), opts.outfile_path('TE_counts.tsv'),
                      write=comm is None or comm.rank == 0)
+    run_bootstrap(ts, ts_model, opts)
     finish(comm)
     lg.info('telescope resume complete (%s)' % format_minutes(time() - total_time))
     return 0
@@ -305,6 +350,7 @@ def run_assign(args, sc=False):
     annotation and the alignments and writes the checkpoint; the other ranks wait for it and read THEIR fragments from the file
     (Telescope.load_shard) — one BAM parse and one whole matrix in host memory per job, not per rank."""
     _refuse_sharded_sc(sc)
+    _refuse_bootstrap(args)
     opts = ResumeOptions(args)
     configure_logging(opts)
     if opts.ncpu != 1:
@@ -396,6 +442,7 @@ def run_assign(args, sc=False):
     if opts.updated_sam:                                     # telescope_assign.py:446-448 (one GPU: refused above otherwise)
         lg.info('Creating updated SAM file...')
         ts.update_sam(ts_model, opts.outfile_path('updated.bam'))
+    run_bootstrap(ts, ts_model, opts)
     finish(comm)
     lg.info('telescope assign complete (%s)' % format_minutes(time() - total_time))
     return 0

@@ -35,6 +35,7 @@
 #define TS_SALT_COL0 0xC2B2AE3D27D4EB4Full
 #define TS_SALT_SCORE 0x165667B19E3779F9ull
 #define TS_SALT_FAM 0x27D4EB2F165667C5ull
+#define TS_SALT_BOOT 0x94D049BB133111EBull   /* bootstrap multiplicities (tsem_boot.hip, synthetic.bootstrap_multiplicities) */
 #define TS_FAMILY 256                 /* loci per family of the synthetic distribution 2 ('family', telescope_amd/synthetic.py) */
 
 __host__ __device__ inline uint64_t ts_mix64(uint64_t z) {
@@ -237,6 +238,14 @@ struct tsem_ctx {
   double* d_ce_lnl = nullptr;       // [ce_cells]
   int32_t ce_class_n[4] = {0, 0, 0, 0};   // cells per class of the last fit: wave | 256 threads | 512 threads | global workspace
   bool ce_fitted = false;
+  // bootstrap replicates (tsem_bootstrap, tsem_boot.hip): the last call's results, replicate-major
+  int64_t opt_boot_hot = -1;        // option "boot_hot_columns": columns with LDS accumulators; -1 auto (the LDS budget), 0 none
+  int64_t opt_boot_batch = 0;       // option "boot_batch": replicates per sweep over the matrix; 0 auto (8)
+  double *d_bt_pi = nullptr, *d_bt_theta = nullptr, *d_bt_counts = nullptr;   // [bt_nrep x K]
+  double* d_bt_lnl = nullptr;       // [bt_nrep]
+  unsigned long long* d_bt_nfrags = nullptr;   // [bt_nrep] sum of the multiplicities
+  int32_t *d_bt_niter = nullptr, *d_bt_conv = nullptr;   // [bt_nrep]
+  int32_t bt_nrep = 0, bt_R = 0, bt_H = 0;   // replicates of the last call (0: none), its batch size and hot columns
   int32_t *d_rep_nb = nullptr, *d_rep_rows = nullptr;   // [N] scratch of tsem_report_colsums, kept between calls
   unsigned long long* d_rep_n = nullptr;
   struct RpChunk* d_rep_chunks = nullptr; int64_t n_rep_chunks = 0; int rep_chunk_E = 0;   // k_report_pack's packing of the rows into wave-sized chunks (tsem_report_pack.h)

@@ -116,6 +116,7 @@ void tsem_free_matrix(tsem_ctx* h) {
   dfree(h->d_gc_key); dfree(h->d_gc_rows); dfree(h->d_gc_eoff); h->gc_version = ~0ull; h->gc_rptr.clear(); h->gc_gent.clear();
   dfree(h->d_gc_ogrp); dfree(h->d_gc_ocol); dfree(h->d_gc_oval); dfree(h->d_gc_gptr); h->gc_nnz = h->gc_cap = 0; h->gc_groups = 0;
   tsem_cellem_free(h);
+  tsem_boot_free(h);
   if (h->d_gtile) { (void)hipFree(h->d_gtile); h->d_gtile = nullptr; h->gtile_bytes = 0; }
   if (h->d_rep_tmp) { (void)hipFree(h->d_rep_tmp); h->d_rep_tmp = nullptr; h->rep_tmp_bytes = 0; }
   h->first_pending = false;
@@ -211,6 +212,14 @@ int tsem_set_option(tsem_ctx* h, const char* key, int64_t v) {
   }
   else if (k == "issue_early") h->opt_issue = v;       // (kept for old scripts; the exchange has one order now)
   else if (k == "group_tile_bytes") h->opt_group_tile = v;   // per-group sums: bytes of output (groups x K doubles) computed per pass over the matrix
+  else if (k == "boot_hot_columns") {                      // tsem_bootstrap: columns with LDS accumulators (-1 auto, 0 none)
+    if (v < -1) TSEM_FAIL(TSEM_ERR_ARG, "boot_hot_columns must be -1 (auto), 0 (none) or a number of columns");
+    h->opt_boot_hot = v;
+  }
+  else if (k == "boot_batch") {                            // tsem_bootstrap: replicates per sweep over the matrix (0 auto; at most 8)
+    if (v < 0) TSEM_FAIL(TSEM_ERR_ARG, "boot_batch must be 0 (auto) or a number of replicates");
+    h->opt_boot_batch = v;
+  }
   else if (k == "use_likelihood") h->opt_lnl_fused = v;      // before the matrix is laid out (tsem_set_model), or followed by tsem_prepare_likelihood
   else if (k == "fused_prof") {
     if (v && !h->d_prof) { if (hipMalloc((void**)&h->d_prof, TS_PROF_WORDS * 8) != hipSuccess) return TSEM_ERR_NOMEM; }

@@ -8,6 +8,7 @@
 //   tsem_csr.hip     csr_matrix_plus primitives on fp64 CSR, numpy's legacy random draw
 //   tsem_cells.hip   sparse per-group counts of the assignment matrix; the grouping (rows of every group in order) cached per map
 //   tsem_cellem.hip  one EM fit per group of rows (single-cell `--pooling_mode individual`)
+//   tsem_boot.hip    bootstrap replicates: the EM refitted with a multiplicity per row, batches of replicates per sweep
 //   tsem_fz_p*.hip   instantiations of the fused kernel (tsem_fused.h), one team size per unit
 //
 // A kernel is launched only from the unit that defines it; other units go through the host functions declared here.
@@ -190,6 +191,8 @@ int tsem_rows_mask_dev(tsem_ctx* h, CsrIds& ids, int which, int method, double t
 int tsem_build_grouping(tsem_ctx* h);                      // d_gc_rows / d_gc_key / d_gc_eoff, gc_rptr / gc_gent for the current group map (cached)
 // tsem_cellem.hip
 void tsem_cellem_free(tsem_ctx* h);                        // the per-cell layout and the last fit
+// tsem_boot.hip
+void tsem_boot_free(tsem_ctx* h);                          // the last bootstrap's results
 // tsem_comm.hip
 bool tsem_comm_on(const tsem_ctx* h);
 int tsem_comm_allreduce_dev(tsem_comm* c, void* buf, size_t count, int dtype, hipStream_t s, std::string& err);

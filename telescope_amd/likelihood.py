@@ -152,6 +152,72 @@ class CellFits(object):
         return tuple(out)
 
 
+BOOTSTRAP_METHODS = ('exclude', 'average', 'conf', 'unique', 'all')
+
+
+def check_bootstrap_args(n_rep, method, multiplicities, n_rows):
+    """The argument checks of `TelescopeLikelihood.bootstrap` (no device).  Returns the multiplicities as a C-contiguous uint8
+    [n_rep x n_rows] array, or None."""
+    if method == 'choose':
+        raise ValueError('bootstrap: reassign mode "choose" draws from numpy\'s random stream per row and is not offered; '
+                         'use one of (exclude, average, conf, unique, all)')
+    if method not in BOOTSTRAP_METHODS:
+        raise ValueError('Argument "method" should be one of (exclude, choose, average, conf, unique, all)')
+    if int(n_rep) != n_rep or int(n_rep) < 1:
+        raise ValueError('bootstrap: n_rep must be an integer >= 1')
+    if multiplicities is None:
+        return None
+    m = np.asarray(multiplicities)
+    if m.dtype != np.uint8:
+        raise ValueError('bootstrap: multiplicities must be uint8 (0..255 copies of every row), not %s' % m.dtype)
+    if m.shape != (int(n_rep), int(n_rows)):
+        raise ValueError('bootstrap: multiplicities must have shape (n_rep, N) = (%d, %d), not %s' % (int(n_rep), int(n_rows), m.shape))
+    return np.ascontiguousarray(m)
+
+
+class BootstrapFits(object):
+    """What `TelescopeLikelihood.bootstrap` returns: B refits of the model on resampled fragments.  `pi`, `theta`, `counts` are
+    [B, K]; `n_frags` (the replicate's fragments, sum of its multiplicities), `n_iter`, `converged`, `lnl` per replicate; `info` =
+    {'batch', 'hot_columns'}: replicates per sweep over the matrix and columns with LDS accumulators the device used.  `fitted`
+    marks the replicates that were fitted (they have fragments) and have finite parameters: the statistics are taken over those."""
+
+    def __init__(self, pi, theta, counts, n_frags, n_iter, converged, lnl, info=None, seed=0, method='exclude'):
+        self.pi, self.theta = np.atleast_2d(np.asarray(pi, dtype=np.float64)), np.atleast_2d(np.asarray(theta, dtype=np.float64))
+        self.counts = np.atleast_2d(np.asarray(counts, dtype=np.float64))
+        self.n_frags = np.asarray(n_frags, dtype=np.int64)
+        self.n_iter = np.asarray(n_iter, dtype=np.int32)
+        self.converged = np.asarray(converged).astype(bool)
+        self.lnl = np.asarray(lnl, dtype=np.float64)
+        self.info = dict(info or {})
+        self.seed, self.method = int(seed), method
+        self.n_rep = len(self.n_iter)
+        if not (self.pi.shape == self.theta.shape == self.counts.shape and self.pi.shape[0] == self.n_rep ==
+                len(self.n_frags) == len(self.converged) == len(self.lnl)):
+            raise ValueError('BootstrapFits: arrays of different shapes')
+        self.K = self.pi.shape[1]
+
+    @property
+    def fitted(self):
+        return (self.n_iter > 0) & np.isfinite(self.pi).all(axis=1) & np.isfinite(self.theta).all(axis=1)
+
+    def summary(self, level=0.95):
+        """{'counts': s, 'pi': s} with s = {'mean', 'sd' (ddof 1), 'lo', 'hi'}: K-vectors over the fitted replicates; lo / hi are
+        `numpy.quantile` at (1 - level) / 2 and 1 - (1 - level) / 2.  NaN where too few replicates are fitted (sd needs two)."""
+        if not 0. < level < 1.:
+            raise ValueError('summary: level must lie in (0, 1)')
+        keep = self.fitted
+        out = {}
+        for name, a in (('counts', self.counts), ('pi', self.pi)):
+            a = a[keep]
+            nan = np.full(self.K, np.nan)
+            if len(a) == 0:
+                out[name] = {'mean': nan, 'sd': nan.copy(), 'lo': nan.copy(), 'hi': nan.copy()}
+                continue
+            lo, hi = np.quantile(a, [(1. - level) / 2., 1. - (1. - level) / 2.], axis=0)
+            out[name] = {'mean': a.mean(axis=0), 'sd': a.std(axis=0, ddof=1) if len(a) > 1 else nan, 'lo': lo, 'hi': hi}
+        return out
+
+
 class TelescopeLikelihood(object):
     """EM model over a fragments x loci score matrix (model.py:631-865)."""
 
@@ -500,6 +566,26 @@ class TelescopeLikelihood(object):
                 int(fitted.sum()), int(fits.converged[fitted].sum()), int(it.min()), float(np.median(it)), int(it.max())))
         else:
             lg.log(loglev, 'Per-cell EM: no cell has fragments.')
+        return fits
+
+    # ---- bootstrap replicates --------------------------------------------------------------------
+    def bootstrap(self, n_rep, seed=0, method='exclude', thresh=0.9, multiplicities=None, loglev=lg.WARNING):
+        """`n_rep` refits of the model on RESAMPLED fragments, on the device over the resident matrix (tsem_bootstrap): replicate b
+        gives row i a multiplicity m_i and is the fit of `raw[np.repeat(arange(N), m_b)]` with the score scale of the whole matrix
+        (model.py:762-806; parameter stop test at `em_epsilon`, `max_iter`).  By default the m_i are Poisson(1) draws of the counter
+        hash (`synthetic.bootstrap_multiplicities(seed, b, rows)`); `multiplicities`: a uint8 [n_rep x N] array instead.  Per
+        replicate pi, theta, lnl and `counts` = column sums of `reassign(method, thresh)` over its fragments (`choose` is not
+        offered).  Returns a `BootstrapFits`.  `tl.pi`, `tl.z`, `tl.lnl` and the per-cell fits are untouched; works before `em()`.
+        One GPU only, and not with engine option "reproducible" (the replicates' column sums are unordered atomics)."""
+        mult = check_bootstrap_args(n_rep, method, multiplicities, self.N)
+        if self.comm.world > 1:
+            raise NotImplementedError('bootstrap: row-sharded runs (WORLD_SIZE > 1) are not supported; run it on one GPU')
+        r = self._eng.bootstrap(int(n_rep), int(seed), mult, method, thresh, self.epsilon, self.max_iter, self.K)
+        fits = BootstrapFits(r['pi'], r['theta'], r['counts'], r['n_frags'], r['n_iter'], r['converged'], r['lnl'],
+                             info={'batch': int(r['info'][0]), 'hot_columns': int(r['info'][1])}, seed=seed, method=method)
+        keep = fits.fitted
+        lg.log(loglev, 'Bootstrap: {:d} replicates, {:d} fitted, {:d} converged; iterations min {:d} / max {:d}.'.format(
+            fits.n_rep, int(keep.sum()), int(fits.converged.sum()), int(fits.n_iter.min()), int(fits.n_iter.max())))
         return fits
 
     def select_z(self, which):

@@ -87,6 +87,22 @@ class NpzSlices(object):
         return out
 
 
+def write_bootstrap_tsv(fh, names, count, fits, level=0.95):
+    """One comment line — replicates, seed, fitted, converged, method, level — then per locus, sorted by name like TE_counts.tsv:
+    `count` (the point estimate, as TE_counts.tsv prints it), mean / sd / lower / upper bound of the bootstrap counts (2 decimals)
+    and of the bootstrap final_prop (%.6g), over the fitted replicates (`BootstrapFits.summary`)."""
+    s = fits.summary(level)
+    cols = OrderedDict([('transcript', list(names)), ('count', np.asarray(count))])
+    for key, pre, fmt in (('counts', 'count', '%.2f'), ('pi', 'prop', '%.6g')):
+        for stat in ('mean', 'sd', 'lo', 'hi'):
+            cols['%s_%s' % (pre, stat)] = [fmt % v for v in s[key][stat]]
+    table = pd.DataFrame(cols)
+    table.sort_values('transcript', inplace=True)
+    fh.write('\t'.join(['## Bootstrap', 'replicates:%d' % fits.n_rep, 'seed:%d' % fits.seed, 'fitted:%d' % int(fits.fitted.sum()),
+                        'converged:%d' % int(fits.converged.sum()), 'method:%s' % fits.method, 'level:%g' % level]) + '\n')
+    table.to_csv(fh, sep='\t', index=False)
+
+
 class Telescope(object):
     def __init__(self, opts=None):
         self.opts = opts
@@ -257,6 +273,16 @@ class Telescope(object):
             stats.to_csv(fh, sep='\t', index=False)
         with open(counts_filename, 'w') as fh:
             counts.to_csv(fh, sep='\t', index=False)
+
+    def output_bootstrap(self, tl, fits, filename, level=0.95):
+        """`<exp_tag>-bootstrap.tsv` of `--bootstrap N`: per locus the count of TE_counts.tsv and the bootstrap statistics of that
+        count and of final_prop (write_bootstrap_tsv)."""
+        mode, prob = self.opts.reassign_mode, self.opts.conf_prob
+        names = sorted(self.feat_index, key=self.feat_index.get)
+        colsum = getattr(tl, 'reassign_colsums', None) or \
+            (lambda m, t=0.9, initial=False: tl.reassign(m, t, initial).sum(0).A1)
+        with open(filename, 'w') as fh:
+            write_bootstrap_tsv(fh, names, colsum(mode, prob), fits, level)
 
     # ---- updated alignment file (model.py:479-521) ---------------------------------------------------------------------------
     def update_sam(self, tl, filename, command_line=None):

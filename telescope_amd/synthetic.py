@@ -33,6 +33,7 @@ SALT_UNIQ = np.uint64(0x5BD1E9955BD1E995)
 SALT_COL0 = np.uint64(0xC2B2AE3D27D4EB4F)
 SALT_SCORE = np.uint64(0x165667B19E3779F9)
 SALT_FAM = np.uint64(0x27D4EB2F165667C5)
+SALT_BOOT = np.uint64(0x94D049BB133111EB)   # bootstrap multiplicities (TS_SALT_BOOT, csrc/tsem_common.h)
 FAMILY = 256               # loci per family of dist 'family' (> MAX_ROW_LEN: a row always fits its family)
 SCORE_LO, SCORE_SPAN = 139, 162
 MAX_ROW_LEN = 255          # slots per row are capped (k + 256*a addressing)
@@ -68,6 +69,14 @@ def poisson_cdf_u32(mean):
         p *= mean / n
         cdf += p
     return np.asarray(out, dtype=np.uint32)
+
+
+def bootstrap_multiplicities(seed, rep, rows):
+    """The multiplicities replicate `rep` of `TelescopeLikelihood.bootstrap(seed=seed)` gives the (global) rows `rows`: Poisson(1)
+    draws m = #{n : T[n] <= hash3(seed ^ SALT_BOOT, row, rep) >> 32} with T = poisson_cdf_u32(1.0), as uint8 (at most 14).  The
+    device evaluates the same expression per row and replicate on the fly (tsem_boot.hip); nothing is stored."""
+    h = (hash3((int(seed) & MASK64) ^ int(SALT_BOOT), rows, int(rep)) >> np.uint64(32)).astype(np.uint32)
+    return np.searchsorted(poisson_cdf_u32(1.0), h, side='right').astype(np.uint8)
 
 
 def row_lengths(seed, rows, mean_nnz, n_cols, uniq_frac=0.0, cdf=None):

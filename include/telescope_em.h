@@ -116,6 +116,12 @@ int  tsem_set_stream(tsem_ctx* h, void* hip_stream); /* launch on this hipStream
  *   "boot_hot_columns", "boot_batch"  tsem_bootstrap (below): how many of the most popular columns get workgroup-private LDS accumulators
  *                  (-1, default: as many as 32 KiB of LDS hold for the batch, 4096 / batch; 0 none: every sum is a global fp64 atomic;
  *                  at most 5120 / batch) and how many replicates share one sweep over the matrix (0, default: 8, the most)
+ *   "cell_em_spread_entries"  tsem_cell_em (below): a group of the map with MORE stored entries than this is not fitted by one workgroup
+ *                  but spread over the whole grid, one set of short kernel launches per iteration (a cell type of a single-cell run).
+ *                  0: never spread; negative values are rejected.  May be set at any time; the next tsem_cell_em reads it.  Default
+ *                  32768.  Measured with tools/time_group_em.py (profiles/r14_group_em.txt): one group of 2^14 ... 2^22 entries is
+ *                  fitted 1.2 x ... 22 x faster spread than by one workgroup — no crossover inside the sweep; 2^15 (1.5-1.9 x) is
+ *                  the smallest power of two above every group a droplet cell gives (and above every cell of the unit's older tests)
  *   "em_precision" 1: the EM pass in fp32 arithmetic (row sums, posteriors and column sums in fp32) — a
  *                  DIAGNOSTIC for the fp32-vs-fp64 tolerance sweep of BASELINE config 3, not a product path
  *   "fused_dbg"    test hooks, a sum of bits: 32 / 64 the fused EM / lnl pass behaves like a hand-off time-out; 8192 the lnl pass
@@ -387,10 +393,20 @@ int  tsem_group_counts_shape(tsem_ctx* h, int32_t* n_groups, int64_t* nnz);
  * model.py:570-625).  The fit of cell c is TelescopeLikelihood(raw[rows of c]) with the score scale of the whole matrix: the cell's
  * own weights, total_wt / ambig_wt, prior weights prior x (the cell's largest weight) (model.py:690-697) and pisum0 (:699); all K
  * columns count: a column the cell never touches has the closed-form value prior_wt / (total + prior_wt K) and takes part in
- * diff_est (model.py:781).  Priors as given to tsem_set_model; needs tsem_rowstats and the score table.  Every cell is fitted by one
- * workgroup from its first iteration to its last, all cells in one call; column sums are taken in ascending row order (scipy's), so
- * the result is deterministic and exact twins inside a cell keep bit-identical pi / theta.  A cell stops after the same iteration
- * whatever else is in the batch.  A cell without rows is not fitted: n_iter 0, converged 0, lnl NaN.
+ * diff_est (model.py:781).  Priors as given to tsem_set_model; needs tsem_rowstats and the score table.  A group of up to
+ * "cell_em_spread_entries" stored entries is fitted by one workgroup from its first iteration to its last, all such groups in one
+ * launch per class (by Kc: <= 256 columns and <= 4096 entries a wave | <= 1024 256 threads | <= 3840 512 threads, tables in LDS |
+ * beyond, tables in a global workspace); column sums are taken in ascending row order (scipy's).  A group with more entries — one
+ * enormous group, a cell type — is no longer served by one workgroup: the SPREAD class fits all such groups together with the whole
+ * grid, a row kernel, a column kernel and a one-workgroup-per-group finish kernel per iteration (under use_likelihood the lnl kernel
+ * as well), no workgroup waiting for another; the host enqueues 8 iterations per look at the groups' done marks, which changes no
+ * result.  There a column of n entries is added by one lane ascending from 0 for n <= 32, by a wave for n <= 4096 (lane l the
+ * ascending piece of ceil(n / 64) entries, the 64 partials through a fixed tree) and by a 256-thread workgroup beyond (pieces of
+ * ceil(n / 256), a fixed tree); rows are handled in chunks of 1024 and the weights' totals and lnl are sums of the chunks' parts in
+ * chunk order.  In every class the order of a sum depends on the group alone, so the result is deterministic, exact twins inside a
+ * group keep bit-identical pi / theta, and a group stops after the same iteration and gets the same bits whatever else is in the
+ * call; the spread class's orders differ from the one-workgroup classes', so a group's BITS depend on its class (spread or not).
+ * A cell without rows is not fitted: n_iter 0, converged 0, lnl NaN.
  * Installs the per-cell final z — the last E-step's (model.py:795), NaN outside z's pattern and for rows in no cell — as the
  * TSEM_Z_USER buffer: every report entry point reads it with which = TSEM_Z_USER.  Leaves the pooled state (pi, theta,
  * TSEM_Z_PREV/CUR, lnl) untouched.  The compacted per-cell layout (18 B per stored entry of the cells' rows, 38 B while it is
@@ -491,8 +507,9 @@ int  tsem_layout_info(tsem_ctx* h, int64_t* info32);
  * index per stored entry of the blocked layout — 3 where the fused kernel reads fp64 entries of a non-split layout (a 13-bit column
  * slot and an 11-bit row slot per entry, four entries in 12 bytes), 4 (local row << 16 | local column) everywhere else; [33]-[36] the
  * cells the last tsem_cell_em fitted per kernel class — a wave per cell | 256 threads | 512 threads, tables in LDS | 512 threads,
- * tables in a global workspace — all 0 before a fit. */
-#define TSEM_LAYOUT_INFO_N 37
+ * tables in a global workspace — all 0 before a fit; [37] the groups the last tsem_cell_em spread over the grid (option
+ * "cell_em_spread_entries"): a spread group is counted here and in none of [33]-[36]. */
+#define TSEM_LAYOUT_INFO_N 38
 int  tsem_layout_info_n(tsem_ctx* h, int64_t* info, int32_t n);
 /* per-block shader-clock stamps of team 0 / member 0 of the fused kernel (option "fused_prof") */
 int  tsem_debug_fused_prof(tsem_ctx* h, uint64_t* out512);

@@ -32,13 +32,25 @@ def format_minutes(seconds):
     return '%d minutes and %d secs' % (seconds // 60, seconds % 60)
 
 
+class _ScParser(argparse.ArgumentParser):
+    """`sc assign` / `sc resume`: `--pooling_mode celltype` has no meaning without its file, so the command line itself is refused,
+    with a message, wherever it is parsed."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, extra = super().parse_known_args(args, namespace)
+        if getattr(ns, 'pooling_mode', None) == 'celltype' and getattr(ns, 'celltype_tsv', None) is None:
+            raise SystemExit('telescope %s: --pooling_mode celltype needs --celltype_tsv FILE (barcode<TAB>celltype lines)'
+                             % ' '.join(self.prog.split()[1:]))
+        return ns, extra
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog='telescope', description='Telescope EM reassignment on MI355X')
     sub = ap.add_subparsers(dest='command')
     _bootstrap_args(_resume_args(sub.add_parser('resume', help='Resume from a checkpoint: EM + reports')))
     _bootstrap_args(_assign_args(sub.add_parser('assign', help='Load alignments + annotation, checkpoint, EM, reports')))
     sc = sub.add_parser('sc', help='Single-cell mode: per-barcode count matrices (scTelescope)')
-    scsub = sc.add_subparsers(dest='sc_command')
+    scsub = sc.add_subparsers(dest='sc_command', parser_class=_ScParser)
     _sc_args(_assign_args(scsub.add_parser('assign', help='Load alignments (with cell barcodes) + annotation, checkpoint, EM, reports')), True)
     _sc_args(_resume_args(scsub.add_parser('resume', help='Resume from a single-cell checkpoint: EM + reports')), False)
     return ap
@@ -141,13 +153,18 @@ def _sc_args(p, assign):
     if assign:
         groups['Input Options'].add_argument('--barcode_tag', type=str, default='CB',
                                              help='Name of the field in the BAM/SAM file containing the barcode for each read.')
+    groups['Input Options'].add_argument('--celltype_tsv', metavar='FILE', default=None,
+                                         help='With --pooling_mode celltype: tab-separated barcode<TAB>celltype lines, no header '
+                                              '(empty lines and lines starting with # are skipped).')
     g = groups['Run Modes']
     g.add_argument('--use_every_reassign_mode', action='store_true',
                    help='Output count matrices generated using every reassign mode (conf, all, unique, exclude, choose, average).')
-    g.add_argument('--pooling_mode', default='pseudobulk', choices=['pseudobulk', 'individual'],
+    g.add_argument('--pooling_mode', default='pseudobulk', choices=['pseudobulk', 'individual', 'celltype'],
                    help='pseudobulk (default): one model fitted to the pool of all cells, as the reference does.  individual: after '
                         'the pooled fit, one model per cell (all cells in one device call); the count matrices come from the per-cell '
-                        'posteriors and <exp_tag>-cell_stats.tsv lists every cell\'s fit.')
+                        'posteriors and <exp_tag>-cell_stats.tsv lists every cell\'s fit.  celltype: one model per cell type of '
+                        '--celltype_tsv; every cell\'s counts come from the posteriors of its type\'s fit (a barcode the file does '
+                        'not list counts nowhere) and <exp_tag>-celltype_stats.tsv lists every type\'s fit.')
     g = groups['Reporting Options']
     g.add_argument('--count_format', default='tsv', choices=['tsv', 'mtx'],
                    help='tsv: the dense cells x features table the reference writes; mtx: Matrix Market (cells x features) with '
@@ -171,6 +188,8 @@ class ResumeOptions(object):
                 'pi_prior', 'theta_prior', 'em_epsilon', 'max_iter', 'use_likelihood', 'skip_em', 'pooling_mode')
         lines = ['{:34}{}'.format('Version:', self.version)]
         lines += ['    {:30}{}'.format(k + ':', getattr(self, k)) for k in keys if hasattr(self, k)]
+        if getattr(self, 'celltype_tsv', None) is not None:
+            lines.append('    {:30}{}'.format('celltype_tsv:', self.celltype_tsv))
         return '\n'.join(lines)
 
 
@@ -267,6 +286,38 @@ def _refuse_individual_updated_sam(opts):
                          'updated file come from the pooled posteriors); run the two separately')
 
 
+def _read_celltypes(opts, command):
+    """`--pooling_mode celltype` / `--celltype_tsv`: what cannot run is refused, and the file is read, before the device, the
+    alignments or the checkpoint are touched.  Leaves {barcode: type name} in `opts.celltypes` (None in the other modes)."""
+    opts.celltypes = None
+    tsv = getattr(opts, 'celltype_tsv', None)
+    if pooling_mode(opts) != 'celltype':
+        if tsv is not None:
+            raise SystemExit('telescope %s: --celltype_tsv is read by --pooling_mode celltype only (this run: %s)'
+                             % (command, pooling_mode(opts)))
+        return
+    if getattr(opts, 'updated_sam', False):
+        raise SystemExit('telescope %s: --pooling_mode celltype with --updated_sam is not supported (the tags of the '
+                         'updated file come from the pooled posteriors); run the two separately' % command)
+    if tsv is None:
+        raise SystemExit('telescope %s: --pooling_mode celltype needs --celltype_tsv FILE (barcode<TAB>celltype lines)' % command)
+    from .run_container import read_celltype_tsv
+    try:
+        opts.celltypes = read_celltype_tsv(tsv)
+    except ValueError as e:
+        raise SystemExit('telescope %s: --celltype_tsv: %s' % (command, e))
+
+
+def _set_celltypes(ts, opts, command):
+    """once the run's barcodes are known: the file must name one of them at least"""
+    if getattr(opts, 'celltypes', None) is None:
+        return
+    try:
+        ts.set_celltypes(opts.celltypes)
+    except ValueError as e:
+        raise SystemExit('telescope %s: --celltype_tsv %s: %s' % (command, opts.celltype_tsv, e))
+
+
 def _refuse_bootstrap(args):
     """--bootstrap with what the device's bootstrap does not offer: refused before anything is read or written."""
     n = getattr(args, 'bootstrap', 0)
@@ -305,6 +356,8 @@ def run_resume(args, sc=False):
     _refuse_bootstrap(args)
     opts = ResumeOptions(args)
     configure_logging(opts)
+    if sc:
+        _read_celltypes(opts, 'sc resume')
     warm = None if opts.skip_em else warm_device(opts)       # (before the heavy imports below: they run while the device comes up)
     from .likelihood import TelescopeLikelihood
     from .run_container import Telescope, scTelescope
@@ -318,6 +371,7 @@ def run_resume(args, sc=False):
             ts = scTelescope.load(opts.checkpoint)
         except ValueError as e:
             raise SystemExit('telescope sc resume: %s' % e)
+        _set_celltypes(ts, opts, 'sc resume')
     else:
         ts = Telescope.load_shard(opts.checkpoint, world, rank) if world > 1 else Telescope.load(opts.checkpoint)
     ts.opts = opts
@@ -357,6 +411,8 @@ def run_assign(args, sc=False):
         raise SystemExit('--ncpu > 1 is not available in this engine')
     _refuse_sharded_updated_sam(opts)
     _refuse_individual_updated_sam(opts)
+    if sc:
+        _read_celltypes(opts, 'sc assign')
     warm = None if opts.skip_em else warm_device(opts)       # (the device comes up while the BAM is parsed)
     from .likelihood import TelescopeLikelihood
     from .loader import Annotation
@@ -384,6 +440,8 @@ def run_assign(args, sc=False):
                 os.makedirs(opts.outdir, exist_ok=True)          # (the load writes <exp_tag>-other.bam and -tmp_tele.bam there)
             ts.load_alignment(annot)
             lg.info('Loaded alignment in {}'.format(format_minutes(time() - stime)))
+            if sc:
+                _set_celltypes(ts, opts, 'sc assign')
             ts.print_summary(lg.INFO)
             if ts.run_info['overlap_unique'] + ts.run_info['overlap_ambig'] == 0:
                 lg.info('No alignments overlapping annotation')

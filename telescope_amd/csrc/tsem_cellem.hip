@@ -21,6 +21,28 @@
 //
 // Numerators are formed as the reference forms them, both terms (model.py:718-720): (Q Y)(pi theta) + (Q (1 - Y)) pi — so that a NaN
 // theta (a cell without ambiguous rows at theta_prior = 0) spreads exactly as it does there.
+//
+// The SPREAD class (option "cell_em_spread_entries"): a group with more stored entries than the option says — a cell TYPE of a
+// single-cell run, 10^5 - 10^7 fragments — is not given to one workgroup.  All spread groups are fitted together by the whole grid,
+// one set of short launches per iteration, on the layout above and the global per-column arrays of the global-workspace class (plus
+// one per-column array for |pi - previous pi|):
+//   row kernel     E-step over chunks of CE_SP_ROWS rows of the row-ordered view (a chunk never straddles two groups; a lane per
+//                  row, the arithmetic of k_cell_em); leaves every entry's value in the scratch
+//   column kernel  M-step over batches of CE_SP_T compacted columns (a batch never straddles two groups)
+//   lnl kernel     the row kernel's twin of lnl_pass: a partial per chunk; after the last iteration once more, writing z
+//   finish kernel  a workgroup per spread group: diff, the stop test, n_iter / converged / the done mark, current -> previous
+// Chunks and batches of a group marked done by an EARLIER launch are skipped; nothing is polled, no workgroup waits for another:
+// kernel boundaries are the only synchronisation.  The host enqueues CE_SP_LOOK iterations, then reads the done marks back only to
+// stop enqueueing (a finished group's launches do nothing): how often it looks changes no result.
+// Order of sums of the spread class — a function of the column's entry count n alone, so that twins stay bit-identical and a group's
+// result does not depend on what else is in the call:
+//   n <= CE_SP_LANE   one lane adds the entries ascending from 0 (scipy's order, the order of k_cell_em)
+//   n <= CE_SP_WAVE   a wave: lane l adds the contiguous ascending piece [l m, (l + 1) m) of m = ceil(n / 64) entries from 0, the 64
+//                     partials go through the sg_sum tree
+//   beyond            the workgroup: thread t adds the piece [t m, (t + 1) m) of m = ceil(n / CE_SP_T) entries, a wave's partials
+//                     through the sg_sum tree, the waves' sums added in wave order
+// Block-wide scalars (the weights' totals, diff, lnl) are sums of per-chunk / per-column parts taken in a fixed order that differs
+// from k_cell_em's.  A group's BITS therefore depend on its class (spread or not); within a class they depend on the group alone.
 #include "tsem_runs.h"
 
 namespace {
@@ -33,6 +55,12 @@ constexpr int CE_KC_WAVE = 256, CE_ENT_WAVE = 4096;        // a wave per cell: 1
 constexpr int CE_KC_SMALL = 1024;                          // 256 threads, up to 40 KiB
 constexpr int CE_KC_LARGE = 3840;                          // 512 threads, up to 150 KiB; beyond: the tables in a global workspace
 constexpr int CE_RED = 16;                                 // doubles of LDS in front of the tables (block reductions)
+// the spread class (see the top of this file; tests/_group_em_reference.py restates these four)
+constexpr int CE_SP_T = 256;                               // threads of every spread kernel = columns per batch
+constexpr int CE_SP_ROWS = 1024;                           // rows per chunk
+constexpr int CE_SP_LANE = 32;                             // a column of up to this many entries is added by one lane
+constexpr int CE_SP_WAVE = 4096;                           // ... of up to this many by a wave; beyond: by the workgroup
+constexpr int CE_SP_LOOK = 8;                              // iterations enqueued per look at the done marks
 
 struct CeArgs {
   int32_t K, max_iter, use_lnl;
@@ -226,6 +254,210 @@ __global__ __launch_bounds__(T) void k_cell_em(CeArgs A) {
   (void)rest_th_prev;
 }
 
+// ---- the spread class -------------------------------------------------------------------------------------------------------
+struct SpRange { int32_t slot, pad; int64_t a, b; };       // rows [a, b) of the group order | compacted columns [a, b) of spread group `slot`
+struct SpArgs {
+  const int32_t* gid;              // [S] the group of every spread slot
+  const SpRange* chunk;            // row chunks, slot by slot
+  const SpRange* batch;            // column batches
+  const int64_t* cfirst;           // [S + 1] first chunk of every slot
+  double* cpart;                   // [3 chunks] per-chunk parts: tw, aw, wm at set-up; lnl afterwards ([3 k])
+  double* dabs;                    // [n_cols] |pi - previous pi| of every column
+  double* st;                      // [S][8] theta prior weight, theta denominator, pi prior weight, pi denominator, previous lnl
+  int32_t* ctl;                    // [S][2] iterations done, the done mark
+};
+
+// set-up, a lane per row: the chunk's parts of the weights (model.py:690-697), Q (1 - Y) into the scratch (pisum0, model.py:699)
+__global__ __launch_bounds__(CE_SP_T) void k_sp_weights(SpArgs S, CeArgs A) {
+  __shared__ double red[CE_RED];
+  const SpRange ch = S.chunk[blockIdx.x];
+  double tw = 0.0, aw = 0.0, wm = 0.0;
+  for (int64_t i = ch.a + threadIdx.x; i < ch.b; i += CE_SP_T) {
+    const uint32_t info = A.rinfo[i];
+    const int cls = (int)(info >> 16);
+    const double w = cls ? A.lut[info & 0xFFFFu] : 0.0, y = cls == 2 ? 1.0 : 0.0;
+    tw += w; aw += w * y; wm = fmax(wm, w);
+    for (int64_t e = A.eoff[i]; e < A.eoff[i + 1]; ++e) A.scratch[e] = A.lut[A.code[e]] * (1.0 - y);
+  }
+  tw = ce_sum<CE_SP_T>(tw, red); aw = ce_sum<CE_SP_T>(aw, red); wm = ce_max<CE_SP_T>(wm, red);
+  if (threadIdx.x == 0) { S.cpart[3 * (int64_t)blockIdx.x] = tw; S.cpart[3 * (int64_t)blockIdx.x + 1] = aw; S.cpart[3 * (int64_t)blockIdx.x + 2] = wm; }
+}
+// set-up, a workgroup per spread group: its weights from the chunks' parts in chunk order, the prior weights and denominators
+__global__ __launch_bounds__(CE_SP_T) void k_sp_begin(SpArgs S, CeArgs A) {
+  __shared__ double red[CE_RED];
+  const int s = blockIdx.x;
+  double tw = 0.0, aw = 0.0, wm = 0.0;
+  for (int64_t k = S.cfirst[s] + threadIdx.x; k < S.cfirst[s + 1]; k += CE_SP_T) {
+    tw += S.cpart[3 * k]; aw += S.cpart[3 * k + 1]; wm = fmax(wm, S.cpart[3 * k + 2]);
+  }
+  tw = ce_sum<CE_SP_T>(tw, red); aw = ce_sum<CE_SP_T>(aw, red); wm = ce_max<CE_SP_T>(wm, red);
+  if (threadIdx.x == 0) {
+    const double ppw = A.pi_prior * wm, tpw = A.theta_prior * wm;
+    double* st = S.st + 8 * (int64_t)s;
+    st[0] = tpw; st[1] = aw + tpw * A.K; st[2] = ppw; st[3] = tw + ppw * A.K; st[4] = INFINITY;
+    S.ctl[2 * s] = 0; S.ctl[2 * s + 1] = 0;
+  }
+}
+
+// E-step (model.py:702-722) of one chunk of rows, a lane per row, from the group's previous parameters: k_cell_em's arithmetic
+__global__ __launch_bounds__(CE_SP_T) void k_sp_rows(SpArgs S, CeArgs A) {
+  const SpRange ch = S.chunk[blockIdx.x];
+  if (S.ctl[2 * ch.slot + 1]) return;                       // (marked by an earlier launch)
+  const int64_t c0 = A.col_ptr[S.gid[ch.slot]];
+  const double *pp = A.ws_pi_prev + c0, *tp = A.ws_theta_prev + c0;
+  for (int64_t i = ch.a + threadIdx.x; i < ch.b; i += CE_SP_T) {
+    const uint32_t info = A.rinfo[i];
+    const int cls = (int)(info >> 16);
+    const double w = cls ? A.lut[info & 0xFFFFu] : 0.0, y = cls == 2 ? 1.0 : 0.0;
+    const int64_t a = A.eoff[i], b = A.eoff[i + 1];
+    double sum = 0.0;
+    for (int64_t e = a; e < b; ++e) { const int lc = A.lcol[e]; sum += ce_numer(A.lut[A.code[e]], y, pp[lc], tp[lc]); }
+    const double rinv = ce_recip0(sum);
+    for (int64_t e = a; e < b; ++e) {
+      const int lc = A.lcol[e];
+      const double n = ce_numer(A.lut[A.code[e]], y, pp[lc], tp[lc]);
+      A.scratch[e] = n != 0.0 ? ((n * rinv) * w) * y : 0.0;            // products that are exactly zero leave z's pattern
+    }
+  }
+}
+
+// calculate_lnl(z(previous parameters), current parameters) (model.py:744-760) of one chunk of rows: lnl_pass of k_cell_em; WRITE: the
+// final pass — every group, z to its CSR positions
+template <bool WRITE>
+__global__ __launch_bounds__(CE_SP_T) void k_sp_lnl(SpArgs S, CeArgs A) {
+  __shared__ double red[CE_RED];
+  const SpRange ch = S.chunk[blockIdx.x];
+  if (!WRITE && S.ctl[2 * ch.slot + 1]) return;
+  const int64_t c0 = A.col_ptr[S.gid[ch.slot]];
+  const double *pp = A.ws_pi_prev + c0, *tp = A.ws_theta_prev + c0, *pi = A.pi + c0, *th = A.theta + c0;
+  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  double part = 0.0;
+  for (int64_t i = ch.a + threadIdx.x; i < ch.b; i += CE_SP_T) {
+    const uint32_t info = A.rinfo[i];
+    const double y = (info >> 16) == 2 ? 1.0 : 0.0;
+    const int64_t a = A.eoff[i], b = A.eoff[i + 1];
+    double sum = 0.0;
+    for (int64_t e = a; e < b; ++e) { const int lc = A.lcol[e]; sum += ce_numer(A.lut[A.code[e]], y, pp[lc], tp[lc]); }
+    const double rinv = ce_recip0(sum);
+    const int64_t zo = WRITE ? A.indptr[A.rows[i]] - a : 0;
+    for (int64_t e = a; e < b; ++e) {
+      const int lc = A.lcol[e];
+      const double q = A.lut[A.code[e]];
+      const double n = ce_numer(q, y, pp[lc], tp[lc]);
+      const bool inp = n != 0.0;
+      const double z = n * rinv;
+      if (WRITE) A.user_z[zo + e] = inp ? z : nan;
+      const double m = ce_numer(q, y, pi[lc], th[lc]);
+      if (inp && m != 0.0) part += z * log1p(m);
+    }
+  }
+  part = ce_sum<CE_SP_T>(part, red);
+  if (threadIdx.x == 0) S.cpart[3 * (int64_t)blockIdx.x] = part;
+}
+
+// The sums of one batch of compacted columns over the scratch, in the order the top of this file states (by the column's entry
+// count alone).  MSTEP: the closed forms (model.py:724-742) and |pi - previous pi|; otherwise pisum0 and the start values 1 / K.
+template <bool MSTEP>
+__global__ __launch_bounds__(CE_SP_T) void k_sp_cols(SpArgs S, CeArgs A) {
+  __shared__ double red[CE_RED];
+  __shared__ uint32_t big_p[CE_SP_T], big_n[CE_SP_T];
+  const SpRange bt = S.batch[blockIdx.x];
+  if (MSTEP && S.ctl[2 * bt.slot + 1]) return;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t col = bt.a + tid;
+  const bool live = col < bt.b;
+  const uint32_t p0 = live ? A.cptr[col] : 0u, n = live ? A.cptr[col + 1] - p0 : 0u;
+  double s = 0.0;
+  if (n <= (uint32_t)CE_SP_LANE)
+    for (uint32_t p = p0; p < p0 + n; ++p) s += A.scratch[A.cpos[p]];
+  for (unsigned long long m = __ballot(n > (uint32_t)CE_SP_LANE && n <= (uint32_t)CE_SP_WAVE); m; m &= m - 1) {
+    const int src = __ffsll((long long)m) - 1;
+    const uint32_t q0 = (uint32_t)__shfl((int)p0, src, 64), qn = (uint32_t)__shfl((int)n, src, 64);
+    const uint32_t piece = (qn + 63u) / 64u, lo = min(qn, (uint32_t)lane * piece), hi = min(qn, lo + piece);
+    double t = 0.0;
+    for (uint32_t j = lo; j < hi; ++j) t += A.scratch[A.cpos[q0 + j]];
+    t = sg_sum<64>(t);
+    if (lane == src) s = t;
+  }
+  const bool big = n > (uint32_t)CE_SP_WAVE;
+  big_p[tid] = p0; big_n[tid] = big ? n : 0u;
+  if (__syncthreads_or(big)) {
+    for (int c = 0; c < CE_SP_T; ++c) {
+      const uint32_t qn = big_n[c];
+      if (!qn) continue;                                     // (the same in every thread)
+      const uint32_t q0 = big_p[c], piece = (qn + CE_SP_T - 1u) / CE_SP_T, lo = min(qn, (uint32_t)tid * piece), hi = min(qn, lo + piece);
+      double t = 0.0;
+      for (uint32_t j = lo; j < hi; ++j) t += A.scratch[A.cpos[q0 + j]];
+      t = ce_sum<CE_SP_T>(t, red);
+      if (tid == c) s = t;
+    }
+  }
+  if (!live) return;
+  if (!MSTEP) {
+    const double inv_k = 1.0 / A.K;
+    A.ws_pisum0[col] = s; A.ws_pi_prev[col] = inv_k; A.ws_theta_prev[col] = inv_k; A.pi[col] = inv_k; A.theta[col] = inv_k;
+  } else {
+    const double* st = S.st + 8 * (int64_t)bt.slot;
+    const double thn = (s + st[0]) / st[1];
+    const double pin = ((A.ws_pisum0[col] + s) + st[2]) / st[3];
+    S.dabs[col] = fabs(pin - A.ws_pi_prev[col]);
+    A.pi[col] = pin; A.theta[col] = thn;
+    if (S.ctl[2 * bt.slot] == 0) { A.pi_init[col] = pin; A.theta_init[col] = thn; }
+  }
+}
+
+// End of an iteration, a workgroup per spread group still running: diff over all K columns (model.py:781) from the columns' parts,
+// the stop test (model.py:783-789), n_iter / converged, the done mark; current -> previous only if the group goes on — a group
+// that stops keeps the parameter pair of its last iteration for the final pass.
+__global__ __launch_bounds__(CE_SP_T) void k_sp_finish(SpArgs S, CeArgs A) {
+  __shared__ double red[CE_RED];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  if (S.ctl[2 * s + 1]) return;
+  const int c = S.gid[s];
+  const int64_t c0 = A.col_ptr[c];
+  const int Kc = (int)(A.col_ptr[c + 1] - c0), K = A.K;
+  double* st = S.st + 8 * (int64_t)s;
+  const int it = S.ctl[2 * s];
+  bool conv;
+  if (A.use_lnl) {
+    double l = 0.0;
+    for (int64_t k = S.cfirst[s] + tid; k < S.cfirst[s + 1]; k += CE_SP_T) l += S.cpart[3 * k];
+    l = ce_sum<CE_SP_T>(l, red);
+    conv = fabs(l - st[4]) < A.eps;
+    __syncthreads();
+    if (tid == 0) st[4] = l;
+  } else {
+    double d = 0.0;
+    for (int lc = tid; lc < Kc; lc += CE_SP_T) d += S.dabs[c0 + lc];
+    d = ce_sum<CE_SP_T>(d, red);
+    const double rest_pi = ((0.0 + 0.0) + st[2]) / st[3], rest_pi_prev = it == 0 ? 1.0 / K : rest_pi;
+    conv = d + (K > Kc ? (double)(K - Kc) * fabs(rest_pi - rest_pi_prev) : 0.0) < A.eps;
+  }
+  const bool stop = conv || it + 1 >= A.max_iter;
+  if (!stop)
+    for (int lc = tid; lc < Kc; lc += CE_SP_T) { A.ws_pi_prev[c0 + lc] = A.pi[c0 + lc]; A.ws_theta_prev[c0 + lc] = A.theta[c0 + lc]; }
+  if (tid == 0) {
+    S.ctl[2 * s] = it + 1; S.ctl[2 * s + 1] = stop ? 1 : 0;
+    A.n_iter[c] = it + 1; A.converged[c] = conv ? 1 : 0;
+  }
+}
+// after the final pass: the group's lnl from the chunks' parts in chunk order, and the columns it never touches
+__global__ __launch_bounds__(CE_SP_T) void k_sp_end(SpArgs S, CeArgs A) {
+  __shared__ double red[CE_RED];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  double l = 0.0;
+  for (int64_t k = S.cfirst[s] + tid; k < S.cfirst[s + 1]; k += CE_SP_T) l += S.cpart[3 * k];
+  l = ce_sum<CE_SP_T>(l, red);
+  if (tid == 0) {
+    const int c = S.gid[s];
+    const double* st = S.st + 8 * (int64_t)s;
+    const double rest_pi = ((0.0 + 0.0) + st[2]) / st[3], rest_th = (0.0 + st[0]) / st[1];
+    A.lnl[c] = l;
+    double* r = A.rest + 4 * (int64_t)c;
+    r[0] = rest_pi; r[1] = rest_th; r[2] = rest_pi; r[3] = rest_th;
+  }
+}
+
 // ---- set-up kernels -----------------------------------------------------------------------------------------------------------
 // per row of the group order: class and weight code; per entry: key (cell << cbits | column) and score code (a lane per row)
 __global__ void k_ce_rows(int64_t M, const int32_t* __restrict__ rows, const uint32_t* __restrict__ gkey, const int64_t* __restrict__ eoff,
@@ -268,9 +500,10 @@ void ce_free_layout(tsem_ctx* h) {
 }
 void ce_free_result(tsem_ctx* h) {
   dfree(h->d_ce_pi); dfree(h->d_ce_theta); dfree(h->d_ce_pi_init); dfree(h->d_ce_theta_init); dfree(h->d_ce_ws0); dfree(h->d_ce_ws1);
-  dfree(h->d_ce_ws2); dfree(h->d_ce_rest); dfree(h->d_ce_niter); dfree(h->d_ce_conv); dfree(h->d_ce_lnl); dfree(h->d_ce_list);
+  dfree(h->d_ce_ws2); dfree(h->d_ce_ws3); dfree(h->d_ce_rest); dfree(h->d_ce_niter); dfree(h->d_ce_conv); dfree(h->d_ce_lnl); dfree(h->d_ce_list);
   h->ce_fitted = false;
   for (int k = 0; k < 4; ++k) h->ce_class_n[k] = 0;
+  h->ce_spread_n = 0;
 }
 
 // the compacted, column-ordered copy of the grouped rows (see the top of this file), cached per group map
@@ -361,6 +594,71 @@ int ce_launch(tsem_ctx* h, CeArgs A, const int32_t* d_list, int n, int kc_max) {
   return TSEM_OK;
 }
 
+// The spread groups of a fit (see the top of this file): set-up, then CE_SP_LOOK iterations enqueued per look at the done marks,
+// bounded by max_iter; the final pass writes z and the lnl.
+int ce_fit_spread(tsem_ctx* h, const CeArgs& A, const std::vector<int32_t>& groups) {
+  const int S = (int)groups.size();
+  if (S == 0) return TSEM_OK;
+  std::vector<SpRange> chunk, batch;
+  std::vector<int64_t> cfirst((size_t)S + 1, 0);
+  for (int s = 0; s < S; ++s) {
+    const int32_t c = groups[(size_t)s];
+    cfirst[(size_t)s] = (int64_t)chunk.size();
+    for (int64_t r = h->gc_rptr[c]; r < h->gc_rptr[c + 1]; r += CE_SP_ROWS)
+      chunk.push_back(SpRange{s, 0, r, std::min<int64_t>(r + CE_SP_ROWS, h->gc_rptr[c + 1])});
+    for (int64_t k = h->ce_colptr[c]; k < h->ce_colptr[c + 1]; k += CE_SP_T)
+      batch.push_back(SpRange{s, 0, k, std::min<int64_t>(k + CE_SP_T, h->ce_colptr[c + 1])});
+  }
+  cfirst[(size_t)S] = (int64_t)chunk.size();
+  const int n_chunk = (int)chunk.size(), n_batch = (int)batch.size();   // (a spread group has entries: rows and columns)
+  DevTmp t_gid, t_chunk, t_batch, t_cfirst, t_cpart, t_st, t_ctl;
+  TSEM_TMP(t_gid, 4 * (size_t)S); TSEM_TMP(t_chunk, sizeof(SpRange) * chunk.size()); TSEM_TMP(t_batch, sizeof(SpRange) * batch.size());
+  TSEM_TMP(t_cfirst, 8 * ((size_t)S + 1)); TSEM_TMP(t_cpart, 24 * chunk.size()); TSEM_TMP(t_st, 64 * (size_t)S); TSEM_TMP(t_ctl, 8 * (size_t)S);
+  TSEM_HIP(hipMemcpyAsync(t_gid.p, groups.data(), 4 * (size_t)S, hipMemcpyHostToDevice, h->stream));
+  TSEM_HIP(hipMemcpyAsync(t_chunk.p, chunk.data(), sizeof(SpRange) * chunk.size(), hipMemcpyHostToDevice, h->stream));
+  TSEM_HIP(hipMemcpyAsync(t_batch.p, batch.data(), sizeof(SpRange) * batch.size(), hipMemcpyHostToDevice, h->stream));
+  TSEM_HIP(hipMemcpyAsync(t_cfirst.p, cfirst.data(), 8 * ((size_t)S + 1), hipMemcpyHostToDevice, h->stream));
+  SpArgs P{};
+  P.gid = t_gid.as<int32_t>(); P.chunk = t_chunk.as<SpRange>(); P.batch = t_batch.as<SpRange>(); P.cfirst = t_cfirst.as<int64_t>();
+  P.cpart = t_cpart.as<double>(); P.dabs = h->d_ce_ws3; P.st = t_st.as<double>(); P.ctl = t_ctl.as<int32_t>();
+  k_sp_weights<<<n_chunk, CE_SP_T, 0, h->stream>>>(P, A);
+  TSEM_HIP(hipGetLastError());
+  k_sp_begin<<<S, CE_SP_T, 0, h->stream>>>(P, A);
+  TSEM_HIP(hipGetLastError());
+  k_sp_cols<false><<<n_batch, CE_SP_T, 0, h->stream>>>(P, A);
+  TSEM_HIP(hipGetLastError());
+  std::vector<int32_t> ctl(2 * (size_t)S);
+  const int iters = std::max(1, A.max_iter);                // (k_cell_em's do-while: one iteration at least)
+  for (int it = 0; it < iters;) {
+    const int n = std::min(CE_SP_LOOK, iters - it);
+    for (int k = 0; k < n; ++k) {
+      k_sp_rows<<<n_chunk, CE_SP_T, 0, h->stream>>>(P, A);
+      TSEM_HIP(hipGetLastError());
+      k_sp_cols<true><<<n_batch, CE_SP_T, 0, h->stream>>>(P, A);
+      TSEM_HIP(hipGetLastError());
+      if (A.use_lnl) {
+        k_sp_lnl<false><<<n_chunk, CE_SP_T, 0, h->stream>>>(P, A);
+        TSEM_HIP(hipGetLastError());
+      }
+      k_sp_finish<<<S, CE_SP_T, 0, h->stream>>>(P, A);
+      TSEM_HIP(hipGetLastError());
+    }
+    it += n;
+    if (it >= iters) break;
+    TSEM_HIP(hipMemcpyAsync(ctl.data(), t_ctl.p, 8 * (size_t)S, hipMemcpyDeviceToHost, h->stream));
+    TSEM_HIP(hipStreamSynchronize(h->stream));
+    int running = 0;
+    for (int s = 0; s < S; ++s) running += ctl[2 * (size_t)s + 1] ? 0 : 1;
+    if (!running) break;
+  }
+  k_sp_lnl<true><<<n_chunk, CE_SP_T, 0, h->stream>>>(P, A);
+  TSEM_HIP(hipGetLastError());
+  k_sp_end<<<S, CE_SP_T, 0, h->stream>>>(P, A);
+  TSEM_HIP(hipGetLastError());
+  TSEM_HIP(hipStreamSynchronize(h->stream));                // (the tables above go out of scope)
+  return TSEM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -384,7 +682,7 @@ int tsem_cell_em(tsem_ctx* h, double epsilon, int32_t max_iter, int32_t use_like
   const int64_t nc = h->ce_ncols;
   if (!h->d_ce_pi) {
     TSEM_ALLOC(h->d_ce_pi, nc); TSEM_ALLOC(h->d_ce_theta, nc); TSEM_ALLOC(h->d_ce_pi_init, nc); TSEM_ALLOC(h->d_ce_theta_init, nc);
-    TSEM_ALLOC(h->d_ce_ws0, nc); TSEM_ALLOC(h->d_ce_ws1, nc); TSEM_ALLOC(h->d_ce_ws2, nc);
+    TSEM_ALLOC(h->d_ce_ws0, nc); TSEM_ALLOC(h->d_ce_ws1, nc); TSEM_ALLOC(h->d_ce_ws2, nc); TSEM_ALLOC(h->d_ce_ws3, nc);
     TSEM_ALLOC(h->d_ce_rest, 4 * (int64_t)G); TSEM_ALLOC(h->d_ce_niter, G); TSEM_ALLOC(h->d_ce_conv, G); TSEM_ALLOC(h->d_ce_lnl, G);
     TSEM_ALLOC(h->d_ce_list, G);
   }
@@ -393,11 +691,12 @@ int tsem_cell_em(tsem_ctx* h, double epsilon, int32_t max_iter, int32_t use_like
     k_ce_fill_nan<<<cdiv64(h->nnz, 256), 256, 0, h->stream>>>(h->nnz, h->d_user_z);   // rows in no cell have no entries
     TSEM_HIP(hipGetLastError());
   }
-  // the cells by class, each class largest first (by entries; ties in cell order)
-  std::vector<int32_t> cls[4];
+  // the cells by class, each class largest first (by entries; ties in cell order); the spread groups in group order
+  std::vector<int32_t> cls[4], spread;
   int kc_max[4] = {0, 0, 0, 0};
   for (int32_t c = 0; c < G; ++c) {
     const int64_t kc = h->ce_colptr[c + 1] - h->ce_colptr[c], ne = h->gc_gent[c + 1] - h->gc_gent[c];
+    if (h->opt_ce_spread > 0 && ne > h->opt_ce_spread) { spread.push_back(c); continue; }
     const int k = (kc <= CE_KC_WAVE && ne <= CE_ENT_WAVE) ? 0 : kc <= CE_KC_SMALL ? 1 : kc <= CE_KC_LARGE ? 2 : 3;
     cls[k].push_back(c);
     kc_max[k] = std::max<int>(kc_max[k], (int)kc);
@@ -412,7 +711,7 @@ int tsem_cell_em(tsem_ctx* h, double epsilon, int32_t max_iter, int32_t use_like
     list.insert(list.end(), cls[k].begin(), cls[k].end());
     first[k + 1] = (int)list.size();
   }
-  if (G) TSEM_HIP(hipMemcpyAsync(h->d_ce_list, list.data(), 4 * (size_t)G, hipMemcpyHostToDevice, h->stream));
+  if (!list.empty()) TSEM_HIP(hipMemcpyAsync(h->d_ce_list, list.data(), 4 * list.size(), hipMemcpyHostToDevice, h->stream));
   CeArgs A{};
   A.K = h->K; A.max_iter = max_iter; A.use_lnl = use_likelihood ? 1 : 0;
   A.eps = epsilon; A.pi_prior = h->pi_prior; A.theta_prior = h->theta_prior;
@@ -426,8 +725,10 @@ int tsem_cell_em(tsem_ctx* h, double epsilon, int32_t max_iter, int32_t use_like
   if (int rc = ce_launch<256, true>(h, A, h->d_ce_list + first[1], first[2] - first[1], kc_max[1])) return rc;
   if (int rc = ce_launch<512, true>(h, A, h->d_ce_list + first[2], first[3] - first[2], kc_max[2])) return rc;
   if (int rc = ce_launch<512, false>(h, A, h->d_ce_list + first[3], first[4] - first[3], kc_max[3])) return rc;
+  if (int rc = ce_fit_spread(h, A, spread)) return rc;
   TSEM_HIP(hipStreamSynchronize(h->stream));
   for (int k = 0; k < 4; ++k) h->ce_class_n[k] = first[k + 1] - first[k];
+  h->ce_spread_n = (int32_t)spread.size();
   h->ce_fitted = true;
   pt.lap("cell_em: fit");
   return TSEM_OK;

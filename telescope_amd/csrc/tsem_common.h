@@ -69,6 +69,8 @@ struct tsem_ctx {
   int64_t* d_indptr = nullptr;
   int32_t* d_indices = nullptr;
   uint16_t* d_raw = nullptr;
+  int64_t opt_ce_spread = 32768;    // option "cell_em_spread_entries": a group with more stored entries is fitted by the whole grid (tsem_cellem.hip); 0 never.
+                                    // Measured (profiles/r14_group_em.txt): spread wins from the smallest group timed, 2^14 entries (1.2-1.4 x), 1.5-1.9 x here
   int64_t opt_drop_indices = -1;    // option "drop_csr_indices": free the CSR column ids (4 B per entry) once the blocked layout and the 2-byte popularity ids
                                     // exist — col = col_of_id[rid16], rebuilt for the span of a call (CsrIds, tsem_internal.h) by the generic row passes, z export, a
                                     // layout rebuild.  -1 auto: from 4e9 stored entries on; 0 never; 1 always
@@ -233,10 +235,12 @@ struct tsem_ctx {
   int32_t ce_cells = 0;             // cells of the layout
   double *d_ce_pi = nullptr, *d_ce_theta = nullptr, *d_ce_pi_init = nullptr, *d_ce_theta_init = nullptr;   // [ce_ncols] the last fit
   double *d_ce_ws0 = nullptr, *d_ce_ws1 = nullptr, *d_ce_ws2 = nullptr;   // [ce_ncols] previous pi / theta, pisum0 of the cells whose tables do not fit LDS
+  double* d_ce_ws3 = nullptr;       // [ce_ncols] |pi - previous pi| per column of the spread groups
   double* d_ce_rest = nullptr;      // [ce_cells][4] pi, theta, pi_init, theta_init of the columns a cell never touches
   int32_t *d_ce_niter = nullptr, *d_ce_conv = nullptr, *d_ce_list = nullptr;   // [ce_cells] iterations, converged, launch order
   double* d_ce_lnl = nullptr;       // [ce_cells]
   int32_t ce_class_n[4] = {0, 0, 0, 0};   // cells per class of the last fit: wave | 256 threads | 512 threads | global workspace
+  int32_t ce_spread_n = 0;          // groups the last fit spread over the grid (counted in none of the four classes)
   bool ce_fitted = false;
   // bootstrap replicates (tsem_bootstrap, tsem_boot.hip): the last call's results, replicate-major
   int64_t opt_boot_hot = -1;        // option "boot_hot_columns": columns with LDS accumulators; -1 auto (the LDS budget), 0 none

@@ -220,6 +220,10 @@ int tsem_set_option(tsem_ctx* h, const char* key, int64_t v) {
     if (v < 0) TSEM_FAIL(TSEM_ERR_ARG, "boot_batch must be 0 (auto) or a number of replicates");
     h->opt_boot_batch = v;
   }
+  else if (k == "cell_em_spread_entries") {                // tsem_cell_em: groups with more stored entries are spread over the grid (0 never)
+    if (v < 0) TSEM_FAIL(TSEM_ERR_ARG, "cell_em_spread_entries must be 0 (never spread) or a number of stored entries");
+    h->opt_ce_spread = v;
+  }
   else if (k == "use_likelihood") h->opt_lnl_fused = v;      // before the matrix is laid out (tsem_set_model), or followed by tsem_prepare_likelihood
   else if (k == "fused_prof") {
     if (v && !h->d_prof) { if (hipMalloc((void**)&h->d_prof, TS_PROF_WORDS * 8) != hipSuccess) return TSEM_ERR_NOMEM; }
@@ -708,6 +712,7 @@ int tsem_layout_info_n(tsem_ctx* h, int64_t* out, int32_t n) {
   int64_t info[TSEM_LAYOUT_INFO_N] = {};
   info[32] = h->idx24 ? 3 : 4;                             // bytes of index per stored entry (3: the packed index of tsem_idx24.h)
   for (int k = 0; k < 4; ++k) info[33 + k] = h->ce_class_n[k];   // cells per class of the last tsem_cell_em (tsem_cellem.hip; 0 before a fit)
+  info[37] = h->ce_spread_n;                               // ... and the groups it spread over the grid (in none of the four)
   info[0] = h->P; info[1] = h->Kp; info[2] = h->R; info[3] = h->nb;
   info[4] = h->N_amb; info[5] = h->N_uni; info[6] = h->nnz_amb; info[7] = h->nnz_pad;
   info[8] = h->n_twin_cols; info[9] = h->G1; info[10] = h->G2; info[11] = h->use_fused ? 1 : 0;

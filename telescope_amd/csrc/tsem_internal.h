@@ -7,7 +7,7 @@
 //   tsem_comm.hip    collectives: RCCL resolved at run time, the in-process transport, the communicator ABI
 //   tsem_csr.hip     csr_matrix_plus primitives on fp64 CSR, numpy's legacy random draw
 //   tsem_cells.hip   sparse per-group counts of the assignment matrix; the grouping (rows of every group in order) cached per map
-//   tsem_cellem.hip  one EM fit per group of rows (single-cell `--pooling_mode individual`)
+//   tsem_cellem.hip  one EM fit per group of rows (single-cell `--pooling_mode individual` / `celltype`)
 //   tsem_boot.hip    bootstrap replicates: the EM refitted with a multiplicity per row, batches of replicates per sweep
 //   tsem_fz_p*.hip   instantiations of the fused kernel (tsem_fused.h), one team size per unit
 //

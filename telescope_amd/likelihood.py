@@ -545,7 +545,9 @@ class TelescopeLikelihood(object):
     def em_cells(self, cell_of_row, n_cells, use_likelihood=False, loglev=lg.WARNING):
         """One EM fit PER CELL instead of one fit of the pool: cell c's model is `TelescopeLikelihood(raw[rows of c])` with the score
         scale of the whole matrix (model.py:762-806 on the cell's rows; its own weights, totals, prior weights and pisum0; all K
-        columns) — all cells in one device call (tsem_cell_em), each fitted by one workgroup, deterministic.  `cell_of_row[i]` in
+        columns) — all cells in one device call (tsem_cell_em), each fitted by one workgroup, or, beyond engine option
+        "cell_em_spread_entries" stored entries (a cell type), spread over the whole grid; deterministic.  The map may be any
+        partition of the rows: barcodes (`--pooling_mode individual`) or cell types (`celltype`).  `cell_of_row[i]` in
         [0, n_cells) or -1 (a row in no cell), as for `reassign_cell_counts`.  Returns a `CellFits`.
 
         Afterwards `tl.z` is the per-cell posterior matrix (rows in no cell have no entries) and `reassign`, `reassign_colsums`,
@@ -562,8 +564,13 @@ class TelescopeLikelihood(object):
         fitted = fits.n_iter > 0
         if fitted.any():
             it = fits.n_iter[fitted]
-            lg.log(loglev, 'Per-cell EM: {:d} cells fitted, {:d} converged; iterations min {:d} / median {:g} / max {:d}.'.format(
-                int(fitted.sum()), int(fits.converged[fitted].sum()), int(it.min()), float(np.median(it)), int(it.max())))
+            try:
+                spread = int(self._eng.layout_info().get('cell_em_spread', 0))
+            except Exception:                                   # noqa: BLE001 — (a tests-only engine without layout_info)
+                spread = 0
+            lg.log(loglev, 'Per-cell EM: {:d} cells fitted, {:d} converged; iterations min {:d} / median {:g} / max {:d}{}.'.format(
+                int(fitted.sum()), int(fits.converged[fitted].sum()), int(it.min()), float(np.median(it)), int(it.max()),
+                '; {:d} spread over the grid'.format(spread) if spread else ''))
         else:
             lg.log(loglev, 'Per-cell EM: no cell has fragments.')
         return fits

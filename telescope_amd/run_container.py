@@ -406,6 +406,48 @@ def write_mtx_counts(mtx_path, csr, barcodes, features):
             fh.writelines('%s\n' % n for n in names)
 
 
+def read_celltype_tsv(path):
+    """`--celltype_tsv`: tab-separated `barcode<TAB>celltype` lines, no header; empty lines and lines starting with `#` are skipped.
+    Returns {barcode: type name} in file order.  ValueError: the file cannot be read, a line without two fields, a barcode listed with
+    two different types."""
+    out = OrderedDict()
+    try:
+        with open(path) as fh:
+            lines = fh.read().splitlines()
+    except (OSError, UnicodeDecodeError) as e:
+        raise ValueError('cannot read %s: %s' % (path, e))
+    for no, line in enumerate(lines, 1):
+        if not line.strip() or line.startswith('#'):
+            continue
+        f = line.split('\t')
+        if len(f) != 2 or not f[0].strip() or not f[1].strip():
+            raise ValueError('%s, line %d: expected barcode<TAB>celltype, got %r' % (path, no, line))
+        bc, name = f[0].strip(), f[1].strip()
+        if out.setdefault(bc, name) != name:
+            raise ValueError('%s, line %d: barcode %s is listed with two cell types (%s, %s)' % (path, no, bc, out[bc], name))
+    return out
+
+
+def celltype_map(barcodes, type_of_barcode):
+    """The types numbered in sorted order of their names, and the type of every cell of the run (-1: a barcode the file does not
+    list; barcodes of the file that the run does not contain are ignored).  ValueError when the file names no barcode of the run."""
+    names = sorted(set(type_of_barcode.values()))
+    number = {n: i for i, n in enumerate(names)}
+    type_of_cell = np.asarray([number[type_of_barcode[b]] if b in type_of_barcode else -1 for b in barcodes], dtype=np.int32)
+    if not np.any(type_of_cell >= 0):
+        raise ValueError('the cell type file names none of the %d barcodes of this run' % len(barcodes))
+    return names, type_of_cell
+
+
+def compose_type_of_row(cell_of_row, type_of_cell):
+    """type_of_cell[cell_of_row], -1 for a fragment without barcode or of a barcode without type"""
+    cor = np.asarray(cell_of_row)
+    out = np.full(cor.shape, -1, np.int32)
+    has = cor >= 0
+    out[has] = np.asarray(type_of_cell, dtype=np.int32)[cor[has]]
+    return out
+
+
 class scTelescope(Telescope):
     """Single-cell run container: the bulk container plus the cell of every fragment (`cell_of_row`, -1 = no barcode) and the cell
     names in first-appearance order (`barcodes`) — what the reference keeps as `barcode_read_indices` (model.py:311-316)."""
@@ -414,6 +456,11 @@ class scTelescope(Telescope):
         super().__init__(opts)
         self.cell_of_row = None
         self.barcodes = []
+        self.type_names, self.type_of_cell = None, None      # `--pooling_mode celltype` (set_celltypes)
+
+    def set_celltypes(self, type_of_barcode):
+        """The cell types of `--celltype_tsv` (read_celltype_tsv) for this run's barcodes; ValueError if it names none of them."""
+        self.type_names, self.type_of_cell = celltype_map(self.barcodes, type_of_barcode)
 
     def load_alignment(self, annotation):
         from . import loader
@@ -481,17 +528,35 @@ class scTelescope(Telescope):
                 fh.write('\t'.join(comment) + '\n')
                 stats.to_csv(fh, sep='\t', index=False)
         n_cells = len(self.barcodes)
-        if getattr(self.opts, 'pooling_mode', 'pseudobulk') == 'individual':
+        pooling = getattr(self.opts, 'pooling_mode', 'pseudobulk')
+        count_map = self.cell_of_row
+        if pooling == 'individual':
             # one model per cell: from here on tl's z is the per-cell posteriors, and the counts below come from them
             fits = tl.em_cells(self.cell_of_row, n_cells, bool(getattr(self.opts, 'use_likelihood', False)), loglev=lg.INFO)
             if write:
                 self.write_cell_stats(tl, fits, stats_filename.replace('run_stats.tsv', 'cell_stats.tsv')
                                       if stats_filename.endswith('run_stats.tsv') else stats_filename + '.cell_stats.tsv')
+        elif pooling == 'celltype':
+            # one model per cell type: every cell's counts come from the posteriors of its type's fit; a barcode without type is
+            # in no group, gets no posterior and counts nowhere
+            if self.type_of_cell is None:
+                self.set_celltypes(self.opts.celltypes)
+            type_of_row = compose_type_of_row(self.cell_of_row, self.type_of_cell)
+            lost = np.asarray(self.cell_of_row) >= 0
+            lost &= type_of_row < 0
+            if lost.any():
+                lg.warning('%d barcodes (%d fragments) have no cell type in %s: their counts are zero'
+                           % (int(np.sum(self.type_of_cell < 0)), int(lost.sum()), getattr(self.opts, 'celltype_tsv', 'the cell type file')))
+            fits = tl.em_cells(type_of_row, len(self.type_names), bool(getattr(self.opts, 'use_likelihood', False)), loglev=lg.INFO)
+            if write:
+                self.write_celltype_stats(tl, fits, stats_filename.replace('run_stats.tsv', 'celltype_stats.tsv')
+                                          if stats_filename.endswith('run_stats.tsv') else stats_filename + '.celltype_stats.tsv')
+            count_map = np.where(type_of_row >= 0, np.asarray(self.cell_of_row), -1).astype(np.int32)
         for method in SC_METHODS:
             if method != mode and not every:
                 continue
             out = counts_filename[:counts_filename.rfind('.')] + '_' + method + '.tsv' if every else counts_filename
-            counts = tl.reassign_cell_counts(method, self.cell_of_row, n_cells, prob)
+            counts = tl.reassign_cell_counts(method, count_map, n_cells, prob)
             if not write:
                 continue
             if fmt == 'mtx':
@@ -514,3 +579,20 @@ class scTelescope(Telescope):
                 fh.write('%s\t%d\t%d\t%d\t%d\t%s\t%s\n' % (_csv_field(self.barcodes[c]), frags[c], amb[c],
                                                             fits.col_ptr[c + 1] - fits.col_ptr[c], fits.n_iter[c],
                                                             bool(fits.converged[c]), _float_repr(fits.lnl[c])))
+
+    def write_celltype_stats(self, tl, fits, filename):
+        """`<exp_tag>-celltype_stats.tsv` of `--pooling_mode celltype`: one line per type — its cells, its fragments, how many of
+        them are ambiguous, the features it touches, and its fit's iterations, convergence and log-likelihood."""
+        n_types = len(self.type_names)
+        toc = np.asarray(self.type_of_cell)
+        tor = compose_type_of_row(self.cell_of_row, toc)
+        in_type = tor >= 0
+        cells = np.bincount(toc[toc >= 0], minlength=n_types)
+        frags = np.bincount(tor[in_type], minlength=n_types)
+        amb = np.bincount(tor[in_type], weights=np.asarray(tl.Y).ravel()[in_type], minlength=n_types).astype(np.int64)
+        with open(filename, 'w') as fh:
+            fh.write('celltype\tcells\tfragments\tambiguous\tcolumns\titerations\tconverged\tlnl\n')
+            for t in range(n_types):
+                fh.write('%s\t%d\t%d\t%d\t%d\t%d\t%s\t%s\n' % (_csv_field(self.type_names[t]), cells[t], frags[t], amb[t],
+                                                                 fits.col_ptr[t + 1] - fits.col_ptr[t], fits.n_iter[t],
+                                                                 bool(fits.converged[t]), _float_repr(fits.lnl[t])))

@@ -97,10 +97,12 @@ int  tsem_set_stream(tsem_ctx* h, void* hip_stream); /* launch on this hipStream
  *                  column's grid has to move (tsem_layout_info[20] counts them); the rows keep their entry order ("deconflict"
  *                  is off), so that a row's partial sum is one run ending in at most two atomics.  That holds for rows of up to
  *                  256 entries; with longer rows tsem_layout_info[21] reports 2 instead of 1 and the last bit of such a row's
- *                  sum may depend on timing.  3: a pass gave up moving a column's grid after 40 repeats — its sums are not
+ *                  sum may depend on timing.  3: a pass gave up moving a column's grid after 84 repeats — its sums are not
  *                  guaranteed exact (never seen; reported instead of hidden).  A hand-off time-out in this mode redoes the pass on the
  *                  fused kernel (the two-pass kernels have no exact sums); repeated time-outs end the run with TSEM_ERR_TIMEOUT on every rank.  Needs the fused kernel and a score table of <= 2048 entries; column sums are
- *                  within (entries of the column) x 2^-41 of exact, typically one fp64 rounding.  The float-valued sums of
+ *                  within (entries of the column) x 2^-41 of exact, typically one fp64 rounding — "exact" being the sum of the fp64
+ *                  contributions w*z as the default mode forms them, the error relative to the sum; the grids stop at 2^-903, so on top
+ *                  of that every contribution may lose up to 2^-964 absolute (a column sum below 1e-290 may come out as 0).  The float-valued sums of
  *                  tsem_reassign / _rows / _groups / tsem_report_colsums (conf, average) are accumulated exactly as well
  *                  (two atomics per value).  1: both pieces in ONE pass over THREE tables per part when they fit the LDS (score
  *                  codes, at most 4800 columns per part with at most 8 parts — i.e. K <= 19k with teams of 4, K <= 38k with

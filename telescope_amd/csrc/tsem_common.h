@@ -94,7 +94,7 @@ struct tsem_ctx {
   int32_t max_code = -1;            // largest raw score of the resident matrix (-1: not taken yet); tsem_max_score
   int32_t min_code = -1;            // smallest stored score above 0 (taken by the same pass; -1: none / not taken yet)
   bool have_rowstats = false;
-  bool bin_inexact = false;         // option "reproducible": a pass gave up moving a column's grid after 40 repeats (its sums are not exact)
+  bool bin_inexact = false;         // option "reproducible": a pass gave up moving a column's grid after 84 repeats (its sums are not exact)
 
   // ---- model scalars (GLOBAL after set_model) ----
   double W_tot = 0, W_amb = 0, w_max = 0, pi_prior = 0, theta_prior = 0;

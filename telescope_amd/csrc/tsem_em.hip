@@ -878,7 +878,12 @@ static int em_pass_impl(tsem_ctx* h, bool lag) {
       TSEM_HIP(hipMemcpyAsync(&redo, h->d_binflag, 4, hipMemcpyDeviceToHost, h->stream));
       TSEM_HIP(hipStreamSynchronize(h->stream));
       if (!redo) break;
-      if (attempt >= 40) {                                   // (40 x 24 bits: from the largest weight down to the smallest normal number)
+      // A grid moves by at most 24 bits per repeat and k_bin_check stops lowering an empty column's at ebias <= 120, so from the start
+      // of tsem_bin_reset (the largest weight, ebias <= 2000) every column is settled after (2000 - 96) / 24 < 80 repeats.  (The cap
+      // was 40 — "from the largest weight down to the smallest normal number" only for weights near 1: with w_max = e^100 a column whose
+      // contributions lie below 1e-245, such as one a resumed run hands in with pi = 1e-300, was given up on and came out as 0 or with
+      // 11 bits: tests/test_gpu_em_pass_exact.py.)
+      if (attempt >= 84) {
         h->bin_inexact = true;                               // the sums of this pass are NOT guaranteed exact: tsem_layout_info[21] says so
         break;
       }

@@ -151,7 +151,10 @@ int  tsem_generate(tsem_ctx* h, int64_t row_begin, int64_t row_end, int32_t n_co
                    const uint32_t* len_cdf, int32_t cdf_len, uint64_t seed,
                    int32_t dist, double uniq_frac);
 /* largest raw score of the local rows; (re)install the Q lookup table once the
- * GLOBAL maximum is known (model.py:640,653) */
+ * GLOBAL maximum is known (model.py:640,653).
+ * What the set-up assumes of a caller's table: finite, non-negative and NON-DECREASING entries.  tsem_rowstats takes a row's weight
+ * from the row's largest CODE (w_i = lut[max code] is max_j Q_ij only then), stats[2] from the largest code of all, and the top of
+ * the grids of the exact pisum0 from the table's LAST entry; none of this is validated. */
 int  tsem_max_score(tsem_ctx* h, int32_t* max_score);
 int  tsem_set_lut(tsem_ctx* h, const double* lut, int32_t lut_len);
 /* The table for a host without numpy (the C host of tests/c_host/): lut[r] = expm1((r * (1 / max_score)) * scale_factor), r = 0 ..
@@ -171,6 +174,15 @@ int  tsem_export_csr(tsem_ctx* h, int64_t* indptr, int32_t* indices, uint16_t* r
  *   unique rows per column; col_count[K] = stored entries per column and
  *   col_hash[K] = order-independent 64-bit signature sum_i hash(global row, score)
  *   (wrap-around).  Multi-GPU hosts all-reduce them (sum,sum,max,sum,sum,sum).
+ *   pisum0 is EXACT — exact sums on 9 grids 26 bits apart, added in a fixed order: independent of the order of
+ *   the rows, of the launch and of the run, within 8 x 2^-53 of the exact sum — while floor(log2(largest entry)) -
+ *   floor(log2(smallest positive entry)) <= 9 x 26 - 53 = 181 (any table whose largest / smallest positive entry is below
+ *   2^181; the reference's span 2^145 to 2^154), the last entry lies in [2^-841, 2^997) and a column has at most 2^26
+ *   unique rows.  Past that range what the grids leave of a Q is added with an ordinary fp64 atomic: pisum0[j] stays within
+ *   (n_j + 9) x 2^-53 relative of the exact sum (n_j unique rows in column j) and is 0 only where the exact sum is 0, but its
+ *   last bits then depend on the order of those atomics.  (Of col_hash only the low 32 bits are a function of the matrix: the
+ *   value is a sum over workgroups of sums modulo 2^32, so its high half depends on how the rows fell to the workgroups —
+ *   alike for twin columns, whose entries every workgroup sees alike, which is all twin detection needs.)
  *   Columns with equal (count, hash) are exact twins (same fragments, same
  *   scores): the reference keeps their pi/theta bit-identical because scipy
  *   accumulates every column in row order, and `reassign` ties depend on it, so
@@ -510,8 +522,10 @@ int  tsem_layout_info(tsem_ctx* h, int64_t* info32);
  * slot and an 11-bit row slot per entry, four entries in 12 bytes), 4 (local row << 16 | local column) everywhere else; [33]-[36] the
  * cells the last tsem_cell_em fitted per kernel class — a wave per cell | 256 threads | 512 threads, tables in LDS | 512 threads,
  * tables in a global workspace — all 0 before a fit; [37] the groups the last tsem_cell_em spread over the grid (option
- * "cell_em_spread_entries"): a spread group is counted here and in none of [33]-[36]. */
-#define TSEM_LAYOUT_INFO_N 38
+ * "cell_em_spread_entries"): a spread group is counted here and in none of [33]-[36]; [38], [39] the lanes per row (1, 2, 4, 8 or
+ * 16, sixteen entries per lane) of the last tsem_rowstats's row-statistics and column-signature kernels — from the mean row length,
+ * and from the row-length histogram (the smallest group that takes 99.5 % of the rows in one step) —, 0 before one ran. */
+#define TSEM_LAYOUT_INFO_N 40
 int  tsem_layout_info_n(tsem_ctx* h, int64_t* info, int32_t n);
 /* per-block shader-clock stamps of team 0 / member 0 of the fused kernel (option "fused_prof") */
 int  tsem_debug_fused_prof(tsem_ctx* h, uint64_t* out512);

@@ -701,12 +701,13 @@ class Engine(object):
         return out[:n]
 
     def layout_info(self):
-        info = np.zeros(38, np.int64)
+        info = np.zeros(40, np.int64)
         self._ck(self._L.tsem_layout_info_n(self._h, ptr(info), info.size))
         return dict(zip(('P', 'Kp', 'R', 'nb', 'N_amb', 'N_uni', 'nnz_amb', 'nnz_pad', 'twin_cols',
                          'G1', 'G2', 'fused', 'slow_path', 'max_subblock', 'value_bytes', 'hot_cols',
                          'lds_bytes', 'row_order', 'geometry', 'fallbacks', 'bin_repeats', 'reproducible', 'exact_single', 'lnl_fused', 'split', 'single_part_rows', 'row_pass_em', 'lnl_tables', 'lnl_linear', 'lnl_mid_entries', 'lnl_mid_limit', 'near_tie_rows', 'index_bytes',
-                         'cell_em_wave', 'cell_em_256', 'cell_em_512', 'cell_em_global', 'cell_em_spread'), info.tolist()))
+                         'cell_em_wave', 'cell_em_256', 'cell_em_512', 'cell_em_global', 'cell_em_spread',
+                         'rowstats_lanes', 'colsig_lanes'), info.tolist()))
 
 
 def legacy_randint(counts):

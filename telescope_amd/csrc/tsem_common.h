@@ -108,6 +108,7 @@ struct tsem_ctx {
   int64_t opt_report_kernel = 1;           // the report passes run the streaming kernels (0: the generic k_rowpass)
   int64_t opt_report_dbg = 0;              // the final z's report kernel: 8 k_report_rows, 128 / 256 k_report_pack32 with 8 / 16 entries per lane
   unsigned long long len_gt[6] = {0, 0, 0, 0, 0, 0};   // rows with more than 8, 16, 32, 64, 128, 256 entries (tsem_rowstats)
+  int rowstats_G = 0, colsig_G = 0;        // lanes per row of the last k_rowstats / k_colsig (0: not launched; tsem_layout_info_n [38], [39])
   int64_t opt_shortcuts = 1;               // tsem_reassign answers `all`(initial) and `unique` from the setup counts
   int32_t* d_twin_rep = nullptr;  // [K] representative column of each exact-twin class
   std::vector<uint64_t> col_count;  // global entries per column

@@ -713,6 +713,7 @@ int tsem_layout_info_n(tsem_ctx* h, int64_t* out, int32_t n) {
   info[32] = h->idx24 ? 3 : 4;                             // bytes of index per stored entry (3: the packed index of tsem_idx24.h)
   for (int k = 0; k < 4; ++k) info[33 + k] = h->ce_class_n[k];   // cells per class of the last tsem_cell_em (tsem_cellem.hip; 0 before a fit)
   info[37] = h->ce_spread_n;                               // ... and the groups it spread over the grid (in none of the four)
+  info[38] = h->rowstats_G; info[39] = h->colsig_G;        // lanes per row of the last k_rowstats / k_colsig (tsem_rowstats; 0: none launched)
   info[0] = h->P; info[1] = h->Kp; info[2] = h->R; info[3] = h->nb;
   info[4] = h->N_amb; info[5] = h->N_uni; info[6] = h->nnz_amb; info[7] = h->nnz_pad;
   info[8] = h->n_twin_cols; info[9] = h->G1; info[10] = h->G2; info[11] = h->use_fused ? 1 : 0;

@@ -14,6 +14,13 @@
 // fp64 atomics this replaced made pi differ in the last bit from run to run): Q is cut into pieces on PIS_LEVELS fixed grids
 // 26 bits apart, from the largest score-table value down past the last mantissa bit of the smallest; a level's sum of up to
 // 2^26 pieces is exact in fp64, k_pisum_finish adds the levels in a fixed order.  A 53-bit Q has pieces on 3-4 levels.
+// The range of that: with the table's last entry in [2^(e-1), 2^e) the grids reach down to multiples of 2^(e - 9 * 26), and a Q in
+// [2^f, 2^(f+1)) has its last mantissa bit at 2^(f-52): nothing is left after the last level while (e - 1) - f <= 9 * 26 - 53 = 181,
+// which every table with largest / smallest positive entry below 2^181 meets (the reference's tables span 2^145 to 2^154).  What IS
+// left of a Q — a table that spans more, a level below the normal range (e < -840), no levels at all where the rounding constant
+// of the top level would overflow (e > 997, pis_e0 < 0) — goes to a tenth array with an ordinary fp64 atomic and is added first:
+// nothing is dropped, pisum0[j] is within (n_j + PIS_LEVELS) 2^-53 of the exact sum (n_j unique rows, every |remainder| <= its Q),
+// and 0 only where the exact sum is 0; but the order of those atomics shows in the last bits: order-independence ends there.
 constexpr int PIS_LEVELS = 9, PIS_W = 26;
 // G lanes per row, sixteen consecutive scores per lane (two 16-byte loads), G from the mean row length: the round-2 shape
 // (16 lanes per row, one 2-byte load per lane and step) read the scores at 1 TB/s: 3.8 ms at 2e9 entries.
@@ -23,7 +30,7 @@ __global__ __launch_bounds__(256) void k_rowstats(int64_t N, const int64_t* __re
     const int32_t* __restrict__ indices, const uint16_t* __restrict__ raw,
     const double* __restrict__ lut, uint16_t* __restrict__ row_code, uint8_t* __restrict__ row_class,
     double* __restrict__ wsum_part /* [grid][2] */, uint32_t* __restrict__ maxcode,
-    double* __restrict__ pis_lv /* [PIS_LEVELS][K] */, int pis_e0 /* biased exponent of a power of two above every Q */,
+    double* __restrict__ pis_lv /* [PIS_LEVELS + 1][K], the last: remainders */, int pis_e0 /* biased exponent of a power of two above every Q; < 0: no levels */,
     uint32_t* __restrict__ ucount /* [K] unique rows with a positive score per column; [K] = 1 if any stored score is 0 */,
     int K, unsigned long long* __restrict__ len_gt /* [6] rows longer than 8, 16, 32, 64, 128, 256 entries */) {
   __shared__ double scratch[16];
@@ -67,12 +74,13 @@ __global__ __launch_bounds__(256) void k_rowstats(int64_t N, const int64_t* __re
         const int col = indices[s];
         for (int lv = 0; lv < PIS_LEVELS && r != 0.0; ++lv) {
           const int eb = pis_e0 - PIS_W * lv;               // pieces of this level: |piece| <= 2^(eb-1023), multiples of 2^(eb-1023-PIS_W)
-          if (eb + 52 - PIS_W < 1) break;                   // (below the normal range: nothing of a finite score table gets here)
+          if (eb + 52 - PIS_W < 1) break;                   // (below the normal range, or no levels: the rest of Q is added below)
           const double mm = __hiloint2double((int)(((uint32_t)(eb + 52 - PIS_W) << 20) | 0x80000u), 0);
           const double piece = (r + mm) - mm;
           if (piece != 0.0) unsafeAtomicAdd(&pis_lv[(size_t)lv * K + col], piece);
           r -= piece;
         }
+        if (r != 0.0) unsafeAtomicAdd(&pis_lv[(size_t)PIS_LEVELS * K + col], r);   // (a table past the levels' range: see PIS_LEVELS)
         if (raw[s]) atomicAdd(&ucount[col], 1u);
       }
     }
@@ -933,7 +941,7 @@ int tsem_choose_geometry(tsem_ctx* h) {
 __global__ void k_pisum_finish(int K, const double* __restrict__ lv, double* __restrict__ pisum0) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= K) return;
-  double t = 0.0;
+  double t = lv[(size_t)PIS_LEVELS * K + j];               // what the levels left over (0 for a table inside their range)
   for (int l = PIS_LEVELS - 1; l >= 0; --l) t += lv[(size_t)l * K + j];   // small to large
   pisum0[j] = t;
 }
@@ -956,11 +964,13 @@ int tsem_rowstats(tsem_ctx* h, double* stats3, double* pisum0, uint64_t* col_cou
   TSEM_ALLOC(h->d_pisum0, K);
   TSEM_ALLOC(h->d_ucount, K + 1);
   TSEM_HIP(hipMemsetAsync(h->d_ucount, 0, sizeof(uint32_t) * (K + 1), h->stream));
-  TSEM_TMP(t_pis, sizeof(double) * PIS_LEVELS * K);
+  TSEM_TMP(t_pis, sizeof(double) * (PIS_LEVELS + 1) * K);
   double* const d_pis_lv = t_pis.as<double>();
-  TSEM_HIP(hipMemsetAsync(d_pis_lv, 0, sizeof(double) * PIS_LEVELS * K, h->stream));
+  TSEM_HIP(hipMemsetAsync(d_pis_lv, 0, sizeof(double) * (PIS_LEVELS + 1) * K, h->stream));
   int pis_e2 = 0;
-  (void)std::frexp(h->lut_host[h->lut_len - 1] > 0 ? h->lut_host[h->lut_len - 1] : 1.0, &pis_e2);   // Q < 2^e2 (the table is increasing)
+  (void)std::frexp(h->lut_host[h->lut_len - 1] > 0 ? h->lut_host[h->lut_len - 1] : 1.0, &pis_e2);   // Q < 2^e2 (the table is non-decreasing)
+  // (the top level rounds with 1.5 x 2^(e2 + 26): past the largest exponent there are no levels, every Q is added as a remainder)
+  const int pis_e0 = pis_e2 + 1023 + 52 - PIS_W <= 2046 ? pis_e2 + 1023 : -1024;
   TSEM_HIP(hipMemsetAsync(h->d_maxcode, 0, 4, h->stream));
   TSEM_HIP(hipMemsetAsync(d_wpart, 0, sizeof(double) * 2 * grid, h->stream));
   TSEM_TMP(t_lg, 64);
@@ -972,7 +982,8 @@ int tsem_rowstats(tsem_ctx* h, double* stats3, double* pisum0, uint64_t* col_cou
     const int G = mean_len * 1.5 <= 16 ? 1 : mean_len * 1.5 <= 32 ? 2 : mean_len * 1.5 <= 64 ? 4 : mean_len * 1.5 <= 128 ? 8 : 16;
     auto rk = G == 1 ? k_rowstats<1> : G == 2 ? k_rowstats<2> : G == 4 ? k_rowstats<4> : G == 8 ? k_rowstats<8> : k_rowstats<16>;
     rk<<<grid, 256, 0, h->stream>>>(N, h->d_indptr, h->d_indices, h->d_raw, h->d_lut, d_code, d_cls,
-                                    d_wpart, h->d_maxcode, d_pis_lv, pis_e2 + 1023, h->d_ucount, K, d_lg);
+                                    d_wpart, h->d_maxcode, d_pis_lv, pis_e0, h->d_ucount, K, d_lg);
+    h->rowstats_G = G;
   }
   k_pisum_finish<<<cdiv64(K, 256), 256, 0, h->stream>>>(K, d_pis_lv, h->d_pisum0);
   TSEM_HIP(hipGetLastError());
@@ -1018,6 +1029,7 @@ int tsem_rowstats(tsem_ctx* h, double* stats3, double* pisum0, uint64_t* col_cou
       int g2 = (int)std::min<int64_t>(h->n_cu, std::max<int64_t>(1, (N + 63) / 64));
       for (int base = 0; base < K; base += SIG_WIN)
         ck<<<g2, 1024, lds, h->stream>>>(N, h->row_offset, h->d_indptr, h->d_indices, h->d_raw, base, K, d_cnt, d_hash);
+      h->colsig_G = cap / 16;
       TSEM_HIP(hipGetLastError());
     }
     TSEM_HIP(hipMemcpyAsync(col_count, d_cnt, sizeof(uint64_t) * K, hipMemcpyDeviceToHost, h->stream));

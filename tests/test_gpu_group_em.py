@@ -132,7 +132,7 @@ def test_option_and_layout_info(gpu_device):
     from telescope_amd import _lib
     eng = _lib.Engine(gpu_device)
     info = eng.layout_info()
-    assert list(info)[-5:] == list(CLASS_NAMES) + ['cell_em_spread'] and len(info) == 38 and info['cell_em_spread'] == 0
+    assert list(info)[33:38] == list(CLASS_NAMES) + ['cell_em_spread'] and len(info) == 40 and info['cell_em_spread'] == 0
     eng.set_option('cell_em_spread_entries', 0)
     eng.set_option('cell_em_spread_entries', 1 << 40)
     with pytest.raises(_lib.EngineError):

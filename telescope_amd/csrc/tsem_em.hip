@@ -1037,12 +1037,7 @@ int tsem_fallback_twopass(tsem_ctx* h) {
   h->opt_dbg &= ~(int64_t)(32 | 64);
   if (int rc = tsem_choose_geometry(h)) return rc;
   if (int rc = tsem_build_layout(h)) return rc;
-  // the permuted pi*theta tables follow the new column map
-  TSEM_ALLOC(h->d_ctab, h->Kpad); TSEM_ALLOC(h->d_ctab_prev, h->Kpad);
-  TSEM_HIP(hipMemsetAsync(h->d_ctab, 0, sizeof(double) * h->Kpad, h->stream));
-  TSEM_HIP(hipMemsetAsync(h->d_ctab_prev, 0, sizeof(double) * h->Kpad, h->stream));
-  if (int rc = tsem_make_ctabs(h)) return rc;
-  TSEM_HIP(hipStreamSynchronize(h->stream));
+  if (int rc = tsem_make_ctabs(h)) return rc;                // the permuted pi*theta tables follow the new column map
   h->n_fallbacks += 1;
   fprintf(stderr, "libtelescope_em: the persistent EM kernel could not keep its workgroups co-resident (watchdog code %u); "
                   "continuing with the two-pass kernels\n", e);

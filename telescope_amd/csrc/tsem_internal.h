@@ -172,7 +172,7 @@ void tsem_free_matrix(tsem_ctx* h);
 int tsem_choose_geometry(tsem_ctx* h);
 int tsem_build_layout(tsem_ctx* h);
 int tsem_bin_reset(tsem_ctx* h);                           // option "reproducible": the slots' bounds as a run finds them
-int tsem_make_ctabs(tsem_ctx* h);                          // the permuted pi * theta tables (current and previous) from the parameters
+int tsem_make_ctabs(tsem_ctx* h);                          // after tsem_build_layout: the permuted pi * theta tables (current and previous), allocated and filled
 void tsem_report_preload(void);                            // the same for the report unit (build_layout, behind the fill)
 void tsem_setup_preload(void);                             // load the set-up unit's code object now (behind a kernel that is running anyway)
 int tsem_ensure_indices(tsem_ctx* h);                      // the CSR column ids, rebuilt from the popularity ids if option "drop_csr_indices" freed

@@ -830,105 +830,103 @@ static bool lnl3_possible(const tsem_ctx* h) {
 int tsem_choose_geometry(tsem_ctx* h) {
   const int K = h->K;
   const int64_t na = h->N_amb, nu = h->N_uni;
-  {
-    // column parts (tables of one part must fit LDS) and rows per block
-    // option "reproducible" = 1: both pieces of the exact sums in ONE pass if three tables per part fit the LDS with at most 8
-    // parts (score codes; 26 B of LDS per column); else — or with "reproducible" = 2 — two passes over two tables
-    h->exact_single = false;
-    if (h->opt_reproducible == 1 && h->em_kernel != TSEM_EMK_TWOPASS && h->opt_format != 1 && h->lut_len > 0 && h->lut_len <= 2048) {
-      const int p3 = h->opt_P > 0 ? (int)h->opt_P : (K + TS_MAX_KP3 - 64 - 1) / (TS_MAX_KP3 - 64);
-      // teams of 5-8 have ONE geometry (384 row slots): worth it only when the rows are long enough to fill their register
-      // tiles (20M x 30k: 100 per row 9.4 -> 6.3 ms per iteration, 18 per row 2.4 -> 3.3; K = 15k, teams of 4: 3.9 -> 2.6 at
-      // 40 per row, 1.9 -> 1.4 at 18; profiles/r03_reproducible.txt)
-      const double ml = na > 0 ? (double)(h->nnz - nu) / (double)na : 0.0;
-      // (one pass costs ~1.25 default passes on a full tile, two passes cost 2: worth it down to tiles ~2/3 full — K = 30k, 40 per
-      //  row, teams of 7: 3.58 against 3.79 ms per iteration)
-      const bool long_enough = p3 <= 4 || h->opt_P > 0 || ml * fz_rmax(2) >= 0.62 * 1.05 * fz_cap(1) * p3;
-      if (p3 >= 1 && p3 <= FZ_MAX_P && (K + p3 - 1) / p3 + 64 <= TS_MAX_KP3 && long_enough) h->exact_single = true;
-    }
-    // option "use_likelihood": three tables per part too (pi*theta of the current and of the previous parameters, the accumulators) —
-    // score codes only (fp64 entries leave the log1p no registers), not together with the exact sums (four tables)
-    h->lnl3 = h->opt_lnl_fused && lnl3_possible(h);
-    const int max_kp = h->exact_single ? TS_MAX_KP3 - 64 : (h->lnl3 ? TS_MAX_KP_LNL - 64 : TS_MAX_KP);
-    int P = h->opt_P > 0 ? (int)h->opt_P : (K + max_kp - 1) / max_kp;
-    if (P < 1) P = 1;
-    // SPLIT layout (round 4): more columns than 8 parts of 7680 hold.  A part's pi*theta table and its accumulators then live in LDS
-    // one at a time — a row-sum pass and a scatter pass per iteration, every entry read twice — with parts of up to 15 360 columns:
-    // K <= 122 880 stays on the fused kernel (the two-pass kernels beyond; they took 7x the time per entry at K = 100k).  Teams of
-    // 5-8 only (the instantiations that exist); option "split" = 1 forces it on a smaller matrix (tests), 0 forbids it.
-    constexpr int SPLIT_MAX_KP = 2 * TS_MAX_KP;
-    h->split = false;
-    if (h->em_kernel != TSEM_EMK_TWOPASS && !h->opt_reproducible && h->opt_precision == 0 && na > 0 && h->opt_split != 0) {
-      const int p2 = std::max(5, (K + SPLIT_MAX_KP - 1) / SPLIT_MAX_KP);       // (a part that needs every slot has no spare ones for hot columns)
-      if (h->opt_P > 0) {
-        const int kp = (K + P - 1) / P;
-        h->split = P >= 5 && P <= FZ_MAX_P && ((kp > TS_MAX_KP && kp <= SPLIT_MAX_KP) || h->opt_split == 1);
-      } else if ((P > FZ_MAX_P || h->opt_split == 1) && p2 <= FZ_MAX_P) {
-        P = std::max(p2, std::min(P, FZ_MAX_P));
-        h->split = true;
-      }
-      if (h->split) { h->lnl3 = false; h->exact_single = false; }
-    }
-    if (h->opt_P <= 0 && h->em_kernel != TSEM_EMK_TWOPASS && P < FZ_MAX_P && na > 0) {
-      // Teams never span XCDs, so floor(cpx / P) * P of an XCD's cpx CUs work: 28 of 32 for teams of 7.
-      // One more member per team is worth it when it puts >= 10 % more CUs to work and the rows are
-      // long enough to fill the register tiles of the larger team (measured: K = 50k, 100 nnz/row,
-      // P 7 -> 8: fp64 5.80 -> 5.48 ms, codes 4.82 -> 4.28 ms; K = 38k, 40 nnz/row is better off at P = 5).
-      const int cpx = std::max(1, h->n_cu / 8);
-      auto util = [&](int p) { return (double)(cpx / p * p) / cpx; };
-      const double mean_len = (double)(h->nnz - nu) / (double)na;
-      for (int p2 = P + 1; p2 <= FZ_MAX_P; ++p2)
-        if (util(p2) >= util(P) + 0.10 && mean_len * fz_rmax(2) >= 1.05 * fz_cap(1) * p2) { P = p2; break; }
-    }
-    // more than 64 column parts (K > 491 520): no blocked layout — the reference takes any number of loci (model.py:643), so the
-    // EM pass and the log-likelihood fall back to plain CSR row passes (global gathers of pi*theta, fp64 atomics on the column
-    // sums: k_em_rows / k_lnl_rows_amb).  The column map is the identity cut into virtual parts, which is all k_update needs.
-    h->em_rows = P > 64 && h->opt_P <= 0;
-    if (P > 64 && !h->em_rows) TSEM_FAIL(TSEM_ERR_ARG, "more than 64 column parts (K > 491520) is not supported");
-    if (h->em_rows) { h->split = false; h->lnl3 = false; h->exact_single = false; }
-    if (h->em_rows && h->opt_reproducible) TSEM_FAIL(TSEM_ERR_ARG, "reproducible mode needs the fused kernel (K <= 61440)");
-    int Kp = h->em_rows ? TS_MAX_KP : (K + P - 1) / P;
-    if (Kp > (h->split ? SPLIT_MAX_KP : TS_MAX_KP)) TSEM_FAIL(TSEM_ERR_ARG, "parts option leaves more than 7680 columns per part");
-    // spare accumulator slots per part for very popular columns (build_layout splits them)
-    h->hot_extra = (h->opt_hot_split && !h->em_rows) ? std::min(64, (h->split ? SPLIT_MAX_KP : (h->exact_single ? TS_MAX_KP3 : (h->lnl3 ? TS_MAX_KP_LNL : TS_MAX_KP))) - Kp) : 0;
-    Kp += h->hot_extra;
-    h->P = P; h->Kp = Kp; h->Kpad = P * Kp;
-    h->use_fused = (h->em_kernel != TSEM_EMK_TWOPASS) && P <= FZ_MAX_P && !h->em_rows;   // AUTO: fused when the layout allows it
-    int R = 2048;
-    h->geo = P > 4 ? 1 : 0;
-    h->run_len_est = na > 0 ? (double)(h->nnz - nu) / (double)na / P : 0.0;   // entries per ambiguous row and part
-    if (h->use_fused && na > 0) {
-      // size blocks so a member's sub-block (~R*len/P entries) fills ~85 % of its register tile
-      double mean_len = (double)(h->nnz - nu) / (double)na;
-      // row SLOTS per block: ~7 % above the average a register tile takes, so blocks end on the
-      // tile's capacity, not on R (the exchange cost depends on R, hence not more than needed)
-      // geometry: teams of 5-8 have one; smaller teams switch to three exchange waves when the rows
-      // are so short that 512 row slots cannot fill the register tile and the pass is bound by the
-      // exchange (fp64 entries; with score codes the 14th data wave is worth more)
-      // (profiles/r02_sweep_short.txt, 50M rows, both entry formats: the third exchange wave pays once the tile
-      // needs more than ~1.25x the 512 row slots of geometry 0 — 20 entries per row: codes 2.21 -> 1.98 ms, fp64
-      // 2.63 -> 2.57; 28 per row: codes 2.55 -> 2.66, fp64 equal)
-      // teams of 5-8 (round 3): 768 row slots (geometry 2: two row pairs per exchange lane, (P - 1) x 2 partner values in its
-      // registers: 118-124 VGPRs, no spill) when 384 cannot fill the register tiles
-      h->geo = P > 4 ? ((1.07 * fz_cap(1) * P / std::max(2.0, mean_len) > 1.25 * fz_rmax(1)) ? 2 : 1)
-                     : ((1.07 * fz_cap(0) * P / std::max(2.0, mean_len) > 1.25 * fz_rmax(0)) ? 2 : 0);
-      // rows so short that 768 of them cannot fill the tile either: geometry 3 (32 B of LDS per row slot instead of 48)
-      // (profiles/r03_sweep_short.txt: 8 / 10 / 12 entries per row 1.27 / 1.31 / 1.39 -> 1.18 / 1.23 / 1.34 ms, 14 equal, 16 and more slower:
-      //  the exchange of a step grows with its row slots)
-      if (P <= 4 && h->geo == 2 && !h->lnl3 && 1.07 * fz_cap(2) * P / std::max(2.0, mean_len) > 1.4 * fz_rmax(2)) h->geo = 3;   // (MODE 4 has no geometry 3: registers)
-      if (h->opt_geo >= 0 && P <= 4) h->geo = (h->opt_geo == 2 || (h->opt_geo == 3 && !h->lnl3)) ? (int)h->opt_geo : 0;
-      if (h->opt_geo >= 0 && P > 4) h->geo = h->opt_geo == 2 ? 2 : 1;
-      double r = 1.07 * fz_cap(h->geo) * P / std::max(2.0, mean_len);
-      const int lut_bytes = (h->lut_len > 0 && h->lut_len <= 2048) ? h->lut_len * 8 : 0;   // the score table shares LDS with the rings
-      int rmax = std::min(fz_rmax(h->geo), (TS_LDS_MAX - 2560 - (h->split ? Kp + 2 : ((h->exact_single || h->lnl3) ? 3 : 2) * Kp) * 8 - lut_bytes - std::max(h->opt_reproducible ? Kp * 2 + 16 : 0, FZ_LOGTAB * 16 + 16)) / ((fz_yr(h->geo) + (h->lnl3 ? 4 : 2)) * 8));
-      rmax = std::min(rmax, FILL_MAX_RP / P);                // (k_sb_fill_sorted keeps R x P counters in LDS)
-      R = (int)std::min<double>(r, rmax);
-      R = std::max(64, (R + 63) / 64 * 64);
-      R = std::min(R, rmax / 8 * 8);
-    }
-    if (h->opt_R > 0) R = (int)h->opt_R;
-    h->R = R;
+  // column parts (tables of one part must fit LDS) and rows per block
+  // option "reproducible" = 1: both pieces of the exact sums in ONE pass if three tables per part fit the LDS with at most 8
+  // parts (score codes; 26 B of LDS per column); else — or with "reproducible" = 2 — two passes over two tables
+  h->exact_single = false;
+  if (h->opt_reproducible == 1 && h->em_kernel != TSEM_EMK_TWOPASS && h->opt_format != 1 && h->lut_len > 0 && h->lut_len <= 2048) {
+    const int p3 = h->opt_P > 0 ? (int)h->opt_P : (K + TS_MAX_KP3 - 64 - 1) / (TS_MAX_KP3 - 64);
+    // teams of 5-8 have ONE geometry (384 row slots): worth it only when the rows are long enough to fill their register
+    // tiles (20M x 30k: 100 per row 9.4 -> 6.3 ms per iteration, 18 per row 2.4 -> 3.3; K = 15k, teams of 4: 3.9 -> 2.6 at
+    // 40 per row, 1.9 -> 1.4 at 18; profiles/r03_reproducible.txt)
+    const double ml = na > 0 ? (double)(h->nnz - nu) / (double)na : 0.0;
+    // (one pass costs ~1.25 default passes on a full tile, two passes cost 2: worth it down to tiles ~2/3 full — K = 30k, 40 per
+    //  row, teams of 7: 3.58 against 3.79 ms per iteration)
+    const bool long_enough = p3 <= 4 || h->opt_P > 0 || ml * fz_rmax(2) >= 0.62 * 1.05 * fz_cap(1) * p3;
+    if (p3 >= 1 && p3 <= FZ_MAX_P && (K + p3 - 1) / p3 + 64 <= TS_MAX_KP3 && long_enough) h->exact_single = true;
   }
+  // option "use_likelihood": three tables per part too (pi*theta of the current and of the previous parameters, the accumulators) —
+  // score codes only (fp64 entries leave the log1p no registers), not together with the exact sums (four tables)
+  h->lnl3 = h->opt_lnl_fused && lnl3_possible(h);
+  const int max_kp = h->exact_single ? TS_MAX_KP3 - 64 : (h->lnl3 ? TS_MAX_KP_LNL - 64 : TS_MAX_KP);
+  int P = h->opt_P > 0 ? (int)h->opt_P : (K + max_kp - 1) / max_kp;
+  if (P < 1) P = 1;
+  // SPLIT layout (round 4): more columns than 8 parts of 7680 hold.  A part's pi*theta table and its accumulators then live in LDS
+  // one at a time — a row-sum pass and a scatter pass per iteration, every entry read twice — with parts of up to 15 360 columns:
+  // K <= 122 880 stays on the fused kernel (the two-pass kernels beyond; they took 7x the time per entry at K = 100k).  Teams of
+  // 5-8 only (the instantiations that exist); option "split" = 1 forces it on a smaller matrix (tests), 0 forbids it.
+  constexpr int SPLIT_MAX_KP = 2 * TS_MAX_KP;
+  h->split = false;
+  if (h->em_kernel != TSEM_EMK_TWOPASS && !h->opt_reproducible && h->opt_precision == 0 && na > 0 && h->opt_split != 0) {
+    const int p2 = std::max(5, (K + SPLIT_MAX_KP - 1) / SPLIT_MAX_KP);       // (a part that needs every slot has no spare ones for hot columns)
+    if (h->opt_P > 0) {
+      const int kp = (K + P - 1) / P;
+      h->split = P >= 5 && P <= FZ_MAX_P && ((kp > TS_MAX_KP && kp <= SPLIT_MAX_KP) || h->opt_split == 1);
+    } else if ((P > FZ_MAX_P || h->opt_split == 1) && p2 <= FZ_MAX_P) {
+      P = std::max(p2, std::min(P, FZ_MAX_P));
+      h->split = true;
+    }
+    if (h->split) { h->lnl3 = false; h->exact_single = false; }
+  }
+  if (h->opt_P <= 0 && h->em_kernel != TSEM_EMK_TWOPASS && P < FZ_MAX_P && na > 0) {
+    // Teams never span XCDs, so floor(cpx / P) * P of an XCD's cpx CUs work: 28 of 32 for teams of 7.
+    // One more member per team is worth it when it puts >= 10 % more CUs to work and the rows are
+    // long enough to fill the register tiles of the larger team (measured: K = 50k, 100 nnz/row,
+    // P 7 -> 8: fp64 5.80 -> 5.48 ms, codes 4.82 -> 4.28 ms; K = 38k, 40 nnz/row is better off at P = 5).
+    const int cpx = std::max(1, h->n_cu / 8);
+    auto util = [&](int p) { return (double)(cpx / p * p) / cpx; };
+    const double mean_len = (double)(h->nnz - nu) / (double)na;
+    for (int p2 = P + 1; p2 <= FZ_MAX_P; ++p2)
+      if (util(p2) >= util(P) + 0.10 && mean_len * fz_rmax(2) >= 1.05 * fz_cap(1) * p2) { P = p2; break; }
+  }
+  // more than 64 column parts (K > 491 520): no blocked layout — the reference takes any number of loci (model.py:643), so the
+  // EM pass and the log-likelihood fall back to plain CSR row passes (global gathers of pi*theta, fp64 atomics on the column
+  // sums: k_em_rows / k_lnl_rows_amb).  The column map is the identity cut into virtual parts, which is all k_update needs.
+  h->em_rows = P > 64 && h->opt_P <= 0;
+  if (P > 64 && !h->em_rows) TSEM_FAIL(TSEM_ERR_ARG, "more than 64 column parts (K > 491520) is not supported");
+  if (h->em_rows) { h->split = false; h->lnl3 = false; h->exact_single = false; }
+  if (h->em_rows && h->opt_reproducible) TSEM_FAIL(TSEM_ERR_ARG, "reproducible mode needs the fused kernel (K <= 61440)");
+  int Kp = h->em_rows ? TS_MAX_KP : (K + P - 1) / P;
+  if (Kp > (h->split ? SPLIT_MAX_KP : TS_MAX_KP)) TSEM_FAIL(TSEM_ERR_ARG, "parts option leaves more than 7680 columns per part");
+  // spare accumulator slots per part for very popular columns (build_layout splits them)
+  h->hot_extra = (h->opt_hot_split && !h->em_rows) ? std::min(64, (h->split ? SPLIT_MAX_KP : (h->exact_single ? TS_MAX_KP3 : (h->lnl3 ? TS_MAX_KP_LNL : TS_MAX_KP))) - Kp) : 0;
+  Kp += h->hot_extra;
+  h->P = P; h->Kp = Kp; h->Kpad = P * Kp;
+  h->use_fused = (h->em_kernel != TSEM_EMK_TWOPASS) && P <= FZ_MAX_P && !h->em_rows;   // AUTO: fused when the layout allows it
+  int R = 2048;
+  h->geo = P > 4 ? 1 : 0;
+  h->run_len_est = na > 0 ? (double)(h->nnz - nu) / (double)na / P : 0.0;   // entries per ambiguous row and part
+  if (h->use_fused && na > 0) {
+    // size blocks so a member's sub-block (~R*len/P entries) fills ~85 % of its register tile
+    double mean_len = (double)(h->nnz - nu) / (double)na;
+    // row SLOTS per block: ~7 % above the average a register tile takes, so blocks end on the
+    // tile's capacity, not on R (the exchange cost depends on R, hence not more than needed)
+    // geometry: teams of 5-8 have one; smaller teams switch to three exchange waves when the rows
+    // are so short that 512 row slots cannot fill the register tile and the pass is bound by the
+    // exchange (fp64 entries; with score codes the 14th data wave is worth more)
+    // (profiles/r02_sweep_short.txt, 50M rows, both entry formats: the third exchange wave pays once the tile
+    // needs more than ~1.25x the 512 row slots of geometry 0 — 20 entries per row: codes 2.21 -> 1.98 ms, fp64
+    // 2.63 -> 2.57; 28 per row: codes 2.55 -> 2.66, fp64 equal)
+    // teams of 5-8 (round 3): 768 row slots (geometry 2: two row pairs per exchange lane, (P - 1) x 2 partner values in its
+    // registers: 118-124 VGPRs, no spill) when 384 cannot fill the register tiles
+    h->geo = P > 4 ? ((1.07 * fz_cap(1) * P / std::max(2.0, mean_len) > 1.25 * fz_rmax(1)) ? 2 : 1)
+                   : ((1.07 * fz_cap(0) * P / std::max(2.0, mean_len) > 1.25 * fz_rmax(0)) ? 2 : 0);
+    // rows so short that 768 of them cannot fill the tile either: geometry 3 (32 B of LDS per row slot instead of 48)
+    // (profiles/r03_sweep_short.txt: 8 / 10 / 12 entries per row 1.27 / 1.31 / 1.39 -> 1.18 / 1.23 / 1.34 ms, 14 equal, 16 and more slower:
+    //  the exchange of a step grows with its row slots)
+    if (P <= 4 && h->geo == 2 && !h->lnl3 && 1.07 * fz_cap(2) * P / std::max(2.0, mean_len) > 1.4 * fz_rmax(2)) h->geo = 3;   // (MODE 4 has no geometry 3: registers)
+    if (h->opt_geo >= 0 && P <= 4) h->geo = (h->opt_geo == 2 || (h->opt_geo == 3 && !h->lnl3)) ? (int)h->opt_geo : 0;
+    if (h->opt_geo >= 0 && P > 4) h->geo = h->opt_geo == 2 ? 2 : 1;
+    double r = 1.07 * fz_cap(h->geo) * P / std::max(2.0, mean_len);
+    const int lut_bytes = (h->lut_len > 0 && h->lut_len <= 2048) ? h->lut_len * 8 : 0;   // the score table shares LDS with the rings
+    int rmax = std::min(fz_rmax(h->geo), (TS_LDS_MAX - 2560 - (h->split ? Kp + 2 : ((h->exact_single || h->lnl3) ? 3 : 2) * Kp) * 8 - lut_bytes - std::max(h->opt_reproducible ? Kp * 2 + 16 : 0, FZ_LOGTAB * 16 + 16)) / ((fz_yr(h->geo) + (h->lnl3 ? 4 : 2)) * 8));
+    rmax = std::min(rmax, FILL_MAX_RP / P);                // (k_sb_fill_sorted keeps R x P counters in LDS)
+    R = (int)std::min<double>(r, rmax);
+    R = std::max(64, (R + 63) / 64 * 64);
+    R = std::min(R, rmax / 8 * 8);
+  }
+  if (h->opt_R > 0) R = (int)h->opt_R;
+  h->R = R;
   if (h->R > 65536 || h->R < 64) TSEM_FAIL(TSEM_ERR_ARG, "block_rows must be in [64, 65536]");
   h->nb = (na + h->R - 1) / h->R;
   h->N_amb_pad = std::max<int64_t>(1, h->nb) * h->R;
@@ -1116,35 +1114,56 @@ static void radix_sort_pairs(std::vector<uint64_t>& key, std::vector<int>& idx) 
 // ---------------------------------------------------------------------------
 // layout: column partition by popularity, blocked COO of ambiguous rows
 // ---------------------------------------------------------------------------
-int tsem_build_layout(tsem_ctx* h) {
-  PhaseTimer pt(h->stream);
+// What the steps of tsem_build_layout hand on (the row blocks and the padded total are h->nb and h->nnz_pad).  Its device temporaries go when
+// the build returns, not with the step that made them: hipFree waits for the device.  A step's own end where it has just synchronised.
+struct LayoutBuild {
+  PhaseTimer pt;
+  std::vector<uint32_t> colmap;                            // the host's copy of d_colmap (the fill's table of split columns)
+  int64_t* d_bs = nullptr;                                 // first compact row of every block, [nb + 1]
+  unsigned long long* d_pc = nullptr;                      // per-row part counts (fused layout only)
+  bool rid_amb_done = false;                               // k_row_partcounts has written the popularity ids of the ambiguous rows
+  DevScope<int64_t> own_bs{d_bs}; DevScope<unsigned long long> own_pc{d_pc};
+  explicit LayoutBuild(hipStream_t s) : pt(s) {}
+};
+
+// exclusive scan of n int64 on the stream; `scratch` (rocprim's temporary storage) is the caller's, to keep until the stream is synchronised
+static int scan_i64(tsem_ctx* h, int64_t* in, int64_t* out, size_t n, DevTmp& scratch) {
+  size_t tb = 0;
+  TSEM_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), h->stream));
+  TSEM_TMP(scratch, tb);
+  TSEM_HIP(rocprim::exclusive_scan(scratch.p, tb, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), h->stream));
+  return TSEM_OK;
+}
+// the large dynamic LDS for one kernel; a kernel that does not exist fails with `missing` where the caller has a text for it
+static int allow_large_lds(tsem_ctx* h, const void* f, const char* missing = nullptr) {
+  if (!f && missing) TSEM_FAIL(TSEM_ERR_ARG, missing);
+  TSEM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+  return TSEM_OK;
+}
+
+// more than 64 column parts: no blocked layout, the identity column map in virtual parts of Kp columns: pc == column (k_update /
+// k_make_ctab / k_colreduce index conventions hold)
+static int layout_identity_map(tsem_ctx* h) {
   const int K = h->K;
-  const int64_t na = h->N_amb;
-  CsrIds ids(h); ids.keep();                               // (the popularity ids go with the old layout: the fill below drops the column ids once it has made the new ones)
-  if (int rc = ids.acquire()) return rc;                   // (a rebuild after option "drop_csr_indices": from the ids of the layout about to go)
-  TSEM_HIP(hipStreamSynchronize(h->stream));
-  tsem_free_layout(h);
-  h->nnz_amb = 0;
-  h->n_single_part = 0;
-  if (h->em_rows) {
-    // identity column map in virtual parts of Kp columns: pc == column (k_update / k_make_ctab / k_colreduce index conventions hold)
-    std::vector<uint32_t> cm((size_t)K);
-    std::vector<int32_t> cpc((size_t)h->Kpad, -1);
-    for (int j = 0; j < K; ++j) { cm[j] = ((uint32_t)(j / h->Kp) << CM_PS) | (uint32_t)(j % h->Kp); cpc[j] = j; }
-    TSEM_ALLOC(h->d_colmap, K);
-    TSEM_ALLOC(h->d_col_of_pc, h->Kpad);
-    TSEM_HIP(hipMemcpy(h->d_colmap, cm.data(), sizeof(uint32_t) * K, hipMemcpyHostToDevice));
-    TSEM_HIP(hipMemcpy(h->d_col_of_pc, cpc.data(), sizeof(int32_t) * h->Kpad, hipMemcpyHostToDevice));
-    h->nb = 0; h->N_amb_pad = 1; h->nnz_pad = 0; h->max_subblock = 0; h->n_hot_cols = 0;
-    h->nnz_amb = h->nnz - h->N_uni;
-    h->fmt_code = h->fmt_wcode = false; h->sorted_layout = false; h->idx24 = false;
-    h->G1 = h->G2 = 1;
-    return TSEM_OK;
-  }
-  // 1. column popularity: global entry counts handed in by set_model
+  std::vector<uint32_t> cm((size_t)K);
+  std::vector<int32_t> cpc((size_t)h->Kpad, -1);
+  for (int j = 0; j < K; ++j) { cm[j] = ((uint32_t)(j / h->Kp) << CM_PS) | (uint32_t)(j % h->Kp); cpc[j] = j; }
+  TSEM_ALLOC(h->d_colmap, K);
+  TSEM_ALLOC(h->d_col_of_pc, h->Kpad);
+  TSEM_HIP(hipMemcpy(h->d_colmap, cm.data(), sizeof(uint32_t) * K, hipMemcpyHostToDevice));
+  TSEM_HIP(hipMemcpy(h->d_col_of_pc, cpc.data(), sizeof(int32_t) * h->Kpad, hipMemcpyHostToDevice));
+  h->nb = 0; h->N_amb_pad = 1; h->nnz_pad = 0; h->max_subblock = 0; h->n_hot_cols = 0;
+  h->nnz_amb = h->nnz - h->N_uni;
+  h->fmt_code = h->fmt_wcode = false; h->sorted_layout = false; h->idx24 = false;
+  h->G1 = h->G2 = 1;
+  return TSEM_OK;
+}
+
+// 1. column popularity: global entry counts handed in by set_model
+// 2. parts: deal columns by popularity so every part carries ~equal nnz
+static int layout_column_map(tsem_ctx* h, LayoutBuild& b) {
+  const int K = h->K, P = h->P, Kp = h->Kp;
   const std::vector<uint64_t>& counts = h->col_count;
-  // 2. parts: deal columns by popularity so every part carries ~equal nnz
-  const int P = h->P, Kp = h->Kp;
   std::vector<int> order(K);
   std::iota(order.begin(), order.end(), 0);
   {                                                        // most popular first, equal counts by column index (a stable sort by count, descending)
@@ -1156,7 +1175,7 @@ int tsem_build_layout(tsem_ctx* h) {
   // part's entries would serialise the LDS scatter (64 f lanes of every ds_add_f64 on ONE address:
   // the hottest column of a Zipf-like matrix, or Telescope's `__no_feature`, reaches 8-way), so it
   // gets 2..16 consecutive slots; k_sb_fill deals its entries over them, k_colreduce adds them up.
-  std::vector<uint32_t> colmap(K);
+  b.colmap.assign(K, 0u);
   std::vector<int32_t> col_of_pc(h->Kpad, -1);
   // Columns go, most popular first, to the part that holds the fewest entries so far (and still has
   // a free slot): every member of a team then streams the same number of entries per row block, so
@@ -1181,14 +1200,14 @@ int tsem_build_layout(tsem_ctx* h) {
     while (lg < 4 && lanes / (1 << lg) > 1.5 && (2 << lg) - 1 <= spare[p]) ++lg;
     spare[p] -= (1 << lg) - 1;
     if (lg) h->n_hot_cols += 1;
-    colmap[j] = ((uint32_t)p << CM_PS) | ((uint32_t)lg << CM_LS) | (uint32_t)cursor[p];
+    b.colmap[j] = ((uint32_t)p << CM_PS) | ((uint32_t)lg << CM_LS) | (uint32_t)cursor[p];
     col_of_pc[p * Kp + cursor[p]] = j;                     // the first slot owns the column; the others stay -1
     cursor[p] += 1 << lg;
   }
-  pt.lap("layout: column map (host)");
+  b.pt.lap("layout: column map (host)");
   TSEM_ALLOC(h->d_colmap, K);
   TSEM_ALLOC(h->d_col_of_pc, h->Kpad);
-  TSEM_HIP(hipMemcpy(h->d_colmap, colmap.data(), sizeof(uint32_t) * K, hipMemcpyHostToDevice));
+  TSEM_HIP(hipMemcpy(h->d_colmap, b.colmap.data(), sizeof(uint32_t) * K, hipMemcpyHostToDevice));
   TSEM_HIP(hipMemcpy(h->d_col_of_pc, col_of_pc.data(), sizeof(int32_t) * h->Kpad, hipMemcpyHostToDevice));
   // popularity ids for the report pass (k_report_rows): id = slot * P + part, 2 bytes per stored entry
   const bool want_rid = h->Kpad <= 65536 && h->opt_report_kernel != 0 && h->nnz > 0;
@@ -1202,151 +1221,153 @@ int tsem_build_layout(tsem_ctx* h) {
     // the padding holds id 0: lanes past the LAST row's end index the pi*theta tables with what they find there (tsem_host.hip)
     TSEM_HIP(hipMemsetAsync(h->d_rid16 + h->nnz, 0, sizeof(uint16_t) * TS_ENTRY_PAD, h->stream));
   }
-  pt.lap("layout: maps to the device, rid16 alloc");
-  // 3. row blocks.  Two-pass layout: R rows each.  Fused layout: as many consecutive rows as the
-  //    register tile takes (no part may exceed FZ_CAP entries, at most R rows) — rows per block vary,
-  //    every block still owns R row SLOTS (holes at the end), so all kernels keep b*R+lr indexing.
-  const int R = h->R;
-  int64_t nb = 0;
-  int64_t* d_bs = nullptr;                                 // first compact row of every block, [nb + 1]
-  unsigned long long* d_pc = nullptr;                      // per-row part counts (fused layout only)
-  TSEM_SCOPED(d_bs); TSEM_SCOPED(d_pc);                    // (temporaries of this function: freed on every return path)
-  bool rid_amb_done = false;
-  if (h->use_fused && na > 0 && P <= FZ_MAX_P) {
-    TSEM_ALLOC(d_pc, 2 * na);
-    {
-      int capc = 256;                                      // lanes per row x 16 entries, from the row-length histogram
-      for (int q = 1; q < 6; ++q)
-        if ((double)h->len_gt[q] <= 0.005 * (double)h->N) { capc = 8 << q; break; }
-      const int G = capc <= 16 ? 1 : capc <= 32 ? 2 : capc <= 64 ? 4 : capc <= 128 ? 8 : 16;
-      if ((size_t)K * 4 <= (size_t)TS_LDS_MAX - 2048 && na >= 65536) {   // the column map fits LDS (K <= 40k) and the matrix is worth a 120 KB preload per CU
-        auto pk = G == 1 ? k_row_partcounts<1, true> : G == 2 ? k_row_partcounts<2, true> : G == 4 ? k_row_partcounts<4, true>
-                : G == 8 ? k_row_partcounts<8, true> : k_row_partcounts<16, true>;
-        TSEM_HIP(hipFuncSetAttribute((const void*)pk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
-        pk<<<h->n_cu, 1024, (size_t)K * 4, h->stream>>>(na, h->d_amb_row, h->d_indptr, h->d_indices, h->d_colmap, K, d_pc, h->d_rid16, P);
-      } else {
-        const unsigned grid = (unsigned)std::min<int64_t>(65535, (na + 256 / G - 1) / (256 / G));
-        auto pk = G == 1 ? k_row_partcounts<1, false> : G == 2 ? k_row_partcounts<2, false> : G == 4 ? k_row_partcounts<4, false>
-                : G == 8 ? k_row_partcounts<8, false> : k_row_partcounts<16, false>;
-        pk<<<grid, 256, 0, h->stream>>>(na, h->d_amb_row, h->d_indptr, h->d_indices, h->d_colmap, K, d_pc, h->d_rid16, P);
-      }
-    }
-    TSEM_HIP(hipGetLastError());
-    rid_amb_done = true;
-    {
-      DevTmp t_sp;
-      TSEM_TMP(t_sp, 8);
-      TSEM_HIP(hipMemsetAsync(t_sp.p, 0, 8, h->stream));
-      k_single_part_rows<<<(unsigned)std::min<int64_t>(4096, (na + 255) / 256), 256, 0, h->stream>>>(na, d_pc, t_sp.as<unsigned long long>());
-      unsigned long long nsp = 0;
-      TSEM_HIP(hipMemcpyAsync(&nsp, t_sp.p, 8, hipMemcpyDeviceToHost, h->stream));
-      TSEM_HIP(hipStreamSynchronize(h->stream));
-      h->n_single_part = (int64_t)nsp;
-    }
-    const int cap = fz_cap(h->geo) - TS_STRANDS * 4;          // sub-blocks are padded to TS_STRANDS*4 entries
-    // chunk length: >= 64 blocks' worth of rows (the forced break at a chunk end costs ~0.8 % more blocks; round 2 used 256 blocks' worth,
-    // 484 sequential waves for 47M rows: 2 x 2.5 ms; four times as many waves walk a quarter each)
-    const int64_t L = std::max<int64_t>((int64_t)R * 64, (na + 16383) / 16384);
-    const int64_t nch = (na + L - 1) / L;
-    int64_t *d_cnt = nullptr, *d_off = nullptr;
-    int* d_flag = nullptr;
-    TSEM_SCOPED(d_cnt); TSEM_SCOPED(d_off); TSEM_SCOPED(d_flag);
-    TSEM_ALLOC(d_cnt, nch + 1); TSEM_ALLOC(d_off, nch + 1); TSEM_ALLOC(d_flag, 1);
-    TSEM_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), h->stream));
-    TSEM_HIP(hipMemsetAsync(d_cnt, 0, sizeof(int64_t) * (nch + 1), h->stream));
-    k_block_greedy<<<(unsigned)nch, 64, 0, h->stream>>>(na, P, R, cap, L, 0, d_pc, d_cnt, nullptr, nullptr, d_flag);
-    TSEM_HIP(hipGetLastError());
-    {
-      size_t tb = 0;
-      TSEM_HIP(rocprim::exclusive_scan(nullptr, tb, d_cnt, d_off, (int64_t)0, (size_t)(nch + 1), rocprim::plus<int64_t>(), h->stream));
-      void* tmp = nullptr;
-      TSEM_SCOPED(tmp);
-      TSEM_HIP(hipMalloc(&tmp, tb ? tb : 1));
-      TSEM_HIP(rocprim::exclusive_scan(tmp, tb, d_cnt, d_off, (int64_t)0, (size_t)(nch + 1), rocprim::plus<int64_t>(), h->stream));
-      int flag = 0;
-      TSEM_HIP(hipMemcpyAsync(&nb, d_off + nch, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-      TSEM_HIP(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      TSEM_HIP(hipStreamSynchronize(h->stream));
-      if (flag) { h->use_fused = false; nb = 0; }          // one row overflows the register tile
-    }
-    if (h->use_fused) {
-      TSEM_ALLOC(d_bs, nb + 1);
-      k_block_greedy<<<(unsigned)nch, 64, 0, h->stream>>>(na, P, R, cap, L, 1, d_pc, d_cnt, d_off, d_bs, d_flag);
-      TSEM_HIP(hipGetLastError());
-      TSEM_HIP(hipMemcpyAsync(d_bs + nb, &na, sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-      TSEM_HIP(hipStreamSynchronize(h->stream));
-    }
-    if (!h->use_fused) { (void)hipFree(d_pc); d_pc = nullptr; }
+  return TSEM_OK;
+}
+
+// the fused layout's blocks (no part may exceed FZ_CAP entries, at most R rows); a row that overflows the tile: use_fused goes, no b.d_bs
+static int layout_greedy_blocks(tsem_ctx* h, LayoutBuild& b, int64_t& nb) {
+  const int K = h->K, P = h->P, R = h->R;
+  const int64_t na = h->N_amb;
+  TSEM_ALLOC(b.d_pc, 2 * na);
+  int capc = 256;                                          // lanes per row x 16 entries, from the row-length histogram
+  for (int q = 1; q < 6; ++q)
+    if ((double)h->len_gt[q] <= 0.005 * (double)h->N) { capc = 8 << q; break; }
+  const int G = capc <= 16 ? 1 : capc <= 32 ? 2 : capc <= 64 ? 4 : capc <= 128 ? 8 : 16;
+  if ((size_t)K * 4 <= (size_t)TS_LDS_MAX - 2048 && na >= 65536) {   // the column map fits LDS (K <= 40k) and the matrix is worth a 120 KB preload per CU
+    auto pk = G == 1 ? k_row_partcounts<1, true> : G == 2 ? k_row_partcounts<2, true> : G == 4 ? k_row_partcounts<4, true>
+            : G == 8 ? k_row_partcounts<8, true> : k_row_partcounts<16, true>;
+    if (int rc = allow_large_lds(h, (const void*)pk)) return rc;
+    pk<<<h->n_cu, 1024, (size_t)K * 4, h->stream>>>(na, h->d_amb_row, h->d_indptr, h->d_indices, h->d_colmap, K, b.d_pc, h->d_rid16, P);
+  } else {
+    const unsigned grid = (unsigned)std::min<int64_t>(65535, (na + 256 / G - 1) / (256 / G));
+    auto pk = G == 1 ? k_row_partcounts<1, false> : G == 2 ? k_row_partcounts<2, false> : G == 4 ? k_row_partcounts<4, false>
+            : G == 8 ? k_row_partcounts<8, false> : k_row_partcounts<16, false>;
+    pk<<<grid, 256, 0, h->stream>>>(na, h->d_amb_row, h->d_indptr, h->d_indices, h->d_colmap, K, b.d_pc, h->d_rid16, P);
   }
-  if (!d_bs) {                                             // two-pass layout: R rows per block
+  TSEM_HIP(hipGetLastError());
+  b.rid_amb_done = true;
+  DevTmp t_sp, t_scan;                                     // (as the chunk arrays below: until the return, where the stream is idle)
+  TSEM_TMP(t_sp, 8);
+  TSEM_HIP(hipMemsetAsync(t_sp.p, 0, 8, h->stream));
+  k_single_part_rows<<<(unsigned)std::min<int64_t>(4096, (na + 255) / 256), 256, 0, h->stream>>>(na, b.d_pc, t_sp.as<unsigned long long>());
+  unsigned long long nsp = 0;
+  TSEM_HIP(hipMemcpyAsync(&nsp, t_sp.p, 8, hipMemcpyDeviceToHost, h->stream));
+  TSEM_HIP(hipStreamSynchronize(h->stream));
+  h->n_single_part = (int64_t)nsp;
+  const int cap = fz_cap(h->geo) - TS_STRANDS * 4;          // sub-blocks are padded to TS_STRANDS*4 entries
+  // chunk length: >= 64 blocks' worth of rows (the forced break at a chunk end costs ~0.8 % more blocks; round 2 used 256 blocks' worth,
+  // 484 sequential waves for 47M rows: 2 x 2.5 ms; four times as many waves walk a quarter each)
+  const int64_t L = std::max<int64_t>((int64_t)R * 64, (na + 16383) / 16384);
+  const int64_t nch = (na + L - 1) / L;
+  int64_t *d_cnt = nullptr, *d_off = nullptr;
+  int* d_flag = nullptr;
+  TSEM_SCOPED(d_cnt); TSEM_SCOPED(d_off); TSEM_SCOPED(d_flag);
+  TSEM_ALLOC(d_cnt, nch + 1); TSEM_ALLOC(d_off, nch + 1); TSEM_ALLOC(d_flag, 1);
+  TSEM_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), h->stream));
+  TSEM_HIP(hipMemsetAsync(d_cnt, 0, sizeof(int64_t) * (nch + 1), h->stream));
+  k_block_greedy<<<(unsigned)nch, 64, 0, h->stream>>>(na, P, R, cap, L, 0, b.d_pc, d_cnt, nullptr, nullptr, d_flag);
+  TSEM_HIP(hipGetLastError());
+  if (int rc = scan_i64(h, d_cnt, d_off, (size_t)(nch + 1), t_scan)) return rc;
+  int flag = 0;
+  TSEM_HIP(hipMemcpyAsync(&nb, d_off + nch, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  TSEM_HIP(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  TSEM_HIP(hipStreamSynchronize(h->stream));
+  if (flag) { h->use_fused = false; nb = 0; }              // one row overflows the register tile
+  if (h->use_fused) {
+    TSEM_ALLOC(b.d_bs, nb + 1);
+    k_block_greedy<<<(unsigned)nch, 64, 0, h->stream>>>(na, P, R, cap, L, 1, b.d_pc, d_cnt, d_off, b.d_bs, d_flag);
+    TSEM_HIP(hipGetLastError());
+    TSEM_HIP(hipMemcpyAsync(b.d_bs + nb, &na, sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    TSEM_HIP(hipStreamSynchronize(h->stream));
+  }
+  return TSEM_OK;
+}
+
+// 3. row blocks.  Two-pass layout: R rows each.  Fused layout: as many consecutive rows as the
+//    register tile takes — rows per block vary, every block still owns R row SLOTS (holes at the end),
+//    so all kernels keep b*R+lr indexing.  Then the popularity ids of the rows not yet visited, and the slots.
+static int layout_row_blocks(tsem_ctx* h, LayoutBuild& b) {
+  const int P = h->P, R = h->R;
+  const int64_t na = h->N_amb;
+  int64_t nb = 0;
+  if (h->use_fused && na > 0 && P <= FZ_MAX_P) {
+    if (int rc = layout_greedy_blocks(h, b, nb)) return rc;
+    if (!h->use_fused) dfree(b.d_pc);
+  }
+  if (!b.d_bs) {                                           // two-pass layout: R rows per block
     nb = (na + R - 1) / R;
-    TSEM_ALLOC(d_bs, nb + 1);
-    k_fixed_blocks<<<cdiv64(nb + 1, 256), 256, 0, h->stream>>>(nb, R, na, d_bs);
+    TSEM_ALLOC(b.d_bs, nb + 1);
+    k_fixed_blocks<<<cdiv64(nb + 1, 256), 256, 0, h->stream>>>(nb, R, na, b.d_bs);
     TSEM_HIP(hipGetLastError());
   }
   if (h->d_rid16 && h->N) {                                // the rows k_row_partcounts did not visit (all of them without the fused layout)
     k_rid16_rows<<<(unsigned)std::min<int64_t>(65535, (h->N + 15) / 16), 256, 0, h->stream>>>(
-        h->N, h->d_indptr, h->d_indices, h->d_colmap, P, rid_amb_done ? 1 : 0, h->d_rid16);
+        h->N, h->d_indptr, h->d_indices, h->d_colmap, P, b.rid_amb_done ? 1 : 0, h->d_rid16);
     TSEM_HIP(hipGetLastError());
   }
   h->nb = nb;
   h->N_amb_pad = std::max<int64_t>(1, nb) * R;
-  {
-    TSEM_ALLOC(h->d_slot_row, h->N_amb_pad);
-    TSEM_ALLOC(h->d_amb_wcode, h->N_amb_pad);
-    if (nb) k_make_slots<<<(unsigned)nb, 256, 0, h->stream>>>(nb, R, d_bs, h->d_amb_row, h->d_amb_wcode_c,
-                                                             h->d_slot_row, h->d_amb_wcode);
-    else TSEM_HIP(hipMemsetAsync(h->d_amb_wcode, 0, sizeof(uint16_t) * h->N_amb_pad, h->stream));
-    TSEM_HIP(hipGetLastError());
-  }
-  pt.lap("layout: part counts, blocks, slots");
-  // 4. sub-block sizes -> offsets, on the device (round 5: the counts used to travel to the host and the offsets back, 12 MB of
-  //    pageable copies and a host loop: 2.3 ms at 146k blocks): pad every count to TS_STRANDS*4 entries, exclusive scan, 32-bit quad
-  //    offsets for the fused kernel; three scalars come back (largest sub-block, stored entries, padded total)
+  TSEM_ALLOC(h->d_slot_row, h->N_amb_pad);
+  TSEM_ALLOC(h->d_amb_wcode, h->N_amb_pad);
+  if (nb) k_make_slots<<<(unsigned)nb, 256, 0, h->stream>>>(nb, R, b.d_bs, h->d_amb_row, h->d_amb_wcode_c,
+                                                           h->d_slot_row, h->d_amb_wcode);
+  else TSEM_HIP(hipMemsetAsync(h->d_amb_wcode, 0, sizeof(uint16_t) * h->N_amb_pad, h->stream));
+  TSEM_HIP(hipGetLastError());
+  return TSEM_OK;
+}
+
+// 4. sub-block sizes -> offsets, on the device (round 5: the counts used to travel to the host and the offsets back, 12 MB of
+//    pageable copies and a host loop: 2.3 ms at 146k blocks): pad every count to TS_STRANDS*4 entries, exclusive scan, 32-bit quad
+//    offsets for the fused kernel; three scalars come back (largest sub-block, stored entries, padded total).  What they rule out
+//    for the fused kernel is decided here, before its quad offsets are made.
+static int layout_subblock_offsets(tsem_ctx* h, LayoutBuild& b) {
+  const int P = h->P;
+  const int64_t nb = h->nb;
   int64_t off = 0;
+  unsigned long long st[2] = {0, 0};
   TSEM_ALLOC(h->d_sb_off, nb * P + 1);
   if (nb) {
     int64_t* d_cnt = nullptr;
     unsigned long long* d_st = nullptr;
+    DevTmp t_scan;
     TSEM_SCOPED(d_cnt); TSEM_SCOPED(d_st);
     TSEM_ALLOC(d_cnt, nb * P + 1); TSEM_ALLOC(d_st, 2);
     TSEM_HIP(hipMemsetAsync(d_st, 0, 16, h->stream));
     TSEM_HIP(hipMemsetAsync(d_cnt + nb * P, 0, 8, h->stream));
-    if (d_pc) k_sb_count_pc<<<(unsigned)nb, 64, 0, h->stream>>>(nb, P, d_bs, d_pc, d_cnt);
-    else k_sb_count<<<(unsigned)nb, 256, 0, h->stream>>>(na, R, P, h->d_slot_row, h->d_indptr, h->d_indices, h->d_colmap, d_cnt);
+    if (b.d_pc) k_sb_count_pc<<<(unsigned)nb, 64, 0, h->stream>>>(nb, P, b.d_bs, b.d_pc, d_cnt);
+    else k_sb_count<<<(unsigned)nb, 256, 0, h->stream>>>(h->N_amb, h->R, P, h->d_slot_row, h->d_indptr, h->d_indices, h->d_colmap, d_cnt);
     k_sb_pad<<<cdiv64(nb * P, 256), 256, 0, h->stream>>>(nb * P, d_cnt, d_st);
     TSEM_HIP(hipGetLastError());
-    size_t tb = 0;
-    TSEM_HIP(rocprim::exclusive_scan(nullptr, tb, d_cnt, h->d_sb_off, (int64_t)0, (size_t)(nb * P + 1), rocprim::plus<int64_t>(), h->stream));
-    void* tmp = nullptr;
-    TSEM_SCOPED(tmp);
-    TSEM_HIP(hipMalloc(&tmp, tb ? tb : 1));
-    TSEM_HIP(rocprim::exclusive_scan(tmp, tb, d_cnt, h->d_sb_off, (int64_t)0, (size_t)(nb * P + 1), rocprim::plus<int64_t>(), h->stream));
-    unsigned long long st[2] = {0, 0};
+    if (int rc = scan_i64(h, d_cnt, h->d_sb_off, (size_t)(nb * P + 1), t_scan)) return rc;
     TSEM_HIP(hipMemcpyAsync(st, d_st, 16, hipMemcpyDeviceToHost, h->stream));
     TSEM_HIP(hipMemcpyAsync(&off, h->d_sb_off + nb * P, 8, hipMemcpyDeviceToHost, h->stream));
     TSEM_HIP(hipStreamSynchronize(h->stream));
-    h->nnz_amb += (int64_t)st[1];
-    if (h->use_fused) {
-      h->max_subblock = (int64_t)st[0];
-      if ((int64_t)st[0] > fz_cap(h->geo)) h->use_fused = false;
-    }
   } else {
     TSEM_HIP(hipMemsetAsync(h->d_sb_off, 0, 8, h->stream));
-    if (h->use_fused) h->max_subblock = 0;
   }
+  h->nnz_amb += (int64_t)st[1];
   h->nnz_pad = off;
-  if (h->use_fused && (off >> 2) < 0xFFFFFFFFll) {
+  if (h->use_fused) {
+    h->max_subblock = (int64_t)st[0];
+    // a sub-block past the register tile, or more quads than 32 bits count: the two-pass kernels
+    if ((int64_t)st[0] > fz_cap(h->geo) || (off >> 2) >= 0xFFFFFFFFll) h->use_fused = false;
+  }
+  if (h->use_fused) {
     TSEM_ALLOC(h->d_sb_q32, nb * P + 2);
     k_sb_q32<<<cdiv64(nb * P + 2, 256), 256, 0, h->stream>>>(nb * P + 1, h->d_sb_off, h->d_sb_q32);
     TSEM_HIP(hipGetLastError());
-  } else if (h->use_fused) {
-    h->use_fused = false;
   }
+  return TSEM_OK;
+}
+
+// What the geometry rules out for the fused kernel, then the entry format and the order of the fill: each of these fields of the
+// context is written here and nowhere else in a build of the blocked layout (layout_identity_map clears them).  No device work.
+static int layout_decide_format(tsem_ctx* h) {
+  const int R = h->R;
   if (h->use_fused && (R > fz_rmax(h->geo) || (R & 1) || fz_lds_bytes(h, false) > (size_t)TS_LDS_MAX - 1024)) h->use_fused = false;
   // the packed index has 13 bits of column slot and 11 of row slot: every non-split fused layout fits by construction (Kp <= TS_MAX_KP,
   // R <= fz_rmax); one that did not would keep the 32-bit index and the two-pass kernels that read it
-  if (h->use_fused && !h->split && (Kp > TS_IDX24_MAX_KP || R > TS_IDX24_MAX_R)) h->use_fused = false;
+  if (h->use_fused && !h->split && (h->Kp > TS_IDX24_MAX_KP || R > TS_IDX24_MAX_R)) h->use_fused = false;
   h->fmt_code = h->use_fused && fz_wants_codes(h) && fz_lds_bytes(h, true) <= (size_t)TS_LDS_MAX - 1024;
   h->fmt_wcode = h->use_fused && !h->fmt_code && h->lut_len > 0 && h->lut_len <= 2048 &&
                  fz_lds_bytes(h, true) <= (size_t)TS_LDS_MAX - 1024;
@@ -1355,45 +1376,51 @@ int tsem_build_layout(tsem_ctx* h) {
   if (h->opt_reproducible && !(h->use_fused && (h->fmt_code || h->fmt_wcode)))
     TSEM_FAIL(TSEM_ERR_ARG, "reproducible mode needs the fused kernel (at most 8 column parts, every row within the register tile) and a score "
                             "table of at most 2048 entries");
-  pt.lap("layout: sub-block offsets");
-  // (zero-filled for the strand-transposed fill only, whose padding is whatever it does not write; the row-order fill writes
-  //  every position, padding included — 12-24 GB of memsets, ~3 ms at 2e9 entries, went away with that)
-  const bool will_sort = h->use_fused && R * P <= FILL_MAX_RP && (h->opt_sorted >= 0 ? h->opt_sorted != 0 : true) && nb > 0;
   // fp64 entries under the fused kernel, non-split: 3 B of index per entry (the instantiations of fz_idx24(), tsem_fused.h).  Decided
   // HERE for every build of the layout, the rebuild of the two-pass fall-back included (use_fused is false then: 4 B again).
   h->idx24 = h->use_fused && !h->split && !h->fmt_code;
-  const int64_t prc_words = h->idx24 ? (off * 3 + 3) / 4 : off;   // (sub-blocks are padded to 64 entries: a multiple of 192 B each)
-  TSEM_ALLOC(h->d_prc, prc_words);
-  if (!will_sort) TSEM_HIP(hipMemsetAsync(h->d_prc, 0, sizeof(uint32_t) * std::max<int64_t>(1, prc_words), h->stream));
-  if (h->fmt_code) {
-    TSEM_ALLOC(h->d_pcode, off);
-    if (!will_sort) TSEM_HIP(hipMemsetAsync(h->d_pcode, 0, sizeof(uint16_t) * std::max<int64_t>(1, off), h->stream));   // code 0 -> Q = 0
-  } else {
-    TSEM_ALLOC(h->d_pval, off);
-    if (!will_sort) TSEM_HIP(hipMemsetAsync(h->d_pval, 0, sizeof(double) * std::max<int64_t>(1, off), h->stream));
-  }
-  pt.lap("layout: entry buffers (alloc + zero)");
   // Row order (row sums reduced in registers, a tenth of the LDS atomics) for every fused layout.  Score codes: 40
   // entries per row at P = 4 4.44 -> 3.59 ms, 20 per row 2.30 -> 1.92, 10 per row 1.65 -> 1.40.  fp64 entries
   // were indifferent to it while the exchange wave stalled behind the memory pipe (round 1: 4.62 against 4.57 ms);
   // since the exchange is one generation per step, the step ends when the LDS queue has drained, and less LDS work
   // shortens it for them too: 40 per row 4.33 -> 4.14 ms (0.73 of the HBM peak), teams of 8 4.42 -> 4.20, 20 per
   // row 2.70 -> 2.48 (profiles/r02_sweep.txt, r02_sweep_short.txt).
-  h->sorted_layout = h->use_fused && R * P <= FILL_MAX_RP &&   // (the fill kernel keeps R x P counters in LDS)
+  h->sorted_layout = h->use_fused && R * h->P <= FILL_MAX_RP &&   // (the fill kernel keeps R x P counters in LDS)
                      (h->opt_sorted >= 0 ? h->opt_sorted != 0 : true);
-  // (the small table of the fill lives until the one synchronisation behind the kernels; nothing GB-sized is allocated next to a
+  return TSEM_OK;
+}
+
+// the entry buffers and the fill: k_sb_fill_sorted (+ k_sb_deconflict) in row order, or the strand-transposed k_sb_fill; ends synchronised
+static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
+  const int K = h->K, P = h->P, R = h->R;
+  const int64_t na = h->N_amb, nb = h->nb, off = h->nnz_pad;
+  // (zero-filled for the strand-transposed fill only, whose padding is whatever it does not write; the row-order fill writes
+  //  every position, padding included — 12-24 GB of memsets, ~3 ms at 2e9 entries, went away with that)
+  const bool row_order = h->sorted_layout && nb > 0;
+  const int64_t prc_words = h->idx24 ? (off * 3 + 3) / 4 : off;   // (sub-blocks are padded to 64 entries: a multiple of 192 B each)
+  TSEM_ALLOC(h->d_prc, prc_words);
+  if (!row_order) TSEM_HIP(hipMemsetAsync(h->d_prc, 0, sizeof(uint32_t) * std::max<int64_t>(1, prc_words), h->stream));
+  if (h->fmt_code) {
+    TSEM_ALLOC(h->d_pcode, off);
+    if (!row_order) TSEM_HIP(hipMemsetAsync(h->d_pcode, 0, sizeof(uint16_t) * std::max<int64_t>(1, off), h->stream));   // code 0 -> Q = 0
+  } else {
+    TSEM_ALLOC(h->d_pval, off);
+    if (!row_order) TSEM_HIP(hipMemsetAsync(h->d_pval, 0, sizeof(double) * std::max<int64_t>(1, off), h->stream));
+  }
+  b.pt.lap("layout: entry buffers (alloc + zero)");
+  // (the small table of the fill lives until the synchronisation behind the kernels; nothing GB-sized is allocated next to a
   //  running kernel: that took 60-300 ms in round 5's first attempt at overlapping this section)
   uint8_t* d_lgtab = nullptr;
   TSEM_SCOPED(d_lgtab);
-  if (nb && h->sorted_layout) {
+  if (row_order) {
     // the popularity ids stand in for the column-map gather when every row's ids are written (they are: k_row_partcounts +
-    // k_rid16_rows above) and the split columns' ids fit the small table
+    // k_rid16_rows of layout_row_blocks) and the split columns' ids fit the small table
     const uint16_t* rid_fill = nullptr;
     int nsplit = 0;
     if (h->d_rid16 && P <= 8) {
       std::vector<uint8_t> lgt;
       for (int j = 0; j < K; ++j) {
-        const uint32_t cm = colmap[j], lg = (cm >> CM_LS) & 7u;
+        const uint32_t cm = b.colmap[j], lg = (cm >> CM_LS) & 7u;
         if (lg) { const uint32_t id = (cm & CM_SM) * P + (cm >> CM_PS); if (id >= lgt.size()) lgt.resize(id + 1, 0); lgt[id] = (uint8_t)lg; }
       }
       nsplit = (int)lgt.size();
@@ -1410,7 +1437,7 @@ int tsem_build_layout(tsem_ctx* h) {
     const uint32_t magicP = (uint32_t)((0x100000000ull + (uint64_t)P - 1) / (uint64_t)P);
     k_sb_fill_sorted<<<(unsigned)nb, 256, fill_lds_bytes(R, P), h->stream>>>(na, R, P, h->d_slot_row, h->d_indptr, h->d_indices, h->d_raw, h->d_lut,
                                                          h->d_colmap, h->d_sb_off, h->d_pval, h->d_pcode, h->d_prc,
-                                                         d_pc ? d_bs : nullptr, d_pc, rid_fill, magicP, nsplit, d_lgtab, h->idx24 ? 1 : 0);
+                                                         b.d_pc ? b.d_bs : nullptr, b.d_pc, rid_fill, magicP, nsplit, d_lgtab, h->idx24 ? 1 : 0);
     TSEM_HIP(hipGetLastError());
     if (deconflict) {
       const int64_t n_win = off / 64;
@@ -1420,10 +1447,8 @@ int tsem_build_layout(tsem_ctx* h) {
     }
     // While the device fills the layout (15 ms at 2e9 entries) the host loads the code object of the fused kernel's unit — 3 ms in a
     // fresh process, at the first hipFuncSetAttribute / launch of one of its kernels — instead of doing so afterwards.
-    if (h->use_fused) {
-      fz_fn f0 = P <= FZ_MAX_P ? fz_kernel(P, h->split ? 5 : 0, fz_fmt(h), h->geo) : nullptr;
-      if (f0) (void)hipFuncSetAttribute((const void*)f0, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024);
-    }
+    fz_fn f0 = P <= FZ_MAX_P ? fz_kernel(P, h->split ? 5 : 0, fz_fmt(h), h->geo) : nullptr;
+    if (f0) (void)hipFuncSetAttribute((const void*)f0, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024);   // (a preload: its error is the later call's)
     tsem_report_preload();                                 // (round 6: the report unit's too — ~10 ms that used to sit in the first report)
     TSEM_HIP(hipStreamSynchronize(h->stream));
     // option "drop_csr_indices": the fill was the last reader of the CSR column ids (the report pass and this layout carry 2-byte
@@ -1435,63 +1460,83 @@ int tsem_build_layout(tsem_ctx* h) {
     TSEM_HIP(hipGetLastError());
   }
   TSEM_HIP(hipStreamSynchronize(h->stream));
-  pt.lap("layout: fill + conflict-aware order");
+  return TSEM_OK;
+}
+
+// launch geometry of the two-pass kernels, the partial sums' and the exchange's buffers, the fused kernels' attributes, option "reproducible"
+static int layout_launch_buffers(tsem_ctx* h) {
+  const int K = h->K, P = h->P, Kp = h->Kp, R = h->R;
   if (!h->use_fused) TSEM_ALLOC(h->d_ypart, (int64_t)P * h->N_amb_pad);   // partial row sums of the two-pass kernels
-  // launch geometry
   const size_t lds1 = (size_t)(Kp + R) * 8, lds2 = (size_t)(2 * Kp + R) * 8;
   if (lds2 > (size_t)TS_LDS_MAX - 1024 && !h->use_fused) TSEM_FAIL(TSEM_ERR_ARG, "LDS budget exceeded (reduce block_rows)");   // (the two-pass kernels' tables; the split layout has its own budget)
   int w1 = std::max(1, std::min(4, (int)(TS_LDS_MAX / lds1)));   // 512-thread WGs per CU
   int w2 = std::max(1, std::min(2, (int)(TS_LDS_MAX / lds2)));   // 1024-thread WGs per CU
-  h->G1 = (int)std::max<int64_t>(1, std::min<int64_t>(nb, (int64_t)h->n_cu * w1 / P));
-  h->G2 = (int)std::max<int64_t>(1, std::min<int64_t>(nb, (int64_t)h->n_cu * w2 / P));
-  if (!h->use_fused) TSEM_ALLOC(h->d_partial, (int64_t)h->G2 * h->Kpad);
-  if (h->use_fused) {
-    {
-      h->fz_grid = h->n_cu;
-      h->fz_teams = std::max(1, h->fz_grid / P);
-      TSEM_ALLOC(h->d_fpartial, (int64_t)h->fz_teams * h->Kpad);
-      TSEM_ALLOC(h->d_xchg, (int64_t)h->fz_teams * FZ_XS * P * R);
-      TSEM_ALLOC(h->d_xflags, FZ_SYNC_WORDS);
-      TSEM_HIP(hipMemsetAsync(h->d_xflags, 0, sizeof(uint32_t) * FZ_SYNC_WORDS, h->stream));
-      if (!h->fmt_code && !h->fmt_wcode) {                 // fp64 row weights; otherwise the kernel reads d_amb_wcode
-        TSEM_ALLOC(h->d_amb_w, h->N_amb_pad);
-        k_row_weights<<<cdiv64(h->N_amb_pad, 256), 256, 0, h->stream>>>(h->N_amb_pad, h->d_amb_wcode, h->d_lut, h->d_amb_w);
-      }
-      if (h->split) {                                      // row-sum pass, scatter pass, log-likelihood over a column half
-        for (int mode : {5, 7, 8}) {
-          fz_fn f = fz_kernel(P, mode, fz_fmt(h), h->geo);
-          if (!f) TSEM_FAIL(TSEM_ERR_ARG, "split layout: no fused kernel for this team size / geometry");
-          TSEM_HIP(hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
-        }
-        TSEM_ALLOC(h->d_rinv, h->N_amb_pad);               // the row factors pass A hands to pass B
-        TSEM_ALLOC(h->d_ypart, (int64_t)P * h->N_amb_pad); // the members' partial row sums (row-sum pass -> k_row_factors)
-        TSEM_HIP(hipMemsetAsync(h->d_rinv, 0, sizeof(double) * h->N_amb_pad, h->stream));
-      } else
-      for (int mode = 0; mode < 2; ++mode)
-        TSEM_HIP(hipFuncSetAttribute((const void*)fz_kernel(P, mode, fz_fmt(h), h->geo),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
-      if (h->lnl3 && !(h->fmt_code && fz_kernel(P, 4, fz_fmt(h), h->geo))) h->lnl3 = false;   // (not score codes after all: the per-iteration lnl pass stays)
-      h->lag_valid = false;
-      if (h->lnl3) {
-        TSEM_HIP(hipFuncSetAttribute((const void*)fz_kernel(P, 4, fz_fmt(h), h->geo), hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
-        TSEM_ALLOC(h->d_rinv, h->N_amb_pad);
-        TSEM_HIP(hipMemsetAsync(h->d_rinv, 0, sizeof(double) * h->N_amb_pad, h->stream));
-      }
-      if (h->opt_reproducible) {
-        if (h->exact_single && !fz_kernel(P, 3, fz_fmt(h), h->geo)) h->exact_single = false;   // (not score codes after all: fz_lds_bytes then counts two tables again)
-        if (h->exact_single) TSEM_ALLOC(h->d_fpartial2, (int64_t)h->fz_teams * h->Kpad);
-        fz_fn f2 = fz_kernel(P, h->exact_single ? 3 : 2, fz_fmt(h), h->geo);
-        if (!f2) TSEM_FAIL(TSEM_ERR_ARG, "reproducible mode needs the fused kernel with a score table of at most 2048 entries");
-        TSEM_HIP(hipFuncSetAttribute((const void*)f2, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
-        TSEM_ALLOC(h->d_ebias, h->Kpad); TSEM_ALLOC(h->d_ovf, h->Kpad); TSEM_ALLOC(h->d_red_hi, K + 2); TSEM_ALLOC(h->d_binflag, 4);
-        TSEM_ALLOC(h->d_ehist, 2 * (size_t)K + 2);
-        if (int rc = tsem_bin_reset(h)) return rc;
-      }
-    }
+  h->G1 = (int)std::max<int64_t>(1, std::min<int64_t>(h->nb, (int64_t)h->n_cu * w1 / P));
+  h->G2 = (int)std::max<int64_t>(1, std::min<int64_t>(h->nb, (int64_t)h->n_cu * w2 / P));
+  if (!h->use_fused) {
+    TSEM_ALLOC(h->d_partial, (int64_t)h->G2 * h->Kpad);
+    return tsem_twopass_attributes(h);
   }
-  if (int rc = tsem_twopass_attributes(h)) return rc;
+  const int fmt = fz_fmt(h), geo = h->geo;
+  h->fz_grid = h->n_cu;
+  h->fz_teams = std::max(1, h->fz_grid / P);
+  TSEM_ALLOC(h->d_fpartial, (int64_t)h->fz_teams * h->Kpad);
+  TSEM_ALLOC(h->d_xchg, (int64_t)h->fz_teams * FZ_XS * P * R);
+  TSEM_ALLOC(h->d_xflags, FZ_SYNC_WORDS);
+  TSEM_HIP(hipMemsetAsync(h->d_xflags, 0, sizeof(uint32_t) * FZ_SYNC_WORDS, h->stream));
+  if (!h->fmt_code && !h->fmt_wcode) {                     // fp64 row weights; otherwise the kernel reads d_amb_wcode
+    TSEM_ALLOC(h->d_amb_w, h->N_amb_pad);
+    k_row_weights<<<cdiv64(h->N_amb_pad, 256), 256, 0, h->stream>>>(h->N_amb_pad, h->d_amb_wcode, h->d_lut, h->d_amb_w);
+  }
+  if (h->split) {                                          // row-sum pass, scatter pass, log-likelihood over a column half
+    for (int mode : {5, 7, 8})
+      if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, mode, fmt, geo), "split layout: no fused kernel for this team size / geometry")) return rc;
+    TSEM_ALLOC(h->d_rinv, h->N_amb_pad);                   // the row factors pass A hands to pass B
+    TSEM_ALLOC(h->d_ypart, (int64_t)P * h->N_amb_pad);     // the members' partial row sums (row-sum pass -> k_row_factors)
+    TSEM_HIP(hipMemsetAsync(h->d_rinv, 0, sizeof(double) * h->N_amb_pad, h->stream));
+  } else
+    for (int mode = 0; mode < 2; ++mode)
+      if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, mode, fmt, geo))) return rc;
+  if (h->lnl3 && !(h->fmt_code && fz_kernel(P, 4, fmt, geo))) h->lnl3 = false;   // (not score codes after all: the per-iteration lnl pass stays)
+  h->lag_valid = false;
+  if (h->lnl3) {
+    if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, 4, fmt, geo))) return rc;
+    TSEM_ALLOC(h->d_rinv, h->N_amb_pad);
+    TSEM_HIP(hipMemsetAsync(h->d_rinv, 0, sizeof(double) * h->N_amb_pad, h->stream));
+  }
+  if (h->opt_reproducible) {
+    if (h->exact_single && !fz_kernel(P, 3, fmt, geo)) h->exact_single = false;   // (not score codes after all: fz_lds_bytes then counts two tables again)
+    if (h->exact_single) TSEM_ALLOC(h->d_fpartial2, (int64_t)h->fz_teams * h->Kpad);
+    if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, h->exact_single ? 3 : 2, fmt, geo),
+                                 "reproducible mode needs the fused kernel with a score table of at most 2048 entries")) return rc;
+    TSEM_ALLOC(h->d_ebias, h->Kpad); TSEM_ALLOC(h->d_ovf, h->Kpad); TSEM_ALLOC(h->d_red_hi, K + 2); TSEM_ALLOC(h->d_binflag, 4);
+    TSEM_ALLOC(h->d_ehist, 2 * (size_t)K + 2);
+    if (int rc = tsem_bin_reset(h)) return rc;
+  }
+  return tsem_twopass_attributes(h);
+}
+
+int tsem_build_layout(tsem_ctx* h) {
+  LayoutBuild b(h->stream);
+  CsrIds ids(h); ids.keep();                               // (the popularity ids go with the old layout: the fill below drops the column ids once it has made the new ones)
+  if (int rc = ids.acquire()) return rc;                   // (a rebuild after option "drop_csr_indices": from the ids of the layout about to go)
   TSEM_HIP(hipStreamSynchronize(h->stream));
-  pt.lap("layout: launch buffers, attributes");
+  tsem_free_layout(h);
+  h->nnz_amb = 0;
+  h->n_single_part = 0;
+  if (h->em_rows) return layout_identity_map(h);
+  if (int rc = layout_column_map(h, b)) return rc;         // 1., 2.: columns by popularity, dealt to the parts; hot columns split
+  b.pt.lap("layout: maps to the device, rid16 alloc");
+  if (int rc = layout_row_blocks(h, b)) return rc;         // 3.: row blocks (greedy for the fused kernel), popularity ids, row slots
+  b.pt.lap("layout: part counts, blocks, slots");
+  if (int rc = layout_subblock_offsets(h, b)) return rc;   // 4.: sub-block sizes -> offsets
+  if (int rc = layout_decide_format(h)) return rc;         //     fused or two-pass, entry format, index width, order of the fill
+  b.pt.lap("layout: sub-block offsets");
+  if (int rc = layout_fill(h, b)) return rc;               //     the entries
+  b.pt.lap("layout: fill + conflict-aware order");
+  if (int rc = layout_launch_buffers(h)) return rc;        //     what the EM kernels need besides
+  TSEM_HIP(hipStreamSynchronize(h->stream));
+  b.pt.lap("layout: launch buffers, attributes");
   return TSEM_OK;
 }
 
@@ -1546,34 +1591,34 @@ int tsem_set_model(tsem_ctx* h, const double* stats3, const double* pisum0, cons
   pt0.lap("set_model: build_layout total");
   TSEM_ALLOC(h->d_pi, K); TSEM_ALLOC(h->d_theta, K); TSEM_ALLOC(h->d_pi_prev, K); TSEM_ALLOC(h->d_theta_prev, K);
   TSEM_ALLOC(h->d_tmp_pi, K); TSEM_ALLOC(h->d_tmp_theta, K);
-  TSEM_ALLOC(h->d_ctab, h->Kpad); TSEM_ALLOC(h->d_ctab_prev, h->Kpad);
   if (!h->d_red) {
     TSEM_ALLOC(h->d_red_own, K + 2);
     h->d_red = h->d_red_own; h->red_count = K + 2;
   } else if (h->red_count < K + 2) {
     TSEM_FAIL(TSEM_ERR_ARG, "bound reduce buffer is smaller than K+2 doubles");
   }
-  TSEM_HIP(hipMemsetAsync(h->d_ctab, 0, sizeof(double) * h->Kpad, h->stream));
-  TSEM_HIP(hipMemsetAsync(h->d_ctab_prev, 0, sizeof(double) * h->Kpad, h->stream));
   const double init = 1.0 / (double)K;   // model.py:667,673
   k_fill<<<cdiv64(K, 256), 256, 0, h->stream>>>(h->d_pi, K, init);
   k_fill<<<cdiv64(K, 256), 256, 0, h->stream>>>(h->d_theta, K, init);
   k_fill<<<cdiv64(K, 256), 256, 0, h->stream>>>(h->d_pi_prev, K, init);
   k_fill<<<cdiv64(K, 256), 256, 0, h->stream>>>(h->d_theta_prev, K, init);
-  k_make_ctab<<<cdiv64(K, 256), 256, 0, h->stream>>>(K, h->d_pi, h->d_theta, h->d_colmap, h->Kp, h->d_ctab);
-  k_make_ctab<<<cdiv64(K, 256), 256, 0, h->stream>>>(K, h->d_pi, h->d_theta, h->d_colmap, h->Kp, h->d_ctab_prev);
-  TSEM_HIP(hipGetLastError());
-  TSEM_HIP(hipStreamSynchronize(h->stream));
+  if (int rc = tsem_make_ctabs(h)) return rc;
   h->have_model = true;
   h->lnl_prev_seed = INFINITY;                             // model.py:683
   h->em_cur = h->em_prev = true;                           // pi = theta = 1/K
   return TSEM_OK;
 }
 
+// What follows every build of the layout: the permuted pi * theta tables (current and previous) go with its column map.  Returns with
+// the stream synchronised.
 int tsem_make_ctabs(tsem_ctx* h) {
+  TSEM_ALLOC(h->d_ctab, h->Kpad); TSEM_ALLOC(h->d_ctab_prev, h->Kpad);
+  TSEM_HIP(hipMemsetAsync(h->d_ctab, 0, sizeof(double) * h->Kpad, h->stream));
+  TSEM_HIP(hipMemsetAsync(h->d_ctab_prev, 0, sizeof(double) * h->Kpad, h->stream));
   k_make_ctab<<<cdiv64(h->K, 256), 256, 0, h->stream>>>(h->K, h->d_pi, h->d_theta, h->d_colmap, h->Kp, h->d_ctab);
   k_make_ctab<<<cdiv64(h->K, 256), 256, 0, h->stream>>>(h->K, h->d_pi_prev, h->d_theta_prev, h->d_colmap, h->Kp, h->d_ctab_prev);
   TSEM_HIP(hipGetLastError());
+  TSEM_HIP(hipStreamSynchronize(h->stream));
   return TSEM_OK;
 }
 
@@ -1594,12 +1639,7 @@ int tsem_prepare_likelihood(tsem_ctx* h) {
     return TSEM_OK;
   }
   if (int rc = tsem_build_layout(h)) return rc;
-  TSEM_ALLOC(h->d_ctab, h->Kpad); TSEM_ALLOC(h->d_ctab_prev, h->Kpad);
-  TSEM_HIP(hipMemsetAsync(h->d_ctab, 0, sizeof(double) * h->Kpad, h->stream));
-  TSEM_HIP(hipMemsetAsync(h->d_ctab_prev, 0, sizeof(double) * h->Kpad, h->stream));
-  if (int rc = tsem_make_ctabs(h)) return rc;
-  TSEM_HIP(hipStreamSynchronize(h->stream));
-  return TSEM_OK;
+  return tsem_make_ctabs(h);
 }
 
 int tsem_set_params(tsem_ctx* h, const double* pi, const double* theta) {

@@ -118,6 +118,8 @@ int  tsem_set_stream(tsem_ctx* h, void* hip_stream); /* launch on this hipStream
  *   "boot_hot_columns", "boot_batch"  tsem_bootstrap (below): how many of the most popular columns get workgroup-private LDS accumulators
  *                  (-1, default: as many as 32 KiB of LDS hold for the batch, 4096 / batch; 0 none: every sum is a global fp64 atomic;
  *                  at most 5120 / batch) and how many replicates share one sweep over the matrix (0, default: 8, the most)
+ *   "boot_group_bytes"  tsem_bootstrap_groups (below): bytes of the per-batch accumulators of the (group, column) pattern at most; the
+ *                  batch is lowered to fit.  0 (default): what is free.  Negative values are rejected.
  *   "cell_em_spread_entries"  tsem_cell_em (below): a group of the map with MORE stored entries than this is not fitted by one workgroup
  *                  but spread over the whole grid, one set of short kernel launches per iteration (a cell type of a single-cell run).
  *                  0: never spread; negative values are rejected.  May be set at any time; the next tsem_cell_em reads it.  Default
@@ -465,6 +467,35 @@ int  tsem_bootstrap(tsem_ctx* h, int32_t n_rep, uint64_t seed, const uint8_t* mu
 int  tsem_bootstrap_copy(tsem_ctx* h, double* pi, double* theta, double* counts /* n_rep x K each, any may be NULL */,
                          int64_t* n_frags /* sum of m_i */, int32_t* n_iter, int32_t* converged, double* lnl /* n_rep each, any may be NULL */,
                          int32_t* info2 /* replicates per batch and hot columns used; may be NULL */);
+/* The same replicates with PER-GROUP counts (single-cell: per barcode): besides everything tsem_bootstrap leaves for
+ * tsem_bootstrap_copy — same definitions, the same fits, fitted once — the call gives, for the row -> group map g(i) set with
+ * tsem_set_groups (a partition, -1 = the row is in no group; G groups), statistics over the replicates of
+ *   X_b[g, j] = sum over the rows i with g(i) = g of m_{b,i} A_b[i, j],   A_b = reassign(method, thresh) of replicate b's last z,
+ * on the PATTERN P: the distinct (g, j) such that some row of group g stores an entry in column j, ordered by (g, j) — group_ptr
+ * [G + 1], cols ascending within a group.  P is structural: it depends on the matrix and the map alone, not on any z or replicate; it
+ * is built once per map (the grouping, entry keys and stable sort of tsem_group_counts, without values; tiles under option
+ * "group_tile_bytes", 32 B per entry of a tile) and stays on the device, 8 B per group and 4 B per slot.  Rows in no group add to
+ * counts[b, :] as before and to no X.  A replicate is GOOD if it has fragments and its lnl is not NaN (the replicates whose counts
+ * are not NaN); n_used counts them.  Per slot, over the good replicates in replicate order, by Welford's update (d = x - mean;
+ * mean += d / k; M2 += d (x - mean); one thread owns a slot): mean (NaN when n_used = 0) and sd with ddof 1 (NaN when n_used < 2;
+ * equal values give exactly 0).  keep_values != 0 also keeps values[n_rep x nnz], X_b per replicate, the row of a bad replicate NaN.
+ * X_b is summed with one fp64 atomic per non-zero m A[i, j]: for exclude, unique and all every addend is an integer and X_b, mean and
+ * sd are exact and reproducible; for average and conf they agree from run to run to rounding.  If every row is in a group, sum_g
+ * X_b[g, j] = counts[b, j] (exactly for the integer methods).
+ * Memory: 16 B per slot (mean, sd), 8 B x n_rep per slot if values are kept, and the batch's accumulators, 8 B x batch per slot.
+ * Option "boot_group_bytes" caps the accumulators (0, default: what is free after results and workspace, less a 64 MiB margin);
+ * where they do not fit at the batch asked for the batch is lowered, down to 1 (tsem_bootstrap_copy's info2 reports the batch
+ * used); if they do not fit at 1 the call is TSEM_ERR_NOMEM with the byte counts in the message.  Limits and refusals are
+ * tsem_bootstrap's (TSEM_RA_CHOOSE, option "reproducible", a row-sharded handle, no model: TSEM_ERR_ARG with a message), and one
+ * more: no group map set.  *nnz = the slots of P. */
+int  tsem_bootstrap_groups(tsem_ctx* h, int32_t n_rep, uint64_t seed, const uint8_t* mult /* NULL | n_rep x N */, int32_t method,
+                           double thresh, double epsilon, int32_t max_iter, int32_t keep_values, int64_t* nnz);
+/* the last grouped call: groups, slots of P, replicates, good replicates, whether values were kept (any pointer may be NULL) */
+int  tsem_bootstrap_groups_shape(tsem_ctx* h, int32_t* n_groups, int64_t* nnz, int32_t* n_rep, int32_t* n_used, int32_t* kept);
+/* copy it out: group_ptr[n_groups + 1], cols[nnz], mean[nnz], sd[nnz], values[n_rep x nnz] (NULL, or the call kept them); any may be
+ * NULL.  TSEM_ERR_ARG once tsem_set_groups was called again (the pattern belongs to the map). */
+int  tsem_bootstrap_groups_copy(tsem_ctx* h, int64_t* group_ptr, int32_t* cols, double* mean, double* sd,
+                                double* values /* n_rep x nnz, or NULL */);
 /* the default multiplicities of replicate `rep` for the handle's rows [row_begin, row_end), computed on the device */
 int  tsem_bootstrap_mult(tsem_ctx* h, uint64_t seed, int32_t rep, int64_t row_begin, int64_t row_end, uint8_t* out);
 

@@ -230,6 +230,9 @@ def lib():
     L.tsem_bootstrap.argtypes = [vp, i32, u64, vp, i32, dbl, dbl, i32]
     L.tsem_bootstrap_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tsem_bootstrap_mult.argtypes = [vp, u64, i32, i64, i64, vp]
+    L.tsem_bootstrap_groups.argtypes = [vp, i32, u64, vp, i32, dbl, dbl, i32, i32, C.POINTER(i64)]
+    L.tsem_bootstrap_groups_shape.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.tsem_bootstrap_groups_copy.argtypes = [vp, vp, vp, vp, vp, vp]
     L.tsem_csr_norm_rows.argtypes = [C.c_int, i64, vp, vp, vp]
     L.tsem_csr_binmax_rows.argtypes = [C.c_int, i64, i32, vp, vp, vp]
     L.tsem_csr_scale.argtypes = [C.c_int, C.c_int, i64, i32, vp, vp, vp]
@@ -643,6 +646,31 @@ class Engine(object):
                  n_iter=np.empty(b, np.int32), converged=np.empty(b, np.int32), lnl=np.empty(b), info=np.zeros(2, np.int32))
         self._ck(self._L.tsem_bootstrap_copy(self._h, *[ptr(r[key]) for key in ('pi', 'theta', 'counts', 'n_frags', 'n_iter', 'converged',
                                                                                'lnl', 'info')]))
+        return r
+
+    def bootstrap_groups(self, n_rep, seed, mult, method, thresh, epsilon, max_iter, n_cols, keep_values=False):
+        """The replicates of `bootstrap` — the same dict — fitted once, with per-group statistics over the map of `set_groups`
+        (tsem_bootstrap_groups) under key `groups`: a dict of group_ptr int64 [n_groups + 1], cols int32 [nnz], mean, sd float64 [nnz],
+        n_used, and values float64 [n_rep x nnz] or None."""
+        if mult is not None:
+            mult = np.ascontiguousarray(mult, dtype=np.uint8)
+        nnz = C.c_int64()
+        self._ck(self._L.tsem_bootstrap_groups(self._h, int(n_rep), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(mult), RA_CODE[method],
+                                               float(thresh), float(epsilon), int(max_iter), int(bool(keep_values)), C.byref(nnz)))
+        b, k = int(n_rep), int(n_cols)
+        r = dict(pi=np.empty((b, k)), theta=np.empty((b, k)), counts=np.empty((b, k)), n_frags=np.empty(b, np.int64),
+                 n_iter=np.empty(b, np.int32), converged=np.empty(b, np.int32), lnl=np.empty(b), info=np.zeros(2, np.int32))
+        self._ck(self._L.tsem_bootstrap_copy(self._h, *[ptr(r[key]) for key in ('pi', 'theta', 'counts', 'n_frags', 'n_iter', 'converged',
+                                                                               'lnl', 'info')]))
+        n_groups, n_reps, n_used, kept = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self._L.tsem_bootstrap_groups_shape(self._h, C.byref(n_groups), C.byref(nnz), C.byref(n_reps), C.byref(n_used),
+                                                     C.byref(kept)))             # (the arrays are sized by the library)
+        s = nnz.value
+        g = dict(group_ptr=np.empty(n_groups.value + 1, np.int64), cols=np.empty(s, np.int32), mean=np.empty(s), sd=np.empty(s),
+                 n_used=int(n_used.value), values=np.empty((n_reps.value, s)) if kept.value else None)
+        self._ck(self._L.tsem_bootstrap_groups_copy(self._h, ptr(g['group_ptr']), ptr(g['cols']), ptr(g['mean']), ptr(g['sd']),
+                                                    ptr(g['values'])))
+        r['groups'] = g
         return r
 
     def bootstrap_mult(self, seed, rep, row_begin, row_end):

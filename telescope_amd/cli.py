@@ -138,12 +138,16 @@ def _assign_args(asg):
 
 
 def _bootstrap_args(p):
-    """Bulk `assign` / `resume` only: bootstrap replicates of the fit (TelescopeLikelihood.bootstrap)."""
+    """Bulk `assign` / `resume` only: bootstrap replicates of the fit (TelescopeLikelihood.bootstrap).  (The `sc` sub-commands keep
+    refusing the options: the per-barcode bootstrap is offered by `TelescopeLikelihood.bootstrap(..., cell_of_row=...)` and
+    `scTelescope.output_cell_bootstrap`.)"""
     g = {g.title: g for g in p._action_groups}['Run Modes']
     g.add_argument('--bootstrap', type=int, default=0, metavar='N',
                    help='After the report, refit the model on N Poisson resamples of the fragments (on the device) and write '
-                        '<exp_tag>-bootstrap.tsv: mean, sd and 95 %% bounds of every count and final_prop.  Default 0: none.')
+                        '<exp_tag>-bootstrap.tsv: mean, sd and 95 %% bounds (--bootstrap_ci) of every count and final_prop.  Default 0: none.')
     g.add_argument('--bootstrap_seed', type=int, default=0, metavar='S', help='Seed of the resampling (default 0).')
+    g.add_argument('--bootstrap_ci', type=float, default=0.95, metavar='L',
+                   help='Level of the bounds in <exp_tag>-bootstrap.tsv, in (0, 1) (default 0.95).')
     return p
 
 
@@ -321,6 +325,9 @@ def _set_celltypes(ts, opts, command):
 def _refuse_bootstrap(args):
     """--bootstrap with what the device's bootstrap does not offer: refused before anything is read or written."""
     n = getattr(args, 'bootstrap', 0)
+    level = getattr(args, 'bootstrap_ci', 0.95)
+    if not 0. < level < 1.:                                  # (NaN fails too)
+        raise SystemExit('telescope: --bootstrap_ci takes a level in (0, 1), not %r' % level)
     if not n:
         return
     if n < 0:
@@ -346,7 +353,7 @@ def run_bootstrap(ts, ts_model, opts):
     lg.info('Bootstrap: %d replicates, seed %d' % (n, opts.bootstrap_seed))
     stime = time()
     fits = ts_model.bootstrap(n, opts.bootstrap_seed, method=opts.reassign_mode, thresh=opts.conf_prob, loglev=lg.INFO)
-    ts.output_bootstrap(ts_model, fits, opts.outfile_path('bootstrap.tsv'))
+    ts.output_bootstrap(ts_model, fits, opts.outfile_path('bootstrap.tsv'), getattr(opts, 'bootstrap_ci', 0.95))
     lg.info('Bootstrap completed in %s' % format_minutes(time() - stime))
 
 

@@ -22,6 +22,11 @@
 // Twin columns (tsem_set_model: same rows, same scores in the whole matrix) are twins in every replicate and share one accumulation,
 // as in k_update.  Columns that are twins only inside one replicate (the rows that tell them apart drew 0) are not recognised: their
 // sums may differ in the last bit, and a tie between them can fall differently from the reference's.
+//
+// tsem_bootstrap_groups runs the same body (bt_run) with a GROUP SINK: the final sweep's fourth instantiation also adds every value
+// m A[i, j] of a row in a group into the slot of (group, j) in the pattern P of the group map (tsem_cells.hip builds it, once per map),
+// one fp64 global atomic each, slots x R accumulators per batch; after k_boot_finish a thread per slot folds the batch's replicates, in
+// replicate order, into mean and M2 (Welford) and clears the accumulators.  tsem_bootstrap passes no sink and launches what it did.
 #include "tsem_internal.h"
 
 namespace {
@@ -66,6 +71,12 @@ struct BtArgs {
   const uint32_t* ctl;
   int64_t rows_per_block;
   BtDraw draw;
+  // the group sink of the final sweep (MODE 3): the row -> group map, the pattern P and the batch's accumulators, one per slot and replicate
+  const int32_t* grp;              // [N] -1 = none
+  int32_t G;
+  const int64_t* gptr;             // [G + 1] first slot of every group
+  const int32_t* gcols;            // [slots] the slots' columns, ascending within a group
+  double* gacc;                    // [slots x R]
 };
 
 __device__ __forceinline__ double bt_recip0(double v) {    // sparse_plus.py:16-22
@@ -85,8 +96,10 @@ __device__ __forceinline__ void bt_add(const BtArgs& A, double* hot, int col, in
 }
 
 // The sweep over the CSR rows for one batch.  MODE 0: the replicates' statistics and pisum0 (into acc); 1: one E-step and the column
-// sums of the M-step for the replicates still running; 2: the last E-step again, the log-likelihood and the counts of one method.
-// A workgroup takes a contiguous range of rows, 8 lanes a row.
+// sums of the M-step for the replicates still running; 2: the last E-step again, the log-likelihood and the counts of one method;
+// 3: what 2 does and, for every value m v != 0 of a row in a group, one fp64 atomic into the slot of (group, column) in the pattern P —
+// the group and its slots' range are read once per row and shared by the row's 8 lanes, the slot is found by a binary search in the
+// group's columns.  A workgroup takes a contiguous range of rows, 8 lanes a row.
 template <int MODE>
 __global__ __launch_bounds__(BT_T) void k_boot_sweep(BtArgs A) {
   extern __shared__ double bt_hot[];                       // [H x R]
@@ -125,6 +138,14 @@ __global__ __launch_bounds__(BT_T) void k_boot_sweep(BtArgs A) {
     mm &= live;
     if (!mm || !cls) continue;
     const int64_t a = A.indptr[row], b = A.indptr[row + 1];
+    [[maybe_unused]] int64_t glo = 0, ghi = 0;             // MODE 3: the slots of the row's group (none: the row is in no group)
+    if constexpr (MODE == 3) {
+      const int32_t g = __shfl(sub == 0 ? A.grp[row] : 0, 0, BT_W);
+      if ((uint32_t)g < (uint32_t)A.G) {
+        const int64_t p = sub < 2 ? A.gptr[g + sub] : 0;
+        glo = __shfl(p, 0, BT_W); ghi = __shfl(p, 1, BT_W);
+      }
+    }
 
     if constexpr (MODE == 0) {                             // pisum0 (model.py:699): the unique rows' Q
       if (cls == 1) {
@@ -229,6 +250,16 @@ __global__ __launch_bounds__(BT_T) void k_boot_sweep(BtArgs A) {
             default: v = z > 0.0 ? 1.0 : 0.0; break;         // all
           }
           if (v != 0.0) bt_add(A, bt_hot, col, A.H ? A.hot_slot[col] : -1, r, m * v);
+          if constexpr (MODE == 3) {
+            if (v != 0.0 && glo < ghi) {
+              int64_t lo = glo, hi = ghi;
+              while (lo < hi) {
+                const int64_t mid = lo + (hi - lo) / 2;
+                if (A.gcols[mid] < col) lo = mid + 1; else hi = mid;
+              }
+              if (lo < ghi && A.gcols[lo] == col) atomicAdd(&A.gacc[lo * R + r], m * v);   // (P holds every stored (group, column))
+            }
+          }
         }
       }
     }
@@ -249,7 +280,7 @@ __global__ __launch_bounds__(BT_T) void k_boot_sweep(BtArgs A) {
       atomicAdd((unsigned long long*)&sc[S_NFRAG], st_bits[tid][1]);
     }
   }
-  if constexpr (MODE == 2) {
+  if constexpr (MODE >= 2) {
 #pragma unroll
     for (int r = 0; r < BT_RMAX; ++r) {
       if (r >= R) continue;                                  // (uniform)
@@ -399,6 +430,50 @@ __global__ __launch_bounds__(256) void k_boot_finish(int K, int R, int rep0, con
   }
 }
 
+// The group sink's fold, after k_boot_finish of the batch: a thread per slot of P takes the batch's replicates in replicate order —
+// a good one (fragments, and a log-likelihood that is not NaN: k_boot_finish's test, the same words) by Welford's update, d = x - mean;
+// mean += d / k; M2 += d (x - mean) — keeps the values where asked (NaN for a bad replicate) and clears the accumulators.
+__global__ __launch_bounds__(256) void k_boot_fold(int64_t n_slots, int R, int rep0, const double* __restrict__ scal,
+                                                   const int32_t* __restrict__ used, double* __restrict__ gacc, double* __restrict__ mean,
+                                                   double* __restrict__ m2, double* __restrict__ values) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_slots) return;
+  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  int k = used[0];
+  double mu = mean[s], q = m2[s];
+  for (int r = 0; r < R; ++r) {
+    const bool good = __double_as_longlong(scal[r * BT_SCAL + S_NFRAG]) != 0ll && !isnan(scal[r * BT_SCAL + S_LNL]);
+    const double x = gacc[s * R + r];
+    if (good) {
+      ++k;
+      const double d = x - mu;
+      mu += d / (double)k;
+      q += d * (x - mu);
+    }
+    if (values) values[(int64_t)(rep0 + r) * n_slots + s] = good ? x : nan;
+    gacc[s * R + r] = 0.0;
+  }
+  mean[s] = mu; m2[s] = q;
+}
+// ... the good replicates so far (after the fold that read the count)
+__global__ void k_boot_fold_count(int R, const double* __restrict__ scal, int32_t* __restrict__ used) {
+  if (blockIdx.x || threadIdx.x) return;
+  int k = used[0];
+  for (int r = 0; r < R; ++r)
+    k += (__double_as_longlong(scal[r * BT_SCAL + S_NFRAG]) != 0ll && !isnan(scal[r * BT_SCAL + S_LNL])) ? 1 : 0;
+  used[0] = k;
+}
+// ... and after the last batch: NaN means without a good replicate, M2 into sd (ddof 1; NaN below two good replicates)
+__global__ __launch_bounds__(256) void k_boot_fold_end(int64_t n_slots, const int32_t* __restrict__ used, double* __restrict__ mean,
+                                                       double* __restrict__ m2) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_slots) return;
+  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  const int k = used[0];
+  if (k < 1) mean[s] = nan;
+  m2[s] = k < 2 ? nan : sqrt(m2[s] / (double)(k - 1));
+}
+
 __global__ void k_boot_mult(BtDraw D, int rep, int64_t row_begin, int64_t n, uint8_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = (uint8_t)bt_draw(D, row_begin + i, rep);
@@ -424,7 +499,9 @@ BtDraw bt_make_draw(const tsem_ctx* h, uint64_t seed) {
 void bt_free(tsem_ctx* h) {
   dfree(h->d_bt_pi); dfree(h->d_bt_theta); dfree(h->d_bt_counts); dfree(h->d_bt_lnl); dfree(h->d_bt_nfrags); dfree(h->d_bt_niter);
   dfree(h->d_bt_conv);
+  dfree(h->d_bg_mean); dfree(h->d_bg_sd); dfree(h->d_bg_vals);
   h->bt_nrep = 0; h->bt_R = h->bt_H = 0;
+  h->bg_nrep = h->bg_used = h->bg_kept = h->bg_groups = 0; h->bg_nnz = 0;
 }
 
 template <int MODE>
@@ -434,32 +511,55 @@ int bt_sweep(tsem_ctx* h, const BtArgs& A, int grid) {
   return TSEM_OK;
 }
 
-}  // namespace
+struct BtSink { int keep_values; };                        // tsem_bootstrap_groups: per-group statistics beside the plain results
 
-extern "C" {
-
-void tsem_boot_free(tsem_ctx* h) { bt_free(h); }
-
-int tsem_bootstrap(tsem_ctx* h, int32_t n_rep, uint64_t seed, const uint8_t* mult, int32_t method, double thresh, double epsilon,
-                   int32_t max_iter) {
+// the body of tsem_bootstrap and tsem_bootstrap_groups: the latter passes a sink, which changes the final sweep's instantiation (the
+// pattern's accumulators), adds the fold after every batch and may lower the batch; without one nothing differs from before
+int bt_run(tsem_ctx* h, int32_t n_rep, uint64_t seed, const uint8_t* mult, int32_t method, double thresh, double epsilon, int32_t max_iter,
+           const BtSink* sink) {
   if (!h || !h->d_indptr) return TSEM_ERR_ARG;
   if (int rc = ensure_device(h)) return rc;
-  if (tsem_comm_on(h)) TSEM_FAIL(TSEM_ERR_ARG, "tsem_bootstrap: row-sharded handles are not supported (one GPU per run)");
+  const std::string who = sink ? "tsem_bootstrap_groups" : "tsem_bootstrap";
+  if (tsem_comm_on(h)) TSEM_FAIL(TSEM_ERR_ARG, who + ": row-sharded handles are not supported (one GPU per run)");
   if (h->opt_reproducible)
-    TSEM_FAIL(TSEM_ERR_ARG, "tsem_bootstrap: option \"reproducible\" is set, and the bootstrap's column sums are unordered fp64 atomics: not supported");
-  if (!h->have_rowstats || !h->d_row_cls || !h->d_row_code) TSEM_FAIL(TSEM_ERR_ARG, "tsem_bootstrap: no row statistics (tsem_rowstats)");
-  if (!h->d_lut || h->lut_len <= 0) TSEM_FAIL(TSEM_ERR_ARG, "tsem_bootstrap: no score table (tsem_set_lut)");
-  if (!h->have_model || !h->d_twin_rep) TSEM_FAIL(TSEM_ERR_ARG, "tsem_bootstrap: no model (tsem_set_model gives the priors and the twin classes)");
-  if (h->K <= 0) TSEM_FAIL(TSEM_ERR_ARG, "tsem_bootstrap: the matrix has no columns");
-  if (n_rep < 1) TSEM_FAIL(TSEM_ERR_ARG, "tsem_bootstrap: n_rep must be at least 1");
-  if (max_iter < 1) TSEM_FAIL(TSEM_ERR_ARG, "tsem_bootstrap: max_iter must be at least 1");
+    TSEM_FAIL(TSEM_ERR_ARG, who + ": option \"reproducible\" is set, and the bootstrap's column sums are unordered fp64 atomics: not supported");
+  if (!h->have_rowstats || !h->d_row_cls || !h->d_row_code) TSEM_FAIL(TSEM_ERR_ARG, who + ": no row statistics (tsem_rowstats)");
+  if (!h->d_lut || h->lut_len <= 0) TSEM_FAIL(TSEM_ERR_ARG, who + ": no score table (tsem_set_lut)");
+  if (!h->have_model || !h->d_twin_rep) TSEM_FAIL(TSEM_ERR_ARG, who + ": no model (tsem_set_model gives the priors and the twin classes)");
+  if (h->K <= 0) TSEM_FAIL(TSEM_ERR_ARG, who + ": the matrix has no columns");
+  if (n_rep < 1) TSEM_FAIL(TSEM_ERR_ARG, who + ": n_rep must be at least 1");
+  if (max_iter < 1) TSEM_FAIL(TSEM_ERR_ARG, who + ": max_iter must be at least 1");
   if (method != TSEM_RA_EXCLUDE && method != TSEM_RA_AVERAGE && method != TSEM_RA_CONF && method != TSEM_RA_UNIQUE && method != TSEM_RA_ALL)
-    TSEM_FAIL(TSEM_ERR_ARG, "tsem_bootstrap: method must be exclude, average, conf, unique or all (choose draws per row from numpy's stream: not offered)");
+    TSEM_FAIL(TSEM_ERR_ARG, who + ": method must be exclude, average, conf, unique or all (choose draws per row from numpy's stream: not offered)");
+  if (sink && !h->d_group && h->N) TSEM_FAIL(TSEM_ERR_ARG, who + ": no group map (tsem_set_groups)");
   bt_free(h);
   const int K = h->K;
   const int64_t N = h->N;
+  if (sink) if (int rc = tsem_build_group_pattern(h)) return rc;
+  const int64_t n_slots = sink ? h->bp_nnz : 0;
+  const int64_t stat_bytes = sink ? 16 * n_slots + (sink->keep_values ? 8 * (int64_t)n_rep * n_slots : 0) : 0;
+  const int64_t mult_bytes = mult ? (int64_t)n_rep * N : 0;
+  const int64_t res_bytes = 3 * 8 * (int64_t)n_rep * K + 32 * (int64_t)n_rep + stat_bytes;
+  auto ws_of = [&](int r) { return (int64_t)K * r * (16 + 16 + 8 + 8 + 8) + 8 * (int64_t)K + (1 << 20); };
+  size_t free_b = 0, total_b = 0;
+  TSEM_HIP(hipMemGetInfo(&free_b, &total_b));
   // batch and hot columns: options "boot_batch" / "boot_hot_columns", else the LDS budget
-  const int R = (int)std::min<int64_t>(n_rep, h->opt_boot_batch > 0 ? std::min<int64_t>(h->opt_boot_batch, BT_RMAX) : BT_RMAX);
+  int R = (int)std::min<int64_t>(n_rep, h->opt_boot_batch > 0 ? std::min<int64_t>(h->opt_boot_batch, BT_RMAX) : BT_RMAX);
+  if (n_slots > 0) {
+    // the sink's accumulators, slots x batch doubles: within option "boot_group_bytes" and what is free beside everything else; a
+    // smaller batch where the batch asked for does not fit
+    auto room = [&](int r) {
+      const int64_t avail = (int64_t)free_b - res_bytes - ws_of(r) - mult_bytes - (64ll << 20);
+      return h->opt_boot_group > 0 ? std::min<int64_t>(h->opt_boot_group, avail) : avail;
+    };
+    while (R > 1 && 8 * n_slots * R > room(R)) --R;
+    if (8 * n_slots > room(1))
+      TSEM_FAIL(TSEM_ERR_NOMEM, who + ": the accumulators of " + std::to_string(n_slots) + " (group, column) slots need " + std::to_string(8 * n_slots) +
+                " B per replicate of a batch; " + std::to_string(std::max<int64_t>(0, room(1))) + " B are allowed (option \"boot_group_bytes\" " +
+                std::to_string(h->opt_boot_group) + ", " + std::to_string(free_b) + " B free, " + std::to_string(res_bytes + ws_of(1) + mult_bytes) +
+                " B of results, workspace and multiplicities)");
+  }
+  const int64_t acc_bytes = 8 * n_slots * R;
   std::vector<int32_t> hot_col;
   {
     const int64_t want = h->opt_boot_hot < 0 ? BT_LDS_AUTO / R : std::min<int64_t>(h->opt_boot_hot, BT_LDS_SLOTS / R);
@@ -473,20 +573,28 @@ int tsem_bootstrap(tsem_ctx* h, int32_t n_rep, uint64_t seed, const uint8_t* mul
     hot_col.assign(ord.begin(), ord.begin() + H);
   }
   const int H = (int)hot_col.size();
-  const int64_t res_bytes = 3 * 8 * (int64_t)n_rep * K + 32 * (int64_t)n_rep;
-  const int64_t ws_bytes = (int64_t)K * R * (16 + 16 + 8 + 8 + 8) + 8 * (int64_t)K + (1 << 20);
-  const int64_t mult_bytes = mult ? (int64_t)n_rep * N : 0;
-  size_t free_b = 0, total_b = 0;
-  TSEM_HIP(hipMemGetInfo(&free_b, &total_b));
+  const int64_t ws_bytes = ws_of(R) + acc_bytes;
   if ((int64_t)free_b < res_bytes + ws_bytes + mult_bytes + (64ll << 20))
-    TSEM_FAIL(TSEM_ERR_NOMEM, "tsem_bootstrap: " + std::to_string(n_rep) + " replicates need " + std::to_string(res_bytes + ws_bytes + mult_bytes) +
+    TSEM_FAIL(TSEM_ERR_NOMEM, who + ": " + std::to_string(n_rep) + " replicates need " + std::to_string(res_bytes + ws_bytes + mult_bytes) +
               " B of device memory (" + std::to_string(mult_bytes) + " B of them the multiplicities given); " + std::to_string(free_b) + " B are free");
   CsrIds ids(h);
   if (int rc = ids.acquire()) return rc;
   PhaseTimer pt(h->stream);
   TSEM_ALLOC(h->d_bt_pi, (int64_t)n_rep * K); TSEM_ALLOC(h->d_bt_theta, (int64_t)n_rep * K); TSEM_ALLOC(h->d_bt_counts, (int64_t)n_rep * K);
   TSEM_ALLOC(h->d_bt_lnl, n_rep); TSEM_ALLOC(h->d_bt_nfrags, n_rep); TSEM_ALLOC(h->d_bt_niter, n_rep); TSEM_ALLOC(h->d_bt_conv, n_rep);
-  DevTmp t_mult, t_slot, t_hcol, t_tab, t_prev, t_theta, t_acc, t_ps0, t_scal, t_ctl, t_diff;
+  DevTmp t_mult, t_slot, t_hcol, t_tab, t_prev, t_theta, t_acc, t_ps0, t_scal, t_ctl, t_diff, t_gacc, t_used;
+  if (sink) {
+    TSEM_ALLOC(h->d_bg_mean, n_slots); TSEM_ALLOC(h->d_bg_sd, n_slots);
+    if (sink->keep_values) TSEM_ALLOC(h->d_bg_vals, (int64_t)n_rep * n_slots);
+    TSEM_TMP(t_used, 4);
+    TSEM_HIP(hipMemsetAsync(t_used.p, 0, 4, h->stream));
+    if (n_slots > 0) {
+      TSEM_TMP(t_gacc, acc_bytes);
+      TSEM_HIP(hipMemsetAsync(t_gacc.p, 0, (size_t)acc_bytes, h->stream));
+      TSEM_HIP(hipMemsetAsync(h->d_bg_mean, 0, 8 * (size_t)n_slots, h->stream));
+      TSEM_HIP(hipMemsetAsync(h->d_bg_sd, 0, 8 * (size_t)n_slots, h->stream));
+    }
+  }
   const int ugrid = cdiv64(K, 256);
   TSEM_TMP(t_slot, 4 * (int64_t)K); TSEM_TMP(t_hcol, 4 * (int64_t)std::max(1, H));
   TSEM_TMP(t_tab, 16 * (int64_t)K * R); TSEM_TMP(t_prev, 16 * (int64_t)K * R); TSEM_TMP(t_theta, 8 * (int64_t)K * R);
@@ -509,6 +617,8 @@ int tsem_bootstrap(tsem_ctx* h, int32_t n_rep, uint64_t seed, const uint8_t* mul
   A.mult = t_mult.as<uint8_t>(); A.hot_slot = t_slot.as<int32_t>(); A.hot_col = t_hcol.as<int32_t>();
   A.scal = t_scal.as<double>(); A.ctl = t_ctl.as<uint32_t>();
   A.draw = bt_make_draw(h, seed);
+  A.grp = h->d_group; A.G = h->n_groups; A.gptr = h->d_bp_gptr; A.gcols = h->d_bp_cols; A.gacc = t_gacc.as<double>();
+  const int fgrid = cdiv64(n_slots, 256);
   // a contiguous range of rows per workgroup (its LDS accumulators are flushed once), four workgroups per CU
   const int rows_at_once = BT_T / BT_W;
   A.rows_per_block = std::max<int64_t>(rows_at_once, ((N + 4ll * h->n_cu - 1) / (4ll * h->n_cu) + rows_at_once - 1) / rows_at_once * rows_at_once);
@@ -545,15 +655,83 @@ int tsem_bootstrap(tsem_ctx* h, int32_t n_rep, uint64_t seed, const uint8_t* mul
     // ---- the last E-step again: lnl and counts ----
     TSEM_HIP(hipMemsetAsync(t_acc.p, 0, 8 * (size_t)K * Rb, h->stream));
     A.tab = prev; A.tab2 = tab;
-    if (grid > 0) if (int rc = bt_sweep<2>(h, A, grid)) return rc;
+    if (grid > 0) if (int rc = n_slots > 0 ? bt_sweep<3>(h, A, grid) : bt_sweep<2>(h, A, grid)) return rc;
     k_boot_finish<<<ugrid, 256, 0, h->stream>>>(K, Rb, rep0, t_scal.as<double>(), t_ctl.as<uint32_t>(), tab, t_theta.as<double>(),
                                                t_acc.as<double>(), h->d_bt_pi, h->d_bt_theta, h->d_bt_counts, h->d_bt_nfrags, h->d_bt_niter,
                                                h->d_bt_conv, h->d_bt_lnl);
     TSEM_HIP(hipGetLastError());
+    if (sink) {                                              // the batch's values into the statistics (the good marks: the same scal words)
+      if (n_slots > 0) {
+        k_boot_fold<<<fgrid, 256, 0, h->stream>>>(n_slots, Rb, rep0, t_scal.as<double>(), t_used.as<int32_t>(), t_gacc.as<double>(),
+                                                  h->d_bg_mean, h->d_bg_sd, h->d_bg_vals);
+        TSEM_HIP(hipGetLastError());
+      }
+      k_boot_fold_count<<<1, 64, 0, h->stream>>>(Rb, t_scal.as<double>(), t_used.as<int32_t>());
+      TSEM_HIP(hipGetLastError());
+    }
+  }
+  if (sink) {
+    if (n_slots > 0) {
+      k_boot_fold_end<<<fgrid, 256, 0, h->stream>>>(n_slots, t_used.as<int32_t>(), h->d_bg_mean, h->d_bg_sd);
+      TSEM_HIP(hipGetLastError());
+    }
+    TSEM_HIP(hipMemcpyAsync(&h->bg_used, t_used.p, 4, hipMemcpyDeviceToHost, h->stream));
   }
   TSEM_HIP(hipStreamSynchronize(h->stream));
   h->bt_nrep = n_rep; h->bt_R = R; h->bt_H = H;
-  pt.lap("bootstrap");
+  if (sink) { h->bg_nrep = n_rep; h->bg_kept = sink->keep_values ? 1 : 0; h->bg_groups = h->n_groups; h->bg_nnz = n_slots; }
+  pt.lap(sink ? "bootstrap_groups" : "bootstrap");
+  return TSEM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void tsem_boot_free(tsem_ctx* h) { bt_free(h); }
+
+int tsem_bootstrap(tsem_ctx* h, int32_t n_rep, uint64_t seed, const uint8_t* mult, int32_t method, double thresh, double epsilon,
+                   int32_t max_iter) {
+  return bt_run(h, n_rep, seed, mult, method, thresh, epsilon, max_iter, nullptr);
+}
+
+int tsem_bootstrap_groups(tsem_ctx* h, int32_t n_rep, uint64_t seed, const uint8_t* mult, int32_t method, double thresh, double epsilon,
+                          int32_t max_iter, int32_t keep_values, int64_t* nnz) {
+  if (!h || !nnz) return TSEM_ERR_ARG;
+  *nnz = 0;
+  const BtSink sink{keep_values ? 1 : 0};
+  if (int rc = bt_run(h, n_rep, seed, mult, method, thresh, epsilon, max_iter, &sink)) return rc;
+  *nnz = h->bg_nnz;
+  return TSEM_OK;
+}
+
+int tsem_bootstrap_groups_shape(tsem_ctx* h, int32_t* n_groups, int64_t* nnz, int32_t* n_rep, int32_t* n_used, int32_t* kept) {
+  if (!h) return TSEM_ERR_ARG;
+  if (h->bg_nrep <= 0) TSEM_FAIL(TSEM_ERR_ARG, "tsem_bootstrap_groups_shape: no result (tsem_bootstrap_groups)");
+  if (n_groups) *n_groups = h->bg_groups;
+  if (nnz) *nnz = h->bg_nnz;
+  if (n_rep) *n_rep = h->bg_nrep;
+  if (n_used) *n_used = h->bg_used;
+  if (kept) *kept = h->bg_kept;
+  return TSEM_OK;
+}
+
+int tsem_bootstrap_groups_copy(tsem_ctx* h, int64_t* group_ptr, int32_t* cols, double* mean, double* sd, double* values) {
+  if (!h) return TSEM_ERR_ARG;
+  if (h->bg_nrep <= 0) TSEM_FAIL(TSEM_ERR_ARG, "tsem_bootstrap_groups_copy: no result (tsem_bootstrap_groups)");
+  if (h->bp_version != h->groups_version || !h->d_bp_gptr)
+    TSEM_FAIL(TSEM_ERR_ARG, "tsem_bootstrap_groups_copy: the group map was set again since the call (its pattern is gone)");
+  if (values && !h->bg_kept) TSEM_FAIL(TSEM_ERR_ARG, "tsem_bootstrap_groups_copy: the call kept no values (keep_values)");
+  if (int rc = ensure_device(h)) return rc;
+  const size_t S = (size_t)h->bg_nnz;
+  if (group_ptr) TSEM_HIP(hipMemcpyAsync(group_ptr, h->d_bp_gptr, 8 * ((size_t)h->bg_groups + 1), hipMemcpyDeviceToHost, h->stream));
+  if (S) {
+    if (cols) TSEM_HIP(hipMemcpyAsync(cols, h->d_bp_cols, 4 * S, hipMemcpyDeviceToHost, h->stream));
+    if (mean) TSEM_HIP(hipMemcpyAsync(mean, h->d_bg_mean, 8 * S, hipMemcpyDeviceToHost, h->stream));
+    if (sd) TSEM_HIP(hipMemcpyAsync(sd, h->d_bg_sd, 8 * S, hipMemcpyDeviceToHost, h->stream));
+    if (values) TSEM_HIP(hipMemcpyAsync(values, h->d_bg_vals, 8 * S * (size_t)h->bg_nrep, hipMemcpyDeviceToHost, h->stream));
+  }
+  TSEM_HIP(hipStreamSynchronize(h->stream));
   return TSEM_OK;
 }
 

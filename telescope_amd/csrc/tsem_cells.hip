@@ -214,11 +214,171 @@ int run_tile(tsem_ctx* h, CsrIds& ids, const TileBufs& B, int method, double thr
   return keep_runs(h, B, n_runs);
 }
 
+// ---- the pattern P of the group map (tsem_bootstrap_groups): the distinct (group, column) of the grouped rows' stored entries, ordered
+// by (group, column).  The same tiles of groups, entry keys and stable sort as the counts above, without values: the heads of the runs
+// of equal keys ARE the pattern.  Structural: no z is read.
+// scratch per stored entry of a pattern tile: keys x 2, run heads, their scan, the rows' entry offsets; the sort's storage beside them
+constexpr int64_t BP_BYTES_PER_ENTRY = 32;
+
+__global__ void k_bp_compact(int64_t n, const uint32_t* __restrict__ head, const uint32_t* __restrict__ hscan, const uint64_t* __restrict__ key,
+                             uint64_t* __restrict__ dkey) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && head[i]) dkey[hscan[i] - 1] = key[i];
+}
+__global__ void k_bp_cols(int64_t n, const uint64_t* __restrict__ dkey, int cbits, int64_t base, int32_t* __restrict__ cols) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < n) cols[base + r] = (int32_t)(dkey[r] & ((1ull << cbits) - 1ull));
+}
+// first slot of the tile's groups [g0, g0 + ng): base + the first distinct key of the group or a later one (a binary search per group)
+__global__ void k_bp_ptr(int32_t ng, int32_t g0, int64_t n, const uint64_t* __restrict__ dkey, int cbits, int64_t base, int64_t* __restrict__ gptr) {
+  const int32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ng) return;
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if ((dkey[mid] >> cbits) < (uint64_t)g) lo = mid + 1; else hi = mid;
+  }
+  gptr[g0 + g] = base + lo;
+}
+// a group with more entries than a tile holds: its columns are marked in a K-sized row (every lane writes the same word) ...
+__global__ void k_bp_mark(int64_t n, const int32_t* __restrict__ rows, const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+                          uint32_t* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t row = rows[i];
+  for (int64_t e = indptr[row]; e < indptr[row + 1]; ++e) flag[indices[e]] = 1u;
+}
+// ... and the marked columns listed in order, the row cleared
+__global__ void k_bp_flag_cols(int32_t K, uint32_t* __restrict__ flag, const uint32_t* __restrict__ fscan, int64_t base, int32_t* __restrict__ cols) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= K) return;
+  if (flag[j]) cols[base + fscan[j] - 1] = j;
+  flag[j] = 0u;
+}
+
+int grow_pattern(tsem_ctx* h, int64_t need) {
+  if (need <= h->bp_cap && h->d_bp_cols) return TSEM_OK;
+  const int64_t cap = std::max<int64_t>(need, std::max<int64_t>(2 * h->bp_cap, 1 << 16));
+  int32_t* c = nullptr;
+  TSEM_ALLOC(c, cap);
+  if (h->bp_nnz && h->d_bp_cols) {
+    (void)hipMemcpyAsync(c, h->d_bp_cols, 4 * (size_t)h->bp_nnz, hipMemcpyDeviceToDevice, h->stream);
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { dfree(c); TSEM_HIP(e); }
+  }
+  dfree(h->d_bp_cols);
+  h->d_bp_cols = c; h->bp_cap = cap;
+  return TSEM_OK;
+}
+
+int build_pattern(tsem_ctx* h) {
+  if (h->bp_version == h->groups_version && h->d_bp_gptr) return TSEM_OK;
+  if (int rc = build_grouping(h)) return rc;
+  PhaseTimer pt(h->stream);
+  const int32_t G = h->n_groups;
+  const int K = h->K;
+  h->bp_version = ~0ull; h->bp_nnz = 0; h->bp_groups = 0;
+  TSEM_ALLOC(h->d_bp_gptr, (int64_t)G + 1);
+  if (int rc = grow_pattern(h, 1)) return rc;
+  CsrIds ids(h);
+  const int64_t total = G ? h->gc_gent[G] : 0, grouped = G ? h->gc_rptr[G] : 0;
+  const int64_t budget = h->opt_group_tile > 0 ? h->opt_group_tile : ((int64_t)1 << 30);
+  int64_t cap = std::min<int64_t>(std::max<int64_t>(budget / BP_BYTES_PER_ENTRY, (int64_t)K + 1), (int64_t)1 << 30);
+  cap = std::max<int64_t>(1, std::min(cap, std::max<int64_t>(total, grouped)));
+  const int cbits = bits_for((uint64_t)std::max(0, K - 1));
+  DevTmp bufs, flag_t, fscan_t, ftmp_t;
+  int64_t* off = nullptr; uint64_t *key = nullptr, *key2 = nullptr; uint32_t *head = nullptr, *hscan = nullptr;
+  void* sort_tmp = nullptr;
+  size_t sort_bytes = 0, flag_bytes = 0;
+  if (total > 0) {
+    if (int rc = ids.acquire()) return rc;
+    size_t sb = 0, sc = 0;
+    TSEM_HIP(rocprim::radix_sort_keys(nullptr, sb, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)cap, 0, std::min(64, cbits + 32), h->stream));
+    TSEM_HIP(rocprim::inclusive_scan(nullptr, sc, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)cap, rocprim::plus<uint32_t>(), h->stream));
+    sort_bytes = std::max(sb, sc);
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t c1 = (size_t)cap + 1;
+    const size_t sz[5] = {8 * c1, 8 * c1, 8 * c1, 4 * c1, 4 * c1};
+    size_t tot = sort_bytes;
+    for (size_t s : sz) tot += up(s);
+    TSEM_TMP(bufs, tot);
+    char* p = bufs.as<char>();
+    off = (int64_t*)p; p += up(sz[0]);
+    key = (uint64_t*)p; p += up(sz[1]);
+    key2 = (uint64_t*)p; p += up(sz[2]);
+    head = (uint32_t*)p; p += up(sz[3]);
+    hscan = (uint32_t*)p; p += up(sz[4]);
+    sort_tmp = p;
+  }
+  for (int32_t g = 0; g < G;) {
+    const int64_t r0 = h->gc_rptr[g], e0 = h->gc_gent[g];
+    if (h->gc_gent[g + 1] - e0 > cap || h->gc_rptr[g + 1] - r0 > cap) {   // one group beyond a tile: marks instead of a sort
+      const int64_t nr = h->gc_rptr[g + 1] - r0;
+      if (!flag_t.p) {
+        TSEM_TMP(flag_t, 4 * (size_t)K); TSEM_TMP(fscan_t, 4 * (size_t)K);
+        TSEM_HIP(rocprim::inclusive_scan(nullptr, flag_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)K, rocprim::plus<uint32_t>(), h->stream));
+        TSEM_TMP(ftmp_t, flag_bytes);
+        TSEM_HIP(hipMemsetAsync(flag_t.p, 0, 4 * (size_t)K, h->stream));
+      }
+      k_bp_mark<<<cdiv64(nr, 256), 256, 0, h->stream>>>(nr, h->d_gc_rows + r0, h->d_indptr, h->d_indices, flag_t.as<uint32_t>());
+      TSEM_HIP(hipGetLastError());
+      size_t tb = flag_bytes;
+      TSEM_HIP(rocprim::inclusive_scan(ftmp_t.p, tb, flag_t.as<uint32_t>(), fscan_t.as<uint32_t>(), (size_t)K, rocprim::plus<uint32_t>(), h->stream));
+      uint32_t n_cols = 0;
+      TSEM_HIP(hipMemcpyAsync(&n_cols, fscan_t.as<uint32_t>() + K - 1, 4, hipMemcpyDeviceToHost, h->stream));
+      TSEM_HIP(hipStreamSynchronize(h->stream));
+      if (int rc = grow_pattern(h, h->bp_nnz + n_cols)) return rc;
+      k_bp_flag_cols<<<cdiv64(K, 256), 256, 0, h->stream>>>(K, flag_t.as<uint32_t>(), fscan_t.as<uint32_t>(), h->bp_nnz, h->d_bp_cols);
+      TSEM_HIP(hipGetLastError());
+      TSEM_HIP(hipMemcpyAsync(h->d_bp_gptr + g, &h->bp_nnz, 8, hipMemcpyHostToDevice, h->stream));
+      TSEM_HIP(hipStreamSynchronize(h->stream));
+      h->bp_nnz += n_cols;
+      ++g;
+      continue;
+    }
+    int32_t g1 = g + 1;
+    while (g1 < G && h->gc_gent[g1 + 1] - e0 <= cap && h->gc_rptr[g1 + 1] - r0 <= cap) ++g1;
+    const int64_t n = h->gc_rptr[g1] - r0, ne = h->gc_gent[g1] - e0;
+    uint32_t n_runs = 0;
+    if (ne > 0) {
+      const int kbits = cbits + bits_for((uint64_t)(g1 - g - 1));
+      k_gc_tile_rows<<<cdiv64(n + 1, 256), 256, 0, h->stream>>>(n, r0, h->d_gc_rows, h->d_gc_eoff, nullptr, off, nullptr);
+      TSEM_HIP(hipGetLastError());
+      k_gc_entry_keys<<<cdiv64(n, 256), 256, 0, h->stream>>>(n, r0, h->d_gc_rows, h->d_gc_key, off, h->d_indptr, h->d_indices, g, cbits, key);
+      TSEM_HIP(hipGetLastError());
+      size_t tb = sort_bytes;
+      TSEM_HIP(rocprim::radix_sort_keys(sort_tmp, tb, key, key2, (size_t)ne, 0, kbits, h->stream));
+      k_run_heads<<<cdiv64(ne, 256), 256, 0, h->stream>>>(ne, key2, head);
+      TSEM_HIP(hipGetLastError());
+      tb = sort_bytes;
+      TSEM_HIP(rocprim::inclusive_scan(sort_tmp, tb, head, hscan, (size_t)ne, rocprim::plus<uint32_t>(), h->stream));
+      TSEM_HIP(hipMemcpyAsync(&n_runs, hscan + ne - 1, 4, hipMemcpyDeviceToHost, h->stream));
+      TSEM_HIP(hipStreamSynchronize(h->stream));
+      k_bp_compact<<<cdiv64(ne, 256), 256, 0, h->stream>>>(ne, head, hscan, key2, key);   // (the unsorted keys are no longer needed)
+      TSEM_HIP(hipGetLastError());
+      if (int rc = grow_pattern(h, h->bp_nnz + n_runs)) return rc;
+      k_bp_cols<<<cdiv64(n_runs, 256), 256, 0, h->stream>>>(n_runs, key, cbits, h->bp_nnz, h->d_bp_cols);
+      TSEM_HIP(hipGetLastError());
+    }
+    k_bp_ptr<<<cdiv64(g1 - g, 256), 256, 0, h->stream>>>(g1 - g, g, (int64_t)n_runs, key, cbits, h->bp_nnz, h->d_bp_gptr);
+    TSEM_HIP(hipGetLastError());
+    h->bp_nnz += n_runs;
+    g = g1;
+  }
+  TSEM_HIP(hipMemcpyAsync(h->d_bp_gptr + G, &h->bp_nnz, 8, hipMemcpyHostToDevice, h->stream));
+  TSEM_HIP(hipStreamSynchronize(h->stream));
+  h->bp_groups = G;
+  h->bp_version = h->groups_version;
+  pt.lap("bootstrap_groups: pattern");
+  return TSEM_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int tsem_build_grouping(tsem_ctx* h) { return build_grouping(h); }   // (the per-cell fits start from the same grouping)
+int tsem_build_group_pattern(tsem_ctx* h) { return build_pattern(h); }
 
 // scTelescope.output_report's per-barcode counts (model.py:611-625) as a sparse matrix: see the top of this file.
 int tsem_group_counts(tsem_ctx* h, int method, double thresh, int which, const int32_t* picks, int64_t* nnz) {

@@ -251,6 +251,17 @@ struct tsem_ctx {
   unsigned long long* d_bt_nfrags = nullptr;   // [bt_nrep] sum of the multiplicities
   int32_t *d_bt_niter = nullptr, *d_bt_conv = nullptr;   // [bt_nrep]
   int32_t bt_nrep = 0, bt_R = 0, bt_H = 0;   // replicates of the last call (0: none), its batch size and hot columns
+  // ... per group (tsem_bootstrap_groups): the pattern P of the group map — the distinct (group, column) of the grouped rows' stored
+  // entries, built by tsem_cells.hip and cached per map — and the last call's statistics per slot of P
+  int64_t opt_boot_group = 0;       // option "boot_group_bytes": bytes of the per-batch accumulators of P at most; 0 auto (what is free)
+  uint64_t bp_version = ~0ull;      // the map version the pattern below was built from
+  int64_t* d_bp_gptr = nullptr;     // [bp_groups + 1] first slot of every group
+  int32_t* d_bp_cols = nullptr;     // [bp_cap] the slots' columns, ascending within a group
+  int64_t bp_nnz = 0, bp_cap = 0;   // slots of P / capacity of d_bp_cols
+  int32_t bp_groups = 0;
+  double *d_bg_mean = nullptr, *d_bg_sd = nullptr, *d_bg_vals = nullptr;   // [bg_nnz] mean, M2 then sd | [bg_nrep x bg_nnz] kept values
+  int64_t bg_nnz = 0;
+  int32_t bg_nrep = 0, bg_used = 0, bg_kept = 0, bg_groups = 0;   // the last grouped call (bg_nrep 0: none): replicates, good ones, values kept
   int32_t *d_rep_nb = nullptr, *d_rep_rows = nullptr;   // [N] scratch of tsem_report_colsums, kept between calls
   unsigned long long* d_rep_n = nullptr;
   struct RpChunk* d_rep_chunks = nullptr; int64_t n_rep_chunks = 0; int rep_chunk_E = 0;   // k_report_pack's packing of the rows into wave-sized chunks (tsem_report_pack.h)

@@ -115,6 +115,7 @@ void tsem_free_matrix(tsem_ctx* h) {
   dfree(h->d_group); h->n_groups = 0;
   dfree(h->d_gc_key); dfree(h->d_gc_rows); dfree(h->d_gc_eoff); h->gc_version = ~0ull; h->gc_rptr.clear(); h->gc_gent.clear();
   dfree(h->d_gc_ogrp); dfree(h->d_gc_ocol); dfree(h->d_gc_oval); dfree(h->d_gc_gptr); h->gc_nnz = h->gc_cap = 0; h->gc_groups = 0;
+  dfree(h->d_bp_gptr); dfree(h->d_bp_cols); h->bp_version = ~0ull; h->bp_nnz = h->bp_cap = 0; h->bp_groups = 0;
   tsem_cellem_free(h);
   tsem_boot_free(h);
   if (h->d_gtile) { (void)hipFree(h->d_gtile); h->d_gtile = nullptr; h->gtile_bytes = 0; }
@@ -219,6 +220,10 @@ int tsem_set_option(tsem_ctx* h, const char* key, int64_t v) {
   else if (k == "boot_batch") {                            // tsem_bootstrap: replicates per sweep over the matrix (0 auto; at most 8)
     if (v < 0) TSEM_FAIL(TSEM_ERR_ARG, "boot_batch must be 0 (auto) or a number of replicates");
     h->opt_boot_batch = v;
+  }
+  else if (k == "boot_group_bytes") {                      // tsem_bootstrap_groups: bytes of the per-batch accumulators of the pattern at most (0 auto)
+    if (v < 0) TSEM_FAIL(TSEM_ERR_ARG, "boot_group_bytes must be 0 (auto: what is free) or a number of bytes");
+    h->opt_boot_group = v;
   }
   else if (k == "cell_em_spread_entries") {                // tsem_cell_em: groups with more stored entries are spread over the grid (0 never)
     if (v < 0) TSEM_FAIL(TSEM_ERR_ARG, "cell_em_spread_entries must be 0 (never spread) or a number of stored entries");

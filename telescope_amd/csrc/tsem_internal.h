@@ -6,9 +6,11 @@
 //   tsem_report.hip  CSR row passes: z export, best hits, reassign, the streaming report pass, per-barcode sums
 //   tsem_comm.hip    collectives: RCCL resolved at run time, the in-process transport, the communicator ABI
 //   tsem_csr.hip     csr_matrix_plus primitives on fp64 CSR, numpy's legacy random draw
-//   tsem_cells.hip   sparse per-group counts of the assignment matrix; the grouping (rows of every group in order) cached per map
+//   tsem_cells.hip   sparse per-group counts of the assignment matrix; the grouping (rows of every group in order) and the pattern
+//                    (distinct (group, column) of the grouped rows' entries) cached per map
 //   tsem_cellem.hip  one EM fit per group of rows (single-cell `--pooling_mode individual` / `celltype`)
-//   tsem_boot.hip    bootstrap replicates: the EM refitted with a multiplicity per row, batches of replicates per sweep
+//   tsem_boot.hip    bootstrap replicates: the EM refitted with a multiplicity per row, batches of replicates per sweep;
+//                    with a group sink also per-(group, column) statistics over the replicates (the pattern comes from tsem_cells.hip)
 //   tsem_fz_p*.hip   instantiations of the fused kernel (tsem_fused.h), one team size per unit
 //
 // A kernel is launched only from the unit that defines it; other units go through the host functions declared here.
@@ -189,6 +191,7 @@ int tsem_rows_mask_dev(tsem_ctx* h, CsrIds& ids, int which, int method, double t
                        const int32_t* d_picks, const int64_t* d_off, double* d_mask);
 // tsem_cells.hip
 int tsem_build_grouping(tsem_ctx* h);                      // d_gc_rows / d_gc_key / d_gc_eoff, gc_rptr / gc_gent for the current group map (cached)
+int tsem_build_group_pattern(tsem_ctx* h);                 // d_bp_gptr / d_bp_cols, bp_nnz: the distinct (group, column) of the current map's rows (cached)
 // tsem_cellem.hip
 void tsem_cellem_free(tsem_ctx* h);                        // the per-cell layout and the last fit
 // tsem_boot.hip

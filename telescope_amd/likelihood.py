@@ -175,6 +175,46 @@ def check_bootstrap_args(n_rep, method, multiplicities, n_rows):
     return np.ascontiguousarray(m)
 
 
+class BootstrapCells(object):
+    """The per-cell part of a bootstrap (`BootstrapFits.cells`): statistics over the replicates of every (cell, locus) count, on the
+    structural pattern of the run — the distinct (cell, locus) of the stored entries of the cells' fragments, CSR-like: cell c owns the
+    slots `group_ptr[c] .. group_ptr[c + 1]`, whose loci `cols` ascend.  `mean`, `sd` (ddof 1) per slot over the `n_used` good
+    replicates (those whose counts are not NaN); mean is NaN when `n_used` is 0, sd when it is below 2.  `values` [n_rep x nnz]: every
+    replicate's counts (the row of a bad replicate NaN), or None when they were not kept."""
+
+    def __init__(self, n_cells, n_cols, group_ptr, cols, mean, sd, n_used, values=None):
+        self.n_cells, self.K = int(n_cells), int(n_cols)
+        self.group_ptr = np.asarray(group_ptr, dtype=np.int64)
+        self.cols = np.asarray(cols, dtype=np.int32)
+        self.mean, self.sd = np.asarray(mean, dtype=np.float64), np.asarray(sd, dtype=np.float64)
+        self.n_used = int(n_used)
+        self.values = None if values is None else np.asarray(values, dtype=np.float64)
+        if self.values is not None and self.values.shape[1:] != (len(self.cols),):
+            raise ValueError('BootstrapCells: values must be [n_rep x slots]')
+        if len(self.group_ptr) != self.n_cells + 1 or not (len(self.cols) == len(self.mean) == len(self.sd) == int(self.group_ptr[-1])):
+            raise ValueError('BootstrapCells: arrays of different shapes')
+        self.nnz = len(self.cols)
+
+    def _matrix(self, data):
+        m = sp.csr_matrix((np.array(data, dtype=np.float64), self.cols.copy(), self.group_ptr.copy()), shape=(self.n_cells, self.K))
+        m.eliminate_zeros()                                      # (NaN is kept: it is not a zero)
+        return m
+
+    def mean_matrix(self):
+        """n_cells x K scipy CSR matrix of the means, zeros dropped."""
+        return self._matrix(self.mean)
+
+    def sd_matrix(self):
+        """n_cells x K scipy CSR matrix of the standard deviations, zeros dropped."""
+        return self._matrix(self.sd)
+
+    def values_matrix(self, b):
+        """Replicate b's counts as an n_cells x K scipy CSR matrix, zeros dropped (needs keep_replicates=True)."""
+        if self.values is None:
+            raise ValueError('values_matrix: the replicates\' values were not kept (bootstrap(..., keep_replicates=True))')
+        return self._matrix(self.values[b])
+
+
 class BootstrapFits(object):
     """What `TelescopeLikelihood.bootstrap` returns: B refits of the model on resampled fragments.  `pi`, `theta`, `counts` are
     [B, K]; `n_frags` (the replicate's fragments, sum of its multiplicities), `n_iter`, `converged`, `lnl` per replicate; `info` =
@@ -190,6 +230,7 @@ class BootstrapFits(object):
         self.lnl = np.asarray(lnl, dtype=np.float64)
         self.info = dict(info or {})
         self.seed, self.method = int(seed), method
+        self.cells = None                                        # a BootstrapCells when the call was given `cell_of_row`
         self.n_rep = len(self.n_iter)
         if not (self.pi.shape == self.theta.shape == self.counts.shape and self.pi.shape[0] == self.n_rep ==
                 len(self.n_frags) == len(self.converged) == len(self.lnl)):
@@ -576,23 +617,44 @@ class TelescopeLikelihood(object):
         return fits
 
     # ---- bootstrap replicates --------------------------------------------------------------------
-    def bootstrap(self, n_rep, seed=0, method='exclude', thresh=0.9, multiplicities=None, loglev=lg.WARNING):
+    def bootstrap(self, n_rep, seed=0, method='exclude', thresh=0.9, multiplicities=None, loglev=lg.WARNING, cell_of_row=None,
+                  n_cells=None, keep_replicates=False):
         """`n_rep` refits of the model on RESAMPLED fragments, on the device over the resident matrix (tsem_bootstrap): replicate b
         gives row i a multiplicity m_i and is the fit of `raw[np.repeat(arange(N), m_b)]` with the score scale of the whole matrix
         (model.py:762-806; parameter stop test at `em_epsilon`, `max_iter`).  By default the m_i are Poisson(1) draws of the counter
         hash (`synthetic.bootstrap_multiplicities(seed, b, rows)`); `multiplicities`: a uint8 [n_rep x N] array instead.  Per
         replicate pi, theta, lnl and `counts` = column sums of `reassign(method, thresh)` over its fragments (`choose` is not
         offered).  Returns a `BootstrapFits`.  `tl.pi`, `tl.z`, `tl.lnl` and the per-cell fits are untouched; works before `em()`.
-        One GPU only, and not with engine option "reproducible" (the replicates' column sums are unordered atomics)."""
+        One GPU only, and not with engine option "reproducible" (the replicates' column sums are unordered atomics).
+
+        `cell_of_row` (with `n_cells`; as for `reassign_cell_counts`: [0, n_cells) or -1, a row in no cell): the same replicates,
+        fitted once, also give `fits.cells`, a `BootstrapCells` — mean and sd over the replicates of every cell's count at every locus
+        one of its fragments aligns to (tsem_bootstrap_groups); `keep_replicates=True` keeps every replicate's per-cell counts as
+        well (n_rep x slots doubles: tests and small runs).  Without `cell_of_row`, `fits.cells` is None."""
         mult = check_bootstrap_args(n_rep, method, multiplicities, self.N)
         if self.comm.world > 1:
             raise NotImplementedError('bootstrap: row-sharded runs (WORLD_SIZE > 1) are not supported; run it on one GPU')
-        r = self._eng.bootstrap(int(n_rep), int(seed), mult, method, thresh, self.epsilon, self.max_iter, self.K)
+        if cell_of_row is None:
+            if n_cells is not None or keep_replicates:
+                raise ValueError('bootstrap: n_cells and keep_replicates belong to cell_of_row')
+            r = self._eng.bootstrap(int(n_rep), int(seed), mult, method, thresh, self.epsilon, self.max_iter, self.K)
+        else:
+            if n_cells is None:
+                raise ValueError('bootstrap: cell_of_row needs n_cells')
+            cor, n_cells = self._check_cells(cell_of_row, n_cells, 'bootstrap')
+            self._set_cells(cor, n_cells)
+            r = self._eng.bootstrap_groups(int(n_rep), int(seed), mult, method, thresh, self.epsilon, self.max_iter, self.K,
+                                           keep_values=keep_replicates)
         fits = BootstrapFits(r['pi'], r['theta'], r['counts'], r['n_frags'], r['n_iter'], r['converged'], r['lnl'],
                              info={'batch': int(r['info'][0]), 'hot_columns': int(r['info'][1])}, seed=seed, method=method)
+        slots = ''
+        if cell_of_row is not None:
+            g = r['groups']
+            fits.cells = BootstrapCells(n_cells, self.K, g['group_ptr'], g['cols'], g['mean'], g['sd'], g['n_used'], g['values'])
+            slots = '; {:d} (cell, locus) slots'.format(fits.cells.nnz)
         keep = fits.fitted
-        lg.log(loglev, 'Bootstrap: {:d} replicates, {:d} fitted, {:d} converged; iterations min {:d} / max {:d}.'.format(
-            fits.n_rep, int(keep.sum()), int(fits.converged.sum()), int(fits.n_iter.min()), int(fits.n_iter.max())))
+        lg.log(loglev, 'Bootstrap: {:d} replicates, {:d} fitted, {:d} converged; iterations min {:d} / max {:d}{}.'.format(
+            fits.n_rep, int(keep.sum()), int(fits.converged.sum()), int(fits.n_iter.min()), int(fits.n_iter.max()), slots))
         return fits
 
     def select_z(self, which):

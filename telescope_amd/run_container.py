@@ -565,6 +565,19 @@ class scTelescope(Telescope):
                 with open(out, 'w') as fh:
                     write_dense_counts(fh, counts, self.barcodes, names)
 
+    def output_cell_bootstrap(self, fits, mean_filename, sd_filename):
+        """`<exp_tag>-TE_counts_boot_mean` / `_boot_sd` of a single-cell run's bootstrap (`tl.bootstrap(..., cell_of_row=self.cell_of_row)`): mean and standard deviation (ddof 1) of every
+        barcode's count over the good replicates (`fits.cells`, a BootstrapCells), in the layout and by the writers of the count
+        matrix itself — dense tsv or Matrix Market, per `--count_format` (the file names are given with `.tsv`)."""
+        fmt = getattr(self.opts, 'count_format', 'tsv')
+        names = sorted(self.feat_index, key=self.feat_index.get)
+        for out, matrix in ((mean_filename, fits.cells.mean_matrix()), (sd_filename, fits.cells.sd_matrix())):
+            if fmt == 'mtx':
+                write_mtx_counts(out[:out.rfind('.')] + '.mtx', matrix, self.barcodes, names)
+            else:
+                with open(out, 'w') as fh:
+                    write_dense_counts(fh, matrix, self.barcodes, names)
+
     def write_cell_stats(self, tl, fits, filename):
         """`<exp_tag>-cell_stats.tsv` of `--pooling_mode individual`: one line per barcode — its fragments, how many of them are
         ambiguous, the features it touches, and its fit's iterations, convergence and log-likelihood."""

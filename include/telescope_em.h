@@ -499,6 +499,26 @@ int  tsem_bootstrap_groups_copy(tsem_ctx* h, int64_t* group_ptr, int32_t* cols, 
 /* the default multiplicities of replicate `rep` for the handle's rows [row_begin, row_end), computed on the device */
 int  tsem_bootstrap_mult(tsem_ctx* h, uint64_t seed, int32_t rep, int64_t row_begin, int64_t row_end, uint8_t* out);
 
+/* ---- single-cell mode: UMI duplicates (telescope_amd/csrc/tsem_umi.hip) ----
+ * The copies of one molecule carry the same cell barcode and the same UMI.  cell_of_row[i] in [-1, n_cells) and umi_of_row[i] in
+ * [-1, n_umis) are HOST arrays of the loaded matrix's N rows (-1: no barcode / no UMI); they are copied to the device and checked there.
+ *   class           the rows with cell >= 0, umi >= 0 and equal (cell, umi)
+ *   link            two rows of one class that both store an entry in the same column (whatever the scores; column ids in any order)
+ *   component       a connected set of a class under the links (A-B, B-C: A and C belong together); a row in no class, and a row
+ *                   without stored entries, is a component by itself
+ *   representative  the row of a component whose largest stored raw score code is largest; the smallest row index among equals
+ * rep_of_row[i] = the representative of i's component (row i is kept iff rep_of_row[i] == i), stats4 = { rows in classes, classes,
+ * components among the rows in classes, rows dropped }.  Integer work: the result is the same whatever the launch order.
+ * Needs only tsem_load_scores (no score table, no model) and changes nothing else the handle holds: parameters, z buffers, group map,
+ * layout, per-cell fits and bootstrap results stay as they are (with option "drop_csr_indices" the column ids are rebuilt for the call).
+ * The components settle in rounds driven by the host, at most as many as the longest class has rows; a call that would need more ends
+ * with TSEM_ERR_TIMEOUT and a message (never seen: reported instead of going on).  Memory: up to 72 B per row and 32 B per stored entry of
+ * the rows in multi-row classes plus the sort's storage, not tiled: TSEM_ERR_NOMEM with the byte counts in the message if that does not
+ * fit.  TSEM_ERR_ARG with a message: a value out of range, a NULL pointer with N > 0, no matrix loaded, a handle with a communicator
+ * attached (single GPU only, like tsem_group_counts).  N = 0 and "no row in any class" are valid calls. */
+int  tsem_umi_dedup(tsem_ctx* h, const int32_t* cell_of_row, const int32_t* umi_of_row, int32_t n_cells, int32_t n_umis,
+                    int32_t* rep_of_row /* N */, int64_t* stats4);
+
 /* ---- csr_matrix_plus primitives on arbitrary fp64 CSR (sparse_plus.py) ---- */
 /* All three: indptr[n_rows + 1] is a HOST array and is checked on the host before the device is touched. TSEM_ERR_ARG (text in
  * tsem_last_error(NULL)) for n_rows < 0, n_cols < 0, indptr NULL, indptr[0] != 0, any indptr[i + 1] < indptr[i], or data / out

@@ -26,14 +26,15 @@ class EngineError(RuntimeError):
     code = 0
 
 
-# host / ABI, set-up, EM support, report / row passes, collectives, CSR primitives, per-cell counts, per-cell fits, bootstrap
-# (telescope_amd/csrc/tsem_internal.h)
-LIB_UNITS = ('tsem_host', 'tsem_setup', 'tsem_em', 'tsem_report', 'tsem_comm', 'tsem_csr', 'tsem_cells', 'tsem_cellem', 'tsem_boot')
+# host / ABI, set-up, EM support, report / row passes, collectives, CSR primitives, per-cell counts, per-cell fits, bootstrap,
+# UMI duplicates (telescope_amd/csrc/tsem_internal.h)
+LIB_UNITS = ('tsem_host', 'tsem_setup', 'tsem_em', 'tsem_report', 'tsem_comm', 'tsem_csr', 'tsem_cells', 'tsem_cellem', 'tsem_boot',
+             'tsem_umi')
 FZ_UNITS = tuple('tsem_fz_p%d' % p for p in range(1, 9))
 
 
 def build_library(force=False, verbose=False, out=None):
-    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  Seventeen translation units — the nine of
+    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  Eighteen translation units — the ten of
     LIB_UNITS and the eight that instantiate the fused kernel for one team size each (most of the build time) — are compiled
     in parallel and linked into one shared object."""
     from concurrent.futures import ThreadPoolExecutor
@@ -233,6 +234,7 @@ def lib():
     L.tsem_bootstrap_groups.argtypes = [vp, i32, u64, vp, i32, dbl, dbl, i32, i32, C.POINTER(i64)]
     L.tsem_bootstrap_groups_shape.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.tsem_bootstrap_groups_copy.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.tsem_umi_dedup.argtypes = [vp, vp, vp, i32, i32, vp, vp]
     L.tsem_csr_norm_rows.argtypes = [C.c_int, i64, vp, vp, vp]
     L.tsem_csr_binmax_rows.argtypes = [C.c_int, i64, i32, vp, vp, vp]
     L.tsem_csr_scale.argtypes = [C.c_int, C.c_int, i64, i32, vp, vp, vp]
@@ -678,6 +680,18 @@ class Engine(object):
         out = np.empty(max(0, int(row_end) - int(row_begin)), np.uint8)
         self._ck(self._L.tsem_bootstrap_mult(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(rep), int(row_begin), int(row_end), ptr(out)))
         return out
+
+    def umi_dedup(self, cell_of_row, umi_of_row, n_cells, n_umis):
+        """The representative of every row's UMI component (tsem_umi_dedup): (rep int32 [N], stats int64 [4] = rows in classes,
+        classes, components among them, rows dropped).  Row i is kept iff rep[i] == i."""
+        n, _, _ = self.dims()
+        cor = np.ascontiguousarray(cell_of_row, dtype=np.int32)
+        uor = np.ascontiguousarray(umi_of_row, dtype=np.int32)
+        if cor.shape != (n,) or uor.shape != (n,):
+            raise ValueError('cell_of_row and umi_of_row must have one entry per row')
+        rep, stats = np.empty(n, np.int32), np.zeros(4, np.int64)
+        self._ck(self._L.tsem_umi_dedup(self._h, ptr(cor), ptr(uor), int(n_cells), int(n_umis), ptr(rep), ptr(stats)))
+        return rep, stats
 
     # -- instrumentation --
     def kernel_stats(self, reset=False):

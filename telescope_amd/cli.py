@@ -12,6 +12,8 @@ telescope/__main__.py:49-92).  Same option names and defaults, same log lines, s
 
 `sc` is single-cell mode (scTelescope, telescope/utils/model.py:567-629; scIDOptions, telescope_assign.py:203-370): per-barcode
 count matrices, built sparse on the device (`<exp_tag>-TE_counts[_<method>].tsv`, or `.mtx` with `--count_format mtx`).
+`sc assign --umi_tag UB` (not in the reference) reads the UMIs, stores them in the checkpoint and collapses the PCR duplicates on the
+device before the model is built (`<exp_tag>-umi_stats.tsv`); `sc resume` collapses iff its checkpoint holds UMIs; `--ignore_umi`.
 
 `assign` (telescope/telescope_assign.py:372-451) uses telescope_amd/loader.py, a pysam-free
 restatement of the reference's sequential loader; `--ncpu > 1` is not offered.  `--updated_sam` writes `<exp_tag>-updated.bam`
@@ -160,7 +162,16 @@ def _sc_args(p, assign):
     groups['Input Options'].add_argument('--celltype_tsv', metavar='FILE', default=None,
                                          help='With --pooling_mode celltype: tab-separated barcode<TAB>celltype lines, no header '
                                               '(empty lines and lines starting with # are skipped).')
+    if assign:
+        groups['Input Options'].add_argument('--umi_tag', type=str, default=None, metavar='TAG',
+                                             help='Name of the Z-type field holding the UMI of each read (e.g. UB).  The UMIs are stored in '
+                                                  'the checkpoint and the PCR duplicates — fragments of one barcode and UMI that share a '
+                                                  'locus, directly or through a chain of such fragments — are collapsed on the device to '
+                                                  'the best-scoring one before the model is built; <exp_tag>-umi_stats.tsv lists the '
+                                                  'fragments kept per barcode.  Default: none, fragments are counted.')
     g = groups['Run Modes']
+    g.add_argument('--ignore_umi', action='store_true',
+                   help='Do not collapse UMI duplicates (the UMIs of --umi_tag are still read and stored by `sc assign`).')
     g.add_argument('--use_every_reassign_mode', action='store_true',
                    help='Output count matrices generated using every reassign mode (conf, all, unique, exclude, choose, average).')
     g.add_argument('--pooling_mode', default='pseudobulk', choices=['pseudobulk', 'individual', 'celltype'],
@@ -194,6 +205,8 @@ class ResumeOptions(object):
         lines += ['    {:30}{}'.format(k + ':', getattr(self, k)) for k in keys if hasattr(self, k)]
         if getattr(self, 'celltype_tsv', None) is not None:
             lines.append('    {:30}{}'.format('celltype_tsv:', self.celltype_tsv))
+        if getattr(self, 'umi_tag', None) is not None:
+            lines.append('    {:30}{}'.format('umi_tag:', self.umi_tag))
         return '\n'.join(lines)
 
 
@@ -322,6 +335,27 @@ def _set_celltypes(ts, opts, command):
         raise SystemExit('telescope %s: --celltype_tsv %s: %s' % (command, opts.celltype_tsv, e))
 
 
+def _refuse_umi_updated_sam(args):
+    """`sc assign --umi_tag` with --updated_sam: refused before anything is read or written (the alignments of the dropped
+    fragments would need tags of their own)."""
+    if getattr(args, 'umi_tag', None) is not None and getattr(args, 'updated_sam', False):
+        raise SystemExit('telescope sc assign: --umi_tag with --updated_sam is not supported (the alignments of the collapsed '
+                         'fragments would need tags of their own); run the two separately')
+
+
+def collapse_umis(ts, opts):
+    """`sc assign --umi_tag` / `sc resume` of a checkpoint with UMIs: the run goes on with the kept fragments (scTelescope.collapse_umis)
+    unless --ignore_umi; <exp_tag>-umi_stats.tsv lists them per barcode."""
+    if getattr(ts, 'umi_of_row', None) is None or getattr(opts, 'ignore_umi', False):
+        return
+    n = ts.shape[0]
+    d = ts.collapse_umis(opts.device)
+    lg.info('UMI duplicates: collapsed %d of %d fragments (%d barcode-UMI classes, %d molecules)'
+            % (d.n_dropped, n, d.n_classes, d.n_components))
+    os.makedirs(opts.outdir, exist_ok=True)
+    ts.write_umi_stats(opts.outfile_path('umi_stats.tsv'))
+
+
 def _refuse_bootstrap(args):
     """--bootstrap with what the device's bootstrap does not offer: refused before anything is read or written."""
     n = getattr(args, 'bootstrap', 0)
@@ -386,6 +420,10 @@ def run_resume(args, sc=False):
     if opts.skip_em:
         lg.info('Skipping EM...')
         return 0
+    if sc:
+        if warm is not None:
+            warm.join()
+        collapse_umis(ts, opts)
     seed = ts.get_random_seed()
     lg.debug('Random seed: {}'.format(seed))
     np.random.seed(seed)
@@ -412,6 +450,7 @@ def run_assign(args, sc=False):
     (Telescope.load_shard) — one BAM parse and one whole matrix in host memory per job, not per rank."""
     _refuse_sharded_sc(sc)
     _refuse_bootstrap(args)
+    _refuse_umi_updated_sam(args)
     opts = ResumeOptions(args)
     configure_logging(opts)
     if opts.ncpu != 1:
@@ -491,6 +530,10 @@ def run_assign(args, sc=False):
             raise load_failure
         raise SystemExit('telescope assign: another rank could not read its fragments from %s.npz — a row-sharded `assign` needs '
                          '--outdir on a file system all ranks share (see that rank\'s message)' % opts.outfile_path('checkpoint'))
+    if sc:                                                   # (after print_summary and the checkpoint, which holds the uncollapsed run)
+        if warm is not None:
+            warm.join()
+        collapse_umis(ts, opts)
     seed = ts.get_random_seed()
     lg.debug('Random seed: {}'.format(seed))
     np.random.seed(seed)

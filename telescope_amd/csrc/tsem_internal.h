@@ -11,6 +11,7 @@
 //   tsem_cellem.hip  one EM fit per group of rows (single-cell `--pooling_mode individual` / `celltype`)
 //   tsem_boot.hip    bootstrap replicates: the EM refitted with a multiplicity per row, batches of replicates per sweep;
 //                    with a group sink also per-(group, column) statistics over the replicates (the pattern comes from tsem_cells.hip)
+//   tsem_umi.hip     UMI duplicates of a single-cell run: classes, links, components, representatives (tsem_umi_dedup)
 //   tsem_fz_p*.hip   instantiations of the fused kernel (tsem_fused.h), one team size per unit
 //
 // A kernel is launched only from the unit that defines it; other units go through the host functions declared here.

@@ -1,5 +1,5 @@
-// The sorted-runs step of the two single-cell units (included by tsem_cells.hip and tsem_cellem.hip only): every stored entry is keyed
-// (group << cbits | column); the keys are stably radix-sorted with a value each and the runs of equal keys — one (group, column) each,
+// The sorted-runs step of the single-cell units (included by tsem_cells.hip, tsem_cellem.hip and tsem_umi.hip only): every stored entry
+// is keyed (group << cbits | column); the keys are stably radix-sorted with a value each and the runs of equal keys — one (group, column) each,
 // its entries in the order they had — are numbered.  Unnamed namespace: each unit launches its own copy of the kernel (tsem_internal.h).
 #pragma once
 #include "tsem_internal.h"

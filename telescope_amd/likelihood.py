@@ -259,6 +259,64 @@ class BootstrapFits(object):
         return out
 
 
+class UmiDedup(object):
+    """What `umi_dedup` returns.  `rep_of_row` (int32 [N]): the representative of every row's component — the rows of one (cell, UMI)
+    that are connected through shared loci (include/telescope_em.h, tsem_umi_dedup); `keep` (bool [N]): rep_of_row[i] == i, the rows a
+    collapsed run keeps.  `n_class_rows`: rows with a barcode and a UMI, `n_classes`: distinct (cell, UMI) among them, `n_components`:
+    molecules (components among those rows), `n_dropped`: rows that are not kept."""
+
+    def __init__(self, rep_of_row, stats, cell_of_row):
+        self.rep_of_row = np.asarray(rep_of_row, dtype=np.int32)
+        self.keep = self.rep_of_row == np.arange(len(self.rep_of_row), dtype=np.int32)
+        self.n_class_rows, self.n_classes, self.n_components, self.n_dropped = (int(x) for x in stats)
+        self.cell_of_row = np.asarray(cell_of_row, dtype=np.int32)
+        if self.cell_of_row.shape != self.rep_of_row.shape:
+            raise ValueError('UmiDedup: cell_of_row must have one entry per row')
+
+    def kept_per_cell(self, n_cells):
+        """the kept rows of every cell (int64 [n_cells]; rows without barcode count nowhere)"""
+        sel = self.keep & (self.cell_of_row >= 0)
+        return np.bincount(self.cell_of_row[sel], minlength=int(n_cells)).astype(np.int64)
+
+
+def check_umi_args(n_rows, cell_of_row, umi_of_row, n_cells=None, n_umis=None):
+    """The argument checks of `umi_dedup` (no device): int32-convertible arrays with one entry per row, values from -1 on and below
+    n_cells / n_umis, which are taken from the data when not given.  Returns (cell_of_row, umi_of_row, n_cells, n_umis)."""
+    out = []
+    for name, a, top in (('cell_of_row', cell_of_row, n_cells), ('umi_of_row', umi_of_row, n_umis)):
+        a = np.asarray(a)
+        if a.dtype.kind not in 'iu' or a.shape != (int(n_rows),):
+            raise ValueError('umi_dedup: %s must be an integer array with one entry per row (%d), not %s %s' % (name, int(n_rows), a.dtype, a.shape))
+        if a.size and (int(a.min()) < -1 or int(a.max()) >= 2 ** 31 - 1):
+            raise ValueError('umi_dedup: %s must hold values from -1 (none) on that fit int32' % name)
+        top = (int(a.max()) + 1 if a.size else 0) if top is None else int(top)
+        if top < 0 or top > 2 ** 31 - 1 or (a.size and int(a.max()) >= top):
+            raise ValueError('umi_dedup: %s holds values outside [-1, %d)' % (name, top))
+        out.append((np.ascontiguousarray(a, dtype=np.int32), top))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+def umi_dedup(raw_scores, cell_of_row, umi_of_row, device=0, n_cells=None, n_umis=None):
+    """Collapse the UMI duplicates of a single-cell run on the device: a `UmiDedup` for the rows of `raw_scores` (the fragments x loci
+    matrix of raw score codes), their cells and their UMIs (-1 = none).  Uses an engine of its own, closed afterwards; no model is
+    fitted.  The collapsed run is the run on `raw_scores[d.keep]` with `cell_of_row[d.keep]`."""
+    raw = raw_scores if isinstance(raw_scores, sp.csr_matrix) else sp.csr_matrix(raw_scores)
+    cor, uor, n_cells, n_umis = check_umi_args(raw.shape[0], cell_of_row, umi_of_row, n_cells, n_umis)
+    if raw.nnz and raw.data.dtype != np.uint16 and (raw.data.min() < 0 or raw.data.max() > 65535 or
+                                                    (raw.data.dtype.kind not in 'ui' and not np.all(raw.data == np.floor(raw.data)))):
+        raise ValueError('score matrix must hold integer alignment scores in [0, 65535]')
+    if not raw.has_sorted_indices:                               # (the engine takes canonical CSR; the result does not depend on the order)
+        raw = raw.copy()
+        raw.sort_indices()
+    eng = Engine(device)
+    try:
+        eng.load_scores(raw.indptr, raw.indices, raw.data.astype(np.uint16, copy=False), raw.shape[1], None)
+        rep, stats = eng.umi_dedup(cor, uor, n_cells, n_umis)
+    finally:
+        eng.close()
+    return UmiDedup(rep, stats, cor)
+
+
 class TelescopeLikelihood(object):
     """EM model over a fragments x loci score matrix (model.py:631-865)."""
 

@@ -45,7 +45,7 @@ _B_SIZE = {'c': 1, 'C': 1, 's': 2, 'S': 2, 'i': 4, 'I': 4, 'f': 4}
 
 
 class Segment(object):
-    __slots__ = ('qname', 'flag', 'ref_id', 'pos', 'nref', 'npos', 'tlen', 'cigar', 'AS', 'bc', 'raw')
+    __slots__ = ('qname', 'flag', 'ref_id', 'pos', 'nref', 'npos', 'tlen', 'cigar', 'AS', 'bc', 'umi', 'raw')
 
     @property
     def is_paired(self): return bool(self.flag & 0x1)
@@ -70,12 +70,13 @@ class Segment(object):
         return out
 
 
-def read_bam(path, barcode_tag=None, raw=False):
+def read_bam(path, barcode_tag=None, raw=False, umi_tag=None):
     """-> (reference names, iterator of Segment) from a BAM file, streamed.  `barcode_tag` (e.g. 'CB'): the value of that Z-type
-    tag goes to Segment.bc (None where the record has no such tag).  `raw=True`: every Segment also keeps its record's bytes
+    tag goes to Segment.bc (None where the record has no such tag); `umi_tag` (e.g. 'UB'): likewise, to Segment.umi.  `raw=True`: every Segment also keeps its record's bytes
     (Segment.raw, without the block size), and a third value is returned: dict(text=header text, refs_block=the binary
     reference list, n_ref included) — what bam_out.BamWriter writes back."""
     btag = barcode_tag.encode() if barcode_tag else None
+    utag = umi_tag.encode() if umi_tag else None
     fh = io.BufferedReader(gzip.open(path, 'rb'), buffer_size=1 << 20)
 
     def need(n):
@@ -115,7 +116,7 @@ def read_bam(path, barcode_tag=None, raw=False):
                 s.qname = buf[p:p + l_rn - 1].decode(); p += l_rn
                 s.cigar = struct.unpack_from('<%dI' % n_cig, buf, p); p += 4 * n_cig
                 p += (l_seq + 1) // 2 + l_seq
-                s.AS = s.bc = None
+                s.AS = s.bc = s.umi = None
                 while p < bs:
                     tag = buf[p:p + 2]; typ = chr(buf[p + 2]); p += 3
                     if typ in _TAG_FMT:
@@ -129,6 +130,8 @@ def read_bam(path, barcode_tag=None, raw=False):
                         end = buf.index(b'\x00', p)
                         if typ == 'Z' and tag == btag:
                             s.bc = buf[p:end].decode()
+                        if typ == 'Z' and tag == utag:
+                            s.umi = buf[p:end].decode()
                         p = end + 1
                     elif typ == 'B':
                         sub = chr(buf[p]); (cnt,) = struct.unpack_from('<i', buf, p + 1)
@@ -290,11 +293,12 @@ CODE_DESC = OrderedDict([('SU', 'single_unmapped'), ('SM', 'single_mapped'), ('P
 
 
 def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_mode='threshold',
-                   overlap_threshold=0.2, stranded_mode='None', barcode_tag=None, updated_sam=None):
+                   overlap_threshold=0.2, stranded_mode='None', barcode_tag=None, updated_sam=None, umi_tag=None):
     """-> dict(raw_scores uint16 CSR, read_index, feat_index, feature_length, run_info fields).  With `barcode_tag` (scTelescope,
     model.py:245-247,311-316) also cell_of_row (int32 per row, -1 = no barcode) and barcodes (the cell names): the tag is read from
     the first read of every mapped fragment; only fragments that become rows count; cells are ordered by the first appearance of
-    their barcode in BAM order among those fragments.  `updated_sam=(other_bam, tmp_bam)` (model.py:214-285): unmapped fragments
+    their barcode in BAM order among those fragments.  With `umi_tag` (e.g. 'UB') also umi_of_row (int32 per row, -1 = no tag) and
+    umis (the distinct values), read and ordered exactly like the barcodes.  `updated_sam=(other_bam, tmp_bam)` (model.py:214-285): unmapped fragments
     (only alns[0] of an SU bundle) and fragments without overlap go to other_bam, every AlignedPair of an overlapping fragment
     (r1 then r2, in pairing order) to tmp_bam, both with the input's header; the pairs of an overlapping fragment carry ZF (its
     feature) and ZT (PRI for the best pair of each feature by alnscore + alnlen, SEC for the others), and every mapped pair ZB
@@ -305,7 +309,7 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
     bam_u = bam_t = None
     if updated_sam:
         from .bam_out import BamWriter
-        refs, records, header = read_bam(samfile, barcode_tag, raw=True)
+        refs, records, header = read_bam(samfile, barcode_tag, raw=True, umi_tag=umi_tag)
         bam_u, bam_t = BamWriter(updated_sam[0], header), BamWriter(updated_sam[1], header)
 
         def write(bam, pairs):
@@ -314,8 +318,9 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
                 if p.r2 is not None:
                     bam.write(p.r2.raw)
     else:
-        refs, records = read_bam(samfile, barcode_tag)
+        refs, records = read_bam(samfile, barcode_tag, umi_tag=umi_tag)
     read_bc = {}                                         # fragment name -> barcode, in BAM order (model.py:245-247)
+    read_umi = {}                                        # ... -> UMI
 
     def assign(pair):
         if pair.r1.is_reverse:
@@ -344,6 +349,8 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
                 continue
             if barcode_tag and alns[0].r1.bc is not None:
                 read_bc[alns[0].r1.qname] = alns[0].r1.bc
+            if umi_tag and alns[0].r1.umi is not None:
+                read_umi[alns[0].r1.qname] = alns[0].r1.umi
             mapped = [a for a in alns if not a.is_unmapped]
             ambig = len(mapped) > 1
             for a in mapped:
@@ -434,4 +441,13 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
                 continue
             cell_of_row[remap[old]] = cells.setdefault(bc, len(cells))
         out['cell_of_row'], out['barcodes'] = cell_of_row, list(cells)
+    if umi_tag:
+        umi_of_row = np.full(keep.size, -1, dtype=np.int32)
+        umis = OrderedDict()
+        for rid, u in read_umi.items():
+            old = ridx.get(rid)
+            if old is None or remap[old] < 0:
+                continue
+            umi_of_row[remap[old]] = umis.setdefault(u, len(umis))
+        out['umi_of_row'], out['umis'] = umi_of_row, list(umis)
     return out

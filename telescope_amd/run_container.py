@@ -457,6 +457,9 @@ class scTelescope(Telescope):
         self.cell_of_row = None
         self.barcodes = []
         self.type_names, self.type_of_cell = None, None      # `--pooling_mode celltype` (set_celltypes)
+        self.umi_of_row, self.umis = None, None              # `--umi_tag`: the UMI of every fragment (-1 = none), the distinct values
+        self.umi_dedup = None                                # the UmiDedup of collapse_umis
+        self._umi_frags = None                               # per barcode, before the collapse: fragments, fragments with a UMI
 
     def set_celltypes(self, type_of_barcode):
         """The cell types of `--celltype_tsv` (read_celltype_tsv) for this run's barcodes; ValueError if it names none of them."""
@@ -467,7 +470,7 @@ class scTelescope(Telescope):
         o = self.opts
         self.run_info['annotated_features'] = len(annotation.loci)
         r = loader.load_alignment(o.samfile, annotation, o.no_feature_key, o.overlap_mode, o.overlap_threshold, o.stranded_mode,
-                                  barcode_tag=o.barcode_tag, updated_sam=self._updated_sam_paths())
+                                  barcode_tag=o.barcode_tag, updated_sam=self._updated_sam_paths(), umi_tag=getattr(o, 'umi_tag', None))
         self.feature_length = r['feature_length']
         self.read_index, self.feat_index = r['read_index'], r['feat_index']
         self.raw_scores = r['raw_scores']
@@ -475,12 +478,18 @@ class scTelescope(Telescope):
         for k, v in r['run_info'].items():
             self.run_info[k] = v
         self.cell_of_row, self.barcodes = r['cell_of_row'], r['barcodes']
+        if 'umi_of_row' in r:
+            self.umi_of_row, self.umis = r['umi_of_row'], r['umis']
 
     def save(self, filename):
         """The bulk checkpoint's keys, byte for byte, plus `_barcode_list` (unicode, cell order) and `_read_barcode` (int32 per row,
-        -1 = none).  The bulk `load` and the reference's `Telescope.load` read named keys only and ignore them."""
+        -1 = none) and, only when UMIs were read (`--umi_tag`), `_umi_list` and `_read_umi` likewise.  The bulk `load` and the
+        reference's `Telescope.load` read named keys only and ignore them."""
         feats = sorted(self.feat_index, key=self.feat_index.get)
         raw = sp.csr_matrix(self.raw_scores)
+        more = {}
+        if self.umi_of_row is not None:
+            more = dict(_umi_list=np.array(list(self.umis), dtype=np.str_), _read_umi=np.asarray(self.umi_of_row, dtype=np.int32))
         np.savez(filename,
                  _run_info=list(self.run_info.items()),
                  _flen_list=[self.feature_length[f] for f in feats],
@@ -490,7 +499,7 @@ class scTelescope(Telescope):
                  _raw_scores_data=raw.data, _raw_scores_indices=raw.indices,
                  _raw_scores_indptr=raw.indptr, _raw_scores_shape=raw.shape,
                  _barcode_list=np.array(list(self.barcodes), dtype=np.str_),
-                 _read_barcode=np.asarray(self.cell_of_row, dtype=np.int32))
+                 _read_barcode=np.asarray(self.cell_of_row, dtype=np.int32), **more)
 
     @classmethod
     def load(cls, filename):
@@ -503,7 +512,48 @@ class scTelescope(Telescope):
         obj.cell_of_row = np.asarray(z['_read_barcode'], dtype=np.int32)
         if obj.cell_of_row.shape != (obj.shape[0],) or (obj.cell_of_row.size and obj.cell_of_row.max() >= len(obj.barcodes)):
             raise ValueError('%s: _read_barcode does not match the matrix / _barcode_list' % filename)
+        if '_umi_list' in z.files or '_read_umi' in z.files:
+            if '_umi_list' not in z.files or '_read_umi' not in z.files:
+                raise ValueError('%s: _umi_list and _read_umi come together' % filename)
+            obj.umis = [str(u) for u in z['_umi_list']]
+            obj.umi_of_row = np.asarray(z['_read_umi'], dtype=np.int32)
+            if obj.umi_of_row.shape != (obj.shape[0],) or (obj.umi_of_row.size and (obj.umi_of_row.max() >= len(obj.umis) or
+                                                                                    obj.umi_of_row.min() < -1)):
+                raise ValueError('%s: _read_umi does not match the matrix / _umi_list' % filename)
         return obj
+
+    def collapse_umis(self, device=0):
+        """Collapse the UMI duplicates (likelihood.umi_dedup): `raw_scores`, `shape`, `cell_of_row`, `umi_of_row` and `read_index`
+        become those of the kept fragments, renumbered in order; K and the feature list stay.  The `UmiDedup` (row numbers of the
+        uncollapsed run) is kept as `self.umi_dedup` and returned."""
+        from .likelihood import umi_dedup
+        if self.umi_of_row is None:
+            raise ValueError('collapse_umis: no UMIs were read (load the alignments with --umi_tag)')
+        d = umi_dedup(self.raw_scores, self.cell_of_row, self.umi_of_row, device=device, n_cells=len(self.barcodes), n_umis=len(self.umis))
+        cor, uor = np.asarray(self.cell_of_row), np.asarray(self.umi_of_row)
+        n_cells = len(self.barcodes)
+        self._umi_frags = (np.bincount(cor[cor >= 0], minlength=n_cells), np.bincount(cor[(cor >= 0) & (uor >= 0)], minlength=n_cells))
+        keep = d.keep
+        self.raw_scores = sp.csr_matrix(self.raw_scores)[np.flatnonzero(keep)]
+        self.shape = self.raw_scores.shape
+        self.cell_of_row, self.umi_of_row = cor[keep].astype(np.int32), uor[keep].astype(np.int32)
+        if self.read_index is not None:
+            new = np.cumsum(keep) - 1
+            self.read_index = {name: int(new[i]) for name, i in self.read_index.items() if keep[i]}
+        self.umi_dedup = d
+        return d
+
+    def write_umi_stats(self, filename):
+        """`<exp_tag>-umi_stats.tsv` of a collapsed run: one line per barcode — its fragments, how many of them carry a UMI, and
+        the fragments kept."""
+        if self.umi_dedup is None:
+            raise ValueError('write_umi_stats: the run is not collapsed (collapse_umis)')
+        frags, with_umi = self._umi_frags
+        kept = self.umi_dedup.kept_per_cell(len(self.barcodes))
+        with open(filename, 'w') as fh:
+            fh.write('barcode\tfragments\twith_umi\tkept\n')
+            for c, b in enumerate(self.barcodes):
+                fh.write('%s\t%d\t%d\t%d\n' % (_csv_field(b), frags[c], with_umi[c], kept[c]))
 
     def output_report(self, tl, stats_filename, counts_filename, write=True):
         """model.py:575-629: the stats TSV (transcript, transcript_length, final_prop, init_prop; sorted by final_prop, rounded; the

@@ -661,7 +661,10 @@ static int launch_fused(tsem_ctx* h, int mode, hipEvent_t* pair, int bin = 0) {
   if (mode == 8) { A.ctab = h->d_ctab_prev; A.ctab2 = h->d_ctab; A.koff = bin * A.Kh; A.lnl_out = h->d_lnl_part + (size_t)bin * h->fz_grid; }
   A.wrow = h->d_amb_w; A.partial = h->d_fpartial; A.xchg = h->d_xchg; A.sorted = h->sorted_layout ? 1 : 0;
   A.sync = h->d_xflags;
-  A.prof = (mode == 0 || mode == 4 || mode == 5) ? h->d_prof : nullptr; A.prof_blocks = A.prof ? h->prof_steps : 0; A.dbg = (int)(h->opt_dbg & (32 | 64));
+  // option "fused_prof": the EM pass runs the timeline instantiation (k_em_fused<..., PROF = true>, tsem_fused_inst.h), the only kernels
+  // that hold time stamps.  The log-likelihood and exact-sum passes never stamped and run as they are.
+  const bool prof = h->d_prof && (mode == 0 || mode == 4 || (mode == 5 && bin == 0));
+  A.prof = prof ? h->d_prof : nullptr; A.prof_blocks = prof ? h->prof_steps : 0; A.dbg = (int)(h->opt_dbg & (32 | 64));
   A.ctl = h->d_ctl;
   A.ebias = h->d_ebias; A.bin = bin; A.ovf = h->d_ovf; A.partial2 = h->d_fpartial2;
 
@@ -692,9 +695,12 @@ static int launch_fused(tsem_ctx* h, int mode, hipEvent_t* pair, int bin = 0) {
     }
   }
   if ((lnl || mode == 8) && h->fz_grid > 2048) TSEM_FAIL(TSEM_ERR_ARG, "fused lnl: more workgroups than partial slots");
-  fz_fn fn = fz_kernel(h->P, kmode, fz_fmt(h), h->geo);
+  fz_fn fn = fz_kernel(h->P, kmode, fz_fmt(h), h->geo, prof);
+  if (!fn && prof) TSEM_FAIL(TSEM_ERR_ARG, "option fused_prof: the timeline kernel exists for the plain EM pass of teams of 1-4 with the score table in LDS "
+                                           "only (not with use_likelihood, the split layout, more than 4 column parts or a score table too large for LDS)");
   if (!fn) TSEM_FAIL(TSEM_ERR_ARG, mode >= 2 ? "reproducible mode needs the fused kernel with a score table of at most 2048 entries"
                                                : "fused kernel supports at most 8 column parts");
+  if (prof) TSEM_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));   // (the layout build allowed it for the product kernels)
   if (pair) TSEM_HIP(hipEventRecord(pair[0], h->stream));   // time the kernel, not the memsets
   fn<<<h->fz_grid, FZ_NT, ldsf, h->stream>>>(A);
   TSEM_HIP(hipGetLastError());

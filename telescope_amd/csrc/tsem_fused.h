@@ -193,9 +193,23 @@ __device__ __forceinline__ double fz_shr1_d(double v) {     // value of lane l-1
 // wavefront shifts on the VALU (as many rounds as the longest chain of lanes lying inside one row:
 // usually 1-3).  Every lane of the wave must call this (idle lanes with idle = true).  The result
 // is right for any entry order; the row order only makes the runs long.
+// A lane issues at most TWO atomics in the common case (a row has ~10 entries in a part: a lane of four
+// entries rarely holds more than one row boundary):
+//   F  the FIRST run that ends inside the lane (before its last entry).  All entries in front of the first
+//      boundary share row r0, so its slot is yb[r0] wherever the boundary lies, and it is the run the carry
+//      from the left belongs to;
+//   L  the run that ends WITH the lane's last entry, unless the right neighbour continues it.
+// Runs that end inside the lane BEHIND the first boundary (a lane with two or three boundaries: rows of one
+// or two entries) start inside the lane, take no carry, and go out between F and L under one wave-uniform
+// branch that the wave skips when no lane has any.  The contributions (row slot, sum) and the order of the
+// additions inside a lane are those of one atomic per run end; only the instruction that carries a run differs.
 __device__ __forceinline__ void fz_row_sums(double* yb, bool idle, uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3,
                                             double m0, double m1, double m2, double m3) {
   const bool e01 = r1 == r0, e12 = r2 == r1, e23 = r3 == r2;
+  // lanes with two or three boundaries, as a wave-wide mask: scalar arithmetic on the compares' own lane masks, taken HERE, next to
+  // the compares (as one boolean expression per lane, or behind the first atomic, the test went through the VALU)
+  const unsigned long long n01 = ~__builtin_amdgcn_ballot_w64(e01), n12 = ~__builtin_amdgcn_ballot_w64(e12), n23 = ~__builtin_amdgcn_ballot_w64(e23);
+  const unsigned long long multi = ((n01 & n12) | (n23 & (n01 | n12))) & ~__builtin_amdgcn_ballot_w64(idle);
   const double s1 = e01 ? m0 + m1 : m1;                     // running sums of the runs inside the lane
   const double s2 = e12 ? s1 + m2 : m2;
   const double s3 = e23 ? s2 + m3 : m3;
@@ -203,22 +217,26 @@ __device__ __forceinline__ void fz_row_sums(double* yb, bool idle, uint32_t r0, 
   const int prev_b = fz_dpp_i<FZ_DPP_WAVE_SHR1, 0xF>(0xFFFE, b);
   const int next_a = fz_dpp_i<FZ_DPP_WAVE_SHL1, 0xF>(0xFFFC, a);
   const bool joins = prev_b == a;                            // my first run continues the left neighbour's last one
-  const bool open = e01 & e12 & e23 & joins;                 // the whole lane lies inside that run: pass the sum on
-  double I = idle ? 0.0 : s3;                                // sum of the run that ends with my last entry
+  const bool whole = e01 & e12 & e23;                        // no boundary inside the lane
+  const bool open = whole & joins;                           // the whole lane lies inside that run: pass the sum on
+  // sum of the run that ends with my last entry.  (An idle lane's products are zeros and nobody reads what it hands on: its
+  // right neighbour never joins the mark 0xFFFD.)
+  double I = s3;
   for (unsigned long long chain = __builtin_amdgcn_ballot_w64(open); chain; chain &= chain << 1) {
     const double up = fz_shr1_d(I);
     if (open) I = s3 + up;
   }
   const double left = fz_shr1_d(I);                          // (not inside the ?: — every lane must execute the move)
   const double C = joins ? left : 0.0;                       // what the lanes to the left bring for my first run
-  if (!idle) {
-    // runs that end before my last entry: the first of them takes the carry
-    if (!e01) lds_add(&yb[r0], m0 + C);
-    const double C1 = e01 ? C : 0.0;
-    if (!e12) lds_add(&yb[r1], s1 + C1);
-    if (!e23) lds_add(&yb[r2], s2 + (e12 ? C1 : 0.0));
-    if (next_a != b) lds_add(&yb[r3], I);                    // my last run ends here (else the right neighbour has it)
+  const double first = e01 ? (e12 ? s2 : s1) : m0;           // the run in front of the lane's first boundary
+  if (!idle && !whole) lds_add(&yb[r0], first + C);          // F
+  if (multi != 0ull) {                                       // a second / third boundary: the runs that end at entry 1 / entry 2 and are not F's
+    // (such a run starts behind a boundary at entry 1 or 2: its sum s1 / s2 IS m1 / m2 / m1 + m2, formed here from the products the
+    // register set keeps anyway, so that s1 and s2 need not stay in registers across F)
+    if (!idle && !e01 && !e12) lds_add(&yb[r1], m1);
+    if (!idle && !e23 && !(e01 && e12)) lds_add(&yb[r2], e12 ? m1 + m2 : m2);
   }
+  if (!idle && next_a != b) lds_add(&yb[r3], I);             // L: my last run ends here (else the right neighbour has it)
 }
 
 // log1p(x), x >= 0 finite, for the fused lnl pass (2e9 evaluations per pass: ts_log1p_pos was 3.7 of its 7.3 ms): 1 + x = 2^k m,
@@ -313,7 +331,7 @@ struct FzX {                 // context handed to the exchange wave
 };
 
 // Exchange wave of member PP of a P-member team (see k_em_fused for the schedule).
-template <int P, int PP, int MODE, int FMT, int GEO>
+template <int P, int PP, int MODE, int FMT, int GEO, bool PROF>
 __device__ __forceinline__ void fz_xchg(const FusedArgs& A, const FzX& X) {
   typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
   constexpr int p = PP;
@@ -480,8 +498,8 @@ __device__ __forceinline__ void fz_xchg(const FusedArgs& A, const FzX& X) {
   };
   int64_t i = 0;
   auto xstep = [&]() {
-    const bool pr = A.prof && team == 0 && p == 0 && lane == 0 && offw && (int)i < A.prof_blocks;
-    if (pr) A.prof[i * FZ_PROF_SLOTS + 6] = clock64();
+    const bool pr = PROF && A.prof && team == 0 && p == 0 && lane == 0 && offw && (int)i < A.prof_blocks;
+    if constexpr (PROF) { if (pr) A.prof[i * FZ_PROF_SLOTS + 6] = clock64(); }
     // ONE generation of partner values, loaded and combined in the SAME step.  The loads go out right after the
     // publish (two steps after the partners published theirs, ahead of this step's burst of the data waves, which
     // comes at its end); they come back through the in-order memory pipe behind the previous burst, and the wave
@@ -561,9 +579,9 @@ __device__ __forceinline__ void fz_xchg(const FusedArgs& A, const FzX& X) {
         __builtin_amdgcn_raw_buffer_store_b128(gq, xs, boff, 0, 0);
       }
     }
-    if (pr) A.prof[i * FZ_PROF_SLOTS + 10] = clock64();   // (waits for the LDS reads of the publish: lgkmcnt)
+    if constexpr (PROF) { if (pr) A.prof[i * FZ_PROF_SLOTS + 10] = clock64(); }   // (waits for the LDS reads of the publish: lgkmcnt)
     issue(g1, i - 2 - FZ_GAP, i + FZ_DL + 2);
-    if (pr) A.prof[i * FZ_PROF_SLOTS + 7] = clock64();
+    if constexpr (PROF) { if (pr) A.prof[i * FZ_PROF_SLOTS + 7] = clock64(); }
     combine(g1, own_q[1 + FZ_GAP], i - 2 - FZ_GAP, i + FZ_DL + 2);   // (geometry 3: block i-2-GAP was read 1+GAP publishes before this one's)
     if (MODE == 4) {                                      // stage the row factors of block i+1 for the data waves' next step
 #pragma unroll
@@ -572,15 +590,19 @@ __device__ __forceinline__ void fz_xchg(const FusedArgs& A, const FzX& X) {
         if (r < rhi) *reinterpret_cast<double2*>(&X.rp[((i + 1) & 1) * R + r]) = g1.rpv[j];
       }
     }
-    if (pr) A.prof[i * FZ_PROF_SLOTS + 5] = clock64();
-    if (A.prof && team == 0 && p == 0 && lane == 0 && X.xw == 1 && (int)i < A.prof_blocks) A.prof[i * FZ_PROF_SLOTS + 9] = clock64();
+    if constexpr (PROF) {
+      if (pr) A.prof[i * FZ_PROF_SLOTS + 5] = clock64();
+      if (A.prof && team == 0 && p == 0 && lane == 0 && X.xw == 1 && (int)i < A.prof_blocks) A.prof[i * FZ_PROF_SLOTS + 9] = clock64();
+    }
     __syncthreads();
     ++i;
   };
   while (i < nsteps) xstep();
 }
 
-template <int PT, int MODE, int FMT, int GEO>
+// PROF: the timeline instantiation (option "fused_prof": tools/fused_prof.py, tools/startup_prof.py).  Every time stamp below sits under
+// `if constexpr (PROF)`: the kernels the product launches hold none of them, not even the test of A.prof.
+template <int PT, int MODE, int FMT, int GEO, bool PROF = false>
 __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int P = PT;
@@ -608,8 +630,8 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
   if (LNL1 && A.sel && ((*A.sel > A.sel_thr) != (A.sel_want != 0))) return;   // the other form of the lnl pass runs (see FusedArgs)
   // start-up timeline (tools/startup_prof.py): 100 MHz wall clock of every workgroup's thread 0 at entry / tickets counted / LDS
   // zeroed / tables loaded / loop start / loop end / exit, behind the per-step slots of team 0
-  unsigned long long* const sprof = (A.prof && tid == 0) ? A.prof + 64 * FZ_PROF_SLOTS + (size_t)blockIdx.x * 8 : nullptr;
-  if (sprof) sprof[0] = wall_clock64();
+  unsigned long long* const sprof = (PROF && A.prof && tid == 0) ? A.prof + 64 * FZ_PROF_SLOTS + (size_t)blockIdx.x * 8 : nullptr;
+  if constexpr (PROF) { if (sprof) sprof[0] = wall_clock64(); }
   if (A.dbg & ((!LNL1 && MODE != 8) ? 32 : 64)) {     // test hook: what a watchdog time-out leaves behind
     if (blockIdx.x == 0 && tid == 0) atomicOr(err, 2u);
     return;
@@ -649,7 +671,7 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
     logtab[tid] = make_double2(1.0 / ci, ts_log1p_pos((double)tid * (1.0 / FZ_LOGTAB)));
   }
   __syncthreads();
-  if (sprof) sprof[2] = wall_clock64();
+  if constexpr (PROF) { if (sprof) sprof[2] = wall_clock64(); }
   const int ticket = __builtin_amdgcn_readfirstlane(ibox[0]);   // LDS broadcasts: tell the compiler they are uniform
   const int u = ticket / P, p = ticket % P;
   if (SPL) {                                               // one half of the part's columns: previous and current pi*theta
@@ -685,10 +707,10 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       if (++spins > FZ_SPIN_LIMIT) { atomicOr(err, 1u); break; }
       if ((spins & 15u) == 0 && fz_ld_u32(err)) break;
     }
-    if (sprof) sprof[1] = wall_clock64();
+    if constexpr (PROF) { if (sprof) sprof[1] = wall_clock64(); }
   }
   __syncthreads();
-  if (sprof) sprof[3] = wall_clock64();
+  if constexpr (PROF) { if (sprof) sprof[3] = wall_clock64(); }
   int T = 0, tbase = 0;
   for (int x = 0; x < 8; ++x) {
     int teams = __builtin_amdgcn_readfirstlane(ibox[1 + x]) / P;
@@ -728,7 +750,7 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
   if (LAG && A.lag && nblk > 0)
     for (int t = tid; t < R; t += FZ_NT) rpS[t] = A.rinv[(int64_t)team * R + t];
   __syncthreads();
-  if (sprof) { sprof[4] = wall_clock64(); sprof[7] = ((unsigned long long)xcc << 48) | ((unsigned long long)team << 32) | ((unsigned long long)p << 16) | (unsigned long long)nblk; }
+  if constexpr (PROF) if (sprof) { sprof[4] = wall_clock64(); sprof[7] = ((unsigned long long)xcc << 48) | ((unsigned long long)team << 32) | ((unsigned long long)p << 16) | (unsigned long long)nblk; }
 
   double lsum = 0.0;                                      // lnl mode: this thread's share of the sum
   if (tid >= FZ_DT) {
@@ -738,14 +760,14 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
     X.lut = lutS; X.y = y; X.s = s; X.rp = rpS; X.offs = offs; X.xbase = xbase; X.err = err; X.R = R; X.team = team; X.T = T;
     X.nblk = nblk; X.nsteps = nsteps; X.lane = (tid - FZ_DT) & 63; X.xw = (tid - FZ_DT) >> 6;
     switch (p) {
-      case 0: fz_xchg<P, 0, MODE, FMT, GEO>(A, X); break;
-      case 1: if (P > 1) fz_xchg<P, (P > 1 ? 1 : 0), MODE, FMT, GEO>(A, X); break;
-      case 2: if (P > 2) fz_xchg<P, (P > 2 ? 2 : 0), MODE, FMT, GEO>(A, X); break;
-      case 3: if (P > 3) fz_xchg<P, (P > 3 ? 3 : 0), MODE, FMT, GEO>(A, X); break;
-      case 4: if (P > 4) fz_xchg<P, (P > 4 ? 4 : 0), MODE, FMT, GEO>(A, X); break;
-      case 5: if (P > 5) fz_xchg<P, (P > 5 ? 5 : 0), MODE, FMT, GEO>(A, X); break;
-      case 6: if (P > 6) fz_xchg<P, (P > 6 ? 6 : 0), MODE, FMT, GEO>(A, X); break;
-      case 7: if (P > 7) fz_xchg<P, (P > 7 ? 7 : 0), MODE, FMT, GEO>(A, X); break;
+      case 0: fz_xchg<P, 0, MODE, FMT, GEO, PROF>(A, X); break;
+      case 1: if (P > 1) fz_xchg<P, (P > 1 ? 1 : 0), MODE, FMT, GEO, PROF>(A, X); break;
+      case 2: if (P > 2) fz_xchg<P, (P > 2 ? 2 : 0), MODE, FMT, GEO, PROF>(A, X); break;
+      case 3: if (P > 3) fz_xchg<P, (P > 3 ? 3 : 0), MODE, FMT, GEO, PROF>(A, X); break;
+      case 4: if (P > 4) fz_xchg<P, (P > 4 ? 4 : 0), MODE, FMT, GEO, PROF>(A, X); break;
+      case 5: if (P > 5) fz_xchg<P, (P > 5 ? 5 : 0), MODE, FMT, GEO, PROF>(A, X); break;
+      case 6: if (P > 6) fz_xchg<P, (P > 6 ? 6 : 0), MODE, FMT, GEO, PROF>(A, X); break;
+      case 7: if (P > 7) fz_xchg<P, (P > 7 ? 7 : 0), MODE, FMT, GEO, PROF>(A, X); break;
       default: break;
     }
   } else {
@@ -907,8 +929,8 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
     uint32_t oqa = offs[FZ_DL * 2], oqb = offs[FZ_DL * 2 + 1];            // offsets of burst(DL), used at step 0
     const int lane_id = tid & 63;
     auto step_em = [&](FzRegs& rs, FzRegs& rp) {
-      const bool pr = A.prof && team == 0 && p == 0 && tid == 0 && (int)i < A.prof_blocks;
-      if (pr) A.prof[i * FZ_PROF_SLOTS + 0] = clock64();
+      const bool pr = PROF && A.prof && team == 0 && p == 0 && tid == 0 && (int)i < A.prof_blocks;
+      if constexpr (PROF) { if (pr) A.prof[i * FZ_PROF_SLOTS + 0] = clock64(); }
       // (Round 4: the exchange wave's publish is late — 900 instead of 200 clk — in the steps where its two LDS reads of y(i-1) queue
       // behind the data waves' gather burst.  `s_sleep` of 64 / 192 clk here, to let them in first: 18 per row 1.70 = 1.70 / 1.78 ms
       // (codes), 2.20 / 2.24 / 2.25 (fp64 entries); 40 per row 3.35 / 3.37 / 3.51 — nothing, then slower.  profiles/r04_ab_delay.txt)
@@ -927,7 +949,7 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
                              (__builtin_amdgcn_ballot_w64(!idle) | __builtin_amdgcn_ballot_w64(!idle2)) == 0ull;
       if (wave_idle) {
         rp.rc.x = FZ_IDLE;
-        if (pr) { A.prof[i * FZ_PROF_SLOTS + 1] = clock64(); A.prof[i * FZ_PROF_SLOTS + 3] = clock64(); }
+        if constexpr (PROF) { if (pr) { A.prof[i * FZ_PROF_SLOTS + 1] = clock64(); A.prof[i * FZ_PROF_SLOTS + 3] = clock64(); } }
       } else {
       // ---- gathers ----
       // (the mark cleared, an idle set decodes to valid slots: its other words are zeros, or a padding quad's last row and column 0)
@@ -950,7 +972,7 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       const double m0 = q0.x * c0, m1 = q0.y * c1, m2 = q1.x * c2, m3 = q1.y * c3;
       rp.v0 = make_double2(m0, m1); rp.v1 = make_double2(m2, m3);
       double* yb = y + (i & (FZ_YR - 1)) * R;
-      if (pr) A.prof[i * FZ_PROF_SLOTS + 1] = clock64();
+      if constexpr (PROF) { if (pr) A.prof[i * FZ_PROF_SLOTS + 1] = clock64(); }
       if (SPB) {
         // no row sums in the scatter pass
       } else if (A.sorted) {
@@ -961,7 +983,7 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
         lds_add(idle ? d : &yb[fz_row<I24, 2>(rp.rc)], m2); lds_add(idle ? d : &yb[fz_row<I24, 3>(rp.rc)], m3);
       }
       if (idle) rp.rc.x = FZ_IDLE;
-      if (pr) A.prof[i * FZ_PROF_SLOTS + 3] = clock64();
+      if constexpr (PROF) { if (pr) A.prof[i * FZ_PROF_SLOTS + 3] = clock64(); }
       asm volatile("" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       // ---- phase 2 of block i-LAG: w*z into the part's column accumulators; ALWAYS four atomics, issued last ----
@@ -1041,14 +1063,16 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       // refill the set at the END of the step.  (Issuing the burst in the middle — products and slots of phase 2 in
       // temporaries — so that it drains before the next step's exchange loads was tried: fp64 entries 4.4 -> 5.2 ms.)
       load_blk(rs, oqa, oqb, i + FZ_DL);
-      if (pr) A.prof[i * FZ_PROF_SLOTS + 2] = clock64();
-      if (A.prof && team == 0 && p == 0 && tid == FZ_DT - 64 && (int)i < A.prof_blocks) A.prof[i * FZ_PROF_SLOTS + 8] = clock64();
+      if constexpr (PROF) {
+        if (pr) A.prof[i * FZ_PROF_SLOTS + 2] = clock64();
+        if (A.prof && team == 0 && p == 0 && tid == FZ_DT - 64 && (int)i < A.prof_blocks) A.prof[i * FZ_PROF_SLOTS + 8] = clock64();
+      }
       __builtin_amdgcn_s_waitcnt(MODE == 3 ? 0xC87F : (SPA ? 0xC07F : 0xC47F));   // lgkmcnt(4): everything but the four (MODE 3: eight; MODE 5: no) scatters above has completed
       oqa = __builtin_amdgcn_readfirstlane(on0); oqb = __builtin_amdgcn_readfirstlane(on1);
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (pr) A.prof[i * FZ_PROF_SLOTS + 4] = clock64();
+      if constexpr (PROF) { if (pr) A.prof[i * FZ_PROF_SLOTS + 4] = clock64(); }
       ++i;
     };
     auto step = [&](FzRegs& rs, FzRegs& rp) {
@@ -1067,7 +1091,7 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
     }
   }
   __syncthreads();
-  if (sprof) sprof[5] = wall_clock64();
+  if constexpr (PROF) { if (sprof) sprof[5] = wall_clock64(); }
   if (LNL1 || LAG || SPL) {                               // one partial per workgroup, summed by k_sum_parts / k_colreduce
     for (int o = 32; o > 0; o >>= 1) lsum += __shfl_down(lsum, o, 64);
     double* wsum = y;                                     // the y ring is idle now
@@ -1087,5 +1111,5 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
     double* out2 = A.partial2 + (int64_t)team * (P * Kp) + p * Kp;
     for (int t = tid; t < Kp; t += FZ_NT) out2[t] = acc2[t];
   }
-  if (sprof) sprof[6] = wall_clock64();
+  if constexpr (PROF) { if (sprof) sprof[6] = wall_clock64(); }
 }

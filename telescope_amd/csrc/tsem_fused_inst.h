@@ -6,7 +6,17 @@
 #include "tsem_fused.h"
 
 typedef void (*fz_fn)(FusedArgs);
-template <int P, int GEO> static fz_fn fz_pick2(int mode, int fmt) {
+// prof: the timeline instantiation (k_em_fused<..., PROF = true>, option "fused_prof").  It exists for what tools/fused_prof.py and
+// tools/startup_prof.py launch — the plain EM pass (mode 0) of teams of 1-4 with the score table in LDS (formats 1, 2) — and nowhere
+// else: every instantiation is build time.  nullptr: no such kernel.
+template <int P, int GEO> static fz_fn fz_pick2(int mode, int fmt, bool prof) {
+  if (prof) {
+    if constexpr (P <= 4) {
+      if (mode == 0 && fmt == 1) return k_em_fused<P, 0, 1, GEO, true>;
+      if (mode == 0 && fmt == 2) return k_em_fused<P, 0, 2, GEO, true>;
+    }
+    return nullptr;
+  }
   if (mode == 4) {                                         // EM pass + the previous iteration's log-likelihood: needs the score table in LDS
     if constexpr (GEO != 3) { if (fmt == 1) return k_em_fused<P, 4, 1, GEO>; }   // (fp64 entries / geometry 3: the log1p finds no registers)
     return nullptr;
@@ -34,7 +44,7 @@ template <int P, int GEO> static fz_fn fz_pick2(int mode, int fmt) {
   if (fmt == 2) return mode ? k_em_fused<P, 1, 2, GEO> : k_em_fused<P, 0, 2, GEO>;
   return mode ? k_em_fused<P, 1, 0, GEO> : k_em_fused<P, 0, 0, GEO>;
 }
-template <int P> static fz_fn fz_pick(int mode, int fmt, int geo) {
-  if constexpr (P > 4) return geo == 2 ? fz_pick2<P, 2>(mode, fmt) : fz_pick2<P, 1>(mode, fmt);   // teams of 5-8: 384 or 768 row slots
-  else return geo == 3 ? fz_pick2<P, 3>(mode, fmt) : (geo == 2 ? fz_pick2<P, 2>(mode, fmt) : fz_pick2<P, 0>(mode, fmt));
+template <int P> static fz_fn fz_pick(int mode, int fmt, int geo, bool prof) {
+  if constexpr (P > 4) return geo == 2 ? fz_pick2<P, 2>(mode, fmt, prof) : fz_pick2<P, 1>(mode, fmt, prof);   // teams of 5-8: 384 or 768 row slots
+  else return geo == 3 ? fz_pick2<P, 3>(mode, fmt, prof) : (geo == 2 ? fz_pick2<P, 2>(mode, fmt, prof) : fz_pick2<P, 0>(mode, fmt, prof));
 }

@@ -132,21 +132,21 @@ static inline int ensure_device(tsem_ctx* h) {
 // live in eight translation units compiled in parallel (tsem_fz_p1.hip ... tsem_fz_p8.hip, tsem_fused_inst.h); each exports one
 // look-up function.  The host launches through the pointer.
 typedef void (*fz_fn)(FusedArgs);
-fz_fn tsem_fz_kernel_p1(int P, int mode, int fmt, int geo);
-fz_fn tsem_fz_kernel_p2(int P, int mode, int fmt, int geo);
-fz_fn tsem_fz_kernel_p3(int P, int mode, int fmt, int geo);
-fz_fn tsem_fz_kernel_p4(int P, int mode, int fmt, int geo);
-fz_fn tsem_fz_kernel_p5(int P, int mode, int fmt, int geo);
-fz_fn tsem_fz_kernel_p6(int P, int mode, int fmt, int geo);
-fz_fn tsem_fz_kernel_p7(int P, int mode, int fmt, int geo);
-fz_fn tsem_fz_kernel_p8(int P, int mode, int fmt, int geo);
+fz_fn tsem_fz_kernel_p1(int P, int mode, int fmt, int geo, bool prof);
+fz_fn tsem_fz_kernel_p2(int P, int mode, int fmt, int geo, bool prof);
+fz_fn tsem_fz_kernel_p3(int P, int mode, int fmt, int geo, bool prof);
+fz_fn tsem_fz_kernel_p4(int P, int mode, int fmt, int geo, bool prof);
+fz_fn tsem_fz_kernel_p5(int P, int mode, int fmt, int geo, bool prof);
+fz_fn tsem_fz_kernel_p6(int P, int mode, int fmt, int geo, bool prof);
+fz_fn tsem_fz_kernel_p7(int P, int mode, int fmt, int geo, bool prof);
+fz_fn tsem_fz_kernel_p8(int P, int mode, int fmt, int geo, bool prof);
 static inline int fz_fmt(const tsem_ctx* h) { return h->fmt_code ? 1 : (h->fmt_wcode ? 2 : 0); }
-static inline fz_fn fz_kernel(int P, int mode, int fmt, int geo) {
+static inline fz_fn fz_kernel(int P, int mode, int fmt, int geo, bool prof = false) {
   switch (P) {
-    case 1: return tsem_fz_kernel_p1(P, mode, fmt, geo); case 2: return tsem_fz_kernel_p2(P, mode, fmt, geo);
-    case 3: return tsem_fz_kernel_p3(P, mode, fmt, geo); case 4: return tsem_fz_kernel_p4(P, mode, fmt, geo);
-    case 5: return tsem_fz_kernel_p5(P, mode, fmt, geo); case 6: return tsem_fz_kernel_p6(P, mode, fmt, geo);
-    case 7: return tsem_fz_kernel_p7(P, mode, fmt, geo); case 8: return tsem_fz_kernel_p8(P, mode, fmt, geo);
+    case 1: return tsem_fz_kernel_p1(P, mode, fmt, geo, prof); case 2: return tsem_fz_kernel_p2(P, mode, fmt, geo, prof);
+    case 3: return tsem_fz_kernel_p3(P, mode, fmt, geo, prof); case 4: return tsem_fz_kernel_p4(P, mode, fmt, geo, prof);
+    case 5: return tsem_fz_kernel_p5(P, mode, fmt, geo, prof); case 6: return tsem_fz_kernel_p6(P, mode, fmt, geo, prof);
+    case 7: return tsem_fz_kernel_p7(P, mode, fmt, geo, prof); case 8: return tsem_fz_kernel_p8(P, mode, fmt, geo, prof);
     default: return nullptr;
   }
 }

@@ -519,6 +519,64 @@ int  tsem_bootstrap_mult(tsem_ctx* h, uint64_t seed, int32_t rep, int64_t row_be
 int  tsem_umi_dedup(tsem_ctx* h, const int32_t* cell_of_row, const int32_t* umi_of_row, int32_t n_cells, int32_t n_umis,
                     int32_t* rep_of_row /* N */, int64_t* stats4);
 
+/* ---- device loader: BAM records to per-fragment (locus, alnscore, alnlen) lists (telescope_amd/csrc/tsem_bam.hip) ----
+ * What telescope_amd/loader.py does between the inflated bytes of a BAM file and its list of mappings, per chunk of the byte stream.
+ * A chunk begins on a record boundary; a record is an int32 block_size and block_size bytes behind it.  A BUNDLE is a run of records
+ * with one query name (compared as the reader does: l_read_name and the l_read_name - 1 bytes in front of the terminator).
+ *
+ * tsem_bam_scan: HOST only, no device.  Walks the block_size chain of bytes[0, n_bytes): rec_off[i] = the offset of record i's size
+ * field, for the *n_rec records that lie completely inside the chunk (at most `cap`; rec_off holds cap + 1 values), and
+ * rec_off[*n_rec] = *consumed = the offset behind the last of them — the trailing partial record belongs to the next chunk.
+ * TSEM_ERR_ARG with a message (tsem_last_error(NULL)): a block_size below 32 (the fixed fields; nothing behind it can be trusted),
+ * a NULL pointer, a negative size. */
+typedef struct tsem_bam tsem_bam;
+#define TSEM_BAM_COLS 34
+int  tsem_bam_scan(const uint8_t* bytes, int64_t n_bytes, int64_t* rec_off /* cap + 1 */, int64_t cap, int64_t* n_rec, int64_t* consumed);
+/* The annotation, uploaded once per load, as loader.Annotation._sorted builds it: reference r of the BAM header (r in [0, n_ref)) owns
+ * the intervals [ref_lo[r], ref_hi[r]) — an empty range for a reference the annotation does not have — and inside such a range
+ *   starts[j]   the interval's first position, ascending, equal starts in the annotation's order
+ *   maxend[j]   the running maximum of ends over the range up to j (so it ascends as well)
+ *   ends[j]     one behind the interval's last position
+ *   locus[j]    an id >= 0 of the interval's locus (the caller's numbering)
+ *   strand[j]   0 '+', 1 '-', 2 anything else
+ * All are HOST arrays and are checked on the host (ranges inside [0, n_intervals], starts and maxend ascending inside a range:
+ * TSEM_ERR_ARG with a message otherwise) before the device is touched; TSEM_ERR_HIP / TSEM_ERR_NOMEM if the device refuses.
+ * `device` is a device index, as for tsem_csr_*: no matrix and no tsem_ctx exist yet.  Errors: tsem_last_error(NULL). */
+int  tsem_bam_open(tsem_bam** out, int device, int32_t n_ref, const int32_t* ref_lo, const int32_t* ref_hi, int64_t n_intervals,
+                   const int64_t* starts, const int64_t* maxend, const int64_t* ends, const int32_t* locus, const int8_t* strand);
+int  tsem_bam_close(tsem_bam* b);                      /* NULL is fine */
+/* One chunk through k_bam_decode, k_bam_pair, k_bam_overlap, k_bam_fragment.  bytes / rec_off / n_rec: as tsem_bam_scan left them
+ * (HOST arrays; checked on the host before the copy: offsets inside the chunk, every record 36 .. 2^31 - 1 bytes, fewer than 2^31 - 1
+ * records — TSEM_ERR_ARG otherwise, so that no kernel sees offsets it cannot trust); the chunk must end on a bundle boundary, the
+ * first record starts a bundle.  barcode_tag / umi_tag: the Z tag's two letters as first | second << 8, or -1.  run_stranded: apply the
+ * strand filter; first_f / last_f: stranded_mode[0] == 'F' / stranded_mode[-1] == 'F'.  record_cap >= 1: a longer bundle is left to
+ * the host.  out: int32 [TSEM_BAM_COLS][n_rec], row c at out + c * n_rec; i = a record's index in the chunk, s = the index of a
+ * bundle's first record:
+ *    0-15  per record i: ref_id, pos, next_ref, next_pos, |tlen| (uint32 bits), flag, l_read_name, n_cigar, l_seq, AS, bits (1: AS
+ *          present, 2: the name differs from record i - 1's, i.e. i starts a bundle, 4: a value only the host reproduces), offset
+ *          (from the record's size field) and length of the barcode tag's value and of the UMI tag's (-1, -1: none; the last such
+ *          tag counts), status (0, or the code below)
+ *   16-18  per record slot: r1 and r2 (record indices, r2 -1: none) of the bundle's k-th alignment pair at slot s + k (-1: no pair at
+ *          this slot), in the order of loader._fragments; s itself
+ *   19-21  per pair slot: the pair's locus (-1: none, i.e. `__no_feature`; -2: r1 unmapped; -3: not computed), alnscore, alnlen
+ *   22-24  per map slot: locus, alnscore, alnlen of the bundle's k-th mapping at slot s + k, in the loader's order
+ *   25-32  per bundle, at s: code (0 SU 1 SM 2 PU 3 PM 4 PX), pairs, mappings, class (0 unmapped 1 nofeat_U 2 nofeat_A 3 feat_U
+ *          4 feat_A 5 left to the host), minimum and maximum alnscore over its mapped pairs, how many those are, flags (1: host)
+ *      33  scratch
+ * A bundle of class 5 has no valid pairs or mappings: the caller runs the host loader on its bytes.  status2[0] = 0, or the code of
+ * the first record in file order that cannot be decoded, status2[1] = that record: 1 block_size against rec_off, 2 l_read_name,
+ * 3 n_cigar past the record, 4 l_seq past the record, 5 an aux field's head past the record, 6 an aux value past the record, 7 a Z / H
+ * value without NUL inside the record, 8 a B array past the record (or a negative count, an unknown element type), 9 an unknown aux
+ * type, 10 a mapped alignment without AS.  The call itself then still returns TSEM_OK, and `out` is not to be used.  TSEM_ERR_HIP /
+ * TSEM_ERR_NOMEM with a message (tsem_last_error(NULL)) if a copy, a launch or an allocation fails.  The handle keeps its device
+ * buffers between calls and grows them as needed: 1 B per chunk byte and 144 B per record. */
+int  tsem_bam_chunk(tsem_bam* b, const uint8_t* bytes, int64_t n_bytes, const int64_t* rec_off, int64_t n_rec, int32_t barcode_tag,
+                    int32_t umi_tag, int32_t run_stranded, int32_t first_f, int32_t last_f, double overlap_threshold,
+                    int32_t record_cap, int32_t* out, int64_t* status2);
+/* HIP-event milliseconds summed over the calls so far: host-to-device, k_bam_decode, k_bam_pair, k_bam_overlap, k_bam_fragment,
+ * device-to-host; *calls = how many; reset != 0 clears both. */
+int  tsem_bam_times(tsem_bam* b, int reset, double* ms6, int64_t* calls);
+
 /* ---- csr_matrix_plus primitives on arbitrary fp64 CSR (sparse_plus.py) ---- */
 /* All three: indptr[n_rows + 1] is a HOST array and is checked on the host before the device is touched. TSEM_ERR_ARG (text in
  * tsem_last_error(NULL)) for n_rows < 0, n_cols < 0, indptr NULL, indptr[0] != 0, any indptr[i + 1] < indptr[i], or data / out

@@ -27,14 +27,14 @@ class EngineError(RuntimeError):
 
 
 # host / ABI, set-up, EM support, report / row passes, collectives, CSR primitives, per-cell counts, per-cell fits, bootstrap,
-# UMI duplicates (telescope_amd/csrc/tsem_internal.h)
+# UMI duplicates, device loader (telescope_amd/csrc/tsem_internal.h)
 LIB_UNITS = ('tsem_host', 'tsem_setup', 'tsem_em', 'tsem_report', 'tsem_comm', 'tsem_csr', 'tsem_cells', 'tsem_cellem', 'tsem_boot',
-             'tsem_umi')
+             'tsem_umi', 'tsem_bam')
 FZ_UNITS = tuple('tsem_fz_p%d' % p for p in range(1, 9))
 
 
 def build_library(force=False, verbose=False, out=None):
-    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  Eighteen translation units — the ten of
+    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  Nineteen translation units — the eleven of
     LIB_UNITS and the eight that instantiate the fused kernel for one team size each (most of the build time) — are compiled
     in parallel and linked into one shared object."""
     from concurrent.futures import ThreadPoolExecutor
@@ -235,6 +235,11 @@ def lib():
     L.tsem_bootstrap_groups_shape.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.tsem_bootstrap_groups_copy.argtypes = [vp, vp, vp, vp, vp, vp]
     L.tsem_umi_dedup.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+    L.tsem_bam_scan.argtypes = [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.tsem_bam_open.argtypes = [C.POINTER(vp), C.c_int, i32, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.tsem_bam_close.argtypes = [vp]
+    L.tsem_bam_chunk.argtypes = [vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, dbl, i32, vp, vp]
+    L.tsem_bam_times.argtypes = [vp, C.c_int, vp, C.POINTER(i64)]
     L.tsem_csr_norm_rows.argtypes = [C.c_int, i64, vp, vp, vp]
     L.tsem_csr_binmax_rows.argtypes = [C.c_int, i64, i32, vp, vp, vp]
     L.tsem_csr_scale.argtypes = [C.c_int, C.c_int, i64, i32, vp, vp, vp]
@@ -892,6 +897,79 @@ def stream_read_gbs(device=0, nbytes=8 << 30, reps=3):
     if rc:
         raise EngineError('tsem_debug_stream_read failed (%d)' % rc)
     return g.value
+
+
+BAM_COLS = 34                  # TSEM_BAM_COLS; the rows of BamLoader.chunk's matrix (include/telescope_em.h)
+BAM_STATUS = {1: 'block_size does not match the record chain', 2: 'l_read_name leaves the record', 3: 'n_cigar runs past the record',
+              4: 'l_seq runs past the record', 5: 'an aux field begins past the record', 6: 'an aux value runs past the record',
+              7: 'a Z / H aux value has no NUL inside the record', 8: 'a B aux array runs past the record',
+              9: 'unknown aux type', 10: 'a mapped alignment has no AS tag'}
+
+
+def bam_scan(data, cap=None):
+    """Record offsets of a chunk of inflated BAM bytes (tsem_bam_scan, host only): (rec_off int64 [n + 1], consumed)."""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    cap = buf.size // 36 + 1 if cap is None else int(cap)
+    off = np.empty(cap + 1, np.int64)
+    n, used = C.c_int64(), C.c_int64()
+    rc = lib().tsem_bam_scan(ptr(buf) if buf.size else None, buf.size, ptr(off), cap, C.byref(n), C.byref(used))
+    if rc != OK:
+        raise _csr_error('tsem_bam_scan', rc)
+    return off[:n.value + 1].copy(), used.value
+
+
+def _tag16(tag):
+    if tag is None:
+        return -1
+    t = tag.encode()
+    if len(t) != 2:
+        raise ValueError('a BAM tag has two letters, not %r' % tag)
+    return t[0] | (t[1] << 8)
+
+
+class BamLoader(object):
+    """The device side of the device loader (tsem_bam_open / tsem_bam_chunk): the annotation's arrays on one GPU and the four
+    kernels per chunk.  `ref_lo`, `ref_hi` per BAM reference; `starts`, `maxend`, `ends`, `locus`, `strand` per interval."""
+
+    def __init__(self, device, ref_lo, ref_hi, starts, maxend, ends, locus, strand):
+        L = lib()
+        a = [np.ascontiguousarray(x, dtype=t) for x, t in ((ref_lo, np.int32), (ref_hi, np.int32), (starts, np.int64), (maxend, np.int64),
+                                                           (ends, np.int64), (locus, np.int32), (strand, np.int8))]
+        h = C.c_void_p()
+        rc = L.tsem_bam_open(C.byref(h), int(device), len(a[0]), ptr(a[0]), ptr(a[1]), len(a[2]), *[ptr(x) for x in a[2:]])
+        if rc != OK:
+            raise _csr_error('tsem_bam_open', rc)
+        self._L, self._h = L, h
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._L.tsem_bam_close(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def chunk(self, data, rec_off, barcode_tag=None, umi_tag=None, run_stranded=False, stranded_mode='None', overlap_threshold=0.2,
+              record_cap=4096):
+        """-> (int32 [BAM_COLS][n_rec], (status code, record)) of one chunk: the raw outputs of the four kernels."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        n = len(off) - 1
+        out = np.empty((BAM_COLS, max(n, 0)), np.int32)
+        st = np.zeros(2, np.int64)
+        rc = self._L.tsem_bam_chunk(self._h, ptr(buf) if buf.size else None, buf.size, ptr(off), n, _tag16(barcode_tag), _tag16(umi_tag),
+                                    int(bool(run_stranded)), int(stranded_mode[0] == 'F'), int(stranded_mode[-1] == 'F'),
+                                    float(overlap_threshold), int(record_cap), ptr(out), ptr(st))
+        if rc != OK:
+            raise _csr_error('tsem_bam_chunk', rc)
+        return out, (int(st[0]), int(st[1]))
+
+    def times(self, reset=False):
+        """HIP-event milliseconds summed over the chunks so far, and their number."""
+        ms, n = np.zeros(6), C.c_int64()
+        rc = self._L.tsem_bam_times(self._h, int(reset), ptr(ms), C.byref(n))
+        if rc != OK:
+            raise _csr_error('tsem_bam_times', rc)
+        return dict(zip(('h2d', 'k_bam_decode', 'k_bam_pair', 'k_bam_overlap', 'k_bam_fragment', 'd2h'), ms.tolist()), chunks=n.value)
 
 
 def _csr_error(fn, rc):

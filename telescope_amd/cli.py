@@ -16,7 +16,8 @@ count matrices, built sparse on the device (`<exp_tag>-TE_counts[_<method>].tsv`
 device before the model is built (`<exp_tag>-umi_stats.tsv`); `sc resume` collapses iff its checkpoint holds UMIs; `--ignore_umi`.
 
 `assign` (telescope/telescope_assign.py:372-451) uses telescope_amd/loader.py, a pysam-free
-restatement of the reference's sequential loader; `--ncpu > 1` is not offered.  `--updated_sam` writes `<exp_tag>-updated.bam`
+restatement of the reference's sequential loader; `--ncpu > 1` is not offered.  `--loader device` (not in the reference) does that
+loader's per-record work on the GPU (telescope_amd/loader_device.py): the same matrix, checkpoint and reports.  `--updated_sam` writes `<exp_tag>-updated.bam`
 (model.py:479-521) beside `<exp_tag>-other.bam` and `<exp_tag>-tmp_tele.bam` of the load, on one GPU.
 """
 import argparse
@@ -101,6 +102,9 @@ def _assign_args(asg):
     g.add_argument('--no_feature_key', default='__no_feature',
                    help='Used internally to represent alignments that do not overlap any feature.')
     g.add_argument('--ncpu', type=int, default=1, help='Only 1 is supported (sequential loader).')
+    g.add_argument('--loader', default='python', choices=['python', 'device'],
+                   help='python (default): the streaming pure-Python BAM parser.  device: the records are decoded, paired and '
+                        'intersected with the annotation on the GPU (--device), the same matrix and checkpoint; not with --updated_sam.')
     g.add_argument('--tempdir', help='(accepted for compatibility; no temporary files are written)')
     g = asg.add_argument_group('Reporting Options')
     g.add_argument('--quiet', action='store_true', help='Silence (most) output.')
@@ -343,6 +347,14 @@ def _refuse_umi_updated_sam(args):
                          'fragments would need tags of their own); run the two separately')
 
 
+def _refuse_device_updated_sam(args):
+    """`--loader device` with --updated_sam: refused before anything is read (the tmp and other BAMs are written record by record
+    during the Python load; the device loader does not write them)."""
+    if getattr(args, 'loader', 'python') == 'device' and getattr(args, 'updated_sam', False):
+        raise SystemExit('telescope assign: --loader device with --updated_sam is not supported (the BAMs of the load are written '
+                         'record by record by the python loader); use --loader python')
+
+
 def collapse_umis(ts, opts):
     """`sc assign --umi_tag` / `sc resume` of a checkpoint with UMIs: the run goes on with the kept fragments (scTelescope.collapse_umis)
     unless --ignore_umi; <exp_tag>-umi_stats.tsv lists them per barcode."""
@@ -451,6 +463,7 @@ def run_assign(args, sc=False):
     _refuse_sharded_sc(sc)
     _refuse_bootstrap(args)
     _refuse_umi_updated_sam(args)
+    _refuse_device_updated_sam(args)
     opts = ResumeOptions(args)
     configure_logging(opts)
     if opts.ncpu != 1:
@@ -484,6 +497,8 @@ def run_assign(args, sc=False):
             stime = time()
             if opts.updated_sam:
                 os.makedirs(opts.outdir, exist_ok=True)          # (the load writes <exp_tag>-other.bam and -tmp_tele.bam there)
+            if opts.loader == 'device' and warm is not None:
+                warm.join()                                      # (the device loader's first call finds the device up)
             ts.load_alignment(annot)
             lg.info('Loaded alignment in {}'.format(format_minutes(time() - stime)))
             if sc:

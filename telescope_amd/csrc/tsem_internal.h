@@ -12,6 +12,8 @@
 //   tsem_boot.hip    bootstrap replicates: the EM refitted with a multiplicity per row, batches of replicates per sweep;
 //                    with a group sink also per-(group, column) statistics over the replicates (the pattern comes from tsem_cells.hip)
 //   tsem_umi.hip     UMI duplicates of a single-cell run: classes, links, components, representatives (tsem_umi_dedup)
+//   tsem_bam.hip     the device loader of `assign`: BAM records of a chunk to per-fragment (locus, alnscore, alnlen) lists (tsem_bam_*;
+//                    the stages' bodies are host / device functions in tsem_bam_rec.h and tsem_bam_stages.h, the record chain in tsem_bam_scan.h)
 //   tsem_fz_p*.hip   instantiations of the fused kernel (tsem_fused.h), one team size per unit
 //
 // A kernel is launched only from the unit that defines it; other units go through the host functions declared here.

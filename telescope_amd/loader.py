@@ -27,7 +27,8 @@ Size: the BAM is STREAMED (one record at a time through a buffered gzip reader: 
 the file), the mappings are kept as four compact integer arrays (16 B per (fragment, locus) hit, like the
 reference's list of tuples but ~10x smaller), and the annotation is indexed per chromosome.  It is still a
 pure-Python record loop: ~50-100 k records/s, i.e. minutes for the 10^7-record BAMs of a typical RNA-seq run
-and hours beyond 10^8 — use the reference's pysam loader and `telescope resume` on its checkpoint for those.
+and hours beyond 10^8 — use `loader='device'` (loader_device.py: decode_record, assign_pair, score_bundle and mappings_to_result below
+are what it shares with this loader) or the reference's pysam loader and `telescope resume` on its checkpoint for those.
 """
 import gzip
 import io
@@ -70,15 +71,46 @@ class Segment(object):
         return out
 
 
-def read_bam(path, barcode_tag=None, raw=False, umi_tag=None):
-    """-> (reference names, iterator of Segment) from a BAM file, streamed.  `barcode_tag` (e.g. 'CB'): the value of that Z-type
-    tag goes to Segment.bc (None where the record has no such tag); `umi_tag` (e.g. 'UB'): likewise, to Segment.umi.  `raw=True`: every Segment also keeps its record's bytes
-    (Segment.raw, without the block size), and a third value is returned: dict(text=header text, refs_block=the binary
-    reference list, n_ref included) — what bam_out.BamWriter writes back."""
-    btag = barcode_tag.encode() if barcode_tag else None
-    utag = umi_tag.encode() if umi_tag else None
-    fh = io.BufferedReader(gzip.open(path, 'rb'), buffer_size=1 << 20)
+def decode_record(buf, btag=None, utag=None, raw=False):
+    """-> Segment of one record's bytes (without the block size).  `btag` / `utag`: the barcode / UMI tag's two letters as bytes, or
+    None; `raw`: the Segment keeps `buf`.  What read_bam yields, and what the device loader runs on the bundles it leaves to the host."""
+    bs = len(buf)
+    s = Segment()
+    (s.ref_id, s.pos, l_rn, _mq, _bin, n_cig, s.flag, l_seq, s.nref, s.npos,
+     s.tlen) = struct.unpack_from('<iiBBHHHiiii', buf, 0)
+    p = 32
+    s.qname = buf[p:p + l_rn - 1].decode(); p += l_rn
+    s.cigar = struct.unpack_from('<%dI' % n_cig, buf, p); p += 4 * n_cig
+    p += (l_seq + 1) // 2 + l_seq
+    s.AS = s.bc = s.umi = None
+    while p < bs:
+        tag = buf[p:p + 2]; typ = chr(buf[p + 2]); p += 3
+        if typ in _TAG_FMT:
+            (val,) = struct.unpack_from('<' + _TAG_FMT[typ], buf, p)
+            p += struct.calcsize(_TAG_FMT[typ])
+            if tag == b'AS':
+                s.AS = val
+        elif typ == 'A':
+            p += 1
+        elif typ in 'ZH':
+            end = buf.index(b'\x00', p)
+            if typ == 'Z' and tag == btag:
+                s.bc = buf[p:end].decode()
+            if typ == 'Z' and tag == utag:
+                s.umi = buf[p:end].decode()
+            p = end + 1
+        elif typ == 'B':
+            sub = chr(buf[p]); (cnt,) = struct.unpack_from('<i', buf, p + 1)
+            p += 5 + cnt * _B_SIZE[sub]
+        else:
+            raise ValueError('unknown BAM tag type %r' % typ)
+    if raw:
+        s.raw = buf
+    return s
 
+
+def read_bam_header(fh, path):
+    """-> (reference names, header text bytes, the binary reference list with n_ref) from an inflated BAM stream at its start"""
     def need(n):
         b = fh.read(n)
         if len(b) != n:
@@ -98,6 +130,25 @@ def read_bam(path, barcode_tag=None, raw=False, umi_tag=None):
         name = need(l_name)
         refs.append(name[:-1].decode())
         block += [ln, name, need(4)]
+    return refs, text, b''.join(block)
+
+
+def read_bam(path, barcode_tag=None, raw=False, umi_tag=None):
+    """-> (reference names, iterator of Segment) from a BAM file, streamed.  `barcode_tag` (e.g. 'CB'): the value of that Z-type
+    tag goes to Segment.bc (None where the record has no such tag); `umi_tag` (e.g. 'UB'): likewise, to Segment.umi.  `raw=True`: every Segment also keeps its record's bytes
+    (Segment.raw, without the block size), and a third value is returned: dict(text=header text, refs_block=the binary
+    reference list, n_ref included) — what bam_out.BamWriter writes back."""
+    btag = barcode_tag.encode() if barcode_tag else None
+    utag = umi_tag.encode() if umi_tag else None
+    fh = io.BufferedReader(gzip.open(path, 'rb'), buffer_size=1 << 20)
+
+    def need(n):
+        b = fh.read(n)
+        if len(b) != n:
+            raise ValueError('%s: truncated BAM' % path)
+        return b
+
+    refs, text, refs_block = read_bam_header(fh, path)
 
     def records():
         try:
@@ -108,43 +159,11 @@ def read_bam(path, barcode_tag=None, raw=False, umi_tag=None):
                 if len(head) != 4:
                     raise ValueError('%s: truncated BAM record' % path)
                 (bs,) = struct.unpack('<i', head)
-                buf = need(bs)
-                s = Segment()
-                (s.ref_id, s.pos, l_rn, _mq, _bin, n_cig, s.flag, l_seq, s.nref, s.npos,
-                 s.tlen) = struct.unpack_from('<iiBBHHHiiii', buf, 0)
-                p = 32
-                s.qname = buf[p:p + l_rn - 1].decode(); p += l_rn
-                s.cigar = struct.unpack_from('<%dI' % n_cig, buf, p); p += 4 * n_cig
-                p += (l_seq + 1) // 2 + l_seq
-                s.AS = s.bc = s.umi = None
-                while p < bs:
-                    tag = buf[p:p + 2]; typ = chr(buf[p + 2]); p += 3
-                    if typ in _TAG_FMT:
-                        (val,) = struct.unpack_from('<' + _TAG_FMT[typ], buf, p)
-                        p += struct.calcsize(_TAG_FMT[typ])
-                        if tag == b'AS':
-                            s.AS = val
-                    elif typ == 'A':
-                        p += 1
-                    elif typ in 'ZH':
-                        end = buf.index(b'\x00', p)
-                        if typ == 'Z' and tag == btag:
-                            s.bc = buf[p:end].decode()
-                        if typ == 'Z' and tag == utag:
-                            s.umi = buf[p:end].decode()
-                        p = end + 1
-                    elif typ == 'B':
-                        sub = chr(buf[p]); (cnt,) = struct.unpack_from('<i', buf, p + 1)
-                        p += 5 + cnt * _B_SIZE[sub]
-                    else:
-                        raise ValueError('unknown BAM tag type %r' % typ)
-                if raw:
-                    s.raw = buf
-                yield s
+                yield decode_record(need(bs), btag, utag, raw)
         finally:
             fh.close()
     if raw:
-        return refs, records(), dict(text=text.split(b'\x00', 1)[0].decode(), refs_block=b''.join(block))
+        return refs, records(), dict(text=text.split(b'\x00', 1)[0].decode(), refs_block=refs_block)
     return refs, records()
 
 
@@ -288,12 +307,47 @@ def _fragments(records):
         yield classify(bundle)
 
 
+def assign_pair(pair, annotation, refs, stranded_mode, no_feature_key, overlap_threshold):
+    """model.py:877-897: the pair's best locus iff its overlap exceeds alnlen * threshold, else `no_feature_key`"""
+    if pair.r1.is_reverse:
+        strand = ('+' if stranded_mode[-1] == 'F' else '-') if pair.is_paired else \
+                 ('-' if stranded_mode[0] == 'F' else '+')
+    else:
+        strand = ('-' if stranded_mode[-1] == 'F' else '+') if pair.is_paired else \
+                 ('+' if stranded_mode[0] == 'F' else '-')
+    f = annotation.intersect_blocks(refs[pair.r1.ref_id], pair.refblocks, strand)
+    if not f:
+        return no_feature_key
+    fname, overlap = f.most_common()[0]
+    return fname if overlap > pair.alnlen * overlap_threshold else no_feature_key
+
+
+def score_bundle(alns, assign, no_feature_key):
+    """One bundle that is not SU / PU -> (mapped pairs, their features, byfeat, maps); byfeat and maps are None when no pair has a
+    feature.  byfeat: feature -> its pairs, best first (model.py:30-63); maps: (qname, feature, alnscore, alnlen) of the best pair
+    per feature, by alnscore descending."""
+    mapped = [a for a in alns if not a.is_unmapped]
+    feats = [assign(a) for a in mapped]
+    if not any(f != no_feature_key for f in feats):
+        return mapped, feats, None, None
+    byfeat = OrderedDict()
+    for a, f in zip(mapped, feats):
+        byfeat.setdefault(f, []).append(a)
+    maps = []
+    for f, fal in byfeat.items():
+        fal.sort(key=lambda x: x.alnscore + x.alnlen, reverse=True)
+        maps.append((alns[0].r1.qname, f, fal[0].alnscore, fal[0].alnlen))
+    maps.sort(key=lambda x: x[2], reverse=True)
+    return mapped, feats, byfeat, maps
+
+
 CODE_DESC = OrderedDict([('SU', 'single_unmapped'), ('SM', 'single_mapped'), ('PU', 'pair_unmapped'),
                          ('PM', 'pair_mapped'), ('PX', 'pair_mixed'), ('PX*', 'pair_mixed_unmapped')])
 
 
 def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_mode='threshold',
-                   overlap_threshold=0.2, stranded_mode='None', barcode_tag=None, updated_sam=None, umi_tag=None):
+                   overlap_threshold=0.2, stranded_mode='None', barcode_tag=None, updated_sam=None, umi_tag=None, loader='python',
+                   device=0, chunk_bytes=None, record_cap=4096):
     """-> dict(raw_scores uint16 CSR, read_index, feat_index, feature_length, run_info fields).  With `barcode_tag` (scTelescope,
     model.py:245-247,311-316) also cell_of_row (int32 per row, -1 = no barcode) and barcodes (the cell names): the tag is read from
     the first read of every mapped fragment; only fragments that become rows count; cells are ordered by the first appearance of
@@ -302,10 +356,21 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
     (only alns[0] of an SU bundle) and fragments without overlap go to other_bam, every AlignedPair of an overlapping fragment
     (r1 then r2, in pairing order) to tmp_bam, both with the input's header; the pairs of an overlapping fragment carry ZF (its
     feature) and ZT (PRI for the best pair of each feature by alnscore + alnlen, SEC for the others), and every mapped pair ZB
-    (the top-score features, comma-joined) — model.py:30-63, set like pysam's set_tag (the old tag goes, the new one is appended)."""
+    (the top-score features, comma-joined) — model.py:30-63, set like pysam's set_tag (the old tag goes, the new one is appended).
+    `loader='device'`: the same dict, key by key, from the device loader (loader_device.py: the records are decoded, paired and
+    intersected on GPU `device`, in chunks of about `chunk_bytes` inflated bytes, default 64 MiB; a bundle of more than `record_cap`
+    records is left to this module's code); not with `updated_sam`."""
     if overlap_mode != 'threshold':
         raise NotImplementedError('only overlap_mode "threshold" is implemented (as in the reference, '
                                   'model.py:899-903)')
+    if loader == 'device':
+        if updated_sam:
+            raise ValueError('the device loader does not write the BAMs of --updated_sam')
+        from .loader_device import load_alignment_device
+        return load_alignment_device(samfile, annotation, no_feature_key, overlap_threshold, stranded_mode, barcode_tag, umi_tag,
+                                     device=device, chunk_bytes=chunk_bytes, record_cap=record_cap)
+    if loader != 'python':
+        raise ValueError("loader must be 'python' or 'device', not %r" % (loader,))
     bam_u = bam_t = None
     if updated_sam:
         from .bam_out import BamWriter
@@ -323,17 +388,7 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
     read_umi = {}                                        # ... -> UMI
 
     def assign(pair):
-        if pair.r1.is_reverse:
-            strand = ('+' if stranded_mode[-1] == 'F' else '-') if pair.is_paired else \
-                     ('-' if stranded_mode[0] == 'F' else '+')
-        else:
-            strand = ('-' if stranded_mode[-1] == 'F' else '+') if pair.is_paired else \
-                     ('+' if stranded_mode[0] == 'F' else '-')
-        f = annotation.intersect_blocks(refs[pair.r1.ref_id], pair.refblocks, strand)
-        if not f:
-            return no_feature_key
-        fname, overlap = f.most_common()[0]
-        return fname if overlap > pair.alnlen * overlap_threshold else no_feature_key
+        return assign_pair(pair, annotation, refs, stranded_mode, no_feature_key, overlap_threshold)
 
     info = Counter()
     ridx, fidx = OrderedDict(), OrderedDict([(no_feature_key, 0)])
@@ -351,25 +406,16 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
                 read_bc[alns[0].r1.qname] = alns[0].r1.bc
             if umi_tag and alns[0].r1.umi is not None:
                 read_umi[alns[0].r1.qname] = alns[0].r1.umi
-            mapped = [a for a in alns if not a.is_unmapped]
+            mapped, feats, byfeat, maps = score_bundle(alns, assign, no_feature_key)
             ambig = len(mapped) > 1
             for a in mapped:
                 min_as, max_as = min(min_as, a.alnscore), max(max_as, a.alnscore)
-            feats = [assign(a) for a in mapped]
-            if not any(f != no_feature_key for f in feats):
+            if maps is None:
                 info['nofeat_A' if ambig else 'nofeat_U'] += 1
                 if bam_u is not None:
                     write(bam_u, alns)
                 continue
             info['feat_A' if ambig else 'feat_U'] += 1
-            byfeat = OrderedDict()
-            for a, f in zip(mapped, feats):
-                byfeat.setdefault(f, []).append(a)
-            maps = []
-            for f, fal in byfeat.items():
-                fal.sort(key=lambda x: x.alnscore + x.alnlen, reverse=True)
-                maps.append((alns[0].r1.qname, f, fal[0].alnscore, fal[0].alnlen))
-            maps.sort(key=lambda x: x[2], reverse=True)
             for rid, fid, ascr, alen in maps:                  # first-appearance ids (model.py:309-311)
                 m_row.append(ridx.setdefault(rid, len(ridx)))
                 m_col.append(fidx.setdefault(fid, len(fidx)))
@@ -390,9 +436,19 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
             bam_u.close()
             bam_t.close()
 
+    return mappings_to_result(annotation, info, ridx, fidx, np.frombuffer(m_row, dtype=np.int64), np.frombuffer(m_col, dtype=np.int32),
+                              np.frombuffer(m_as, dtype=np.int32), np.frombuffer(m_len, dtype=np.int32), min_as, max_as,
+                              read_bc if barcode_tag else None, read_umi if umi_tag else None)
+
+
+def mappings_to_result(annotation, info, ridx, fidx, m_row, m_col, m_as, m_len, min_as, max_as, read_bc, read_umi):
+    """The loaders' common end: the mappings (row id int64, column id int32, alnscore int32, alnlen int32 per hit, in BAM order), the
+    first-appearance ids, the counters of the bundles and the score range -> load_alignment's dict.  read_bc / read_umi: fragment
+    name -> barcode / UMI in BAM order, None when the tag was not asked for."""
+    barcode_tag, umi_tag = read_bc is not None, read_umi is not None
     # model.py:287-362: rescale, max per (fragment, locus), drop the fragments that hit only column 0
-    rr, cc = np.frombuffer(m_row, dtype=np.int64), np.frombuffer(m_col, dtype=np.int32).astype(np.int64)
-    vv = (np.frombuffer(m_as, dtype=np.int32).astype(np.int64) - min_as + 1) + np.frombuffer(m_len, dtype=np.int32)
+    rr, cc = np.asarray(m_row, dtype=np.int64), np.asarray(m_col, dtype=np.int32).astype(np.int64)
+    vv = (np.asarray(m_as, dtype=np.int32).astype(np.int64) - min_as + 1) + np.asarray(m_len, dtype=np.int32)
     if vv.size and vv.max() > 65535:
         raise ValueError('alignment score %d does not fit uint16 (model.py:300)' % int(vv.max()))
     n_feat = len(fidx)

@@ -1,0 +1,267 @@
+"""The device loader of `assign` (`--loader device`): loader.load_alignment's dict, key by key, with the per-record work on the GPU.
+
+  host    BGZF inflate (gzip), the record chain of every chunk (tsem_bam_scan, C), the cut in front of the chunk's last bundle —
+          the last bundle may go on in the next chunk, so it is carried over with the unconsumed tail, and a chunk that holds one
+          bundle only grows until a second one begins;
+  device  one call per chunk (tsem_bam_chunk, telescope_amd/csrc/tsem_bam.hip): k_bam_decode, k_bam_pair, k_bam_overlap,
+          k_bam_fragment -> per bundle the fragment code, the class and the (locus, alnscore, alnlen) list;
+  host    first-appearance row ids per name (the same `setdefault`), first-appearance column ids per locus (np.unique per chunk against
+          a running table), the counters (np.bincount), the barcode / UMI strings, then loader.mappings_to_result — the Python
+          loader's own tail.
+
+A bundle the kernels leave to the host (class 5: more records than `record_cap`, a pair that hits more than 8 loci, a value outside
+int32 ...) is decoded with loader.decode_record and run through loader._fragments / assign_pair / score_bundle; its result replaces the
+device's at the same position, which makes the load exact for every input.  LAST_STATS holds the last load's counts and wall times.
+"""
+import gzip
+import io
+import logging as lg
+from collections import Counter, OrderedDict
+from time import perf_counter
+
+import numpy as np
+
+from . import loader as pyl
+from ._lib import BAM_STATUS, BamLoader, bam_scan
+
+DEFAULT_CHUNK_BYTES = 64 << 20
+CODES = ('SU', 'SM', 'PU', 'PM', 'PX')
+CLS_HOST = 5
+# rows of BamLoader.chunk's matrix (include/telescope_em.h)
+(C_REF, C_POS, C_NREF, C_NPOS, C_ATLEN, C_FLAG, C_LRN, C_NCIG, C_LSEQ, C_AS, C_BITS, C_BCOFF, C_BCLEN, C_UMIOFF, C_UMILEN, C_STATUS,
+ C_PAIR1, C_PAIR2, C_BUNDLE, C_PFEAT, C_PAS, C_PLEN, C_MFEAT, C_MAS, C_MLEN, C_BCODE, C_BNPAIRS, C_BNMAPS, C_BCLASS, C_BMIN, C_BMAX,
+ C_BNMAPPED, C_BFLAG, C_SCRATCH) = range(34)
+BIT_AS, BIT_NEWNAME, BIT_HOST = 1, 2, 4
+
+LAST_STATS = {}
+
+
+def annotation_arrays(annotation, refs):
+    """The arrays of tsem_bam_open from loader.Annotation._sorted, per BAM reference in header order: (ref_lo, ref_hi, starts, maxend,
+    ends, locus, strand, locus names).  The locus ids follow `annotation.loci`."""
+    names = list(annotation.loci)
+    lid = {n: i for i, n in enumerate(names)}
+    ranges, ref_lo, ref_hi = {}, [], []
+    starts, maxend, ends, locus, strand = [], [], [], [], []
+    n = 0
+    for chrom in refs:
+        if chrom not in ranges:
+            ivs, st, mx = annotation._sorted(chrom)
+            ranges[chrom] = (n, n + len(ivs))
+            starts.append(st); maxend.append(mx)
+            ends.append(np.array([iv[1] for iv in ivs], dtype=np.int64))
+            locus.append(np.array([lid[iv[2]] for iv in ivs], dtype=np.int32))
+            strand.append(np.array([0 if iv[3] == '+' else (1 if iv[3] == '-' else 2) for iv in ivs], dtype=np.int8))
+            n += len(ivs)
+        ref_lo.append(ranges[chrom][0]); ref_hi.append(ranges[chrom][1])
+    cat = lambda xs, t: np.concatenate(xs).astype(t) if xs else np.zeros(0, t)
+    return (np.array(ref_lo, np.int32), np.array(ref_hi, np.int32), cat(starts, np.int64), cat(maxend, np.int64), cat(ends, np.int64),
+            cat(locus, np.int32), cat(strand, np.int8), names)
+
+
+def _same_name(data, a, b):
+    l = data[a + 12]
+    return l == data[b + 12] and data[a + 36:a + 35 + l] == data[b + 36:b + 35 + l]
+
+
+def bam_chunks(fh, path, chunk_bytes, max_bundles=None, stats=None):
+    """-> (data, rec_off) per chunk of the inflated record stream `fh`: rec_off (int64 [n + 1], tsem_bam_scan) lists whole records that
+    form whole bundles; what lies behind rec_off[n] in `data` was carried into the next chunk.  `max_bundles`: at most so many bundles
+    per chunk."""
+    stats = {} if stats is None else stats
+    tail = b''
+    while True:
+        t0 = perf_counter()
+        new = fh.read(chunk_bytes)
+        t1 = perf_counter()
+        eof = not new
+        data = tail + new if tail else new
+        off, used = bam_scan(data)
+        stats['inflate_s'] = stats.get('inflate_s', 0.) + t1 - t0
+        stats['scan_s'] = stats.get('scan_s', 0.) + perf_counter() - t1
+        n = len(off) - 1
+        cut = n
+        if not eof:                                          # the last bundle may go on behind the chunk: it waits for the next one
+            cut = n - 1 if n else 0
+            while cut > 0 and _same_name(data, int(off[cut - 1]), int(off[cut])):
+                cut -= 1
+            if cut == 0:                                     # one bundle, or less than a record: the chunk grows
+                tail = data
+                continue
+        elif used != len(data):
+            raise ValueError(('%s: truncated BAM record' if len(data) - used < 4 else '%s: truncated BAM') % path)
+        if max_bundles:                                      # (tests: [0, cut) in pieces of max_bundles bundles)
+            lo = 0
+            while lo < cut:
+                hi, nb = lo + 1, 1
+                while hi < cut:
+                    starts_bundle = not _same_name(data, int(off[hi - 1]), int(off[hi]))
+                    if starts_bundle and nb == max_bundles:
+                        break
+                    nb += starts_bundle
+                    hi += 1
+                base = int(off[lo])
+                yield data[base:int(off[hi])], off[lo:hi + 1] - base
+                lo = hi
+        elif cut:
+            yield data, off[:cut + 1]
+        if eof:
+            return
+        tail = data[int(off[cut]):]
+
+
+def _record_name(data, off, i):
+    o, e = int(off[i]), int(off[i + 1])
+    l = data[o + 12]
+    return data[o + 36:min(o + 35 + l, e)].decode(errors='replace')
+
+
+def host_bundle(data, off, s, e, btag, utag, assign, no_feature_key):
+    """The Python loader's own code on records [s, e) of a chunk (one bundle): dict(code, cls, min, max, maps, bc, umi)."""
+    segs = [pyl.decode_record(data[int(off[i]) + 4:int(off[i + 1])], btag, utag) for i in range(s, e)]
+    (code, alns), = list(pyl._fragments(iter(segs)))
+    r = dict(code=CODES.index(code), cls=0, min=None, max=None, maps=[], bc=None, umi=None)
+    if code in ('SU', 'PU'):
+        return r
+    r['bc'], r['umi'] = alns[0].r1.bc, alns[0].r1.umi
+    mapped, _feats, _byfeat, maps = pyl.score_bundle(alns, assign, no_feature_key)
+    if mapped:
+        r['min'], r['max'] = min(a.alnscore for a in mapped), max(a.alnscore for a in mapped)
+    ambig = len(mapped) > 1
+    r['cls'] = (2 if ambig else 1) if maps is None else (4 if ambig else 3)
+    r['maps'] = maps or []
+    return r
+
+
+def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', overlap_threshold=0.2, stranded_mode='None',
+                          barcode_tag=None, umi_tag=None, device=0, chunk_bytes=None, record_cap=4096, max_bundles=None,
+                          on_chunk=None):
+    """loader.load_alignment(..., loader='device').  `on_chunk(data, rec_off, out)`: called with every chunk's raw device outputs
+    (tests); `max_bundles`: at most so many bundles per device call (tests)."""
+    global LAST_STATS
+    if no_feature_key in annotation.loci:
+        raise ValueError('the device loader needs a no_feature_key that is not a locus of the annotation (%r is)' % no_feature_key)
+    chunk_bytes = DEFAULT_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    if chunk_bytes < 1:
+        raise ValueError('chunk_bytes must be >= 1')
+    t_all = perf_counter()
+    stats = dict(records=0, bundles=0, chunks=0, fallbacks=0, inflate_s=0., scan_s=0., device_s=0., host_ids_s=0., fallback_s=0., tail_s=0.)
+    btag = barcode_tag.encode() if barcode_tag else None
+    utag = umi_tag.encode() if umi_tag else None
+    fh = io.BufferedReader(gzip.open(samfile, 'rb'), buffer_size=1 << 20)
+    dev = None
+    try:
+        refs, _text, _block = pyl.read_bam_header(fh, samfile)
+        arrs = annotation_arrays(annotation, refs)
+        loc_names = arrs[-1]
+        loc_id = {n: i for i, n in enumerate(loc_names)}
+        dev = BamLoader(device, *arrs[:-1])
+
+        def assign(pair):
+            return pyl.assign_pair(pair, annotation, refs, stranded_mode, no_feature_key, overlap_threshold)
+
+        info = Counter()
+        ridx, fidx = OrderedDict(), OrderedDict([(no_feature_key, 0)])
+        col_of = np.full(len(loc_names) + 1, -1, np.int64)   # locus id + 1 -> column; [0]: no locus -> column 0
+        col_of[0] = 0
+        rows, cols, m_as, m_len = [], [], [], []
+        min_as, max_as = pyl.BIG_INT, -pyl.BIG_INT
+        read_bc, read_umi = {}, {}
+        n_code, n_cls = np.zeros(5, np.int64), np.zeros(6, np.int64)
+        for data, off in bam_chunks(fh, samfile, chunk_bytes, max_bundles, stats):
+            t0 = perf_counter()
+            out, (st, rec) = dev.chunk(data, off, barcode_tag, umi_tag, annotation.run_stranded, stranded_mode, overlap_threshold, record_cap)
+            stats['device_s'] += perf_counter() - t0
+            n = len(off) - 1
+            if st:
+                raise ValueError('%s: record %d (%s): %s' % (samfile, stats['records'] + rec, _record_name(data, off, rec),
+                                                            BAM_STATUS.get(st, 'status %d' % st)))
+            if on_chunk is not None:
+                on_chunk(data, off, out)
+            starts = np.flatnonzero(out[C_BITS] & BIT_NEWNAME)
+            code, cls = out[C_BCODE][starts], out[C_BCLASS][starts].copy()
+            nmaps, nmapped = out[C_BNMAPS][starts].copy(), out[C_BNMAPPED][starts].copy()
+            # ---- the bundles left to the host: their results go where the device's would be
+            t0 = perf_counter()
+            hosted = {}
+            for bi in np.flatnonzero(cls == CLS_HOST):
+                s = int(starts[bi]); e = int(starts[bi + 1]) if bi + 1 < len(starts) else n
+                r = host_bundle(data, off, s, e, btag, utag, assign, no_feature_key)
+                hosted[int(bi)] = r
+                code[bi], cls[bi], nmaps[bi], nmapped[bi] = r['code'], r['cls'], len(r['maps']) if r['cls'] >= 3 else 0, 0
+                for k, (_name, f, a, l) in enumerate(r['maps']):
+                    if not (-2 ** 31 <= a < 2 ** 31 and l < 2 ** 31):
+                        raise OverflowError('signed integer is greater than maximum')     # (what the Python loader's array('i') says)
+                    out[C_MFEAT][s + k] = -1 if f == no_feature_key else loc_id[f]
+                    out[C_MAS][s + k], out[C_MLEN][s + k] = a, l
+                if r['min'] is not None:
+                    min_as, max_as = min(min_as, r['min']), max(max_as, r['max'])
+            stats['fallbacks'] += len(hosted)
+            stats['fallback_s'] += perf_counter() - t0
+            t0 = perf_counter()
+            n_code += np.bincount(code, minlength=5)
+            n_cls += np.bincount(cls, minlength=6)
+            have = nmapped > 0
+            if have.any():
+                min_as = min(min_as, int(out[C_BMIN][starts][have].min()))
+                max_as = max(max_as, int(out[C_BMAX][starts][have].max()))
+            # ---- names: a row id per fragment with a feature; with tags, barcode / UMI of every fragment that is not unmapped
+            lrn = out[C_LRN]
+            tagged = barcode_tag or umi_tag
+            which = np.flatnonzero(cls >= 1) if tagged else np.flatnonzero(cls >= 3)
+            rid = {}
+            r1 = out[C_PAIR1]
+            for bi in which.tolist():
+                s = int(starts[bi]); o = int(off[s]) + 36
+                name = data[o:o + int(lrn[s]) - 1].decode()
+                if tagged:
+                    h = hosted.get(bi)
+                    if h is not None:
+                        bc, umi = h['bc'], h['umi']
+                    else:
+                        a = int(r1[s]); oa = int(off[a])
+                        bo, bl, uo, ul = int(out[C_BCOFF][a]), int(out[C_BCLEN][a]), int(out[C_UMIOFF][a]), int(out[C_UMILEN][a])
+                        bc = data[oa + bo:oa + bo + bl].decode() if bo >= 0 else None
+                        umi = data[oa + uo:oa + uo + ul].decode() if uo >= 0 else None
+                    if barcode_tag and bc is not None:
+                        read_bc[name] = bc
+                    if umi_tag and umi is not None:
+                        read_umi[name] = umi
+                if cls[bi] >= 3:
+                    rid[bi] = ridx.setdefault(name, len(ridx))
+            # ---- mappings: gather the lists of the fragments with a feature, first-appearance column ids
+            fb = np.flatnonzero(cls >= 3)
+            if fb.size:
+                cnt = nmaps[fb].astype(np.int64)
+                first = np.cumsum(cnt) - cnt
+                idx = np.repeat(starts[fb], cnt) + (np.arange(int(cnt.sum())) - np.repeat(first, cnt))
+                loc = out[C_MFEAT][idx].astype(np.int64)
+                u, ui = np.unique(loc, return_index=True)
+                new = col_of[u + 1] < 0
+                for l in u[new][np.argsort(ui[new], kind='stable')].tolist():
+                    col_of[l + 1] = fidx.setdefault(loc_names[l], len(fidx))
+                rows.append(np.repeat(np.array([rid[b] for b in fb.tolist()], np.int64), cnt))
+                cols.append(col_of[loc + 1].astype(np.int32))
+                m_as.append(out[C_MAS][idx]); m_len.append(out[C_MLEN][idx])
+            stats['host_ids_s'] += perf_counter() - t0
+            stats['records'] += n; stats['bundles'] += len(starts); stats['chunks'] += 1
+        stats['kernels_ms'] = dev.times()
+    finally:
+        fh.close()
+        if dev is not None:
+            dev.close()
+    t0 = perf_counter()
+    info['total_fragments'] = int(n_code.sum())
+    for c, k in zip(CODES, n_code.tolist()):
+        info[c] = k
+    info['nofeat_U'], info['nofeat_A'], info['feat_U'], info['feat_A'] = (int(x) for x in n_cls[1:5])
+    cat = lambda xs, t: np.concatenate(xs).astype(t, copy=False) if xs else np.zeros(0, t)
+    res = pyl.mappings_to_result(annotation, info, ridx, fidx, cat(rows, np.int64), cat(cols, np.int32), cat(m_as, np.int32),
+                                 cat(m_len, np.int32), min_as, max_as, read_bc if barcode_tag else None, read_umi if umi_tag else None)
+    stats['tail_s'] = perf_counter() - t0
+    stats['total_s'] = perf_counter() - t_all
+    LAST_STATS = stats
+    if stats['fallbacks']:
+        lg.info('device loader: %d of %d fragments were left to the host loader' % (stats['fallbacks'], stats['bundles']))
+    lg.debug('device loader: %d records in %d chunks' % (stats['records'], stats['chunks']))
+    return res

@@ -577,6 +577,43 @@ int  tsem_bam_chunk(tsem_bam* b, const uint8_t* bytes, int64_t n_bytes, const in
  * device-to-host; *calls = how many; reset != 0 clears both. */
 int  tsem_bam_times(tsem_bam* b, int reset, double* ms6, int64_t* calls);
 
+/* ---- device loader: the BGZF blocks of a BAM file inflated on the device (telescope_amd/csrc/tsem_bgzf.hip) ----
+ * A BGZF file is a chain of gzip members ("blocks") of at most 64 KiB compressed and 64 KiB inflated bytes; each needs nothing from
+ * its neighbours and carries the CRC-32 and the length (ISIZE) of its inflated bytes in its trailer.
+ *
+ * tsem_bgzf_scan: HOST only, no device.  Walks the chain of block headers of bytes[0, n_bytes), which begins on a block boundary.  A
+ * header is 1f 8b 08 04 with the subfield 'B' 'C' (SLEN 2: the block's size - 1) among its extra fields, in any position.  Row k of
+ * `blocks` (int64 [cap][5]) = { the block's offset, its payload's offset, the payload's length, ISIZE, CRC-32 } for the *n_blocks
+ * blocks that lie completely inside the bytes (at most `cap`); *consumed = the offset behind the last of them — a trailing partial
+ * block, header or payload or trailer, belongs to the next call.  *not_bgzf = 1 (and nothing consumed) when the first bytes are no BGZF
+ * header: another magic, or a gzip header without the BC subfield, as plain gzip writes it.  TSEM_ERR_ARG with a message
+ * (tsem_last_error(NULL)): such bytes behind the first block, a BSIZE smaller than header plus trailer, a NULL pointer, a negative size. */
+typedef struct tsem_bgzf tsem_bgzf;
+int  tsem_bgzf_scan(const uint8_t* bytes, int64_t n_bytes, int64_t* blocks /* cap x 5 */, int64_t cap, int64_t* n_blocks,
+                    int64_t* consumed, int32_t* not_bgzf);
+/* A handle on device `device` (an index, as for tsem_bam_open); it keeps its device buffers from call to call and grows them when a
+ * batch is larger: 1 B per compressed and per inflated byte, 36 B per block.  Errors: tsem_last_error(NULL). */
+int  tsem_bgzf_open(tsem_bgzf** out, int device);
+int  tsem_bgzf_close(tsem_bgzf* z);                    /* NULL is fine */
+/* One batch through k_bgzf_inflate (one wave per block).  bytes / blocks / n_blocks: as tsem_bgzf_scan left them (HOST arrays).  Block k
+ * inflates into out[o_k, o_k + ISIZE_k), o_k = the sum of the ISIZEs of the blocks in front of it; *out_bytes = their total.  A block
+ * whose ISIZE exceeds 65,536 (the format forbids it, a gzip member can claim it) takes no range and is not inflated: status 255, the
+ * caller inflates it on the host.  status[k]: 0, 255, or
+ *    1 block type 3                       2 stored block: LEN does not match NLEN     3 over-subscribed or incomplete code set
+ *    4 no code for end-of-block           5 invalid symbol (286, 287, distance 30, 31) 6 distance before the start of the output
+ *    7 output longer than ISIZE           8 input exhausted                           9 output shorter than ISIZE
+ *   10 CRC-32 mismatch
+ * first2[0] = 0, or the code of the first block in file order with a code in 1 .. 10, first2[1] = that block (else -1); the other
+ * blocks' bytes are valid all the same.  The call itself then still returns TSEM_OK.  Checked on the host before the device is
+ * touched, TSEM_ERR_ARG with a message: a NULL pointer, a negative size, 2^31 - 1 blocks or more, a payload range outside [0, n_bytes)
+ * or longer than 65,536, an ISIZE or CRC-32 outside 32 bits, a total of the ISIZEs above out_cap, a NULL handle — so no kernel sees a
+ * range it cannot trust.  TSEM_ERR_HIP / TSEM_ERR_NOMEM with a message if a copy, the launch or an allocation fails. */
+int  tsem_bgzf_inflate(tsem_bgzf* z, const uint8_t* bytes, int64_t n_bytes, const int64_t* blocks /* n_blocks x 5 */, int64_t n_blocks,
+                       uint8_t* out, int64_t out_cap, int32_t* status /* n_blocks */, int64_t* first2, int64_t* out_bytes);
+/* HIP-event milliseconds summed over the calls so far: host-to-device, k_bgzf_inflate, device-to-host; *calls = how many; reset != 0
+ * clears both. */
+int  tsem_bgzf_times(tsem_bgzf* z, int reset, double* ms3, int64_t* calls);
+
 /* ---- csr_matrix_plus primitives on arbitrary fp64 CSR (sparse_plus.py) ---- */
 /* All three: indptr[n_rows + 1] is a HOST array and is checked on the host before the device is touched. TSEM_ERR_ARG (text in
  * tsem_last_error(NULL)) for n_rows < 0, n_cols < 0, indptr NULL, indptr[0] != 0, any indptr[i + 1] < indptr[i], or data / out

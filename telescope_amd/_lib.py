@@ -27,14 +27,14 @@ class EngineError(RuntimeError):
 
 
 # host / ABI, set-up, EM support, report / row passes, collectives, CSR primitives, per-cell counts, per-cell fits, bootstrap,
-# UMI duplicates, device loader (telescope_amd/csrc/tsem_internal.h)
+# UMI duplicates, device loader, BGZF inflate (telescope_amd/csrc/tsem_internal.h)
 LIB_UNITS = ('tsem_host', 'tsem_setup', 'tsem_em', 'tsem_report', 'tsem_comm', 'tsem_csr', 'tsem_cells', 'tsem_cellem', 'tsem_boot',
-             'tsem_umi', 'tsem_bam')
+             'tsem_umi', 'tsem_bam', 'tsem_bgzf')
 FZ_UNITS = tuple('tsem_fz_p%d' % p for p in range(1, 9))
 
 
 def build_library(force=False, verbose=False, out=None):
-    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  Nineteen translation units — the eleven of
+    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  Twenty translation units — the twelve of
     LIB_UNITS and the eight that instantiate the fused kernel for one team size each (most of the build time) — are compiled
     in parallel and linked into one shared object."""
     from concurrent.futures import ThreadPoolExecutor
@@ -240,6 +240,11 @@ def lib():
     L.tsem_bam_close.argtypes = [vp]
     L.tsem_bam_chunk.argtypes = [vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, dbl, i32, vp, vp]
     L.tsem_bam_times.argtypes = [vp, C.c_int, vp, C.POINTER(i64)]
+    L.tsem_bgzf_scan.argtypes = [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
+    L.tsem_bgzf_open.argtypes = [C.POINTER(vp), C.c_int]
+    L.tsem_bgzf_close.argtypes = [vp]
+    L.tsem_bgzf_inflate.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, vp, C.POINTER(i64)]
+    L.tsem_bgzf_times.argtypes = [vp, C.c_int, vp, C.POINTER(i64)]
     L.tsem_csr_norm_rows.argtypes = [C.c_int, i64, vp, vp, vp]
     L.tsem_csr_binmax_rows.argtypes = [C.c_int, i64, i32, vp, vp, vp]
     L.tsem_csr_scale.argtypes = [C.c_int, C.c_int, i64, i32, vp, vp, vp]
@@ -904,6 +909,72 @@ BAM_STATUS = {1: 'block_size does not match the record chain', 2: 'l_read_name l
               4: 'l_seq runs past the record', 5: 'an aux field begins past the record', 6: 'an aux value runs past the record',
               7: 'a Z / H aux value has no NUL inside the record', 8: 'a B aux array runs past the record',
               9: 'unknown aux type', 10: 'a mapped alignment has no AS tag'}
+
+
+# status words of tsem_bgzf_inflate (include/telescope_em.h, telescope_amd/csrc/tsem_bgzf_inflate.h); 255: left to the host
+BGZF_HOST = 255
+BGZF_STATUS = {1: 'DEFLATE block type 3', 2: 'a stored block whose LEN does not match NLEN',
+               3: 'an over-subscribed or incomplete Huffman code', 4: 'no code for end-of-block', 5: 'an invalid literal/length or distance symbol',
+               6: 'a distance before the start of the output', 7: 'the output is longer than ISIZE', 8: 'the compressed bytes end inside the stream',
+               9: 'the output is shorter than ISIZE', 10: 'CRC-32 mismatch'}
+
+
+def bgzf_scan(data, cap=None):
+    """Block table of a piece of a BGZF file (tsem_bgzf_scan, host only): (int64 [n][5] = block offset, payload offset, payload length,
+    ISIZE, CRC-32; consumed; not_bgzf)."""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    cap = buf.size // 26 + 1 if cap is None else int(cap)
+    blk = np.empty((cap, 5), np.int64)
+    n, used, nb = C.c_int64(), C.c_int64(), C.c_int32()
+    rc = lib().tsem_bgzf_scan(ptr(buf) if buf.size else None, buf.size, ptr(blk), cap, C.byref(n), C.byref(used), C.byref(nb))
+    if rc != OK:
+        raise _csr_error('tsem_bgzf_scan', rc)
+    return blk[:n.value].copy(), used.value, bool(nb.value)
+
+
+class BgzfInflater(object):
+    """The device side of `--inflate device` (tsem_bgzf_open / tsem_bgzf_inflate): one handle, one GPU, its buffers kept between batches."""
+
+    def __init__(self, device=0):
+        L = lib()
+        h = C.c_void_p()
+        rc = L.tsem_bgzf_open(C.byref(h), int(device))
+        if rc != OK:
+            raise _csr_error('tsem_bgzf_open', rc)
+        self._L, self._h = L, h
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._L.tsem_bgzf_close(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def inflate(self, data, blocks):
+        """-> (uint8 array of the inflated bytes of the blocks that are not left to the host, in order; int32 status per block;
+        (code, block) of the first failing block or (0, -1))."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        blk = np.ascontiguousarray(blocks, dtype=np.int64).reshape(-1, 5)
+        n = len(blk)
+        isz = blk[:, 3]
+        cap = int(isz[isz <= 65536].sum())
+        out = np.empty(cap, np.uint8)
+        st = np.zeros(n, np.int32)
+        first, total = np.zeros(2, np.int64), C.c_int64()
+        rc = self._L.tsem_bgzf_inflate(self._h, ptr(buf) if buf.size else None, buf.size, ptr(blk) if n else None, n, ptr(out) if cap else None,
+                                       cap, ptr(st) if n else None, ptr(first), C.byref(total))
+        if rc != OK:
+            raise _csr_error('tsem_bgzf_inflate', rc)
+        assert total.value == cap
+        return out, st, (int(first[0]), int(first[1]))
+
+    def times(self, reset=False):
+        """HIP-event milliseconds summed over the batches so far, and their number."""
+        ms, n = np.zeros(3), C.c_int64()
+        rc = self._L.tsem_bgzf_times(self._h, int(reset), ptr(ms), C.byref(n))
+        if rc != OK:
+            raise _csr_error('tsem_bgzf_times', rc)
+        return dict(zip(('h2d', 'k_bgzf_inflate', 'd2h'), ms.tolist()), batches=n.value)
 
 
 def bam_scan(data, cap=None):

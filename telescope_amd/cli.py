@@ -105,6 +105,9 @@ def _assign_args(asg):
     g.add_argument('--loader', default='python', choices=['python', 'device'],
                    help='python (default): the streaming pure-Python BAM parser.  device: the records are decoded, paired and '
                         'intersected with the annotation on the GPU (--device), the same matrix and checkpoint; not with --updated_sam.')
+    g.add_argument('--inflate', default='host', choices=['host', 'device'],
+                   help='host (default): the BGZF blocks of the BAM are inflated by gzip on one host core.  device (with --loader device): '
+                        'they are inflated on the GPU as well, one wave per block.')
     g.add_argument('--tempdir', help='(accepted for compatibility; no temporary files are written)')
     g = asg.add_argument_group('Reporting Options')
     g.add_argument('--quiet', action='store_true', help='Silence (most) output.')
@@ -355,6 +358,14 @@ def _refuse_device_updated_sam(args):
                          'record by record by the python loader); use --loader python')
 
 
+def _refuse_device_inflate(args):
+    """`--inflate device` without `--loader device`: refused before anything is read (the python loader reads its records from
+    gzip's stream one by one; the device inflate hands whole batches of blocks to the device loader)."""
+    if getattr(args, 'inflate', 'host') == 'device' and getattr(args, 'loader', 'python') != 'device':
+        raise SystemExit('telescope assign: --inflate device without --loader device is not supported (the python loader reads '
+                         'its records from gzip\'s stream); add --loader device')
+
+
 def collapse_umis(ts, opts):
     """`sc assign --umi_tag` / `sc resume` of a checkpoint with UMIs: the run goes on with the kept fragments (scTelescope.collapse_umis)
     unless --ignore_umi; <exp_tag>-umi_stats.tsv lists them per barcode."""
@@ -464,6 +475,7 @@ def run_assign(args, sc=False):
     _refuse_bootstrap(args)
     _refuse_umi_updated_sam(args)
     _refuse_device_updated_sam(args)
+    _refuse_device_inflate(args)
     opts = ResumeOptions(args)
     configure_logging(opts)
     if opts.ncpu != 1:

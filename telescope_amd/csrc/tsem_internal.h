@@ -14,6 +14,8 @@
 //   tsem_umi.hip     UMI duplicates of a single-cell run: classes, links, components, representatives (tsem_umi_dedup)
 //   tsem_bam.hip     the device loader of `assign`: BAM records of a chunk to per-fragment (locus, alnscore, alnlen) lists (tsem_bam_*;
 //                    the stages' bodies are host / device functions in tsem_bam_rec.h and tsem_bam_stages.h, the record chain in tsem_bam_scan.h)
+//   tsem_bgzf.hip    the BGZF blocks of a BAM file inflated on the device (tsem_bgzf_*; the body is the host / device function of
+//                    tsem_bgzf_inflate.h, the chain of block headers in tsem_bgzf_scan.h)
 //   tsem_fz_p*.hip   instantiations of the fused kernel (tsem_fused.h), one team size per unit
 //
 // A kernel is launched only from the unit that defines it; other units go through the host functions declared here.

@@ -347,7 +347,7 @@ CODE_DESC = OrderedDict([('SU', 'single_unmapped'), ('SM', 'single_mapped'), ('P
 
 def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_mode='threshold',
                    overlap_threshold=0.2, stranded_mode='None', barcode_tag=None, updated_sam=None, umi_tag=None, loader='python',
-                   device=0, chunk_bytes=None, record_cap=4096):
+                   device=0, chunk_bytes=None, record_cap=4096, inflate='host'):
     """-> dict(raw_scores uint16 CSR, read_index, feat_index, feature_length, run_info fields).  With `barcode_tag` (scTelescope,
     model.py:245-247,311-316) also cell_of_row (int32 per row, -1 = no barcode) and barcodes (the cell names): the tag is read from
     the first read of every mapped fragment; only fragments that become rows count; cells are ordered by the first appearance of
@@ -359,16 +359,21 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
     (the top-score features, comma-joined) — model.py:30-63, set like pysam's set_tag (the old tag goes, the new one is appended).
     `loader='device'`: the same dict, key by key, from the device loader (loader_device.py: the records are decoded, paired and
     intersected on GPU `device`, in chunks of about `chunk_bytes` inflated bytes, default 64 MiB; a bundle of more than `record_cap`
-    records is left to this module's code); not with `updated_sam`."""
+    records is left to this module's code); not with `updated_sam`.  `inflate='device'` (with loader='device' only): the file's BGZF
+    blocks are inflated on the GPU as well (bgzf.py) instead of by gzip on one host core."""
     if overlap_mode != 'threshold':
         raise NotImplementedError('only overlap_mode "threshold" is implemented (as in the reference, '
                                   'model.py:899-903)')
+    if inflate not in ('host', 'device'):
+        raise ValueError("inflate must be 'host' or 'device', not %r" % (inflate,))
+    if inflate == 'device' and loader != 'device':
+        raise ValueError("inflate='device' needs loader='device'")
     if loader == 'device':
         if updated_sam:
             raise ValueError('the device loader does not write the BAMs of --updated_sam')
         from .loader_device import load_alignment_device
         return load_alignment_device(samfile, annotation, no_feature_key, overlap_threshold, stranded_mode, barcode_tag, umi_tag,
-                                     device=device, chunk_bytes=chunk_bytes, record_cap=record_cap)
+                                     device=device, chunk_bytes=chunk_bytes, record_cap=record_cap, inflate=inflate)
     if loader != 'python':
         raise ValueError("loader must be 'python' or 'device', not %r" % (loader,))
     bam_u = bam_t = None

@@ -1,6 +1,7 @@
 """The device loader of `assign` (`--loader device`): loader.load_alignment's dict, key by key, with the per-record work on the GPU.
 
-  host    BGZF inflate (gzip), the record chain of every chunk (tsem_bam_scan, C), the cut in front of the chunk's last bundle —
+  host    BGZF inflate (gzip; with inflate='device' the blocks are inflated on the GPU instead: bgzf.DeviceBgzfReader),
+          the record chain of every chunk (tsem_bam_scan, C), the cut in front of the chunk's last bundle —
           the last bundle may go on in the next chunk, so it is carried over with the unconsumed tail, and a chunk that holds one
           bundle only grows until a second one begins;
   device  one call per chunk (tsem_bam_chunk, telescope_amd/csrc/tsem_bam.hip): k_bam_decode, k_bam_pair, k_bam_overlap,
@@ -135,20 +136,28 @@ def host_bundle(data, off, s, e, btag, utag, assign, no_feature_key):
 
 def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', overlap_threshold=0.2, stranded_mode='None',
                           barcode_tag=None, umi_tag=None, device=0, chunk_bytes=None, record_cap=4096, max_bundles=None,
-                          on_chunk=None):
+                          on_chunk=None, inflate='host'):
     """loader.load_alignment(..., loader='device').  `on_chunk(data, rec_off, out)`: called with every chunk's raw device outputs
-    (tests); `max_bundles`: at most so many bundles per device call (tests)."""
+    (tests); `max_bundles`: at most so many bundles per device call (tests).  `inflate`: 'host' (Python's gzip) or 'device' (the BGZF
+    blocks are inflated on the GPU, bgzf.py; a gzip file that is not BGZF is still read by gzip: LAST_STATS['inflate'] says which)."""
     global LAST_STATS
     if no_feature_key in annotation.loci:
         raise ValueError('the device loader needs a no_feature_key that is not a locus of the annotation (%r is)' % no_feature_key)
+    if inflate not in ('host', 'device'):
+        raise ValueError("inflate must be 'host' or 'device', not %r" % (inflate,))
     chunk_bytes = DEFAULT_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
     if chunk_bytes < 1:
         raise ValueError('chunk_bytes must be >= 1')
     t_all = perf_counter()
-    stats = dict(records=0, bundles=0, chunks=0, fallbacks=0, inflate_s=0., scan_s=0., device_s=0., host_ids_s=0., fallback_s=0., tail_s=0.)
+    stats = dict(records=0, bundles=0, chunks=0, fallbacks=0, inflate='host', inflate_fallbacks=0, inflate_s=0., scan_s=0., device_s=0., host_ids_s=0., fallback_s=0., tail_s=0.)
     btag = barcode_tag.encode() if barcode_tag else None
     utag = umi_tag.encode() if umi_tag else None
-    fh = io.BufferedReader(gzip.open(samfile, 'rb'), buffer_size=1 << 20)
+    if inflate == 'device':
+        from .bgzf import DeviceBgzfReader
+        fh = DeviceBgzfReader(samfile, device=device)
+        stats['inflate'] = fh.inflate
+    else:
+        fh = io.BufferedReader(gzip.open(samfile, 'rb'), buffer_size=1 << 20)
     dev = None
     try:
         refs, _text, _block = pyl.read_bam_header(fh, samfile)
@@ -246,6 +255,8 @@ def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', ov
             stats['host_ids_s'] += perf_counter() - t0
             stats['records'] += n; stats['bundles'] += len(starts); stats['chunks'] += 1
         stats['kernels_ms'] = dev.times()
+        if inflate == 'device':
+            stats['inflate_fallbacks'], stats['inflate_blocks'], stats['inflate_ms'] = fh.fallbacks, fh.blocks, fh.times()
     finally:
         fh.close()
         if dev is not None:
@@ -261,6 +272,8 @@ def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', ov
     stats['tail_s'] = perf_counter() - t0
     stats['total_s'] = perf_counter() - t_all
     LAST_STATS = stats
+    if stats['inflate_fallbacks']:
+        lg.info('device inflate: %d of %d BGZF blocks were left to zlib on the host' % (stats['inflate_fallbacks'], stats['inflate_blocks']))
     if stats['fallbacks']:
         lg.info('device loader: %d of %d fragments were left to the host loader' % (stats['fallbacks'], stats['bundles']))
     lg.debug('device loader: %d records in %d chunks' % (stats['records'], stats['chunks']))

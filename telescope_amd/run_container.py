@@ -131,7 +131,7 @@ class Telescope(object):
         self.run_info['annotated_features'] = len(annotation.loci)
         r = loader.load_alignment(o.samfile, annotation, o.no_feature_key, o.overlap_mode,
                                   o.overlap_threshold, o.stranded_mode, updated_sam=self._updated_sam_paths(),
-                                  loader=getattr(o, 'loader', 'python'), device=getattr(o, 'device', 0))
+                                  loader=getattr(o, 'loader', 'python'), device=getattr(o, 'device', 0), inflate=getattr(o, 'inflate', 'host'))
         self.feature_length = r['feature_length']
         self.read_index, self.feat_index = r['read_index'], r['feat_index']
         self.raw_scores = r['raw_scores']
@@ -472,7 +472,7 @@ class scTelescope(Telescope):
         self.run_info['annotated_features'] = len(annotation.loci)
         r = loader.load_alignment(o.samfile, annotation, o.no_feature_key, o.overlap_mode, o.overlap_threshold, o.stranded_mode,
                                   barcode_tag=o.barcode_tag, updated_sam=self._updated_sam_paths(), umi_tag=getattr(o, 'umi_tag', None),
-                                  loader=getattr(o, 'loader', 'python'), device=getattr(o, 'device', 0))
+                                  loader=getattr(o, 'loader', 'python'), device=getattr(o, 'device', 0), inflate=getattr(o, 'inflate', 'host'))
         self.feature_length = r['feature_length']
         self.read_index, self.feat_index = r['read_index'], r['feat_index']
         self.raw_scores = r['raw_scores']

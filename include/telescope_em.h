@@ -645,6 +645,22 @@ int  tsem_kernel_stats(tsem_ctx* h, int reset, double* em_ms, int64_t* em_launch
  * threshold), and which kernel it was: 0 none yet, 1 generic row pass, 2 capacity kernel (k_report_rows), 3 score codes only
  * (k_report_init_codes), 4 packed fp32 filter (k_report_pack32).  model.py:432-457 is what the pass computes. */
 int  tsem_report_stats(tsem_ctx* h, double* kernel_ms, int64_t* algo_bytes, int64_t* deferred_rows, int32_t* kernel);
+/* Which kernel INSTANCE served the last tsem_report_colsums (values [0 .. 16)) and the last tsem_reassign_groups ([16 .. 32)): the
+ * first min(n, TSEM_REPORT_INFO_N) values (the Python binding names them: _lib.Engine.report_info).  Read-only: the report calls
+ * note host values next to their launches and gain no copy, synchronisation or kernel; this query counts the deferred rows from the
+ * list the launch left on the device and synchronises the handle's stream.  Per half:
+ *   [0] kernel family, the codes of tsem_report_stats (0 none yet .. 4 k_report_pack32), and 5: k_group_unique (per-group `unique`);
+ *   [1] lanes per row G and [2] entries per lane E of the instance (k_report_pack32: 64, the most lanes a row takes; the generic row
+ *       pass: 16 and 0);  [3] 1 the initial z, 0 the model's;  [4] group mode (0 column sums, 1 exclude, 2 average, 3 conf, 4 all);
+ *   [5] COLD of k_report_pack32 (its table of the ids does not fit LDS: [7] < the number of ids);
+ *   [6] Hs, the ids with accumulator slots in LDS;  [7] HC, the ids whose pi*theta sits in LDS;  [8] lut_rep (log2 of the copies of the
+ *       score table in LDS);  [9] grid and [10] block of the launch;
+ *   [11] rows left to k_report_slow because they are longer than G * E entries, [12] rows left to it as near-ties (k_report_pack32:
+ *       everything else its filter did not decide — ties, near-ties, rows on the threshold); both -1 where there is no such list
+ *       (family 1 and 5) or the other of the two calls has reused it since.  Of a tsem_reassign_groups they are those of its LAST tile;
+ *   [13] tiles of the last tsem_reassign_groups and [14] groups in its last tile (0 in the first half);  [15] 0. */
+#define TSEM_REPORT_INFO_N 32
+int  tsem_report_info_n(tsem_ctx* h, int64_t* info, int32_t n);
 /* Option "phase_timing" = 1: tsem_em_chunk records a HIP event at every phase boundary of every iteration it enqueues (a
  * diagnostic: ~5 events per iteration on the engine's stream).  ms6 = summed milliseconds over *n_iter iterations of
  * { EM pass | column reduce | all-reduce of the K+2 sums (0 without a communicator) | update | gap to the next iteration's

@@ -254,6 +254,7 @@ def lib():
     L.tsem_device_memory.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64), vp]
     L.tsem_layout_info.argtypes = [vp, vp]
     L.tsem_layout_info_n.argtypes = [vp, vp, i32]
+    L.tsem_report_info_n.argtypes = [vp, vp, i32]
     L.tsem_debug_fused_prof.argtypes = [vp, vp]
     L.tsem_debug_fused_startup.argtypes = [vp, vp]
     L.tsem_debug_log1p.argtypes = [C.c_int, C.c_int32, vp, vp]
@@ -715,6 +716,22 @@ class Engine(object):
         self._ck(self._L.tsem_report_stats(self._h, C.byref(ms), C.byref(b), C.byref(d), C.byref(k)))
         return dict(kernel_ms=ms.value, algo_bytes=b.value, deferred_rows=d.value,
                     kernel={0: None, 1: 'k_rowpass', 2: 'k_report_rows', 3: 'k_report_init_codes', 4: 'k_report_pack32'}[k.value])
+
+    def report_info(self):
+        """Which kernel instance served the last report_colsums ('colsums') and the last reassign_groups ('groups', its last tile):
+        tsem_report_info_n.  Per call a dict of kernel (as report_stats names it; 'k_group_unique' too), G, E, initial, group_mode,
+        cold, Hs, HC, lut_rep, grid, block, deferred_long, deferred_near (-1: no list), tiles, tile_groups."""
+        info = np.zeros(32, np.int64)
+        self._ck(self._L.tsem_report_info_n(self._h, ptr(info), info.size))
+        names = ('kernel', 'G', 'E', 'initial', 'group_mode', 'cold', 'Hs', 'HC', 'lut_rep', 'grid', 'block', 'deferred_long',
+                 'deferred_near', 'tiles', 'tile_groups')
+        kern = {0: None, 1: 'k_rowpass', 2: 'k_report_rows', 3: 'k_report_init_codes', 4: 'k_report_pack32', 5: 'k_group_unique'}
+        out = {}
+        for key, half in (('colsums', info[:16]), ('groups', info[16:])):
+            d = dict(zip(names, half.tolist()))
+            d['kernel'] = kern[d['kernel']]
+            out[key] = d
+        return out
 
     def device_memory(self):
         """dict(free, total, resident=dict(csr, csr_indices, ids, layout, rows)) in bytes."""

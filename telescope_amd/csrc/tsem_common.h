@@ -305,6 +305,13 @@ struct tsem_ctx {
   std::vector<hipEvent_t> ev;       // pairs
   hipEvent_t ev_rep[2] = {nullptr, nullptr};   // around the dominant kernel of the last tsem_report_colsums (tsem_report_stats)
   bool rep_timed = false; int rep_kernel = 0; int64_t rep_deferred = 0;
+  // What the last tsem_report_colsums ([0]) and the last tsem_reassign_groups ([1]: its last tile) launched (tsem_report_info_n): host
+  // values noted next to the launch.  `list`: d_rep_rows / d_rep_n still hold THIS launch's deferred rows (the two calls share them).
+  struct ReportLaunch {
+    int family = 0, G = 0, E = 0, init = 0, gm = 0, cold = 0, Hs = 0, HC = 0, lut_rep = 0, grid = 0, block = 0, tiles = 0, tile_groups = 0;
+    bool list = false;
+  } rep_launch[2];
+  int32_t* d_rep_sel = nullptr; unsigned long long* d_rep_sel_n = nullptr;   // [N], [1] the tied rows as ties_of_counts selects them (the deferred list stays)
   size_t ev_used = 0;
   double em_ms_acc = 0;
   int64_t em_launches = 0, em_timed = 0;

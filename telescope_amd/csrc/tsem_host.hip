@@ -111,7 +111,9 @@ void tsem_free_matrix(tsem_ctx* h) {
   dfree(h->d_ctl); dfree(h->d_ctld); dfree(h->d_lnls); dfree(h->d_pi_first); dfree(h->d_theta_first); dfree(h->d_user_z);
   dfree(h->d_tie_rows); dfree(h->d_tie_cnt); h->n_ties = 0;
   if (h->d_rep_chunks) { (void)hipFree(h->d_rep_chunks); h->d_rep_chunks = nullptr; h->n_rep_chunks = 0; }
-  dfree(h->d_rep_nb); dfree(h->d_rep_rows); dfree(h->d_rep_n); dfree(h->d_exact_n); dfree(h->d_flag_bits); h->flag_words = 0;
+  dfree(h->d_rep_nb); dfree(h->d_rep_rows); dfree(h->d_rep_n); dfree(h->d_rep_sel); dfree(h->d_rep_sel_n);
+  h->rep_launch[0] = h->rep_launch[1] = tsem_ctx::ReportLaunch();
+  dfree(h->d_exact_n); dfree(h->d_flag_bits); h->flag_words = 0;
   dfree(h->d_group); h->n_groups = 0;
   dfree(h->d_gc_key); dfree(h->d_gc_rows); dfree(h->d_gc_eoff); h->gc_version = ~0ull; h->gc_rptr.clear(); h->gc_gent.clear();
   dfree(h->d_gc_ogrp); dfree(h->d_gc_ocol); dfree(h->d_gc_oval); dfree(h->d_gc_gptr); h->gc_nnz = h->gc_cap = 0; h->gc_groups = 0;

@@ -1020,14 +1020,17 @@ template <bool FIX> static RowKern rowpass_kern(int mode, int meth) {
   }
 }
 
-// the streaming report kernels for a launch: GM 0 the column sums (k_report_init_codes where codes_only), 1 .. 4 the per-group sums
+// the streaming report kernels for a launch: GM 0 the column sums (k_report_init_codes where codes_only), 1 .. 4 the per-group sums.
+// An instance carries its own template arguments, so that the launch record (tsem_report_info_n) names what was launched, not what
+// the host meant to launch.
 typedef void (*ReportKern)(ReportArgs);
-template <int G, int E, int GM> static ReportKern report_rows_at(bool init, bool codes_only) {
-  if constexpr (GM == 0) { if (codes_only) return k_report_init_codes<G, E>; }
-  return init ? k_report_rows<G, E, true, GM> : k_report_rows<G, E, false, GM>;
+struct ReportInst { ReportKern k; int G, E; };
+template <int G, int E, int GM> static ReportInst report_rows_at(bool init, bool codes_only) {
+  if constexpr (GM == 0) { if (codes_only) return {k_report_init_codes<G, E>, G, E}; }
+  return {init ? k_report_rows<G, E, true, GM> : k_report_rows<G, E, false, GM>, G, E};
 }
 // the instance for a capacity: G lanes of E entries per row
-template <int GM> static ReportKern report_rows_kernel(int cap, bool init, bool codes_only) {
+template <int GM> static ReportInst report_rows_kernel(int cap, bool init, bool codes_only) {
   if (cap <= 8) return report_rows_at<1, 8, GM>(init, codes_only);
   if (cap <= 16) return report_rows_at<1, 16, GM>(init, codes_only);
   if (cap <= 32) return report_rows_at<2, 16, GM>(init, codes_only);
@@ -1415,6 +1418,15 @@ static int report_scratch(tsem_ctx* h) {
   if (!h->d_rep_nb) { TSEM_ALLOC(h->d_rep_nb, h->N); TSEM_ALLOC(h->d_rep_rows, h->N); TSEM_ALLOC(h->d_rep_n, 1); }
   return TSEM_OK;
 }
+// the launch record of a report call (tsem_report_info_n): started afresh; the deferred list now belongs to this call, if to any
+static tsem_ctx::ReportLaunch& launch_record(tsem_ctx* h, int call, int family, bool init, int gm) {
+  const bool streaming = family >= 2 && family <= 4;      // (the other kernels leave the list alone)
+  if (streaming) h->rep_launch[0].list = h->rep_launch[1].list = false;
+  tsem_ctx::ReportLaunch& L = h->rep_launch[call];
+  L = tsem_ctx::ReportLaunch();
+  L.family = family; L.init = init ? 1 : 0; L.gm = gm; L.list = streaming;
+  return L;
+}
 // The streaming report kernels' arguments for the z of a row pass (A.pi == null: the initial z; else pi*theta | pi by id are written
 // to c2 [2 IDN]).  Rows they leave to k_report_slow go to the report scratch; outputs and LDS budgets are the caller's.
 static ReportArgs report_args(tsem_ctx* h, const RowPassArgs& A, double thresh, double* c2) {
@@ -1476,8 +1488,12 @@ static int report_packed(tsem_ctx* h, const ReportArgs& R, DevTmp& tabs, PhaseTi
   P.t32 = t32; P.l32 = l32; P.thresh = (float)R.thresh; P.win = reinterpret_cast<uint32_t*>(R.nbest);
   P.defer_rows = R.defer_rows; P.defer_n = R.defer_n; P.chunks = h->d_rep_chunks; P.nchunks = h->n_rep_chunks;
   const size_t lds = (size_t)((E + 1) * (E / 2) + P.HC + 1 + (P.lut_len << P.lut_rep)) * 4;
-  void (*pk)(Rp32Args) = E == 16 ? (P.HC < IDN ? k_report_pack32<16, true> : k_report_pack32<16, false>)
-                                 : (P.HC < IDN ? k_report_pack32<8, true> : k_report_pack32<8, false>);
+  struct PackInst { void (*k)(Rp32Args); int E, cold; };
+  const PackInst inst = E == 16 ? (P.HC < IDN ? PackInst{k_report_pack32<16, true>, 16, 1} : PackInst{k_report_pack32<16, false>, 16, 0})
+                              : (P.HC < IDN ? PackInst{k_report_pack32<8, true>, 8, 1} : PackInst{k_report_pack32<8, false>, 8, 0});
+  void (*const pk)(Rp32Args) = inst.k;
+  tsem_ctx::ReportLaunch& L = launch_record(h, 0, 4, false, 0);
+  L.G = 64; L.E = inst.E; L.cold = inst.cold; L.HC = P.HC; L.lut_rep = P.lut_rep; L.grid = h->n_cu; L.block = nwv * 64;   // (a row takes up to 64 lanes)
   TSEM_HIP(hipFuncSetAttribute((const void*)pk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
   if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[0], h->stream));
   pk<<<h->n_cu, nwv * 64, lds, h->stream>>>(P);
@@ -1502,7 +1518,10 @@ static int report_streaming(tsem_ctx* h, ReportArgs& R, bool codes_only) {
   R.HC = init ? 0 : std::max(0, std::min(R.IDN, (lds_avail - R.Hs * slot_bytes) / 8));
   if (codes_only) R.Hs = std::min(R.IDN, (TS_LDS_MAX - 2048) / 8);
   const size_t lds = codes_only ? (size_t)R.Hs * 8 : (size_t)R.lut_len * 8 + (size_t)R.HC * 8 + (size_t)R.Hs * slot_bytes;
-  const ReportKern rk = report_rows_kernel<0>(report_capacity(h), init, codes_only);
+  const ReportInst ri = report_rows_kernel<0>(report_capacity(h), init, codes_only);
+  const ReportKern rk = ri.k;
+  tsem_ctx::ReportLaunch& L = launch_record(h, 0, codes_only ? 3 : 2, init, 0);
+  L.G = ri.G; L.E = ri.E; L.Hs = R.Hs; L.HC = R.HC; L.grid = h->n_cu; L.block = rr_nt(init);
   TSEM_HIP(hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
   if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[0], h->stream));
   rk<<<h->n_cu, rr_nt(init), lds, h->stream>>>(R);
@@ -1515,6 +1534,8 @@ static int report_streaming(tsem_ctx* h, ReportArgs& R, bool codes_only) {
 static int report_generic(tsem_ctx* h, CsrIds& ids, RowPassArgs& A, double* d_cs) {
   const bool parts = h->d_colmap && h->d_col_of_pc && h->P > 0;
   if (parts) { h->rep_timed = false; h->rep_kernel = 1; h->rep_deferred = 0; }
+  tsem_ctx::ReportLaunch& L = launch_record(h, 0, 1, A.pi == nullptr, 0);
+  L.G = RP_SUB; L.grid = parts ? h->n_cu * 2 : tsem_rowpass_grid(h); L.block = parts ? 1024 : 256;
   if (int rc = ids.acquire(A)) return rc;
   const int64_t n = 3 * (int64_t)h->K;
   if (!parts) return rowpass_exact(h, A, RP_REPORT, -1, tsem_rowpass_grid(h), 256, (size_t)A.lut_len * 8, d_cs, n);
@@ -1547,11 +1568,13 @@ static int ties_of_deferred(tsem_ctx* h) {
   TSEM_HIP(rocprim::radix_sort_keys(h->d_rep_tmp, tb, d_unsorted, d_sorted, (size_t)nt, 0, 32, h->stream));
   return install_ties(h, d_sorted, h->d_rep_nb, (int64_t)nt);
 }
-// ... after the other passes: a select over the best-hit counts
+// ... after the other passes: a select over the best-hit counts, into a list of its own (the deferred rows stay where they are for
+// tsem_report_info_n)
 static int ties_of_counts(tsem_ctx* h) {
   unsigned long long n = 0;
-  if (int rc = select_ties(h, h->d_rep_nb, h->d_rep_rows, h->d_rep_n, &n)) return rc;
-  return install_ties(h, h->d_rep_rows, h->d_rep_nb, (int64_t)n);
+  if (!h->d_rep_sel) { TSEM_ALLOC(h->d_rep_sel, h->N); TSEM_ALLOC(h->d_rep_sel_n, 1); }
+  if (int rc = select_ties(h, h->d_rep_nb, h->d_rep_sel, h->d_rep_sel_n, &n)) return rc;
+  return install_ties(h, h->d_rep_sel, h->d_rep_nb, (int64_t)n);
 }
 
 // One pass for the column sums output_report takes from one z (model.py:432-457): conf | exclude | average, and the rows
@@ -1559,7 +1582,7 @@ static int ties_of_counts(tsem_ctx* h) {
 int tsem_report_colsums(tsem_ctx* h, int which, double thresh, double* out3K, int64_t* n_ties) {
   if (!h || !h->d_indptr || !out3K) return TSEM_ERR_ARG;
   if (int rc = ensure_device(h)) return rc;
-  const bool want_conf = !(thresh < 0.0);                  // thresh < 0: no `conf` column wanted (its third of out3K stays 0)
+  const bool want_conf = !(thresh < 0.0);                  // thresh < 0: no `conf` column wanted (its third of out3K is not meaningful: the deferred rows' share at 0.9, or all of it)
   PhaseTimer pt(h->stream);                                // (TSEM_TRACE=1)
   if (!want_conf) thresh = 0.9;                            // (what the paths that compute it anyway use)
   CsrIds ids(h);
@@ -1626,6 +1649,49 @@ int tsem_report_ties(tsem_ctx* h, int64_t cap, int32_t* rows, int32_t* counts) {
   TSEM_HIP(hipMemcpyAsync(rows, h->d_tie_rows, sizeof(int32_t) * h->n_ties, hipMemcpyDeviceToHost, h->stream));
   TSEM_HIP(hipMemcpyAsync(counts, h->d_tie_cnt, sizeof(int32_t) * h->n_ties, hipMemcpyDeviceToHost, h->stream));
   TSEM_HIP(hipStreamSynchronize(h->stream));
+  return TSEM_OK;
+}
+
+// the deferred list of the last streaming launch, counted for tsem_report_info_n: out[0] rows stored as they are, out[1] those of them
+// longer than `cap` entries, out[2] rows stored as ~row (the near-ties of k_report_rows)
+__global__ void k_deferred_kinds(const unsigned long long* __restrict__ nd, const int32_t* __restrict__ defer_rows, const int64_t* __restrict__ indptr,
+                                 int64_t cap, unsigned long long* __restrict__ out) {
+  const int64_t n = (int64_t)*nd;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t rc = defer_rows[i];
+    if (rc < 0) { atomicAdd(&out[2], 1ull); continue; }
+    atomicAdd(&out[0], 1ull);
+    if (indptr[rc + 1] - indptr[rc] > cap) atomicAdd(&out[1], 1ull);
+  }
+}
+
+// What the last tsem_report_colsums (out[0 .. 16)) and the last tsem_reassign_groups (out[16 .. 32)) launched: see telescope_em.h.
+// The deferred rows are counted HERE, from the list the launch left (one small kernel and a copy of three counters: the query
+// synchronises the stream, the report calls do nothing for it).
+int tsem_report_info_n(tsem_ctx* h, int64_t* out, int32_t n) {
+  if (!h || !out || n < 0) return TSEM_ERR_ARG;
+  if (int rc = ensure_device(h)) return rc;
+  int64_t info[TSEM_REPORT_INFO_N] = {};
+  for (int c = 0; c < 2; ++c) {
+    const tsem_ctx::ReportLaunch& L = h->rep_launch[c];
+    int64_t* const o = info + 16 * c;
+    o[0] = L.family; o[1] = L.G; o[2] = L.E; o[3] = L.init; o[4] = L.gm; o[5] = L.cold; o[6] = L.Hs; o[7] = L.HC; o[8] = L.lut_rep;
+    o[9] = L.grid; o[10] = L.block; o[11] = -1; o[12] = -1; o[13] = L.tiles; o[14] = L.tile_groups;
+    if (!L.list || !h->d_rep_rows || !h->d_rep_n || !h->d_indptr) continue;
+    DevTmp cnt;
+    TSEM_TMP(cnt, 3 * sizeof(unsigned long long));
+    unsigned long long c3[3] = {0, 0, 0};
+    TSEM_HIP(hipMemsetAsync(cnt.p, 0, sizeof(c3), h->stream));
+    k_deferred_kinds<<<64, 256, 0, h->stream>>>(h->d_rep_n, h->d_rep_rows, h->d_indptr, (int64_t)L.G * L.E, cnt.as<unsigned long long>());
+    TSEM_HIP(hipGetLastError());
+    TSEM_HIP(hipMemcpyAsync(c3, cnt.p, sizeof(c3), hipMemcpyDeviceToHost, h->stream));
+    TSEM_HIP(hipStreamSynchronize(h->stream));
+    // k_report_rows / k_report_init_codes mark what they defer: a row as it is was too long for the row's lanes, ~row is a near-tie;
+    // k_report_pack32 stores every deferred row as it is: the too long ones are told by their length, the rest its filter left undecided
+    if (L.family == 4) { o[11] = (int64_t)c3[1]; o[12] = (int64_t)(c3[0] - c3[1]); }
+    else { o[11] = (int64_t)c3[0]; o[12] = (int64_t)c3[2]; }
+  }
+  for (int i = 0; i < std::min<int>(n, TSEM_REPORT_INFO_N); ++i) out[i] = info[i];
   return TSEM_OK;
 }
 
@@ -1884,6 +1950,9 @@ int tsem_reassign_groups(tsem_ctx* h, int method, double thresh, int which, cons
   ReportArgs R{};
   ReportKern rk = nullptr, rs = nullptr;
   size_t lds = 0;
+  const bool unique_kernel = !stream_ok && h->N && method == TSEM_RA_UNIQUE && which != TSEM_Z_USER && !h->opt_reproducible;
+  tsem_ctx::ReportLaunch& L = launch_record(h, 1, stream_ok ? 2 : (unique_kernel ? 5 : 1), init, stream_ok ? gm : 0);
+  L.tiles = (n_groups + tile - 1) / tile;
   if (stream_ok) {
     // (d_rep_rows / d_rep_n are only scratch here: the tie list of the last tsem_report_colsums lives in its own d_tie_rows / d_tie_cnt,
     //  which tsem_reassign_rows(rows = NULL) and `choose` still use after this call — ADVICE r4)
@@ -1895,8 +1964,10 @@ int tsem_reassign_groups(tsem_ctx* h, int method, double thresh, int which, cons
     R.HC = init ? 0 : std::max(0, std::min(IDN, (TS_LDS_MAX - 2048 - R.lut_len * 8) / 8));
     lds = (size_t)R.lut_len * 8 + (size_t)R.HC * 8;
     const int cap = report_capacity(h);
-    rk = gm == 1 ? report_rows_kernel<1>(cap, init, false) : gm == 2 ? report_rows_kernel<2>(cap, init, false)
-       : gm == 4 ? report_rows_kernel<4>(cap, init, false) : report_rows_kernel<3>(cap, init, false);
+    const ReportInst ri = gm == 1 ? report_rows_kernel<1>(cap, init, false) : gm == 2 ? report_rows_kernel<2>(cap, init, false)
+                        : gm == 4 ? report_rows_kernel<4>(cap, init, false) : report_rows_kernel<3>(cap, init, false);
+    rk = ri.k;
+    L.G = ri.G; L.E = ri.E; L.HC = R.HC; L.grid = h->n_cu; L.block = rr_nt(init);
     rs = gm == 1 ? report_slow_kernel<1>(init) : gm == 2 ? report_slow_kernel<2>(init)
        : gm == 4 ? report_slow_kernel<4>(init) : report_slow_kernel<3>(init);
     TSEM_HIP(hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
@@ -1904,6 +1975,7 @@ int tsem_reassign_groups(tsem_ctx* h, int method, double thresh, int which, cons
   for (int g0 = 0; g0 < n_groups; g0 += tile) {
     const int g1 = std::min(n_groups, g0 + tile);
     const int64_t n_out = (int64_t)(g1 - g0) * K;
+    L.tile_groups = g1 - g0;
     TSEM_HIP(hipMemsetAsync(d_out, 0, sizeof(double) * n_out, h->stream));
     if (stream_ok) {
       const int64_t n_id = (int64_t)(g1 - g0) * IDN;
@@ -1916,7 +1988,7 @@ int tsem_reassign_groups(tsem_ctx* h, int method, double thresh, int which, cons
       TSEM_HIP(hipGetLastError());
       k_group_finish<<<cdiv64(n_id, 256), 256, 0, h->stream>>>(n_id, IDN, K, h->d_col_of_id, R.t_cnt, R.t_val, d_out);
       TSEM_HIP(hipGetLastError());
-    } else if (h->N && method == TSEM_RA_UNIQUE && which != TSEM_Z_USER && !h->opt_reproducible) {
+    } else if (unique_kernel) {
       if (int rc = ids.acquire(A)) return rc;
       k_group_unique<<<cdiv64(h->N, 256), 256, 0, h->stream>>>(h->N, h->d_indptr, h->d_indices, h->d_raw, h->d_lut, A.pi, h->d_group, g0, g1, K, d_out);
       TSEM_HIP(hipGetLastError());

@@ -131,6 +131,10 @@ int  tsem_set_stream(tsem_ctx* h, void* hip_stream); /* launch on this hipStream
  *   "fused_dbg"    test hooks, a sum of bits: 32 / 64 the fused EM / lnl pass behaves like a hand-off time-out; 8192 the lnl pass
  *                  takes a logarithm per entry, 16384 looks log Q up where the arithmetic form applies, 32768 takes the log
  *                  form whatever the parameters.  Any other bit: TSEM_ERR_ARG.
+ *   "fused_dbg_skip"  n: bits 32 / 64 of "fused_dbg" reach the kernel only after n fused launches of the kind they aim at (EM passes
+ *                  for 32, lnl passes for 64; a split or "reproducible" EM pass is several launches) have gone by since either
+ *                  option was set — a time-out placed inside a chunk.  0 (default): at once.  The hook stays an early return that
+ *                  leaves the error word behind.  Negative: TSEM_ERR_ARG.
  *   "fused_prof", "chunk_blocks"     timing experiments */
 int  tsem_set_option(tsem_ctx* h, const char* key, int64_t value);
 int  tsem_synchronize(tsem_ctx* h);
@@ -305,6 +309,9 @@ typedef struct tsem_local_group tsem_local_group;
 int  tsem_comm_local_group(tsem_local_group** out, int device, int world /* <= 8 */);
 void tsem_comm_local_group_destroy(tsem_local_group* g);      /* after every communicator of the group */
 int  tsem_comm_create_local(tsem_comm** out, tsem_local_group* g, int rank);
+/* How long a rank waits at the host rendezvous for its peers before its collective fails with TSEM_ERR_TIMEOUT and the
+ * group counts as broken (default 120 s; seconds > 0).  Tests set a short one, so that a rank that raised ends them soon. */
+int  tsem_comm_local_group_set_timeout(tsem_local_group* g, double seconds);
 
 /* ---- results -------------------------------------------------------------- */
 /* z aligned to the CSR pattern of the loaded scores (-1 where the reference

@@ -202,6 +202,7 @@ def lib():
     L.tsem_comm_local_group_destroy.argtypes = [vp]
     L.tsem_comm_local_group_destroy.restype = None
     L.tsem_comm_create_local.argtypes = [C.POINTER(vp), vp, C.c_int]
+    L.tsem_comm_local_group_set_timeout.argtypes = [vp, dbl]
     L.tsem_set_prev_lnl.argtypes = [vp, dbl]
     L.tsem_legacy_randint.argtypes = [vp, C.POINTER(i32), vp, i64, vp]
     L.tsem_em_run.argtypes = [vp, dbl, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(dbl),
@@ -820,6 +821,12 @@ class LocalGroup(object):
 
     def comm(self, rank):
         return LibComm(self.device, None, rank, self.world, group=self)
+
+    def set_timeout(self, seconds):
+        """How long a rank waits for its peers at a collective before it fails (default 120 s)."""
+        rc = self._L.tsem_comm_local_group_set_timeout(self.handle, float(seconds))
+        if rc != OK:
+            raise EngineError('tsem_comm_local_group_set_timeout failed (%d)' % rc)
 
     def close(self):
         if getattr(self, 'handle', None):

@@ -251,6 +251,14 @@ int tsem_comm_local_group(tsem_local_group** out, int device, int world) {
   return TSEM_OK;
 }
 
+// how long a rank waits at the host rendezvous for its peers (default 120 s); tests that expect a rank to fail set a short one
+int tsem_comm_local_group_set_timeout(tsem_local_group* g, double seconds) {
+  if (!g || !(seconds > 0.0)) return TSEM_ERR_ARG;
+  std::lock_guard<std::mutex> lk(g->mu);
+  g->timeout_s = seconds;
+  return TSEM_OK;
+}
+
 // The group lives until its creator's handle AND every communicator made from it are gone (`refs`): a caller that destroys the group
 // while a rank's communicator still exists — an error path that skipped a rank's close, a garbage-collected Python object — used to
 // leave that communicator with a dangling pointer, and its destructor locked a destroyed mutex (std::system_error, found by the

@@ -185,6 +185,8 @@ struct tsem_ctx {
   double* d_lnl_part = nullptr;     // [4096]
   int em_kernel = TSEM_EMK_AUTO;
   int64_t opt_R = 0, opt_P = 0, opt_chunk = 0, opt_dbg = 0;
+  int64_t opt_dbg_skip = 0;         // option "fused_dbg_skip": fused launches of the kind fused_dbg's bits 32 / 64 aim at that go by untouched first
+  int64_t dbg_seen[2] = {0, 0};     // ... and how many went by since either option was set (0: EM passes, 1: lnl passes)
   bool use_fused = false;
   int64_t max_subblock = 0;
   int64_t last_slow_path = 0;       // exchange granules that missed their tag in the last checked pass

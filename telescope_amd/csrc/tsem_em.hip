@@ -664,7 +664,18 @@ static int launch_fused(tsem_ctx* h, int mode, hipEvent_t* pair, int bin = 0) {
   // option "fused_prof": the EM pass runs the timeline instantiation (k_em_fused<..., PROF = true>, tsem_fused_inst.h), the only kernels
   // that hold time stamps.  The log-likelihood and exact-sum passes never stamped and run as they are.
   const bool prof = h->d_prof && (mode == 0 || mode == 4 || (mode == 5 && bin == 0));
-  A.prof = prof ? h->d_prof : nullptr; A.prof_blocks = prof ? h->prof_steps : 0; A.dbg = (int)(h->opt_dbg & (32 | 64));
+  A.prof = prof ? h->d_prof : nullptr; A.prof_blocks = prof ? h->prof_steps : 0;
+  {
+    // test hook (fused_dbg 32 / 64, fused_dbg_skip): the kernel sees the bit of ITS kind of pass — the lnl kernels (modes 1, 9, 8)
+    // test 64, every other mode 32 — once fused_dbg_skip launches of that kind have gone by since the option was set
+    const int kind = (mode == 1 || mode == 8) ? 1 : 0;
+    const int64_t bit = kind ? 64 : 32;
+    A.dbg = 0;
+    if (h->opt_dbg & bit) {
+      if (h->dbg_seen[kind] >= h->opt_dbg_skip) A.dbg = (int)bit;
+      h->dbg_seen[kind] += 1;
+    }
+  }
   A.ctl = h->d_ctl;
   A.ebias = h->d_ebias; A.bin = bin; A.ovf = h->d_ovf; A.partial2 = h->d_fpartial2;
 

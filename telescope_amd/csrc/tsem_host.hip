@@ -192,6 +192,12 @@ int tsem_set_option(tsem_ctx* h, const char* key, int64_t v) {
   else if (k == "fused_dbg") {                             // test hooks: 32 / 64 a hand-off time-out of the EM / lnl pass, 8192 / 16384 / 32768 a form of the lnl pass
     if (v & ~(int64_t)(32 | 64 | 8192 | 16384 | 32768)) TSEM_FAIL(TSEM_ERR_ARG, "fused_dbg takes the bits 32, 64, 8192, 16384 and 32768 only");
     h->opt_dbg = v;
+    h->dbg_seen[0] = h->dbg_seen[1] = 0;
+  }
+  else if (k == "fused_dbg_skip") {                        // bits 32 / 64 of fused_dbg reach the kernel only after this many fused launches of their kind
+    if (v < 0) TSEM_FAIL(TSEM_ERR_ARG, "fused_dbg_skip must be 0 or a number of launches");
+    h->opt_dbg_skip = v;
+    h->dbg_seen[0] = h->dbg_seen[1] = 0;
   }
   else if (k == "split") h->opt_split = v;
   else if (k == "value_format") h->opt_format = v;

@@ -340,9 +340,16 @@ class ThreadGroup(object):
         self.barrier = threading.Barrier(world)
         self.slots = [None] * world
         self.box = None
+        self.timeout = None                                   # (host barriers of gather / scatter: wait for ever, as the library's default nearly does)
 
     def comm(self, rank):
         return ThreadComm(self, rank)
+
+    def set_timeout(self, seconds):
+        """A rank waits at most `seconds` for its peers, in the library's collectives and at the host barriers of gather_rows /
+        scatter_rows; then it raises instead of waiting on (tests: a rank that failed ends the others within seconds)."""
+        self.lib_group.set_timeout(seconds)
+        self.timeout = float(seconds)
 
     def close(self):
         self.lib_group.close()
@@ -382,18 +389,18 @@ class ThreadComm(object):
     def gather_rows(self, a):
         g = self.g
         g.slots[self.rank] = np.asarray(a)
-        g.barrier.wait()
+        g.barrier.wait(g.timeout)
         out = list(g.slots) if self.rank == 0 else [None] * self.world
-        g.barrier.wait()
+        g.barrier.wait(g.timeout)
         return out
 
     def scatter_rows(self, parts):
         g = self.g
         if self.rank == 0:
             g.box = list(parts)
-        g.barrier.wait()
+        g.barrier.wait(g.timeout)
         mine = g.box[self.rank]
-        g.barrier.wait()
+        g.barrier.wait(g.timeout)
         return mine
 
     def barrier(self):

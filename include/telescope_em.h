@@ -583,6 +583,46 @@ int  tsem_bam_chunk(tsem_bam* b, const uint8_t* bytes, int64_t n_bytes, const in
 /* HIP-event milliseconds summed over the calls so far: host-to-device, k_bam_decode, k_bam_pair, k_bam_overlap, k_bam_fragment,
  * device-to-host; *calls = how many; reset != 0 clears both. */
 int  tsem_bam_times(tsem_bam* b, int reset, double* ms6, int64_t* calls);
+/* ---- the BAMs of --updated_sam from records rewritten on the device (telescope_amd/csrc/tsem_bam_edit.h) ----
+ * A rewritten record keeps every byte but its block_size, flag, MAPQ and the aux fields that are replaced: those are removed wherever
+ * they stand and whatever their type, the new ones are appended (bam_out.set_tag).  Streams are FRAMED records (block_size and body),
+ * ready for a BGZF writer.  An output SLOT is a record index of the chunk: a bundle writes into the slots of its own records, in
+ * the order of loader._fragments' pairs, r1 then r2, and never more records than it holds.
+ *
+ * tsem_bam_names: the names the load stage writes, uploaded once per load: name j = bytes[off[j], off[j + 1]) for the locus of id j
+ * (the ids of tsem_bam_open's `locus`), the last one (j = n_names - 1) the no_feature_key.  HOST arrays, checked on the host:
+ * TSEM_ERR_ARG with a message when off[0] != 0, the offsets descend, or the annotation holds a locus id >= n_names - 1.
+ * Device memory: the bytes and 8 B per name. */
+int  tsem_bam_names(tsem_bam* b, const uint8_t* bytes, const int64_t* off /* n_names + 1 */, int32_t n_names);
+/* Load stage, sizing: k_bam_rw_plan, k_bam_rw_size and an exclusive scan per stream over the chunk the last tsem_bam_chunk left on the
+ * device (it must have returned status 0; TSEM_ERR_ARG otherwise, or without names).  Bundles of class 0 send their first pair's
+ * records to `other`, of class 1 / 2 every pair's, unchanged; of class 3 / 4 every pair's to `tmp`: an unmapped pair unchanged, a
+ * mapped one without its ZF / ZT / ZB and with ZF:Z:<locus name | no_feature_key>, ZT:Z:PRI (the first pair of its locus, in pair
+ * order, that reaches the locus's largest alnscore + alnlen) or SEC, ZB:Z:<the names of the bundle's mappings whose alnscore is the
+ * first mapping's, comma-joined> appended.  A bundle of class 5 writes nothing: the caller splices its records in.
+ * pos_other / pos_tmp (int64 [n_rec + 1], HOST): slot i writes [pos[i], pos[i + 1]) of the stream; pos[n_rec] = the stream's length; at
+ * a bundle's first slot: where the bundle's bytes begin.  status2 as for tsem_bam_chunk (a record the aux walk cannot follow; the
+ * streams are then not to be fetched).  Device memory: 32 B per record on top of tsem_bam_chunk's. */
+int  tsem_bam_rewrite_size(tsem_bam* b, int64_t* pos_other, int64_t* pos_tmp, int64_t* status2);
+/* Update stage, sizing: a chunk of the tmp BAM's records (bytes / rec_off / n_rec as for tsem_bam_chunk, checked the same way on the
+ * host before the copy) and one word per record: bits 30-31 the kind, 0 unchanged, 1 SEC (flag |= 0x100, MAPQ 0, YC:Z:248,248,248
+ * replaces every YC), 2 PRI (bits 0-17 the tsem_entry_tags word of the pair's entry: MAPQ, XP:C and YC replace every XP / YC, 0x100
+ * cleared when assigned and set otherwise) — bam_out.update_pair.  Every record is walked again, the file having been re-read:
+ * status2 = (code, record) of the first one that cannot be, with the codes of tsem_bam_chunk (and 9 for a kind of 3).
+ * pos (int64 [n_rec + 1], HOST): record i becomes [pos[i], pos[i + 1]) of the updated stream.  Needs no annotation (a handle opened
+ * with n_ref = 0 will do) and no names.  Device memory: 1 B per chunk byte, 44 B per record. */
+int  tsem_bam_update_size(tsem_bam* b, const uint8_t* bytes, int64_t n_bytes, const int64_t* rec_off, int64_t n_rec, const uint32_t* words,
+                          int64_t* pos /* n_rec + 1 */, int64_t* status2);
+/* Between a sizing call and its fetch: per slot the kind (0 nothing, 1 other, 2 tmp unchanged, 3 tmp PRI, 4 tmp SEC, 5 update stage)
+ * and the pair slot (-1: none) — what the caller's table for the update stage is made from.  n = the sizing call's record count. */
+int  tsem_bam_rewrite_slots(tsem_bam* b, int32_t* kind /* n */, int32_t* pair /* n */, int64_t n);
+/* k_bam_rw_write for the last sizing call (status 0) and the streams to the host.  n_other / n_tmp must be that call's stream lengths
+ * (the update stage: other = NULL, 0; tmp = the updated stream), TSEM_ERR_ARG otherwise; one fetch per sizing call.  Device memory:
+ * 1 B per output byte. */
+int  tsem_bam_rewrite_fetch(tsem_bam* b, uint8_t* other, int64_t n_other, uint8_t* tmp, int64_t n_tmp);
+/* HIP-event milliseconds of the rewriting, summed: host-to-device (the update stage's chunk), k_bam_rw_plan, the size kernel with its
+ * scans, k_bam_rw_write, device-to-host; *calls = sizing calls; reset != 0 clears both. */
+int  tsem_bam_rewrite_times(tsem_bam* b, int reset, double* ms5, int64_t* calls);
 
 /* ---- device loader: the BGZF blocks of a BAM file inflated on the device (telescope_amd/csrc/tsem_bgzf.hip) ----
  * A BGZF file is a chain of gzip members ("blocks") of at most 64 KiB compressed and 64 KiB inflated bytes; each needs nothing from

@@ -241,6 +241,12 @@ def lib():
     L.tsem_bam_close.argtypes = [vp]
     L.tsem_bam_chunk.argtypes = [vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, dbl, i32, vp, vp]
     L.tsem_bam_times.argtypes = [vp, C.c_int, vp, C.POINTER(i64)]
+    L.tsem_bam_names.argtypes = [vp, vp, vp, i32]
+    L.tsem_bam_rewrite_size.argtypes = [vp, vp, vp, vp]
+    L.tsem_bam_update_size.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp]
+    L.tsem_bam_rewrite_slots.argtypes = [vp, vp, vp, i64]
+    L.tsem_bam_rewrite_fetch.argtypes = [vp, vp, i64, vp, i64]
+    L.tsem_bam_rewrite_times.argtypes = [vp, C.c_int, vp, C.POINTER(i64)]
     L.tsem_bgzf_scan.argtypes = [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
     L.tsem_bgzf_open.argtypes = [C.POINTER(vp), C.c_int]
     L.tsem_bgzf_close.argtypes = [vp]
@@ -1065,6 +1071,63 @@ class BamLoader(object):
         if rc != OK:
             raise _csr_error('tsem_bam_times', rc)
         return dict(zip(('h2d', 'k_bam_decode', 'k_bam_pair', 'k_bam_overlap', 'k_bam_fragment', 'd2h'), ms.tolist()), chunks=n.value)
+
+    # ---- the BAMs of --updated_sam (tsem_bam_names / _rewrite_size / _update_size / _rewrite_slots / _rewrite_fetch)
+    def names(self, names):
+        """The locus names in the order of their ids, the no_feature_key last (what the load stage writes as ZF / ZB)."""
+        enc = [n.encode() for n in names]
+        off = np.zeros(len(enc) + 1, np.int64)
+        np.cumsum([len(e) for e in enc], out=off[1:])
+        buf = np.frombuffer(b''.join(enc), dtype=np.uint8)
+        rc = self._L.tsem_bam_names(self._h, ptr(buf) if buf.size else None, ptr(off), len(enc))
+        if rc != OK:
+            raise _csr_error('tsem_bam_names', rc)
+
+    def rewrite_size(self, n):
+        """Load stage, over the chunk of the last `chunk` call (n records) -> (pos_other, pos_tmp int64 [n + 1], (status code, record))"""
+        po, pt, st = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64), np.zeros(2, np.int64)
+        rc = self._L.tsem_bam_rewrite_size(self._h, ptr(po), ptr(pt), ptr(st))
+        if rc != OK:
+            raise _csr_error('tsem_bam_rewrite_size', rc)
+        return po, pt, (int(st[0]), int(st[1]))
+
+    def update_size(self, data, rec_off, words):
+        """Update stage: a chunk of tmp records and their words -> (pos int64 [n + 1], (status code, record))"""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        n = len(off) - 1
+        if len(w) != n:
+            raise ValueError('one word per record: %d words, %d records' % (len(w), n))
+        pos, st = np.zeros(n + 1, np.int64), np.zeros(2, np.int64)
+        rc = self._L.tsem_bam_update_size(self._h, ptr(buf) if buf.size else None, buf.size, ptr(off), n, ptr(w) if n else None, ptr(pos), ptr(st))
+        if rc != OK:
+            raise _csr_error('tsem_bam_update_size', rc)
+        return pos, (int(st[0]), int(st[1]))
+
+    def rewrite_slots(self, n):
+        """(kind, pair slot) int32 [n] of the last sizing call, before its fetch"""
+        kind, pair = np.empty(n, np.int32), np.empty(n, np.int32)
+        rc = self._L.tsem_bam_rewrite_slots(self._h, ptr(kind), ptr(pair), n)
+        if rc != OK:
+            raise _csr_error('tsem_bam_rewrite_slots', rc)
+        return kind, pair
+
+    def rewrite_fetch(self, n_other, n_tmp):
+        """The streams of the last sizing call: (other, tmp) uint8 arrays of exactly these lengths"""
+        other, tmp = np.empty(int(n_other), np.uint8), np.empty(int(n_tmp), np.uint8)
+        if n_other or n_tmp:
+            rc = self._L.tsem_bam_rewrite_fetch(self._h, ptr(other) if n_other else None, int(n_other), ptr(tmp) if n_tmp else None, int(n_tmp))
+            if rc != OK:
+                raise _csr_error('tsem_bam_rewrite_fetch', rc)
+        return other, tmp
+
+    def rewrite_times(self, reset=False):
+        ms, n = np.zeros(5), C.c_int64()
+        rc = self._L.tsem_bam_rewrite_times(self._h, int(reset), ptr(ms), C.byref(n))
+        if rc != OK:
+            raise _csr_error('tsem_bam_rewrite_times', rc)
+        return dict(zip(('h2d', 'k_bam_rw_plan', 'k_bam_rw_size', 'k_bam_rw_write', 'd2h'), ms.tolist()), calls=n.value)
 
 
 def _csr_error(fn, rc):

@@ -1,7 +1,8 @@
 """BAM output of `--updated_sam` (model.py:214-285 `_load_sequential`, :479-521 `update_sam`), stdlib only.
 
   * `BgzfWriter`: BGZF blocks (zlib raw deflate, at most 64 KiB each) and the EOF block;
-  * `BamWriter`: the BAM header (text + the input's binary reference list) and raw records;
+  * `BamWriter`: the BAM header (text + the input's binary reference list) and raw records, or pieces of an already framed record
+    stream (`write_framed`: what the device rewrite of `--rewrite device` hands over);
   * `set_tag` / `get_tag` / `set_flag` / `set_mapq`: edits of a record's raw bytes (as `read_bam(..., raw=True)` yields them)
     that change the flag, the MAPQ and the tags and re-encode nothing else.  `set_tag` is pysam's `AlignedSegment.set_tag`:
     an existing tag of that name is deleted and the new one APPENDED; a Python int gets the smallest type that holds it
@@ -37,10 +38,21 @@ class BgzfWriter(object):
         self._level = level
 
     def write(self, data):
-        self._buf += data
-        while len(self._buf) >= _BLOCK_IN:
-            self._block(bytes(self._buf[:_BLOCK_IN]))
-            del self._buf[:_BLOCK_IN]
+        """the stream is cut every _BLOCK_IN bytes however the bytes arrive; whole blocks of a large piece are deflated straight from
+        it, without a pass through the buffer"""
+        mv = memoryview(data).cast('B')
+        p, n = 0, len(mv)
+        if self._buf:
+            p = min(n, _BLOCK_IN - len(self._buf))
+            self._buf += mv[:p]
+            if len(self._buf) < _BLOCK_IN:
+                return
+            self._block(bytes(self._buf))
+            self._buf = bytearray()
+        while n - p >= _BLOCK_IN:
+            self._block(bytes(mv[p:p + _BLOCK_IN]))
+            p += _BLOCK_IN
+        self._buf += mv[p:]
 
     def _block(self, data):
         co = zlib.compressobj(self._level, zlib.DEFLATED, -15)
@@ -78,6 +90,10 @@ class BamWriter(object):
 
     def write(self, rec):
         self._z.write(struct.pack('<i', len(rec)) + rec)
+
+    def write_framed(self, stream):
+        """a piece of an already framed stream (records with their block_size, cut anywhere): bytes, a memoryview or a uint8 array"""
+        self._z.write(stream)
 
     def close(self):
         self._z.close()

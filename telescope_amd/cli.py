@@ -18,7 +18,8 @@ device before the model is built (`<exp_tag>-umi_stats.tsv`); `sc resume` collap
 `assign` (telescope/telescope_assign.py:372-451) uses telescope_amd/loader.py, a pysam-free
 restatement of the reference's sequential loader; `--ncpu > 1` is not offered.  `--loader device` (not in the reference) does that
 loader's per-record work on the GPU (telescope_amd/loader_device.py): the same matrix, checkpoint and reports.  `--updated_sam` writes `<exp_tag>-updated.bam`
-(model.py:479-521) beside `<exp_tag>-other.bam` and `<exp_tag>-tmp_tele.bam` of the load, on one GPU.
+(model.py:479-521) beside `<exp_tag>-other.bam` and `<exp_tag>-tmp_tele.bam` of the load, on one GPU; with `--loader device --rewrite
+device` the records of all three are rewritten on the GPU (the same files, byte for byte; the BGZF compression stays on the host).
 """
 import argparse
 import logging as lg
@@ -104,7 +105,12 @@ def _assign_args(asg):
     g.add_argument('--ncpu', type=int, default=1, help='Only 1 is supported (sequential loader).')
     g.add_argument('--loader', default='python', choices=['python', 'device'],
                    help='python (default): the streaming pure-Python BAM parser.  device: the records are decoded, paired and '
-                        'intersected with the annotation on the GPU (--device), the same matrix and checkpoint; not with --updated_sam.')
+                        'intersected with the annotation on the GPU (--device), the same matrix and checkpoint; with --updated_sam '
+                        'only together with --rewrite device.')
+    g.add_argument('--rewrite', default='host', choices=['host', 'device'],
+                   help='host (default): the BAMs of --updated_sam are written record by record by the python loader.  device (with '
+                        '--loader device and --updated_sam): their records are rewritten on the GPU, the same three files byte for byte; '
+                        'the BGZF compression stays on the host.')
     g.add_argument('--inflate', default='host', choices=['host', 'device'],
                    help='host (default): the BGZF blocks of the BAM are inflated by gzip on one host core.  device (with --loader device): '
                         'they are inflated on the GPU as well, one wave per block.')
@@ -353,9 +359,16 @@ def _refuse_umi_updated_sam(args):
 def _refuse_device_updated_sam(args):
     """`--loader device` with --updated_sam: refused before anything is read (the tmp and other BAMs are written record by record
     during the Python load; the device loader does not write them)."""
-    if getattr(args, 'loader', 'python') == 'device' and getattr(args, 'updated_sam', False):
+    rewrite = getattr(args, 'rewrite', 'host')
+    if rewrite == 'device' and not getattr(args, 'updated_sam', False):
+        raise SystemExit('telescope assign: --rewrite device without --updated_sam is not supported (there is no BAM to write); '
+                         'add --updated_sam')
+    if rewrite == 'device' and getattr(args, 'loader', 'python') != 'device':
+        raise SystemExit('telescope assign: --rewrite device without --loader device is not supported (the records are rewritten '
+                         'while the device loader holds them); add --loader device')
+    if getattr(args, 'loader', 'python') == 'device' and getattr(args, 'updated_sam', False) and rewrite != 'device':
         raise SystemExit('telescope assign: --loader device with --updated_sam is not supported (the BAMs of the load are written '
-                         'record by record by the python loader); use --loader python')
+                         'record by record by the python loader); use --loader python, or add --rewrite device')
 
 
 def _refuse_device_inflate(args):

@@ -24,8 +24,21 @@
 // (record << 8 | code), so the first such record in file order is the one reported.  What these kernels do not reproduce exactly — a
 // bundle above the record cap, more than 8 loci per pair, a value outside int32, a reference id outside the header's list — marks
 // the bundle for the host (class 5), which runs the Python loader's own code on that bundle's bytes.
+//
+// The BAMs of `--updated_sam` (tsem_bam_edit.h holds the bodies) come from three more kernels, one lane per bundle or per output slot:
+//
+//   k_bam_rw_plan   one lane per bundle: which record each of the bundle's output slots writes (pair order, r1 then r2).
+//   k_bam_rw_size   one lane per slot: other or tmp, PRI or SEC (the first pair of its locus reaching the largest alnscore + alnlen),
+//                   and the record's new length: the aux walk that skips ZF / ZT / ZB plus the bytes of the new fields.
+//                   k_bam_upd_size is its sibling of the update stage: the edit comes from the record's word.
+//   k_bam_rw_write  one lane per slot, behind an exclusive scan of the lengths per stream (rocprim): the record's bytes, edited.
+//
+// A lane per record, not a wave: the aux walk that decides which bytes stay is serial, and a wave per record of about 260 B would run
+// it on one lane while 63 wait, then copy four bytes per lane.  The lane's byte copy does not coalesce (64 lanes read 64 records);
+// DESIGN.md 4.12 has the measured rate and why it does not matter next to the host's deflate.
 #include "tsem_internal.h"
-#include "tsem_bam_stages.h"
+#include <rocprim/device/device_scan.hpp>
+#include "tsem_bam_edit.h"
 #include "tsem_bam_scan.h"
 
 struct tsem_bam {
@@ -43,6 +56,18 @@ struct tsem_bam {
   bool have_ev = false;
   double ms[6] = {0, 0, 0, 0, 0, 0};             // host-to-device, decode, pair, overlap, fragment, device-to-host
   int64_t calls = 0;
+  // ---- the rewriting of --updated_sam
+  int32_t max_locus = -1;                         // the largest locus id of the annotation: the name table must reach it
+  uint8_t* d_names = nullptr; int64_t* d_name_off = nullptr; int32_t n_loci = -1;   // tsem_bam_names (-1: none yet)
+  int64_t chunk_n = -1;                           // records of the chunk the device holds (-1: none a rewrite may use)
+  int64_t sized_n = -1;                           // slots of the last *_size call (-1: nothing to fetch)
+  int64_t total_other = 0, total_tmp = 0;         // ... and the lengths of its streams
+  bool sized_update = false;
+  int32_t* d_rw = nullptr; int64_t* d_pos = nullptr; uint32_t* d_words = nullptr; size_t cap_rw = 0;
+  void* d_scan = nullptr; size_t cap_scan = 0;
+  uint8_t *d_other = nullptr, *d_tmp = nullptr; size_t cap_other = 0, cap_tmp = 0;
+  double rw_ms[5] = {0, 0, 0, 0, 0};              // host-to-device, plan, size and scan, write, device-to-host
+  int64_t rw_calls = 0;
 };
 
 // (file scope, not the unnamed namespace: a profile lists them as k_bam_decode, k_bam_pair, k_bam_overlap, k_bam_fragment)
@@ -64,6 +89,29 @@ __global__ __launch_bounds__(256) void k_bam_overlap(int64_t N, const uint8_t* _
 __global__ __launch_bounds__(256) void k_bam_fragment(int64_t N, BamCols C) {
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s < N) bam_fragment_stage(s, C);
+}
+
+__global__ __launch_bounds__(256) void k_bam_rw_plan(int64_t N, BamCols C, BamRw W) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < N) bam_rw_plan_stage(s, N, C, W);
+}
+__global__ __launch_bounds__(256) void k_bam_rw_size(int64_t N, const uint8_t* __restrict__ bytes, const int64_t* __restrict__ off, BamCols C,
+                                                     BamNames nm, BamRw W, unsigned long long* status) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < N) bam_rw_size_stage(i, bytes, off, C, nm, W, status);
+  if (i == N) { W.pos_other[N] = 0; W.pos_tmp[N] = 0; }       // (the scan's last element: the stream's length)
+}
+__global__ __launch_bounds__(256) void k_bam_upd_size(int64_t N, const uint8_t* __restrict__ bytes, const int64_t* __restrict__ off,
+                                                      const uint32_t* __restrict__ words, BamRw W, unsigned long long* status) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < N) bam_upd_size_stage(i, bytes, off, words, W, status);
+  if (i == N) { W.pos_other[N] = 0; W.pos_tmp[N] = 0; }
+}
+__global__ __launch_bounds__(256) void k_bam_rw_write(int64_t N, const uint8_t* __restrict__ bytes, const int64_t* __restrict__ off, BamCols C,
+                                                      BamNames nm, const uint32_t* __restrict__ words, BamRw W, uint8_t* __restrict__ other,
+                                                      uint8_t* __restrict__ tmp) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < N) bam_rw_write_stage(i, bytes, off, C, nm, words, W, other, tmp);
 }
 
 namespace {
@@ -95,6 +143,7 @@ int tsem_bam_close(tsem_bam* b) {
   (void)hipSetDevice(b->device);
   dfree(b->d_ref_lo); dfree(b->d_ref_hi); dfree(b->d_locus); dfree(b->d_starts); dfree(b->d_maxend); dfree(b->d_ends); dfree(b->d_strand);
   dfree(b->d_bytes); dfree(b->d_off); dfree(b->d_cols); dfree(b->d_status);
+  dfree(b->d_names); dfree(b->d_name_off); dfree(b->d_rw); dfree(b->d_pos); dfree(b->d_words); dfree(b->d_scan); dfree(b->d_other); dfree(b->d_tmp);
   if (b->have_ev) for (hipEvent_t& e : b->ev) (void)hipEventDestroy(e);
   delete b;
   return TSEM_OK;
@@ -117,6 +166,7 @@ int tsem_bam_open(tsem_bam** out, int device, int32_t n_ref, const int32_t* ref_
   if (hipSetDevice(device) != hipSuccess) return bam_fail(TSEM_ERR_HIP, "hipSetDevice failed (no usable HIP device)");
   tsem_bam* b = new tsem_bam;
   b->device = device; b->n_ref = n_ref; b->n_iv = n_iv;
+  for (int64_t j = 0; j < n_iv; ++j) b->max_locus = std::max(b->max_locus, locus[j]);
   int rc = bam_upload(&b->d_ref_lo, ref_lo, (size_t)n_ref);
   if (!rc) rc = bam_upload(&b->d_ref_hi, ref_hi, (size_t)n_ref);
   if (!rc) rc = bam_upload(&b->d_starts, starts, (size_t)n_iv);
@@ -148,6 +198,7 @@ int tsem_bam_chunk(tsem_bam* b, const uint8_t* bytes, int64_t n_bytes, const int
     if (rec_off[i + 1] - rec_off[i] < 36 || rec_off[i + 1] - rec_off[i] > (int64_t)INT32_MAX)
       return bam_fail(TSEM_ERR_ARG, "tsem_bam_chunk: record " + std::to_string(i) + " is shorter than 36 bytes or longer than 2^31 - 1 (rec_off must ascend)");
   status2[0] = 0; status2[1] = -1;
+  b->chunk_n = -1; b->sized_n = -1;
   if (n_rec == 0) return TSEM_OK;
   BAM_HIP(hipSetDevice(b->device));
   const size_t nb = (size_t)rec_off[n_rec];
@@ -197,6 +248,195 @@ int tsem_bam_chunk(tsem_bam* b, const uint8_t* bytes, int64_t n_bytes, const int
   }
   ++b->calls;
   if (st != none) { status2[0] = (int64_t)(st & 0xFF); status2[1] = (int64_t)(st >> 8); }
+  else b->chunk_n = n_rec;
+  return TSEM_OK;
+}
+
+int tsem_bam_names(tsem_bam* b, const uint8_t* bytes, const int64_t* off, int32_t n_names) {
+  if (!b) return bam_fail(TSEM_ERR_ARG, "tsem_bam_names: NULL handle");
+  if (n_names < 1 || !off) return bam_fail(TSEM_ERR_ARG, "tsem_bam_names: no offsets, or fewer than one name (the last one is the no_feature_key)");
+  if ((int64_t)n_names - 1 <= (int64_t)b->max_locus)
+    return bam_fail(TSEM_ERR_ARG, "tsem_bam_names: " + std::to_string(n_names - 1) + " locus names, the annotation's locus ids reach " + std::to_string(b->max_locus));
+  if (off[0] != 0) return bam_fail(TSEM_ERR_ARG, "tsem_bam_names: off[0] must be 0");
+  for (int32_t j = 0; j < n_names; ++j)
+    if (off[j + 1] < off[j]) return bam_fail(TSEM_ERR_ARG, "tsem_bam_names: the offsets of name " + std::to_string(j) + " descend");
+  if (off[n_names] && !bytes) return bam_fail(TSEM_ERR_ARG, "tsem_bam_names: NULL bytes");
+  BAM_HIP(hipSetDevice(b->device));
+  dfree(b->d_names); dfree(b->d_name_off); b->n_loci = -1;
+  int rc = bam_upload(&b->d_names, bytes, (size_t)off[n_names]);
+  if (!rc) rc = bam_upload(&b->d_name_off, off, (size_t)n_names + 1);
+  if (rc) return rc;
+  b->n_loci = n_names - 1;
+  return TSEM_OK;
+}
+
+namespace {
+
+// the slot arrays of n slots, and the scan's scratch
+int bam_rw_reserve(tsem_bam* b, int64_t n) {
+  if ((size_t)n > b->cap_rw) {
+    dfree(b->d_rw); dfree(b->d_pos); dfree(b->d_words); b->cap_rw = 0;
+    const size_t cr = (size_t)n + (size_t)n / 4;
+    if (hipMalloc((void**)&b->d_rw, cr * 12) != hipSuccess) { b->d_rw = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam rewrite: hipMalloc failed"); }
+    if (hipMalloc((void**)&b->d_pos, (cr + 1) * 16) != hipSuccess) { b->d_pos = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam rewrite: hipMalloc failed"); }
+    if (hipMalloc((void**)&b->d_words, cr * 4) != hipSuccess) { b->d_words = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam rewrite: hipMalloc failed"); }
+    b->cap_rw = cr;
+  }
+  size_t tb = 0;
+  BAM_HIP(rocprim::exclusive_scan(nullptr, tb, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), 0));
+  if (tb > b->cap_scan) {
+    dfree(b->d_scan); b->cap_scan = 0;
+    if (hipMalloc(&b->d_scan, tb) != hipSuccess) { b->d_scan = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam rewrite: hipMalloc failed"); }
+    b->cap_scan = tb;
+  }
+  return TSEM_OK;
+}
+BamRw bam_rw_of(tsem_bam* b, int64_t n) {
+  return BamRw{b->d_rw, b->d_rw + b->cap_rw, b->d_rw + 2 * b->cap_rw, b->d_pos, b->d_pos + n + 1};
+}
+// behind the size kernel: both scans, the positions and the status word to the host
+int bam_rw_scan_fetch(tsem_bam* b, int64_t n, int64_t* pos_other, int64_t* pos_tmp, int64_t* status2) {
+  BamRw W = bam_rw_of(b, n);
+  size_t tb = b->cap_scan;
+  BAM_HIP(rocprim::exclusive_scan(b->d_scan, tb, W.pos_other, W.pos_other, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), 0));
+  tb = b->cap_scan;
+  BAM_HIP(rocprim::exclusive_scan(b->d_scan, tb, W.pos_tmp, W.pos_tmp, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), 0));
+  BAM_HIP(hipEventRecord(b->ev[3], 0));
+  if (pos_other) BAM_HIP(hipMemcpyAsync(pos_other, W.pos_other, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, 0));
+  BAM_HIP(hipMemcpyAsync(pos_tmp, W.pos_tmp, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, 0));
+  BAM_HIP(hipMemcpyAsync(&b->h_status, b->d_status, 8, hipMemcpyDeviceToHost, 0));
+  BAM_HIP(hipEventRecord(b->ev[4], 0));
+  BAM_HIP(hipStreamSynchronize(0));
+  static const int slot[4] = {0, 1, 2, 4};                    // ev[k] .. ev[k + 1]: h2d, plan, size and scan, d2h
+  for (int k = 0; k < 4; ++k) {
+    float ms = 0.f;
+    BAM_HIP(hipEventElapsedTime(&ms, b->ev[k], b->ev[k + 1]));
+    b->rw_ms[slot[k]] += ms;
+  }
+  ++b->rw_calls;
+  if (b->h_status != ~0ull) { status2[0] = (int64_t)(b->h_status & 0xFF); status2[1] = (int64_t)(b->h_status >> 8); return TSEM_OK; }
+  b->sized_n = n; b->total_tmp = pos_tmp[n]; b->total_other = pos_other ? pos_other[n] : 0;
+  return TSEM_OK;
+}
+
+}  // namespace
+
+int tsem_bam_rewrite_size(tsem_bam* b, int64_t* pos_other, int64_t* pos_tmp, int64_t* status2) {
+  if (!b || !pos_other || !pos_tmp || !status2) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_size: NULL pointer");
+  status2[0] = 0; status2[1] = -1;
+  b->sized_n = -1;
+  if (b->chunk_n < 1) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_size: no chunk on the device (tsem_bam_chunk with status 0 comes first)");
+  if (b->n_loci < 0) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_size: no names (tsem_bam_names comes first)");
+  const int64_t n = b->chunk_n;
+  BAM_HIP(hipSetDevice(b->device));
+  if (int rc = bam_rw_reserve(b, n)) return rc;
+  BamCols C{b->d_cols, n};
+  BamRw W = bam_rw_of(b, n);
+  BamNames nm{b->d_names, b->d_name_off, b->n_loci};
+  b->sized_update = false;
+  BAM_HIP(hipEventRecord(b->ev[0], 0));
+  BAM_HIP(hipMemsetAsync(b->d_status, 0xFF, 8, 0));
+  BAM_HIP(hipEventRecord(b->ev[1], 0));
+  k_bam_rw_plan<<<cdiv64(n, 256), 256>>>(n, C, W);
+  BAM_HIP(hipGetLastError());
+  BAM_HIP(hipEventRecord(b->ev[2], 0));
+  k_bam_rw_size<<<cdiv64(n + 1, 256), 256>>>(n, b->d_bytes, b->d_off, C, nm, W, b->d_status);
+  BAM_HIP(hipGetLastError());
+  return bam_rw_scan_fetch(b, n, pos_other, pos_tmp, status2);
+}
+
+int tsem_bam_update_size(tsem_bam* b, const uint8_t* bytes, int64_t n_bytes, const int64_t* rec_off, int64_t n_rec, const uint32_t* words,
+                         int64_t* pos, int64_t* status2) {
+  if (!b) return bam_fail(TSEM_ERR_ARG, "tsem_bam_update_size: NULL handle");
+  if (n_rec < 0 || n_bytes < 0 || n_rec >= (int64_t)INT32_MAX || !rec_off || !status2 || !pos || (n_rec && (!bytes || !words)))
+    return bam_fail(TSEM_ERR_ARG, "tsem_bam_update_size: NULL pointer, negative size or more than 2^31 - 2 records");
+  if (rec_off[0] < 0 || rec_off[n_rec] > n_bytes) return bam_fail(TSEM_ERR_ARG, "tsem_bam_update_size: rec_off leaves the chunk");
+  for (int64_t i = 0; i < n_rec; ++i)
+    if (rec_off[i + 1] - rec_off[i] < 36 || rec_off[i + 1] - rec_off[i] > (int64_t)INT32_MAX)
+      return bam_fail(TSEM_ERR_ARG, "tsem_bam_update_size: record " + std::to_string(i) + " is shorter than 36 bytes or longer than 2^31 - 1 (rec_off must ascend)");
+  status2[0] = 0; status2[1] = -1;
+  b->chunk_n = -1; b->sized_n = -1;
+  pos[0] = 0;
+  if (n_rec == 0) return TSEM_OK;
+  BAM_HIP(hipSetDevice(b->device));
+  const size_t nb = (size_t)rec_off[n_rec];
+  if (nb > b->cap_bytes) {
+    dfree(b->d_bytes); b->cap_bytes = 0;
+    if (hipMalloc((void**)&b->d_bytes, nb + nb / 4) != hipSuccess) { b->d_bytes = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_update_size: hipMalloc(" + std::to_string(nb + nb / 4) + " B) failed"); }
+    b->cap_bytes = nb + nb / 4;
+  }
+  if ((size_t)n_rec > b->cap_rec) {                            // (d_cols is not used here, but one capacity covers both arrays)
+    dfree(b->d_off); dfree(b->d_cols); b->cap_rec = 0;
+    const size_t cr = (size_t)n_rec + (size_t)n_rec / 4;
+    if (hipMalloc((void**)&b->d_off, (cr + 1) * 8) != hipSuccess) { b->d_off = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_update_size: hipMalloc failed"); }
+    if (hipMalloc((void**)&b->d_cols, cr * 4 * TSEM_BAM_COLS) != hipSuccess) { b->d_cols = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_update_size: hipMalloc failed"); }
+    b->cap_rec = cr;
+  }
+  if (int rc = bam_rw_reserve(b, n_rec)) return rc;
+  BamRw W = bam_rw_of(b, n_rec);
+  b->sized_update = true;
+  BAM_HIP(hipEventRecord(b->ev[0], 0));
+  BAM_HIP(hipMemcpyAsync(b->d_bytes, bytes, nb, hipMemcpyHostToDevice, 0));
+  BAM_HIP(hipMemcpyAsync(b->d_off, rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, 0));
+  BAM_HIP(hipMemcpyAsync(b->d_words, words, (size_t)n_rec * 4, hipMemcpyHostToDevice, 0));
+  BAM_HIP(hipMemsetAsync(b->d_status, 0xFF, 8, 0));
+  BAM_HIP(hipEventRecord(b->ev[1], 0));
+  BAM_HIP(hipEventRecord(b->ev[2], 0));
+  k_bam_upd_size<<<cdiv64(n_rec + 1, 256), 256>>>(n_rec, b->d_bytes, b->d_off, b->d_words, W, b->d_status);
+  BAM_HIP(hipGetLastError());
+  return bam_rw_scan_fetch(b, n_rec, nullptr, pos, status2);
+}
+
+int tsem_bam_rewrite_fetch(tsem_bam* b, uint8_t* other, int64_t n_other, uint8_t* tmp, int64_t n_tmp) {
+  if (!b) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_fetch: NULL handle");
+  if (b->sized_n < 1) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_fetch: nothing sized (tsem_bam_rewrite_size or tsem_bam_update_size with status 0 comes first)");
+  if (n_other != b->total_other || n_tmp != b->total_tmp || (n_other && !other) || (n_tmp && !tmp))
+    return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_fetch: the buffers must hold exactly " + std::to_string(b->total_other) + " and " +
+                                  std::to_string(b->total_tmp) + " bytes");
+  const int64_t n = b->sized_n;
+  b->sized_n = -1;
+  BAM_HIP(hipSetDevice(b->device));
+  if ((size_t)n_other > b->cap_other) {
+    dfree(b->d_other); b->cap_other = 0;
+    if (hipMalloc((void**)&b->d_other, (size_t)n_other + (size_t)n_other / 4) != hipSuccess) { b->d_other = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_rewrite_fetch: hipMalloc failed"); }
+    b->cap_other = (size_t)n_other + (size_t)n_other / 4;
+  }
+  if ((size_t)n_tmp > b->cap_tmp) {
+    dfree(b->d_tmp); b->cap_tmp = 0;
+    if (hipMalloc((void**)&b->d_tmp, (size_t)n_tmp + (size_t)n_tmp / 4) != hipSuccess) { b->d_tmp = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_rewrite_fetch: hipMalloc failed"); }
+    b->cap_tmp = (size_t)n_tmp + (size_t)n_tmp / 4;
+  }
+  BamCols C{b->d_cols, n};
+  BamNames nm{b->d_names, b->d_name_off, b->n_loci};
+  BAM_HIP(hipEventRecord(b->ev[0], 0));
+  k_bam_rw_write<<<cdiv64(n, 256), 256>>>(n, b->d_bytes, b->d_off, C, nm, b->d_words, bam_rw_of(b, n), b->d_other, b->d_tmp);
+  BAM_HIP(hipGetLastError());
+  BAM_HIP(hipEventRecord(b->ev[1], 0));
+  if (n_other) BAM_HIP(hipMemcpyAsync(other, b->d_other, (size_t)n_other, hipMemcpyDeviceToHost, 0));
+  if (n_tmp) BAM_HIP(hipMemcpyAsync(tmp, b->d_tmp, (size_t)n_tmp, hipMemcpyDeviceToHost, 0));
+  BAM_HIP(hipEventRecord(b->ev[2], 0));
+  BAM_HIP(hipStreamSynchronize(0));
+  float ms = 0.f;
+  BAM_HIP(hipEventElapsedTime(&ms, b->ev[0], b->ev[1])); b->rw_ms[3] += ms;
+  BAM_HIP(hipEventElapsedTime(&ms, b->ev[1], b->ev[2])); b->rw_ms[4] += ms;
+  return TSEM_OK;
+}
+
+int tsem_bam_rewrite_slots(tsem_bam* b, int32_t* kind, int32_t* pair, int64_t n) {
+  if (!b || !kind || !pair) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_slots: NULL pointer");
+  if (b->sized_n < 1 || n != b->sized_n) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_slots: n is not the slot count of the last size call");
+  BAM_HIP(hipSetDevice(b->device));
+  const BamRw W = bam_rw_of(b, n);
+  BAM_HIP(hipMemcpy(kind, W.kind, (size_t)n * 4, hipMemcpyDeviceToHost));
+  BAM_HIP(hipMemcpy(pair, W.pair, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return TSEM_OK;
+}
+
+int tsem_bam_rewrite_times(tsem_bam* b, int reset, double* ms5, int64_t* calls) {
+  if (!b || !ms5 || !calls) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_times: NULL pointer");
+  for (int k = 0; k < 5; ++k) ms5[k] = b->rw_ms[k];
+  *calls = b->rw_calls;
+  if (reset) { for (double& m : b->rw_ms) m = 0; b->rw_calls = 0; }
   return TSEM_OK;
 }
 

@@ -341,13 +341,26 @@ def score_bundle(alns, assign, no_feature_key):
     return mapped, feats, byfeat, maps
 
 
+def tag_bundle(mapped, byfeat, maps):
+    """model.py:43-61 (ZF / ZT per feature, then ZB), :276-277, on the raw records of a bundle with a feature (score_bundle's values)"""
+    for f, fal in byfeat.items():
+        fal[0].set_tag('ZF', f)
+        fal[0].set_tag('ZT', 'PRI')
+        for a in fal[1:]:
+            a.set_tag('ZF', f)
+            a.set_tag('ZT', 'SEC')
+    top = ','.join(m[1] for m in maps if m[2] == maps[0][2])
+    for a in mapped:
+        a.set_tag('ZB', top)
+
+
 CODE_DESC = OrderedDict([('SU', 'single_unmapped'), ('SM', 'single_mapped'), ('PU', 'pair_unmapped'),
                          ('PM', 'pair_mapped'), ('PX', 'pair_mixed'), ('PX*', 'pair_mixed_unmapped')])
 
 
 def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_mode='threshold',
                    overlap_threshold=0.2, stranded_mode='None', barcode_tag=None, updated_sam=None, umi_tag=None, loader='python',
-                   device=0, chunk_bytes=None, record_cap=4096, inflate='host'):
+                   device=0, chunk_bytes=None, record_cap=4096, inflate='host', rewrite='host'):
     """-> dict(raw_scores uint16 CSR, read_index, feat_index, feature_length, run_info fields).  With `barcode_tag` (scTelescope,
     model.py:245-247,311-316) also cell_of_row (int32 per row, -1 = no barcode) and barcodes (the cell names): the tag is read from
     the first read of every mapped fragment; only fragments that become rows count; cells are ordered by the first appearance of
@@ -359,7 +372,9 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
     (the top-score features, comma-joined) — model.py:30-63, set like pysam's set_tag (the old tag goes, the new one is appended).
     `loader='device'`: the same dict, key by key, from the device loader (loader_device.py: the records are decoded, paired and
     intersected on GPU `device`, in chunks of about `chunk_bytes` inflated bytes, default 64 MiB; a bundle of more than `record_cap`
-    records is left to this module's code); not with `updated_sam`.  `inflate='device'` (with loader='device' only): the file's BGZF
+    records is left to this module's code); with `updated_sam` only under `rewrite='device'`: the records of the two BAMs are then
+    rewritten on the GPU as well (the same files, byte for byte), and loader_device.LAST_TMP_TABLE holds what update_sam needs per
+    record of the tmp BAM.  `inflate='device'` (with loader='device' only): the file's BGZF
     blocks are inflated on the GPU as well (bgzf.py) instead of by gzip on one host core."""
     if overlap_mode != 'threshold':
         raise NotImplementedError('only overlap_mode "threshold" is implemented (as in the reference, '
@@ -368,12 +383,17 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
         raise ValueError("inflate must be 'host' or 'device', not %r" % (inflate,))
     if inflate == 'device' and loader != 'device':
         raise ValueError("inflate='device' needs loader='device'")
+    if rewrite not in ('host', 'device'):
+        raise ValueError("rewrite must be 'host' or 'device', not %r" % (rewrite,))
+    if rewrite == 'device' and not (loader == 'device' and updated_sam):
+        raise ValueError("rewrite='device' needs loader='device' and updated_sam")
     if loader == 'device':
-        if updated_sam:
+        if updated_sam and rewrite != 'device':
             raise ValueError('the device loader does not write the BAMs of --updated_sam')
         from .loader_device import load_alignment_device
         return load_alignment_device(samfile, annotation, no_feature_key, overlap_threshold, stranded_mode, barcode_tag, umi_tag,
-                                     device=device, chunk_bytes=chunk_bytes, record_cap=record_cap, inflate=inflate)
+                                     device=device, chunk_bytes=chunk_bytes, record_cap=record_cap, inflate=inflate,
+                                     updated_sam=updated_sam if rewrite == 'device' else None)
     if loader != 'python':
         raise ValueError("loader must be 'python' or 'device', not %r" % (loader,))
     bam_u = bam_t = None
@@ -425,16 +445,8 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
                 m_row.append(ridx.setdefault(rid, len(ridx)))
                 m_col.append(fidx.setdefault(fid, len(fidx)))
                 m_as.append(ascr); m_len.append(alen)
-            if bam_t is not None:                              # model.py:43-61 (ZF / ZT per feature, then ZB), :276-277
-                for f, fal in byfeat.items():
-                    fal[0].set_tag('ZF', f)
-                    fal[0].set_tag('ZT', 'PRI')
-                    for a in fal[1:]:
-                        a.set_tag('ZF', f)
-                        a.set_tag('ZT', 'SEC')
-                top = ','.join(m[1] for m in maps if m[2] == maps[0][2])
-                for a in mapped:
-                    a.set_tag('ZB', top)
+            if bam_t is not None:
+                tag_bundle(mapped, byfeat, maps)
                 write(bam_t, alns)
     finally:                                               # (a failed load still ends both files with the EOF block)
         if bam_u is not None:

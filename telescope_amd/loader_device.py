@@ -13,15 +13,21 @@
 A bundle the kernels leave to the host (class 5: more records than `record_cap`, a pair that hits more than 8 loci, a value outside
 int32 ...) is decoded with loader.decode_record and run through loader._fragments / assign_pair / score_bundle; its result replaces the
 device's at the same position, which makes the load exact for every input.  LAST_STATS holds the last load's counts and wall times.
+
+With `updated_sam` (`--updated_sam --rewrite device`) the two BAMs of the load are written as well: per chunk three more kernels
+(tsem_bam_rewrite_size / _fetch, telescope_amd/csrc/tsem_bam_edit.h) turn the chunk into the framed record streams of other.bam and
+tmp_tele.bam, the host splices in the records of the bundles it kept (host_bundle(..., streams=True)) and bam_out.BgzfWriter deflates.
 """
 import gzip
 import io
 import logging as lg
+import struct
 from collections import Counter, OrderedDict
 from time import perf_counter
 
 import numpy as np
 
+from . import bam_out
 from . import loader as pyl
 from ._lib import BAM_STATUS, BamLoader, bam_scan
 
@@ -35,6 +41,8 @@ CLS_HOST = 5
 BIT_AS, BIT_NEWNAME, BIT_HOST = 1, 2, 4
 
 LAST_STATS = {}
+LAST_TMP_TABLE = None
+_KIND_OF_SLOT = np.array([0, 0, 0, 2, 1], np.uint8)          # BAM_RW_* (tsem_bam_edit.h) of a tmp slot -> 0 unchanged, 1 SEC, 2 PRI
 
 
 def annotation_arrays(annotation, refs):
@@ -117,12 +125,21 @@ def _record_name(data, off, i):
     return data[o + 36:min(o + 35 + l, e)].decode(errors='replace')
 
 
-def host_bundle(data, off, s, e, btag, utag, assign, no_feature_key):
-    """The Python loader's own code on records [s, e) of a chunk (one bundle): dict(code, cls, min, max, maps, bc, umi)."""
-    segs = [pyl.decode_record(data[int(off[i]) + 4:int(off[i + 1])], btag, utag) for i in range(s, e)]
+def _framed(pairs):
+    recs = [r for p in pairs for r in p.records()]
+    return b''.join(struct.pack('<i', len(r)) + r for r in recs)
+
+
+def host_bundle(data, off, s, e, btag, utag, assign, no_feature_key, streams=False):
+    """The Python loader's own code on records [s, e) of a chunk (one bundle): dict(code, cls, min, max, maps, bc, umi).  `streams`:
+    also what the bundle sends to the BAMs of --updated_sam: other, tmp (framed records) and side = [(kind, ZF | None)] per tmp record
+    (kind 0 unchanged, 1 SEC, 2 PRI)."""
+    segs = [pyl.decode_record(data[int(off[i]) + 4:int(off[i + 1])], btag, utag, raw=streams) for i in range(s, e)]
     (code, alns), = list(pyl._fragments(iter(segs)))
-    r = dict(code=CODES.index(code), cls=0, min=None, max=None, maps=[], bc=None, umi=None)
+    r = dict(code=CODES.index(code), cls=0, min=None, max=None, maps=[], bc=None, umi=None, other=b'', tmp=b'', side=[])
     if code in ('SU', 'PU'):
+        if streams:
+            r['other'], r['n_other'] = _framed(alns[:1]), len(alns[0].records())
         return r
     r['bc'], r['umi'] = alns[0].r1.bc, alns[0].r1.umi
     mapped, _feats, _byfeat, maps = pyl.score_bundle(alns, assign, no_feature_key)
@@ -131,16 +148,30 @@ def host_bundle(data, off, s, e, btag, utag, assign, no_feature_key):
     ambig = len(mapped) > 1
     r['cls'] = (2 if ambig else 1) if maps is None else (4 if ambig else 3)
     r['maps'] = maps or []
+    if streams and maps is None:
+        r['other'], r['n_other'] = _framed(alns), sum(len(p.records()) for p in alns)
+    elif streams:
+        pyl.tag_bundle(mapped, _byfeat, maps)
+        r['tmp'] = _framed(alns)
+        for p in alns:
+            zt = None if p.is_unmapped else bam_out.get_tag(p.r1.raw, 'ZT')
+            r['side'] += [(0, None) if zt is None else (1 if zt == 'SEC' else 2, bam_out.get_tag(p.r1.raw, 'ZF'))] * len(p.records())
     return r
 
 
 def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', overlap_threshold=0.2, stranded_mode='None',
                           barcode_tag=None, umi_tag=None, device=0, chunk_bytes=None, record_cap=4096, max_bundles=None,
-                          on_chunk=None, inflate='host'):
+                          on_chunk=None, inflate='host', updated_sam=None):
     """loader.load_alignment(..., loader='device').  `on_chunk(data, rec_off, out)`: called with every chunk's raw device outputs
     (tests); `max_bundles`: at most so many bundles per device call (tests).  `inflate`: 'host' (Python's gzip) or 'device' (the BGZF
-    blocks are inflated on the GPU, bgzf.py; a gzip file that is not BGZF is still read by gzip: LAST_STATS['inflate'] says which)."""
-    global LAST_STATS
+    blocks are inflated on the GPU, bgzf.py; a gzip file that is not BGZF is still read by gzip: LAST_STATS['inflate'] says which).
+    `updated_sam=(other_bam, tmp_bam)` (rewrite='device'): the two BAMs of the Python loader, byte for byte — per chunk the device
+    rewrites the records into two framed streams (tsem_bam_rewrite_size / _fetch), the records of the bundles left to the host are
+    spliced in at their bundles' offsets, bam_out.BgzfWriter deflates on the host.  LAST_TMP_TABLE then holds, per record of the tmp
+    BAM in order, row (the fragment's row of the matrix, int32), col (the pair's column, int32) and kind (uint8: 0 unchanged, 1 SEC,
+    2 PRI) for Telescope.update_sam; it is not part of the returned dict or of the checkpoint."""
+    global LAST_STATS, LAST_TMP_TABLE
+    LAST_TMP_TABLE = None
     if no_feature_key in annotation.loci:
         raise ValueError('the device loader needs a no_feature_key that is not a locus of the annotation (%r is)' % no_feature_key)
     if inflate not in ('host', 'device'):
@@ -158,13 +189,19 @@ def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', ov
         stats['inflate'] = fh.inflate
     else:
         fh = io.BufferedReader(gzip.open(samfile, 'rb'), buffer_size=1 << 20)
-    dev = None
+    dev = w_other = w_tmp = None
+    side = ([], [], [])                                      # per chunk: pre-trim row, column, kind of every tmp record
     try:
         refs, _text, _block = pyl.read_bam_header(fh, samfile)
         arrs = annotation_arrays(annotation, refs)
         loc_names = arrs[-1]
         loc_id = {n: i for i, n in enumerate(loc_names)}
         dev = BamLoader(device, *arrs[:-1])
+        if updated_sam:
+            dev.names(loc_names + [no_feature_key])
+            header = dict(text=_text.split(b'\x00', 1)[0].decode(), refs_block=_block)
+            w_other, w_tmp = bam_out.BamWriter(updated_sam[0], header), bam_out.BamWriter(updated_sam[1], header)
+            stats.update(records_other=0, records_tmp=0, bytes_other=0, bytes_tmp=0, rewrite_s=0., splice_s=0., deflate_s=0.)
 
         def assign(pair):
             return pyl.assign_pair(pair, annotation, refs, stranded_mode, no_feature_key, overlap_threshold)
@@ -195,7 +232,7 @@ def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', ov
             hosted = {}
             for bi in np.flatnonzero(cls == CLS_HOST):
                 s = int(starts[bi]); e = int(starts[bi + 1]) if bi + 1 < len(starts) else n
-                r = host_bundle(data, off, s, e, btag, utag, assign, no_feature_key)
+                r = host_bundle(data, off, s, e, btag, utag, assign, no_feature_key, streams=w_tmp is not None)
                 hosted[int(bi)] = r
                 code[bi], cls[bi], nmaps[bi], nmapped[bi] = r['code'], r['cls'], len(r['maps']) if r['cls'] >= 3 else 0, 0
                 for k, (_name, f, a, l) in enumerate(r['maps']):
@@ -253,14 +290,64 @@ def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', ov
                 cols.append(col_of[loc + 1].astype(np.int32))
                 m_as.append(out[C_MAS][idx]); m_len.append(out[C_MLEN][idx])
             stats['host_ids_s'] += perf_counter() - t0
+            if w_tmp is not None:
+                # ---- the BAMs of --updated_sam: the device's streams, the hosted bundles' records at their bundles' offsets
+                t0 = perf_counter()
+                pos_o, pos_t, (st, rec) = dev.rewrite_size(n)
+                if st:
+                    raise ValueError('%s: record %d (%s): %s' % (samfile, stats['records'] + rec, _record_name(data, off, rec),
+                                                                BAM_STATUS.get(st, 'status %d' % st)))
+                kind, pslot = dev.rewrite_slots(n)
+                s_other, s_tmp = dev.rewrite_fetch(pos_o[n], pos_t[n])
+                t1 = perf_counter()
+                stats['rewrite_s'] += t1 - t0
+                sel = np.flatnonzero(kind >= 2)
+                rid_of = np.full(len(starts), -1, np.int64)
+                for b, v in rid.items():
+                    rid_of[b] = v
+                t_kind = _KIND_OF_SLOT[kind[sel]]
+                t_row = rid_of[np.searchsorted(starts, out[C_BUNDLE][sel])]
+                t_col = np.where(t_kind > 0, col_of[np.maximum(out[C_PFEAT][np.maximum(pslot[sel], 0)].astype(np.int64), -1) + 1], 0)
+                stats['records_other'] += int(np.count_nonzero(kind == 1)); stats['records_tmp'] += int(sel.size)
+                pieces_o, pieces_t, at_o, at_t = [], [], 0, 0
+                ins = ([], [], [], [])
+                for bi in sorted(hosted):
+                    s, h = int(starts[bi]), hosted[bi]
+                    if h['other']:
+                        pieces_o += [s_other[at_o:int(pos_o[s])], h['other']]; at_o = int(pos_o[s])
+                        stats['records_other'] += h['n_other']
+                    if h['tmp']:
+                        pieces_t += [s_tmp[at_t:int(pos_t[s])], h['tmp']]; at_t = int(pos_t[s])
+                        at = int(np.searchsorted(sel, s))
+                        for k, f in h['side']:
+                            ins[0].append(at); ins[1].append(rid[bi]); ins[2].append(fidx[f] if k else 0); ins[3].append(k)
+                        stats['records_tmp'] += len(h['side'])
+                if ins[0]:
+                    t_row, t_col, t_kind = np.insert(t_row, ins[0], ins[1]), np.insert(t_col, ins[0], ins[2]), np.insert(t_kind, ins[0], ins[3])
+                side[0].append(t_row); side[1].append(t_col); side[2].append(t_kind)
+                t2 = perf_counter()
+                stats['splice_s'] += t2 - t1
+                for p in pieces_o + [s_other[at_o:]]:
+                    w_other.write_framed(p); stats['bytes_other'] += len(p)
+                for p in pieces_t + [s_tmp[at_t:]]:
+                    w_tmp.write_framed(p); stats['bytes_tmp'] += len(p)
+                stats['deflate_s'] += perf_counter() - t2
             stats['records'] += n; stats['bundles'] += len(starts); stats['chunks'] += 1
         stats['kernels_ms'] = dev.times()
+        if w_tmp is not None:
+            stats['rewrite_ms'] = dev.rewrite_times()
         if inflate == 'device':
             stats['inflate_fallbacks'], stats['inflate_blocks'], stats['inflate_ms'] = fh.fallbacks, fh.blocks, fh.times()
     finally:
         fh.close()
         if dev is not None:
             dev.close()
+        if w_other is not None:                              # (a failed load still ends both files with the EOF block)
+            t0 = perf_counter()
+            w_other.close()
+        if w_tmp is not None:
+            w_tmp.close()
+            stats['deflate_s'] += perf_counter() - t0
     t0 = perf_counter()
     info['total_fragments'] = int(n_code.sum())
     for c, k in zip(CODES, n_code.tolist()):
@@ -269,6 +356,11 @@ def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', ov
     cat = lambda xs, t: np.concatenate(xs).astype(t, copy=False) if xs else np.zeros(0, t)
     res = pyl.mappings_to_result(annotation, info, ridx, fidx, cat(rows, np.int64), cat(cols, np.int32), cat(m_as, np.int32),
                                  cat(m_len, np.int32), min_as, max_as, read_bc if barcode_tag else None, read_umi if umi_tag else None)
+    if updated_sam:                                          # the rows of the tmp records: the ids of the trimmed matrix
+        final = np.array([res['read_index'].get(name, -1) for name in ridx], np.int64)
+        row = cat(side[0], np.int64)
+        LAST_TMP_TABLE = dict(row=np.where(row >= 0, final[row] if final.size else -1, -1).astype(np.int32), col=cat(side[1], np.int32),
+                              kind=cat(side[2], np.uint8))
     stats['tail_s'] = perf_counter() - t0
     stats['total_s'] = perf_counter() - t_all
     LAST_STATS = stats

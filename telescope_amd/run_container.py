@@ -131,7 +131,9 @@ class Telescope(object):
         self.run_info['annotated_features'] = len(annotation.loci)
         r = loader.load_alignment(o.samfile, annotation, o.no_feature_key, o.overlap_mode,
                                   o.overlap_threshold, o.stranded_mode, updated_sam=self._updated_sam_paths(),
-                                  loader=getattr(o, 'loader', 'python'), device=getattr(o, 'device', 0), inflate=getattr(o, 'inflate', 'host'))
+                                  loader=getattr(o, 'loader', 'python'), device=getattr(o, 'device', 0), inflate=getattr(o, 'inflate', 'host'),
+                                  rewrite=getattr(o, 'rewrite', 'host'))
+        self._take_tmp_table()
         self.feature_length = r['feature_length']
         self.read_index, self.feat_index = r['read_index'], r['feat_index']
         self.raw_scores = r['raw_scores']
@@ -303,6 +305,8 @@ class Telescope(object):
         asg = tl.reassign(mode, prob)                            # (choose: the draw happens here, as in the reference)
         raw = sp.csr_matrix(self.raw_scores)
         indptr, indices = raw.indptr, raw.indices
+        if getattr(self, 'tmp_table', None) is not None:         # --rewrite device: the load left what every tmp record needs
+            return self._update_sam_device(tl, filename, command_line, asg, indptr, indices, raw.shape[1])
         tiles = tl.entry_tag_tiles(mode, prob, assignment=asg)
         cur = (0, 0, None)                                       # the tile in hand: rows [r0, r1), their words
         back = {}                                                # rows met again behind the tile in hand
@@ -353,6 +357,116 @@ class Telescope(object):
                             out.write(r)
         finally:
             tiles.close()
+
+    def _take_tmp_table(self):
+        """after a load: the device loader's table of the tmp BAM's records (`--rewrite device`), None otherwise"""
+        self.tmp_table = None
+        if getattr(self.opts, 'rewrite', 'host') == 'device':
+            from . import loader_device
+            self.tmp_table = loader_device.LAST_TMP_TABLE
+
+    UPDATE_CHUNK_BYTES = 64 << 20
+    LAST_UPDATE_STATS = {}
+
+    def _update_sam_device(self, tl, filename, command_line, asg, indptr, indices, n_cols):
+        """update_sam with the records rewritten on the GPU (tsem_bam_update_size / tsem_bam_rewrite_fetch): the same file, byte for
+        byte.  The load's table says per tmp record the kind, the row and the column; the tag words of the PRI records are looked up
+        with numpy against the CSR, tile by tile of tl.entry_tag_tiles; the tmp BAM is read in chunks (gzip, or the device inflate
+        under --inflate device), every chunk's records are walked again on the device, rewritten and handed to the BGZF writer.  No
+        per-record Python."""
+        import gzip
+        import io
+        import sys
+        from time import perf_counter
+        from . import bam_out, loader
+        from ._lib import BAM_STATUS, BamLoader, EngineError, bam_scan
+        t_all = perf_counter()
+        stats = dict(records=0, chunks=0, bytes=0, lookup_s=0., read_s=0., device_s=0., deflate_s=0.)
+        mode, prob = self.opts.reassign_mode, self.opts.conf_prob
+        tab = self.tmp_table
+        kind, row, col = tab['kind'], tab['row'].astype(np.int64), tab['col'].astype(np.int64)
+        words = kind.astype(np.uint32) << np.uint32(30)
+        t0 = perf_counter()
+        pri = np.flatnonzero(kind == 2)
+        tiles = tl.entry_tag_tiles(mode, prob, assignment=asg)
+        try:
+            if pri.size:
+                if row[pri].min() < 0 or row[pri].max() >= len(indptr) - 1:
+                    raise AssertionError('update_sam: a row outside the matrix')
+                key_e = np.repeat(np.arange(len(indptr) - 1, dtype=np.int64), np.diff(indptr)) * n_cols + indices
+                key_q = row[pri] * n_cols + col[pri]
+                pos = np.searchsorted(key_e, key_q)
+                ok = pos < key_e.size
+                ok[ok] = key_e[pos[ok]] == key_q[ok]
+                pos = np.where(ok, pos, -1)                      # the entry of (row, column), -1: not stored -> word 0
+                del key_e, key_q
+                for r0, r1, w in tiles:
+                    m = (pos >= indptr[r0]) & (pos < indptr[r1])
+                    words[pri[m]] |= np.asarray(w, dtype=np.uint32)[pos[m] - indptr[r0]]
+        finally:
+            tiles.close()
+        stats['lookup_s'] = perf_counter() - t0
+        device = getattr(self.opts, 'device', 0)
+        if getattr(self.opts, 'inflate', 'host') == 'device':
+            from .bgzf import DeviceBgzfReader
+            fh = DeviceBgzfReader(self.tmp_bam, device=device)
+        else:
+            fh = io.BufferedReader(gzip.open(self.tmp_bam, 'rb'), buffer_size=1 << 20)
+        dev = out = None
+        z = np.zeros(0, np.int64)
+        try:
+            _refs, text, block = loader.read_bam_header(fh, self.tmp_bam)
+            header = dict(text=text.split(b'\x00', 1)[0].decode(), refs_block=block)
+            text = bam_out.header_with_pg(header['text'], self.run_info.get('version', getattr(self.opts, 'version', '')),
+                                          ' '.join(sys.argv) if command_line is None else command_line)
+            out = bam_out.BamWriter(filename, header, text)
+            dev = BamLoader(device, z, z, z, z, z, z, z)
+            done, tail = 0, b''
+            while True:
+                t0 = perf_counter()
+                new = fh.read(self.UPDATE_CHUNK_BYTES)
+                data = tail + new if tail else new
+                try:
+                    off, used = bam_scan(data)
+                except EngineError as e:
+                    raise ValueError('%s: behind record %d: %s' % (self.tmp_bam, done, e))
+                n = len(off) - 1
+                t1 = perf_counter()
+                stats['read_s'] += t1 - t0
+                if done + n > len(words):
+                    raise ValueError('%s holds more records than the %d the load wrote' % (self.tmp_bam, len(words)))
+                if n:
+                    pos, (st, rec) = dev.update_size(data[:used], off, words[done:done + n])
+                    if st:
+                        o = int(off[rec])
+                        name = bytes(data[o + 36:min(o + 35 + data[o + 12], int(off[rec + 1]))]).decode(errors='replace')
+                        raise ValueError('%s: record %d (%s): %s' % (self.tmp_bam, done + rec, name, BAM_STATUS.get(st, 'status %d' % st)))
+                    _, stream = dev.rewrite_fetch(0, pos[n])
+                    t2 = perf_counter()
+                    stats['device_s'] += t2 - t1
+                    out.write_framed(stream)
+                    stats['deflate_s'] += perf_counter() - t2
+                    stats['bytes'] += int(pos[n])
+                done += n; stats['chunks'] += 1
+                tail = data[used:]
+                if not new:
+                    break
+            if tail:
+                raise ValueError('%s: truncated BAM record behind record %d' % (self.tmp_bam, done))
+            if done != len(words):
+                raise ValueError('%s holds %d records, the load wrote %d' % (self.tmp_bam, done, len(words)))
+            stats['records'] = done
+            stats['kernels_ms'] = dev.rewrite_times()
+        finally:
+            fh.close()
+            if dev is not None:
+                dev.close()
+            if out is not None:
+                t0 = perf_counter()
+                out.close()
+                stats['deflate_s'] += perf_counter() - t0
+        stats['total_s'] = perf_counter() - t_all
+        Telescope.LAST_UPDATE_STATS = stats
 
 
 # ---- single-cell mode (scTelescope, model.py:567-629) -----------------------------------------------------------------------------
@@ -472,7 +586,9 @@ class scTelescope(Telescope):
         self.run_info['annotated_features'] = len(annotation.loci)
         r = loader.load_alignment(o.samfile, annotation, o.no_feature_key, o.overlap_mode, o.overlap_threshold, o.stranded_mode,
                                   barcode_tag=o.barcode_tag, updated_sam=self._updated_sam_paths(), umi_tag=getattr(o, 'umi_tag', None),
-                                  loader=getattr(o, 'loader', 'python'), device=getattr(o, 'device', 0), inflate=getattr(o, 'inflate', 'host'))
+                                  loader=getattr(o, 'loader', 'python'), device=getattr(o, 'device', 0), inflate=getattr(o, 'inflate', 'host'),
+                                  rewrite=getattr(o, 'rewrite', 'host'))
+        self._take_tmp_table()
         self.feature_length = r['feature_length']
         self.read_index, self.feat_index = r['read_index'], r['feat_index']
         self.raw_scores = r['raw_scores']

@@ -118,6 +118,9 @@ int  tsem_set_stream(tsem_ctx* h, void* hip_stream); /* launch on this hipStream
  *   "boot_hot_columns", "boot_batch"  tsem_bootstrap (below): how many of the most popular columns get workgroup-private LDS accumulators
  *                  (-1, default: as many as 32 KiB of LDS hold for the batch, 4096 / batch; 0 none: every sum is a global fp64 atomic;
  *                  at most 5120 / batch) and how many replicates share one sweep over the matrix (0, default: 8, the most)
+ *   "boot_rows_per_block"  tsem_bootstrap (below): a test and timing hook.  0 (default): every workgroup of the sweeps takes
+ *                  max(32, ceil(rows / (4 x compute units)) rounded up to 32) rows.  n > 0: n rounded up to a multiple of 32 instead.
+ *                  Negative values are rejected.  The results do not depend on it beyond the order of the fp64 atomics.
  *   "boot_group_bytes"  tsem_bootstrap_groups (below): bytes of the per-batch accumulators of the (group, column) pattern at most; the
  *                  batch is lowered to fit.  0 (default): what is free.  Negative values are rejected.
  *   "cell_em_spread_entries"  tsem_cell_em (below): a group of the map with MORE stored entries than this is not fitted by one workgroup

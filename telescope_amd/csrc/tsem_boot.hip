@@ -622,6 +622,8 @@ int bt_run(tsem_ctx* h, int32_t n_rep, uint64_t seed, const uint8_t* mult, int32
   // a contiguous range of rows per workgroup (its LDS accumulators are flushed once), four workgroups per CU
   const int rows_at_once = BT_T / BT_W;
   A.rows_per_block = std::max<int64_t>(rows_at_once, ((N + 4ll * h->n_cu - 1) / (4ll * h->n_cu) + rows_at_once - 1) / rows_at_once * rows_at_once);
+  if (h->opt_boot_rows > 0)                                  // option "boot_rows_per_block": a test and timing hook
+    A.rows_per_block = (std::min<int64_t>(h->opt_boot_rows, 1ll << 40) + rows_at_once - 1) / rows_at_once * rows_at_once;
   const int grid = cdiv64(N, A.rows_per_block);
   double2 *tab = t_tab.as<double2>(), *prev = t_prev.as<double2>();
   for (int rep0 = 0; rep0 < n_rep; rep0 += R) {

@@ -248,6 +248,7 @@ struct tsem_ctx {
   // bootstrap replicates (tsem_bootstrap, tsem_boot.hip): the last call's results, replicate-major
   int64_t opt_boot_hot = -1;        // option "boot_hot_columns": columns with LDS accumulators; -1 auto (the LDS budget), 0 none
   int64_t opt_boot_batch = 0;       // option "boot_batch": replicates per sweep over the matrix; 0 auto (8)
+  int64_t opt_boot_rows = 0;        // option "boot_rows_per_block": rows per workgroup of the sweeps, rounded up to 32; 0 the formula
   double *d_bt_pi = nullptr, *d_bt_theta = nullptr, *d_bt_counts = nullptr;   // [bt_nrep x K]
   double* d_bt_lnl = nullptr;       // [bt_nrep]
   unsigned long long* d_bt_nfrags = nullptr;   // [bt_nrep] sum of the multiplicities

@@ -233,6 +233,10 @@ int tsem_set_option(tsem_ctx* h, const char* key, int64_t v) {
     if (v < 0) TSEM_FAIL(TSEM_ERR_ARG, "boot_group_bytes must be 0 (auto: what is free) or a number of bytes");
     h->opt_boot_group = v;
   }
+  else if (k == "boot_rows_per_block") {                   // tsem_bootstrap: rows per workgroup of the sweeps (0 the formula); a test and timing hook
+    if (v < 0) TSEM_FAIL(TSEM_ERR_ARG, "boot_rows_per_block must be 0 (the formula) or a number of rows");
+    h->opt_boot_rows = v;
+  }
   else if (k == "cell_em_spread_entries") {                // tsem_cell_em: groups with more stored entries are spread over the grid (0 never)
     if (v < 0) TSEM_FAIL(TSEM_ERR_ARG, "cell_em_spread_entries must be 0 (never spread) or a number of stored entries");
     h->opt_ce_spread = v;

@@ -747,6 +747,15 @@ int  tsem_debug_fused_startup(tsem_ctx* h, uint64_t* out4096);
 /* the local row << 16 | local column words of one sub-block of the blocked layout (layout studies); a layout that stores the 3-byte
  * index (tsem_layout_info_n [32] == 3) is decoded on the host: the same words either way */
 int64_t tsem_debug_subblock(tsem_ctx* h, int64_t block, int32_t part, uint32_t* out, int64_t cap);
+/* the fp64 values of the same sub-block in the same (entry) order: out[e] belongs to word e of tsem_debug_subblock, wherever the layout
+ * keeps it (a layout the fused kernel reads groups a sub-block's values by wave; the host applies the map the fill kernels used).
+ * rows / cols (each may be null): the CSR row and the column that word e names (-1: an empty row slot; every slot of a hot column names it); the
+ * padding of a sub-block has value 0.  TSEM_ERR_ARG on a layout of score codes; returns the number of values */
+int64_t tsem_debug_subblock_values(tsem_ctx* h, int64_t block, int32_t part, double* out, int32_t* rows, int32_t* cols, int64_t cap);
+/* host only, no device: pos[e] = the index (in doubles from the sub-block's first value) at which a layout read by the fused kernel
+ * keeps the value of entry e of a sub-block of nq quads (nq a multiple of 16), e = 0 .. 4 nq - 1, by the inline function the fill
+ * kernels and the read-back use */
+int  tsem_debug_valmap(int32_t nq, uint32_t* pos);
 /* host only, no device: four local row << 16 | local column words (rows < 2048, columns < 8192; TSEM_ERR_ARG otherwise) packed into
  * the 12 bytes of a quad of the 3-byte index — entry k is the 24-bit little-endian number row << 13 | column at bytes 3k .. 3k+2 —
  * and unpacked again into back4, both with the inline functions the fill kernels and the fused kernel use */

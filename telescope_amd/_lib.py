@@ -271,12 +271,15 @@ def lib():
     L.tsem_debug_stream_read.argtypes = [C.c_int, i64, i32, C.POINTER(dbl)]
     L.tsem_debug_subblock.argtypes = [vp, C.c_int64, C.c_int32, vp, C.c_int64]
     L.tsem_debug_idx24.argtypes = [vp, vp, vp]
+    L.tsem_debug_subblock_values.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int64]
+    L.tsem_debug_valmap.argtypes = [C.c_int32, vp]
     for name in exported_symbols():
         fn = getattr(L, name)
         if name not in ('tsem_destroy', 'tsem_last_error', 'tsem_comm_destroy', 'tsem_comm_last_error',
-                        'tsem_debug_subblock', 'tsem_comm_local_group_destroy'):
+                        'tsem_debug_subblock', 'tsem_debug_subblock_values', 'tsem_comm_local_group_destroy'):
             fn.restype = C.c_int
     L.tsem_debug_subblock.restype = C.c_int64
+    L.tsem_debug_subblock_values.restype = C.c_int64
     _lib = L
     return L
 
@@ -775,6 +778,15 @@ class Engine(object):
         if n < 0:
             raise EngineError('tsem_debug_subblock failed (%d)' % n)
         return out[:n]
+
+    def debug_subblock_values(self, block, part, cap=8192):
+        """(values, rows, cols) of a sub-block in entry order: entry e is word e of `debug_subblock`; rows / cols are the CSR row
+        and the column its word names.  Padding has value 0."""
+        out, rows, cols = np.zeros(cap, np.float64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        n = self._L.tsem_debug_subblock_values(self._h, int(block), int(part), ptr(out), ptr(rows), ptr(cols), cap)
+        if n < 0:
+            raise EngineError('tsem_debug_subblock_values failed (%d)' % n)
+        return out[:n], rows[:n], cols[:n]
 
     def layout_info(self):
         info = np.zeros(40, np.int64)

@@ -178,6 +178,7 @@ struct tsem_ctx {
   int n_hot_cols = 0;               // columns that were split
   int64_t opt_format = 0;           // 0 auto (codes when the fused kernel runs and the table fits LDS), 1 fp64, 2 codes
   uint32_t* d_prc = nullptr;        // [nnz_pad]  lrow<<16 | lcol — or, idx24, 3 bytes per entry (tsem_idx24.h)
+  bool valmap = false;              // d_pval holds every sub-block's values grouped by wave (tsem_valmap.h): fused kernel, fp64 entries (set by every layout build)
   bool idx24 = false;               // d_prc holds the 3-byte packed index: fused kernel, non-split layout, fp64 entries (set by every layout build)
   double* d_ypart = nullptr;        // [P][N_amb_pad] partial row sums
   int G1 = 1, G2 = 1, T1 = 512, T2 = 1024;

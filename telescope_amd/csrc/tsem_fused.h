@@ -37,6 +37,7 @@
 // time; every wait is bounded and reports through an error word.
 #pragma once
 #include "tsem_idx24.h"
+#include "tsem_valmap.h"
 
 constexpr int FZ_NT = 1024;            // threads per workgroup
 // Geometry (GEO): the exchange waves keep (P-1) partner values per row pair in registers, so larger
@@ -774,6 +775,8 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
     // ============================== data waves ================================
     // Loads of block k: resources rebased to the sub-block, so thread t reads quad t at a constant
     // offset and every lane past the sub-block's end (or a whole step past the last block) reads zeros.
+    const uint32_t wq0 = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6) * (uint32_t)TS_VALMAP_GROUP;   // first quad of this wave's group
+    const unsigned vlane16 = (unsigned)(tid & 63) * 16;
     auto load_blk = [&](FzRegs& rr, uint32_t oq0v, uint32_t oq1v, int64_t k) {
       const uint32_t oq0 = __builtin_amdgcn_readfirstlane(oq0v);
       const uint32_t nq = (k >= 0 && k < nblk) ? __builtin_amdgcn_readfirstlane(oq1v) - oq0 : 0u;
@@ -788,9 +791,17 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
         fz_u32x2 cd = __builtin_amdgcn_raw_buffer_load_b64(fz_rsrc(A.pcode, (uint64_t)oq0 * 8, nq * 8), (unsigned)tid * 8, 0, FZ_STREAM);
         rr.cd = make_uint2(cd.x, cd.y);
       } else {
-        __amdgpu_buffer_rsrc_t vr = fz_rsrc(A.pval, (uint64_t)oq0 * 32, nq * 32);
-        rr.v0 = fz_as_double2(__builtin_amdgcn_raw_buffer_load_b128(vr, (unsigned)tid * 32, 0, FZ_STREAM));
-        rr.v1 = fz_as_double2(__builtin_amdgcn_raw_buffer_load_b128(vr, (unsigned)tid * 32 + 16, 0, FZ_STREAM));
+        // The values are grouped by wave (tsem_valmap.h): this wave's gq quads keep their first value pairs in gq * 16 contiguous
+        // bytes and their second pairs in the gq * 16 behind them, so each of the two loads takes whole 128-byte lines (entry by
+        // entry, each spanned 2 KB and used half of every line).  Both resources are rebased to the wave's group and end with the
+        // group's first pairs: a lane past the sub-block's end reads zeros from both, and the offset is the same lane * 16 in both.
+        // gq is scalar arithmetic on nq (a wave behind the sub-block's end, or a step without a block: 0, two empty resources).
+        // (two scalar minima and a subtraction.  Written as a clamped difference, the compiler picks v_sub_u32 ... clamp or v_med3_i32,
+        // which have no scalar form: gq lands in a VGPR and the loads in a loop over its distinct values.)
+        const uint32_t gq = min(nq, wq0 + (uint32_t)TS_VALMAP_GROUP) - min(nq, wq0);
+        const uint64_t vbase = (uint64_t)(oq0 + wq0) * 32;
+        rr.v0 = fz_as_double2(__builtin_amdgcn_raw_buffer_load_b128(fz_rsrc(A.pval, vbase, gq * 16), vlane16, 0, FZ_STREAM));
+        rr.v1 = fz_as_double2(__builtin_amdgcn_raw_buffer_load_b128(fz_rsrc(A.pval, vbase + gq * 16, gq * 16), vlane16, 0, FZ_STREAM));
       }
     };
     // phase 1: numerators n = Q * (pi*theta) kept in the registers, partial row sums into y(k).

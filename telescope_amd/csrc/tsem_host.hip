@@ -708,6 +708,46 @@ int64_t tsem_debug_subblock(tsem_ctx* h, int64_t block, int32_t part, uint32_t* 
   return n;
 }
 
+/* debug: the fp64 values of sub-block (block, part) in entry order, through the value map where the layout uses it (tsem_valmap.h),
+ * and the CSR row / column each entry's index word names */
+int64_t tsem_debug_subblock_values(tsem_ctx* h, int64_t block, int32_t part, double* out, int32_t* rows, int32_t* cols, int64_t cap) {
+  if (!h || !h->d_pval || !h->d_sb_off || !out || block < 0 || block >= h->nb || part < 0 || part >= h->P) return TSEM_ERR_ARG;
+  if ((rows && !h->d_slot_row) || (cols && !h->d_col_of_pc)) return TSEM_ERR_ARG;
+  int64_t o[2];
+  if (hipMemcpy(o, h->d_sb_off + block * h->P + part, 16, hipMemcpyDeviceToHost) != hipSuccess) return TSEM_ERR_HIP;
+  const int64_t len = o[1] - o[0], n = std::min(cap, len);
+  std::vector<double> raw((size_t)std::max<int64_t>(1, len));   // (the whole sub-block: a mapped value may lie behind position n)
+  if (len > 0 && hipMemcpy(raw.data(), h->d_pval + o[0], sizeof(double) * (size_t)len, hipMemcpyDeviceToHost) != hipSuccess) return TSEM_ERR_HIP;
+  for (int64_t e = 0; e < n; ++e) out[e] = raw[ts_valmap_slot((uint32_t)e, (uint32_t)(len >> 2), h->valmap ? 1 : 0)];
+  if (rows || cols) {
+    std::vector<uint32_t> w((size_t)std::max<int64_t>(1, n));
+    std::vector<int32_t> slot_row((size_t)h->R), col_of((size_t)h->Kp);
+    const int64_t got = tsem_debug_subblock(h, block, part, w.data(), n);
+    if (got != n) return got < 0 ? got : TSEM_ERR_HIP;
+    if (hipMemcpy(slot_row.data(), h->d_slot_row + block * h->R, sizeof(int32_t) * (size_t)h->R, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(col_of.data(), h->d_col_of_pc + (int64_t)part * h->Kp, sizeof(int32_t) * (size_t)h->Kp, hipMemcpyDeviceToHost) != hipSuccess)
+      return TSEM_ERR_HIP;
+    for (int64_t e = 0; e < n; ++e) {
+      const uint32_t lr = w[e] >> 16, lc = w[e] & 0xFFFFu;
+      if (lr >= (uint32_t)h->R || lc >= (uint32_t)h->Kp) return TSEM_ERR_ARG;
+      if (rows) rows[e] = slot_row[lr];
+      if (cols) {                                          // (a hot column is dealt over several slots: the first one owns it, the others hold -1)
+        uint32_t c = lc;
+        while (c > 0 && col_of[c] < 0) --c;
+        cols[e] = col_of[c];
+      }
+    }
+  }
+  return n;
+}
+
+/* host only: the value map of a sub-block of nq quads, entry by entry */
+int tsem_debug_valmap(int32_t nq, uint32_t* pos) {
+  if (nq < 0 || (nq & 15) || !pos) return TSEM_ERR_ARG;
+  for (uint32_t e = 0; e < 4u * (uint32_t)nq; ++e) pos[e] = ts_valmap_pos(e, (uint32_t)nq);
+  return TSEM_OK;
+}
+
 /* host only: four lrow << 16 | lcol words through the packed 3-byte index of tsem_idx24.h — the 12 bytes of the quad, and the words
  * unpacked from them again (rows < 2048, columns < 8192) */
 int tsem_debug_idx24(const uint32_t* rc4, uint8_t* out12, uint32_t* back4) {

@@ -394,7 +394,8 @@ __device__ __forceinline__ void sb_store_index(uint32_t* __restrict__ prc, int64
 __global__ __launch_bounds__(256) void k_sb_fill(int64_t N_amb, int R, int P, const int32_t* __restrict__ amb_row,
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, const uint16_t* __restrict__ raw,
     const double* __restrict__ lut, const uint32_t* __restrict__ colmap, const int64_t* __restrict__ sb_off,
-    double* __restrict__ pval, uint16_t* __restrict__ pcode, uint32_t* __restrict__ prc, int idx24) {
+    double* __restrict__ pval, uint16_t* __restrict__ pcode, uint32_t* __restrict__ prc, int idx24,
+    int valmap /* fp64 values at their slot of tsem_valmap.h */) {
   __shared__ uint32_t cur[64];
   if (threadIdx.x < 64) cur[threadIdx.x] = 0;
   __syncthreads();
@@ -416,7 +417,7 @@ __global__ __launch_bounds__(256) void k_sb_fill(int64_t N_amb, int R, int P, co
       const uint32_t t = atomicAdd(&cur[p], 1u);
       int64_t pos = base + (int64_t)(t % TS_STRANDS) * L + t / TS_STRANDS;
       if (pcode) pcode[pos] = raw[k];
-      else pval[pos] = lut[raw[k]];
+      else pval[base + ts_valmap_slot((uint32_t)(pos - base), L * (TS_STRANDS / 4), valmap)] = lut[raw[k]];
       sb_store_index(prc, pos, (uint32_t)lr, (cm & CM_SM) + (t & ((1u << ((cm >> CM_LS) & 7u)) - 1u)), idx24);   // hot column: deal over its slots
     }
   }
@@ -440,13 +441,14 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
     const int64_t* __restrict__ bstart, const unsigned long long* __restrict__ pc,
     const uint16_t* __restrict__ rid /* popularity ids (slot * P + part) instead of the column-map gather, or null */,
     uint32_t magicP /* ceil(2^32 / P) */, int nsplit /* ids below this may be split columns */, const uint8_t* __restrict__ lgtab,
-    int idx24 /* store the 3-byte packed index (sb_store_index) */) {
+    int idx24 /* store the 3-byte packed index (sb_store_index) */, int valmap /* fp64 values at their slot of tsem_valmap.h */) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fl_lds[];
   uint32_t* const cnt = reinterpret_cast<uint32_t*>(fl_lds);                   // [row slot][part]: counts, then write cursors
   int64_t* const rstart = reinterpret_cast<int64_t*>(cnt + ((R * P + 1) & ~1));   // [row slot] first entry of the row in the CSR
   int32_t* const rlen = reinterpret_cast<int32_t*>(rstart + R);                // [row slot] its length (0: empty slot)
   __shared__ uint32_t total[8], lastrow[8];
   __shared__ int64_t sbase[8];
+  __shared__ uint32_t snq[8];                              // quads of the sub-block (tsem_valmap.h)
   const int64_t b = blockIdx.x;
   const int sub = threadIdx.x / RS_SUB, lane = threadIdx.x % RS_SUB, subs = blockDim.x / RS_SUB;
   for (int t = threadIdx.x; t < R * P; t += blockDim.x) cnt[t] = 0;
@@ -455,7 +457,10 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
     const int64_t s0 = i >= 0 ? indptr[i] : 0;
     rstart[lr] = s0; rlen[lr] = i >= 0 ? (int32_t)(indptr[i + 1] - s0) : 0;
   }
-  if (threadIdx.x < P) sbase[threadIdx.x] = sb_off[b * P + threadIdx.x];
+  if (threadIdx.x < P) {
+    sbase[threadIdx.x] = sb_off[b * P + threadIdx.x];
+    snq[threadIdx.x] = (uint32_t)((sb_off[b * P + threadIdx.x + 1] - sb_off[b * P + threadIdx.x]) >> 2);
+  }
   __syncthreads();
   if (pc) {                                                // the per-row part counts are already known
     const int64_t a0 = bstart[b], n = bstart[b + 1] - a0;
@@ -527,7 +532,7 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
       t += cnt[lr * P + p];
       const int64_t pos = sbase[p] + t;
       if (pcode) pcode[pos] = (uint16_t)code;
-      else pval[pos] = lut[code];
+      else pval[sbase[p] + ts_valmap_slot(t, snq[p], valmap)] = lut[code];
       sb_store_index(prc, pos, (uint32_t)lr, (cm & CM_SM) + (t & ((1u << ((cm >> CM_LS) & 7u)) - 1u)), idx24);   // hot column: deal over its slots
     }
   };
@@ -577,7 +582,7 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
     const int64_t base = sbase[p], end = sb_off[b * P + p + 1];
     for (int64_t pos = base + total[p] + threadIdx.x; pos < end; pos += blockDim.x) {
       sb_store_index(prc, pos, lastrow[p], 0u, idx24);
-      if (pcode) pcode[pos] = (uint16_t)0; else pval[pos] = 0.0;
+      if (pcode) pcode[pos] = (uint16_t)0; else pval[base + ts_valmap_slot((uint32_t)(pos - base), snq[p], valmap)] = 0.0;
     }
   }
 }
@@ -1154,7 +1159,7 @@ static int layout_identity_map(tsem_ctx* h) {
   TSEM_HIP(hipMemcpy(h->d_col_of_pc, cpc.data(), sizeof(int32_t) * h->Kpad, hipMemcpyHostToDevice));
   h->nb = 0; h->N_amb_pad = 1; h->nnz_pad = 0; h->max_subblock = 0; h->n_hot_cols = 0;
   h->nnz_amb = h->nnz - h->N_uni;
-  h->fmt_code = h->fmt_wcode = false; h->sorted_layout = false; h->idx24 = false;
+  h->fmt_code = h->fmt_wcode = false; h->sorted_layout = false; h->idx24 = false; h->valmap = false;
   h->G1 = h->G2 = 1;
   return TSEM_OK;
 }
@@ -1379,6 +1384,9 @@ static int layout_decide_format(tsem_ctx* h) {
   // fp64 entries under the fused kernel, non-split: 3 B of index per entry (the instantiations of fz_idx24(), tsem_fused.h).  Decided
   // HERE for every build of the layout, the rebuild of the two-pass fall-back included (use_fused is false then: 4 B again).
   h->idx24 = h->use_fused && !h->split && !h->fmt_code;
+  // ... and their values grouped by wave (tsem_valmap.h) wherever the fused kernel's load_blk reads fp64 entries: FMT 0 and 2, every
+  // geometry, the split layout's passes too.  The two-pass kernels read the values entry by entry: their rebuild clears it.
+  h->valmap = h->use_fused && !h->fmt_code;
   // Row order (row sums reduced in registers, a tenth of the LDS atomics) for every fused layout.  Score codes: 40
   // entries per row at P = 4 4.44 -> 3.59 ms, 20 per row 2.30 -> 1.92, 10 per row 1.65 -> 1.40.  fp64 entries
   // were indifferent to it while the exchange wave stalled behind the memory pipe (round 1: 4.62 against 4.57 ms);
@@ -1437,7 +1445,8 @@ static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
     const uint32_t magicP = (uint32_t)((0x100000000ull + (uint64_t)P - 1) / (uint64_t)P);
     k_sb_fill_sorted<<<(unsigned)nb, 256, fill_lds_bytes(R, P), h->stream>>>(na, R, P, h->d_slot_row, h->d_indptr, h->d_indices, h->d_raw, h->d_lut,
                                                          h->d_colmap, h->d_sb_off, h->d_pval, h->d_pcode, h->d_prc,
-                                                         b.d_pc ? b.d_bs : nullptr, b.d_pc, rid_fill, magicP, nsplit, d_lgtab, h->idx24 ? 1 : 0);
+                                                         b.d_pc ? b.d_bs : nullptr, b.d_pc, rid_fill, magicP, nsplit, d_lgtab, h->idx24 ? 1 : 0,
+                                                         h->valmap ? 1 : 0);
     TSEM_HIP(hipGetLastError());
     if (deconflict) {
       const int64_t n_win = off / 64;
@@ -1456,7 +1465,7 @@ static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
     if (rid_fill && h->d_col_of_id && drops_indices(h)) dfree(h->d_indices);
   } else if (nb) {
     k_sb_fill<<<(unsigned)nb, 256, 0, h->stream>>>(na, R, P, h->d_slot_row, h->d_indptr, h->d_indices, h->d_raw, h->d_lut,
-                                                  h->d_colmap, h->d_sb_off, h->d_pval, h->d_pcode, h->d_prc, h->idx24 ? 1 : 0);
+                                                  h->d_colmap, h->d_sb_off, h->d_pval, h->d_pcode, h->d_prc, h->idx24 ? 1 : 0, h->valmap ? 1 : 0);
     TSEM_HIP(hipGetLastError());
   }
   TSEM_HIP(hipStreamSynchronize(h->stream));

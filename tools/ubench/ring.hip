@@ -20,7 +20,9 @@ __device__ __forceinline__ void lds_add(double* p, double v) { __hip_atomic_fetc
 
 template <int Q> struct Set { uint4 rc[Q]; double2 v0[Q], v1[Q]; };
 
-template <int NT, int Q, int NS, int DL, int LAG>
+// VT 1: the values of a wave's 64 quads grouped (first value pairs of all 64, then the second pairs: each 16-byte load of a wave takes
+// 1 KB of whole lines) instead of quad by quad (each load spans 2 KB and uses half of every line) — tsem_valmap.h
+template <int NT, int Q, int NS, int DL, int LAG, int VT = 0>
 __global__ __launch_bounds__(NT) void k_ring(const uint32_t* __restrict__ rc, const double* __restrict__ val,
                                              int64_t nblocks, int R, int Kp, double* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -43,8 +45,14 @@ __global__ __launch_bounds__(NT) void k_ring(const uint32_t* __restrict__ rc, co
     for (int i = 0; i < Q; ++i) {
       int64_t q = q0 + (int64_t)i * NT + tid;
       st.rc[i] = reinterpret_cast<const uint4*>(rc)[q];
+      if (VT) {
+        const int64_t g2 = 2 * (q & ~(int64_t)63) + (q & 63);   // the wave's group starts at double2 index 2 * (q & ~63)
+        st.v0[i] = reinterpret_cast<const double2*>(val)[g2];
+        st.v1[i] = reinterpret_cast<const double2*>(val)[g2 + 64];
+      } else {
       st.v0[i] = reinterpret_cast<const double2*>(val)[2 * q];
       st.v1[i] = reinterpret_cast<const double2*>(val)[2 * q + 1];
+      }
     }
   };
   auto p1 = [&](Set<Q>& st, int64_t k) {
@@ -88,22 +96,22 @@ __global__ __launch_bounds__(NT) void k_ring(const uint32_t* __restrict__ rc, co
   if (t == 123.456) out[0] = t;
 }
 
-template <int NT, int Q, int NS, int DL, int LAG>
+template <int NT, int Q, int NS, int DL, int LAG, int VT = 0>
 void run(const uint32_t* rc, const double* val, int64_t n, int R, int Kp, double* out, int grid) {
   static_assert((DL + LAG) % NS == 0 || DL + LAG < NS, "ring too small");
   const int BLK = NT * Q * 4;
   int64_t nblocks = n / BLK;
   size_t lds = (size_t)(2 * Kp + 5 * R) * 8;
-  CK(hipFuncSetAttribute((const void*)k_ring<NT, Q, NS, DL, LAG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+  CK(hipFuncSetAttribute((const void*)k_ring<NT, Q, NS, DL, LAG, VT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
   hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
-  k_ring<NT, Q, NS, DL, LAG><<<grid, NT, lds>>>(rc, val, nblocks, R, Kp, out);
+  k_ring<NT, Q, NS, DL, LAG, VT><<<grid, NT, lds>>>(rc, val, nblocks, R, Kp, out);
   CK(hipDeviceSynchronize());
   CK(hipEventRecord(a));
-  for (int r = 0; r < 3; ++r) k_ring<NT, Q, NS, DL, LAG><<<grid, NT, lds>>>(rc, val, nblocks, R, Kp, out);
+  for (int r = 0; r < 3; ++r) k_ring<NT, Q, NS, DL, LAG, VT><<<grid, NT, lds>>>(rc, val, nblocks, R, Kp, out);
   CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
   float ms; CK(hipEventElapsedTime(&ms, a, b)); ms /= 3;
   double bytes = 12.0 * nblocks * BLK;
-  printf("NT=%4d Q=%d NS=%d DL=%d LAG=%d blk=%5d  %7.3f ms  %7.1f GB/s  %6.1f Gnnz/s\n", NT, Q, NS, DL, LAG, BLK, ms,
+  printf("NT=%4d Q=%d NS=%d DL=%d LAG=%d VT=%d blk=%5d  %7.3f ms  %7.1f GB/s  %6.1f Gnnz/s\n", NT, Q, NS, DL, LAG, VT, BLK, ms,
          bytes / ms * 1e-6, bytes / 12 / ms * 1e-6);
   fflush(stdout);
 }
@@ -124,6 +132,8 @@ int main() {
     run<896, 1, 6, 2, 4>(rc, val, n, R, Kp, out, G);
     run<896, 1, 7, 2, 5>(rc, val, n, R, Kp, out, G);
     run<1024, 1, 6, 2, 4>(rc, val, n, R, Kp, out, G);
+    run<896, 1, 6, 2, 4, 1>(rc, val, n, R, Kp, out, G);
+    run<1024, 1, 6, 2, 4, 1>(rc, val, n, R, Kp, out, G);
   }
   return 0;
 }

@@ -79,10 +79,6 @@ struct BtArgs {
   double* gacc;                    // [slots x R]
 };
 
-__device__ __forceinline__ double bt_recip0(double v) {    // sparse_plus.py:16-22
-  const double r = 1.0 / v;
-  return isinf(r) ? 0.0 : r;
-}
 __device__ __forceinline__ uint32_t bt_draw(const BtDraw& D, int64_t row, int rep) {
   const uint32_t hsh = (uint32_t)(ts_hash3(D.seed, (uint64_t)(D.row_offset + row), (uint64_t)rep) >> 32);
   uint32_t m = 0;
@@ -169,11 +165,11 @@ __global__ __launch_bounds__(BT_T) void k_boot_sweep(BtArgs A) {
         const double2* t = A.tab + (int64_t)A.indices[e] * R;
 #pragma unroll
         for (int r = 0; r < BT_RMAX; ++r)
-          if (r < R && ((mm >> (8 * r)) & 0xFFu)) { const double2 cp = t[r]; s[r] += qa * cp.x + qu * cp.y; }
+          if (r < R && ((mm >> (8 * r)) & 0xFFu)) { const double2 cp = t[r]; s[r] += tm_numer_qq(qa, qu, cp.x, cp.y); }
       }
 #pragma unroll
       for (int r = 0; r < BT_RMAX; ++r)
-        if (r < R) s[r] = bt_recip0(sg_sum<BT_W>(s[r]));
+        if (r < R) s[r] = recip0(sg_sum<BT_W>(s[r]));
       // ---- the M-step's sums (model.py:724-729): m w z Y per entry; products that are exactly zero are not in z's pattern ----
       for (int64_t e = a + sub; e < b; e += BT_W) {
         const int col = A.indices[e];
@@ -185,7 +181,7 @@ __global__ __launch_bounds__(BT_T) void k_boot_sweep(BtArgs A) {
           const uint32_t mr = (uint32_t)(mm >> (8 * r)) & 0xFFu;
           if (r < R && mr) {
             const double2 cp = t[r];
-            const double n = qa * cp.x + qu * cp.y;
+            const double n = tm_numer_qq(qa, qu, cp.x, cp.y);
             const double v = n != 0.0 ? (((n * s[r]) * w) * y) * (double)mr : 0.0;
             if (v != 0.0) bt_add(A, bt_hot, col, slot, r, v);      // (a unique row adds nothing — unless its z is NaN, which spreads)
           }
@@ -202,18 +198,18 @@ __global__ __launch_bounds__(BT_T) void k_boot_sweep(BtArgs A) {
         for (int64_t e = a + sub; e < b; e += BT_W) {
           const double q = A.lut[A.raw[e]];
           const double2 cp = A.tab[(int64_t)A.indices[e] * R + r];
-          sum += (q * y) * cp.x + (q * (1.0 - y)) * cp.y;
+          sum += tm_numer(q, y, cp.x, cp.y);
         }
-        const double rinv = bt_recip0(sg_sum<BT_W>(sum));
+        const double rinv = recip0(sg_sum<BT_W>(sum));
         double zmax = -INFINITY, cs = 0.0;
         int hole = (b - a) < A.K ? 1 : 0;                    // the row maximum counts the zeros that are not stored (sparse_plus.py:117-129)
         for (int64_t e = a + sub; e < b; e += BT_W) {
           const double q = A.lut[A.raw[e]], qa = q * y, qu = q * (1.0 - y);
           const int64_t ix = (int64_t)A.indices[e] * R + r;
           const double2 cp = A.tab[ix], cq = A.tab2[ix];
-          const double n = qa * cp.x + qu * cp.y;
+          const double n = tm_numer_qq(qa, qu, cp.x, cp.y);
           if (n != 0.0) {
-            const double z = n * rinv, n2 = qa * cq.x + qu * cq.y;
+            const double z = n * rinv, n2 = tm_numer_qq(qa, qu, cq.x, cq.y);
             zmax = fmax(zmax, z);
             if (z >= A.thresh) cs += z;
             if (n2 != 0.0) lnl[r] += m * (z * log1p(n2));
@@ -228,17 +224,17 @@ __global__ __launch_bounds__(BT_T) void k_boot_sweep(BtArgs A) {
           for (int64_t e = a + sub; e < b; e += BT_W) {
             const double q = A.lut[A.raw[e]];
             const double2 cp = A.tab[(int64_t)A.indices[e] * R + r];
-            const double n = (q * y) * cp.x + (q * (1.0 - y)) * cp.y;
+            const double n = tm_numer(q, y, cp.x, cp.y);
             if (n != 0.0 && n * rinv == zmax) ++best;
           }
           best = sg_sum_i<BT_W>(best);
         }
-        const double share = A.method == TSEM_RA_AVERAGE ? bt_recip0((double)best) : bt_recip0(cs);
+        const double share = A.method == TSEM_RA_AVERAGE ? recip0((double)best) : recip0(cs);
         for (int64_t e = a + sub; e < b; e += BT_W) {
           const int col = A.indices[e];
           const double q = A.lut[A.raw[e]];
           const double2 cp = A.tab[(int64_t)col * R + r];
-          const double n = (q * y) * cp.x + (q * (1.0 - y)) * cp.y;
+          const double n = tm_numer(q, y, cp.x, cp.y);
           if (n == 0.0) continue;
           const double z = n * rinv;
           double v;
@@ -332,9 +328,8 @@ __global__ __launch_bounds__(256) void k_boot_init(int K, int R, double pi_prior
     if (t < R) {
       double* sc = scal + t * BT_SCAL;
       const double wmax = sc[S_WMAX];                      // (the bits of the largest weight are the value)
-      const double ppw = pi_prior * wmax, tpw = theta_prior * wmax;
-      sc[S_TPW] = tpw; sc[S_DEN_TH] = sc[S_WAMB] + tpw * K;
-      sc[S_PPW] = ppw; sc[S_DEN_PI] = sc[S_WTOT] + ppw * K;
+      const TmPrior P = tm_prior(pi_prior, theta_prior, K, sc[S_WTOT], sc[S_WAMB], wmax);
+      sc[S_TPW] = P.tpw; sc[S_DEN_TH] = P.den_th; sc[S_PPW] = P.ppw; sc[S_DEN_PI] = P.den_pi;
     }
   }
 }
@@ -361,14 +356,10 @@ __global__ __launch_bounds__(256) void k_boot_update(int K, int R, double eps, i
     const int64_t ix = (int64_t)j * R + r;
     const int jr = twin_rep[j];
     double ts = acc[ix], ps = ps0[ix];
-    if (jr != j) {                                         // exact twins share one accumulation while their sums agree to rounding
-      const double tr = acc[(int64_t)jr * R + r], pr = ps0[(int64_t)jr * R + r];
-      if (fabs(ts - tr) <= 1e-12 * fmax(fabs(ts), fabs(tr))) ts = tr;
-      if (fabs(ps - pr) <= 1e-12 * fmax(fabs(ps), fabs(pr))) ps = pr;
-    }
+    if (jr != j) { ts = tm_twin(ts, acc[(int64_t)jr * R + r]); ps = tm_twin(ps, ps0[(int64_t)jr * R + r]); }   // (tsem_model.h)
     const double* sc = scal + r * BT_SCAL;
-    const double th = (ts + sc[S_TPW]) / sc[S_DEN_TH];
-    const double ph = ((ps + ts) + sc[S_PPW]) / sc[S_DEN_PI];
+    const double th = tm_theta(ts, sc[S_TPW], sc[S_DEN_TH]);
+    const double ph = tm_pi(ps, ts, sc[S_PPW], sc[S_DEN_PI]);
     const double2 old = tab[ix];
     d[r] = fabs(ph - old.y);
     tab_prev[ix] = old;

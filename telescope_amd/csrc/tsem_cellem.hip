@@ -27,22 +27,24 @@
 // one set of short launches per iteration, on the layout above and the global per-column arrays of the global-workspace class (plus
 // one per-column array for |pi - previous pi|):
 //   row kernel     E-step over chunks of CE_SP_ROWS rows of the row-ordered view (a chunk never straddles two groups; a lane per
-//                  row, the arithmetic of k_cell_em); leaves every entry's value in the scratch
+//                  row: ce_row_estep, the function k_cell_em calls); leaves every entry's value in the scratch
 //   column kernel  M-step over batches of CE_SP_T compacted columns (a batch never straddles two groups)
-//   lnl kernel     the row kernel's twin of lnl_pass: a partial per chunk; after the last iteration once more, writing z
+//   lnl kernel     ce_row_lnl over the same chunks: a partial per chunk; after the last iteration once more, writing z
 //   finish kernel  a workgroup per spread group: diff, the stop test, n_iter / converged / the done mark, current -> previous
 // Chunks and batches of a group marked done by an EARLIER launch are skipped; nothing is polled, no workgroup waits for another:
 // kernel boundaries are the only synchronisation.  The host enqueues CE_SP_LOOK iterations, then reads the done marks back only to
 // stop enqueueing (a finished group's launches do nothing): how often it looks changes no result.
 // Order of sums of the spread class — a function of the column's entry count n alone, so that twins stay bit-identical and a group's
 // result does not depend on what else is in the call:
-//   n <= CE_SP_LANE   one lane adds the entries ascending from 0 (scipy's order, the order of k_cell_em)
+//   n <= CE_SP_LANE   one lane adds the entries ascending from 0 (scipy's order; ce_col_sum, as in k_cell_em)
 //   n <= CE_SP_WAVE   a wave: lane l adds the contiguous ascending piece [l m, (l + 1) m) of m = ceil(n / 64) entries from 0, the 64
 //                     partials go through the sg_sum tree
 //   beyond            the workgroup: thread t adds the piece [t m, (t + 1) m) of m = ceil(n / CE_SP_T) entries, a wave's partials
 //                     through the sg_sum tree, the waves' sums added in wave order
 // Block-wide scalars (the weights' totals, diff, lnl) are sums of per-chunk / per-column parts taken in a fixed order that differs
 // from k_cell_em's.  A group's BITS therefore depend on its class (spread or not); within a class they depend on the group alone.
+// Everything else — a row's weights, E-step and lnl, a column's M-step, the untouched columns, diff — is one device function (ce_*,
+// on the scalar forms of tsem_model.h) that both classes call.
 #include "tsem_runs.h"
 
 namespace {
@@ -109,12 +111,79 @@ __device__ __forceinline__ double ce_max(double v, double* red) {
   for (int i = 1; i < T / 64; ++i) t = fmax(t, red[i]);
   return t;
 }
-__device__ __forceinline__ double ce_recip0(double v) {    // sparse_plus.py:16-22
-  const double r = 1.0 / v;
-  return isinf(r) ? 0.0 : r;
+
+// ---- the steps of a fit, each once: k_cell_em and the spread kernels decide who owns a row or a column, where the group's parameter
+// tables are (LDS or its slices of the global arrays: the pointers) and how block-wide scalars are reduced; the arithmetic is here ----
+// row i's part of the weights (model.py:690-697); Q (1 - Y) of its entries into the scratch (pisum0, model.py:699)
+__device__ __forceinline__ void ce_row_weights(const CeArgs& A, int64_t i, double& tw, double& aw, double& wm) {
+  const uint32_t info = A.rinfo[i];
+  const int cls = (int)(info >> 16);
+  const double w = cls ? A.lut[info & 0xFFFFu] : 0.0, y = cls == 2 ? 1.0 : 0.0;
+  tw += w; aw += w * y; wm = fmax(wm, w);
+  for (int64_t e = A.eoff[i]; e < A.eoff[i + 1]; ++e) A.scratch[e] = A.lut[A.code[e]] * (1.0 - y);
 }
-// model.py:718-720 for one entry: (Q Y)(pi theta) + (Q (1 - Y)) pi
-__device__ __forceinline__ double ce_numer(double q, double y, double p, double t) { return (q * y) * (p * t) + (q * (1.0 - y)) * p; }
+// E-step (model.py:702-722) of row i from the previous parameters: every entry's z w Y into the scratch, for the column pass
+__device__ __forceinline__ void ce_row_estep(const CeArgs& A, int64_t i, const double* pp, const double* tp) {
+  const uint32_t info = A.rinfo[i];
+  const int cls = (int)(info >> 16);
+  const double w = cls ? A.lut[info & 0xFFFFu] : 0.0, y = cls == 2 ? 1.0 : 0.0;
+  const int64_t a = A.eoff[i], b = A.eoff[i + 1];
+  double sum = 0.0;
+  for (int64_t e = a; e < b; ++e) { const int lc = A.lcol[e]; const double p = pp[lc]; sum += tm_numer(A.lut[A.code[e]], y, p * tp[lc], p); }
+  const double rinv = recip0(sum);
+  for (int64_t e = a; e < b; ++e) {
+    const int lc = A.lcol[e];
+    const double p = pp[lc], n = tm_numer(A.lut[A.code[e]], y, p * tp[lc], p);
+    A.scratch[e] = n != 0.0 ? ((n * rinv) * w) * y : 0.0;              // products that are exactly zero leave z's pattern
+  }
+}
+// calculate_lnl(z(previous parameters), current parameters) (model.py:744-760) of row i, added to `part` entry by entry; WRITE: z goes
+// to its CSR positions as well
+template <bool WRITE>
+__device__ __forceinline__ void ce_row_lnl(const CeArgs& A, int64_t i, const double* pi, const double* th, const double* pp,
+                                           const double* tp, double& part) {
+  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  const uint32_t info = A.rinfo[i];
+  const double y = (info >> 16) == 2 ? 1.0 : 0.0;
+  const int64_t a = A.eoff[i], b = A.eoff[i + 1];
+  double sum = 0.0;
+  for (int64_t e = a; e < b; ++e) { const int lc = A.lcol[e]; const double p = pp[lc]; sum += tm_numer(A.lut[A.code[e]], y, p * tp[lc], p); }
+  const double rinv = recip0(sum);
+  const int64_t zo = WRITE ? A.indptr[A.rows[i]] - a : 0;
+  for (int64_t e = a; e < b; ++e) {
+    const int lc = A.lcol[e];
+    const double q = A.lut[A.code[e]], p = pp[lc], c = pi[lc];
+    const double n = tm_numer(q, y, p * tp[lc], p);
+    const bool inp = n != 0.0;
+    const double z = n * rinv;
+    if (WRITE) A.user_z[zo + e] = inp ? z : nan;
+    const double m = tm_numer(q, y, c * th[lc], c);
+    if (inp && m != 0.0) part += z * log1p(m);
+  }
+}
+// one lane adds the entries [p0, p1) of the column-ordered view over the scratch, ascending from 0 (scipy's order)
+__device__ __forceinline__ double ce_col_sum(const CeArgs& A, uint32_t p0, uint32_t p1) {
+  double s = 0.0;
+  for (uint32_t p = p0; p < p1; ++p) s += A.scratch[A.cpos[p]];
+  return s;
+}
+// M-step closed forms (model.py:724-742) of compacted column `col` from its sum s; the first iteration's values are kept; returns
+// |pi - previous pi|
+__device__ __forceinline__ double ce_col_mstep(const CeArgs& A, const TmPrior& P, int64_t col, bool first, double s, double ps0,
+                                               double pi_prev, double& pi, double& th) {
+  const double thn = tm_theta(s, P.tpw, P.den_th);
+  const double pin = tm_pi(ps0, s, P.ppw, P.den_pi);
+  pi = pin; th = thn;
+  if (first) { A.pi_init[col] = pin; A.theta_init[col] = thn; }
+  return fabs(pin - pi_prev);
+}
+// the columns a group never touches: the closed forms of empty sums
+__device__ __forceinline__ double ce_rest_pi(const TmPrior& P) { return tm_pi(0.0, 0.0, P.ppw, P.den_pi); }
+__device__ __forceinline__ double ce_rest_th(const TmPrior& P) { return tm_theta(0.0, P.tpw, P.den_th); }
+// diff over all K columns (model.py:781) from the sum d over the Kc touched ones
+__device__ __forceinline__ double ce_diff(double d, int K, int Kc, double rest_pi, double rest_pi_prev) {
+  return d + (K > Kc ? (double)(K - Kc) * fabs(rest_pi - rest_pi_prev) : 0.0);
+}
 
 __global__ void k_ce_fill_nan(int64_t n, double* __restrict__ z) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -145,50 +214,20 @@ __global__ __launch_bounds__(T) void k_cell_em(CeArgs A) {
   }
   // ---- the cell's weights (model.py:690-697) and pisum0 (model.py:699) ----
   double tw = 0.0, aw = 0.0, wm = 0.0;
-  for (int64_t i = r0 + tid; i < r1; i += T) {
-    const uint32_t info = A.rinfo[i];
-    const int cls = (int)(info >> 16);
-    const double w = cls ? A.lut[info & 0xFFFFu] : 0.0, y = cls == 2 ? 1.0 : 0.0;
-    tw += w; aw += w * y; wm = fmax(wm, w);
-    for (int64_t e = A.eoff[i]; e < A.eoff[i + 1]; ++e) A.scratch[e] = A.lut[A.code[e]] * (1.0 - y);
-  }
+  for (int64_t i = r0 + tid; i < r1; i += T) ce_row_weights(A, i, tw, aw, wm);
   tw = ce_sum<T>(tw, red); aw = ce_sum<T>(aw, red); wm = ce_max<T>(wm, red);
   __syncthreads();
   const double inv_k = 1.0 / K;
-  for (int lc = tid; lc < Kc; lc += T) {
-    double s = 0.0;
-    for (uint32_t p = A.cptr[c0 + lc]; p < A.cptr[c0 + lc + 1]; ++p) s += A.scratch[A.cpos[p]];
-    ps0[lc] = s; pi[lc] = inv_k; th[lc] = inv_k;
-  }
-  const double ppw = A.pi_prior * wm, tpw = A.theta_prior * wm;
-  const double den_th = aw + tpw * K, den_pi = tw + ppw * K;
+  for (int lc = tid; lc < Kc; lc += T) { ps0[lc] = ce_col_sum(A, A.cptr[c0 + lc], A.cptr[c0 + lc + 1]); pi[lc] = inv_k; th[lc] = inv_k; }
+  const TmPrior P = tm_prior(A.pi_prior, A.theta_prior, K, tw, aw, wm);
   double rest_pi = inv_k, rest_th = inv_k, rest_pi_prev = inv_k, rest_th_prev = inv_k, rest_pi_init = nan, rest_th_init = nan;
   int it = 0;
   bool conv = false;
   double lnl_prev = INFINITY;
 
-  // calculate_lnl(z(previous parameters), current parameters) (model.py:744-760); WRITE: z goes to its CSR positions as well
   auto lnl_pass = [&](auto write) -> double {
     double part = 0.0;
-    for (int64_t i = r0 + tid; i < r1; i += T) {
-      const uint32_t info = A.rinfo[i];
-      const double y = (info >> 16) == 2 ? 1.0 : 0.0;
-      const int64_t a = A.eoff[i], b = A.eoff[i + 1];
-      double sum = 0.0;
-      for (int64_t e = a; e < b; ++e) { const int lc = A.lcol[e]; sum += ce_numer(A.lut[A.code[e]], y, pp[lc], tp[lc]); }
-      const double rinv = ce_recip0(sum);
-      const int64_t zo = decltype(write)::value ? A.indptr[A.rows[i]] - a : 0;
-      for (int64_t e = a; e < b; ++e) {
-        const int lc = A.lcol[e];
-        const double q = A.lut[A.code[e]];
-        const double n = ce_numer(q, y, pp[lc], tp[lc]);
-        const bool inp = n != 0.0;
-        const double z = n * rinv;
-        if constexpr (decltype(write)::value) A.user_z[zo + e] = inp ? z : nan;
-        const double m = ce_numer(q, y, pi[lc], th[lc]);
-        if (inp && m != 0.0) part += z * log1p(m);
-      }
-    }
+    for (int64_t i = r0 + tid; i < r1; i += T) ce_row_lnl<decltype(write)::value>(A, i, pi, th, pp, tp, part);
     return ce_sum<T>(part, red);
   };
 
@@ -198,38 +237,17 @@ __global__ __launch_bounds__(T) void k_cell_em(CeArgs A) {
     for (int lc = tid; lc < Kc; lc += T) { pp[lc] = pi[lc]; tp[lc] = th[lc]; }
     rest_pi_prev = rest_pi; rest_th_prev = rest_th;
     __syncthreads();
-    // ---- E-step (model.py:702-722), a lane per row: every entry's z w Y for the column pass ----
-    for (int64_t i = r0 + tid; i < r1; i += T) {
-      const uint32_t info = A.rinfo[i];
-      const int cls = (int)(info >> 16);
-      const double w = cls ? A.lut[info & 0xFFFFu] : 0.0, y = cls == 2 ? 1.0 : 0.0;
-      const int64_t a = A.eoff[i], b = A.eoff[i + 1];
-      double sum = 0.0;
-      for (int64_t e = a; e < b; ++e) { const int lc = A.lcol[e]; sum += ce_numer(A.lut[A.code[e]], y, pp[lc], tp[lc]); }
-      const double rinv = ce_recip0(sum);
-      for (int64_t e = a; e < b; ++e) {
-        const int lc = A.lcol[e];
-        const double n = ce_numer(A.lut[A.code[e]], y, pp[lc], tp[lc]);
-        A.scratch[e] = n != 0.0 ? ((n * rinv) * w) * y : 0.0;          // products that are exactly zero leave z's pattern
-      }
-    }
+    // ---- E-step, a lane per row ----
+    for (int64_t i = r0 + tid; i < r1; i += T) ce_row_estep(A, i, pp, tp);
     __syncthreads();
-    // ---- M-step (model.py:724-742), a lane per column of the cell, ascending row order ----
+    // ---- M-step, a lane per column of the cell, ascending row order ----
     double dpart = 0.0;
-    for (int lc = tid; lc < Kc; lc += T) {
-      double s = 0.0;
-      for (uint32_t p = A.cptr[c0 + lc]; p < A.cptr[c0 + lc + 1]; ++p) s += A.scratch[A.cpos[p]];
-      const double thn = (s + tpw) / den_th;
-      const double pin = ((ps0[lc] + s) + ppw) / den_pi;
-      dpart += fabs(pin - pp[lc]);
-      pi[lc] = pin; th[lc] = thn;
-      if (it == 0) { A.pi_init[c0 + lc] = pin; A.theta_init[c0 + lc] = thn; }
-    }
-    rest_th = (0.0 + tpw) / den_th;
-    rest_pi = ((0.0 + 0.0) + ppw) / den_pi;
+    for (int lc = tid; lc < Kc; lc += T)
+      dpart += ce_col_mstep(A, P, c0 + lc, it == 0, ce_col_sum(A, A.cptr[c0 + lc], A.cptr[c0 + lc + 1]), ps0[lc], pp[lc], pi[lc], th[lc]);
+    rest_th = ce_rest_th(P); rest_pi = ce_rest_pi(P);
     if (it == 0) { rest_pi_init = rest_pi; rest_th_init = rest_th; }
     ++it;
-    const double diff = ce_sum<T>(dpart, red) + (K > Kc ? (double)(K - Kc) * fabs(rest_pi - rest_pi_prev) : 0.0);   // model.py:781, all K columns
+    const double diff = ce_diff(ce_sum<T>(dpart, red), K, Kc, rest_pi, rest_pi_prev);
     __syncthreads();
     if (A.use_lnl) {                                        // model.py:783-789
       const double lnl = lnl_pass(std::false_type());
@@ -263,26 +281,21 @@ struct SpArgs {
   const int64_t* cfirst;           // [S + 1] first chunk of every slot
   double* cpart;                   // [3 chunks] per-chunk parts: tw, aw, wm at set-up; lnl afterwards ([3 k])
   double* dabs;                    // [n_cols] |pi - previous pi| of every column
-  double* st;                      // [S][8] theta prior weight, theta denominator, pi prior weight, pi denominator, previous lnl
+  double* st;                      // [S][8] the prior scale (TmPrior's four numbers, in its order), previous lnl
   int32_t* ctl;                    // [S][2] iterations done, the done mark
 };
+__device__ __forceinline__ TmPrior sp_prior(const double* st) { return TmPrior{st[0], st[1], st[2], st[3]}; }
 
-// set-up, a lane per row: the chunk's parts of the weights (model.py:690-697), Q (1 - Y) into the scratch (pisum0, model.py:699)
+// set-up, a lane per row (ce_row_weights): the chunk's parts of the weights, Q (1 - Y) into the scratch
 __global__ __launch_bounds__(CE_SP_T) void k_sp_weights(SpArgs S, CeArgs A) {
   __shared__ double red[CE_RED];
   const SpRange ch = S.chunk[blockIdx.x];
   double tw = 0.0, aw = 0.0, wm = 0.0;
-  for (int64_t i = ch.a + threadIdx.x; i < ch.b; i += CE_SP_T) {
-    const uint32_t info = A.rinfo[i];
-    const int cls = (int)(info >> 16);
-    const double w = cls ? A.lut[info & 0xFFFFu] : 0.0, y = cls == 2 ? 1.0 : 0.0;
-    tw += w; aw += w * y; wm = fmax(wm, w);
-    for (int64_t e = A.eoff[i]; e < A.eoff[i + 1]; ++e) A.scratch[e] = A.lut[A.code[e]] * (1.0 - y);
-  }
+  for (int64_t i = ch.a + threadIdx.x; i < ch.b; i += CE_SP_T) ce_row_weights(A, i, tw, aw, wm);
   tw = ce_sum<CE_SP_T>(tw, red); aw = ce_sum<CE_SP_T>(aw, red); wm = ce_max<CE_SP_T>(wm, red);
   if (threadIdx.x == 0) { S.cpart[3 * (int64_t)blockIdx.x] = tw; S.cpart[3 * (int64_t)blockIdx.x + 1] = aw; S.cpart[3 * (int64_t)blockIdx.x + 2] = wm; }
 }
-// set-up, a workgroup per spread group: its weights from the chunks' parts in chunk order, the prior weights and denominators
+// set-up, a workgroup per spread group: its weights from the chunks' parts in chunk order, the prior scale (tm_prior)
 __global__ __launch_bounds__(CE_SP_T) void k_sp_begin(SpArgs S, CeArgs A) {
   __shared__ double red[CE_RED];
   const int s = blockIdx.x;
@@ -292,71 +305,38 @@ __global__ __launch_bounds__(CE_SP_T) void k_sp_begin(SpArgs S, CeArgs A) {
   }
   tw = ce_sum<CE_SP_T>(tw, red); aw = ce_sum<CE_SP_T>(aw, red); wm = ce_max<CE_SP_T>(wm, red);
   if (threadIdx.x == 0) {
-    const double ppw = A.pi_prior * wm, tpw = A.theta_prior * wm;
+    const TmPrior P = tm_prior(A.pi_prior, A.theta_prior, A.K, tw, aw, wm);
     double* st = S.st + 8 * (int64_t)s;
-    st[0] = tpw; st[1] = aw + tpw * A.K; st[2] = ppw; st[3] = tw + ppw * A.K; st[4] = INFINITY;
+    st[0] = P.tpw; st[1] = P.den_th; st[2] = P.ppw; st[3] = P.den_pi; st[4] = INFINITY;
     S.ctl[2 * s] = 0; S.ctl[2 * s + 1] = 0;
   }
 }
 
-// E-step (model.py:702-722) of one chunk of rows, a lane per row, from the group's previous parameters: k_cell_em's arithmetic
+// E-step of one chunk of rows, a lane per row (ce_row_estep), from the group's previous parameters
 __global__ __launch_bounds__(CE_SP_T) void k_sp_rows(SpArgs S, CeArgs A) {
   const SpRange ch = S.chunk[blockIdx.x];
   if (S.ctl[2 * ch.slot + 1]) return;                       // (marked by an earlier launch)
   const int64_t c0 = A.col_ptr[S.gid[ch.slot]];
-  const double *pp = A.ws_pi_prev + c0, *tp = A.ws_theta_prev + c0;
-  for (int64_t i = ch.a + threadIdx.x; i < ch.b; i += CE_SP_T) {
-    const uint32_t info = A.rinfo[i];
-    const int cls = (int)(info >> 16);
-    const double w = cls ? A.lut[info & 0xFFFFu] : 0.0, y = cls == 2 ? 1.0 : 0.0;
-    const int64_t a = A.eoff[i], b = A.eoff[i + 1];
-    double sum = 0.0;
-    for (int64_t e = a; e < b; ++e) { const int lc = A.lcol[e]; sum += ce_numer(A.lut[A.code[e]], y, pp[lc], tp[lc]); }
-    const double rinv = ce_recip0(sum);
-    for (int64_t e = a; e < b; ++e) {
-      const int lc = A.lcol[e];
-      const double n = ce_numer(A.lut[A.code[e]], y, pp[lc], tp[lc]);
-      A.scratch[e] = n != 0.0 ? ((n * rinv) * w) * y : 0.0;            // products that are exactly zero leave z's pattern
-    }
-  }
+  for (int64_t i = ch.a + threadIdx.x; i < ch.b; i += CE_SP_T) ce_row_estep(A, i, A.ws_pi_prev + c0, A.ws_theta_prev + c0);
 }
 
-// calculate_lnl(z(previous parameters), current parameters) (model.py:744-760) of one chunk of rows: lnl_pass of k_cell_em; WRITE: the
-// final pass — every group, z to its CSR positions
+// the lnl pass of one chunk of rows, a lane per row (ce_row_lnl): a partial per chunk; WRITE: the final pass — every group, z to its
+// CSR positions
 template <bool WRITE>
 __global__ __launch_bounds__(CE_SP_T) void k_sp_lnl(SpArgs S, CeArgs A) {
   __shared__ double red[CE_RED];
   const SpRange ch = S.chunk[blockIdx.x];
   if (!WRITE && S.ctl[2 * ch.slot + 1]) return;
   const int64_t c0 = A.col_ptr[S.gid[ch.slot]];
-  const double *pp = A.ws_pi_prev + c0, *tp = A.ws_theta_prev + c0, *pi = A.pi + c0, *th = A.theta + c0;
-  const double nan = __longlong_as_double(0x7FF8000000000000ll);
   double part = 0.0;
-  for (int64_t i = ch.a + threadIdx.x; i < ch.b; i += CE_SP_T) {
-    const uint32_t info = A.rinfo[i];
-    const double y = (info >> 16) == 2 ? 1.0 : 0.0;
-    const int64_t a = A.eoff[i], b = A.eoff[i + 1];
-    double sum = 0.0;
-    for (int64_t e = a; e < b; ++e) { const int lc = A.lcol[e]; sum += ce_numer(A.lut[A.code[e]], y, pp[lc], tp[lc]); }
-    const double rinv = ce_recip0(sum);
-    const int64_t zo = WRITE ? A.indptr[A.rows[i]] - a : 0;
-    for (int64_t e = a; e < b; ++e) {
-      const int lc = A.lcol[e];
-      const double q = A.lut[A.code[e]];
-      const double n = ce_numer(q, y, pp[lc], tp[lc]);
-      const bool inp = n != 0.0;
-      const double z = n * rinv;
-      if (WRITE) A.user_z[zo + e] = inp ? z : nan;
-      const double m = ce_numer(q, y, pi[lc], th[lc]);
-      if (inp && m != 0.0) part += z * log1p(m);
-    }
-  }
+  for (int64_t i = ch.a + threadIdx.x; i < ch.b; i += CE_SP_T)
+    ce_row_lnl<WRITE>(A, i, A.pi + c0, A.theta + c0, A.ws_pi_prev + c0, A.ws_theta_prev + c0, part);
   part = ce_sum<CE_SP_T>(part, red);
   if (threadIdx.x == 0) S.cpart[3 * (int64_t)blockIdx.x] = part;
 }
 
 // The sums of one batch of compacted columns over the scratch, in the order the top of this file states (by the column's entry
-// count alone).  MSTEP: the closed forms (model.py:724-742) and |pi - previous pi|; otherwise pisum0 and the start values 1 / K.
+// count alone).  MSTEP: the closed forms (ce_col_mstep) and |pi - previous pi|; otherwise pisum0 and the start values 1 / K.
 template <bool MSTEP>
 __global__ __launch_bounds__(CE_SP_T) void k_sp_cols(SpArgs S, CeArgs A) {
   __shared__ double red[CE_RED];
@@ -368,8 +348,7 @@ __global__ __launch_bounds__(CE_SP_T) void k_sp_cols(SpArgs S, CeArgs A) {
   const bool live = col < bt.b;
   const uint32_t p0 = live ? A.cptr[col] : 0u, n = live ? A.cptr[col + 1] - p0 : 0u;
   double s = 0.0;
-  if (n <= (uint32_t)CE_SP_LANE)
-    for (uint32_t p = p0; p < p0 + n; ++p) s += A.scratch[A.cpos[p]];
+  if (n <= (uint32_t)CE_SP_LANE) s = ce_col_sum(A, p0, p0 + n);
   for (unsigned long long m = __ballot(n > (uint32_t)CE_SP_LANE && n <= (uint32_t)CE_SP_WAVE); m; m &= m - 1) {
     const int src = __ffsll((long long)m) - 1;
     const uint32_t q0 = (uint32_t)__shfl((int)p0, src, 64), qn = (uint32_t)__shfl((int)n, src, 64);
@@ -397,12 +376,8 @@ __global__ __launch_bounds__(CE_SP_T) void k_sp_cols(SpArgs S, CeArgs A) {
     const double inv_k = 1.0 / A.K;
     A.ws_pisum0[col] = s; A.ws_pi_prev[col] = inv_k; A.ws_theta_prev[col] = inv_k; A.pi[col] = inv_k; A.theta[col] = inv_k;
   } else {
-    const double* st = S.st + 8 * (int64_t)bt.slot;
-    const double thn = (s + st[0]) / st[1];
-    const double pin = ((A.ws_pisum0[col] + s) + st[2]) / st[3];
-    S.dabs[col] = fabs(pin - A.ws_pi_prev[col]);
-    A.pi[col] = pin; A.theta[col] = thn;
-    if (S.ctl[2 * bt.slot] == 0) { A.pi_init[col] = pin; A.theta_init[col] = thn; }
+    S.dabs[col] = ce_col_mstep(A, sp_prior(S.st + 8 * (int64_t)bt.slot), col, S.ctl[2 * bt.slot] == 0, s, A.ws_pisum0[col], A.ws_pi_prev[col],
+                               A.pi[col], A.theta[col]);
   }
 }
 
@@ -430,8 +405,8 @@ __global__ __launch_bounds__(CE_SP_T) void k_sp_finish(SpArgs S, CeArgs A) {
     double d = 0.0;
     for (int lc = tid; lc < Kc; lc += CE_SP_T) d += S.dabs[c0 + lc];
     d = ce_sum<CE_SP_T>(d, red);
-    const double rest_pi = ((0.0 + 0.0) + st[2]) / st[3], rest_pi_prev = it == 0 ? 1.0 / K : rest_pi;
-    conv = d + (K > Kc ? (double)(K - Kc) * fabs(rest_pi - rest_pi_prev) : 0.0) < A.eps;
+    const double rest_pi = ce_rest_pi(sp_prior(st));
+    conv = ce_diff(d, K, Kc, rest_pi, it == 0 ? 1.0 / K : rest_pi) < A.eps;
   }
   const bool stop = conv || it + 1 >= A.max_iter;
   if (!stop)
@@ -450,8 +425,8 @@ __global__ __launch_bounds__(CE_SP_T) void k_sp_end(SpArgs S, CeArgs A) {
   l = ce_sum<CE_SP_T>(l, red);
   if (tid == 0) {
     const int c = S.gid[s];
-    const double* st = S.st + 8 * (int64_t)s;
-    const double rest_pi = ((0.0 + 0.0) + st[2]) / st[3], rest_th = (0.0 + st[0]) / st[1];
+    const TmPrior P = sp_prior(S.st + 8 * (int64_t)s);
+    const double rest_pi = ce_rest_pi(P), rest_th = ce_rest_th(P);
     A.lnl[c] = l;
     double* r = A.rest + 4 * (int64_t)c;
     r[0] = rest_pi; r[1] = rest_th; r[2] = rest_pi; r[3] = rest_th;

@@ -281,13 +281,9 @@ __global__ __launch_bounds__(256) void k_update(UpdCtl C, int K, const double* _
     // sums agree to rounding, i.e. their parameters are still symmetric
     const int jr = twin_rep[j];
     double ts = red[j];
-    if (jr != j) {
-      double tr = red[jr];
-      if (fabs(ts - tr) <= 1e-12 * fmax(fabs(ts), fabs(tr))) ts = tr;
-    }
-    double th = (ts + theta_pw) / theta_den;
-    double ps = pisum0[j] + ts;
-    double ph = (ps + pi_pw) / pi_den;
+    if (jr != j) ts = tm_twin(ts, red[jr]);
+    double th = tm_theta(ts, theta_pw, theta_den);
+    double ph = tm_pi(pisum0[j], ts, pi_pw, pi_den);
     double po = pi[j], to = theta[j];
     d += fabs(ph - po);
     pi_prev[j] = po; theta_prev[j] = to;

@@ -17,6 +17,7 @@
 //   tsem_bgzf.hip    the BGZF blocks of a BAM file inflated on the device (tsem_bgzf_*; the body is the host / device function of
 //                    tsem_bgzf_inflate.h, the chain of block headers in tsem_bgzf_scan.h)
 //   tsem_fz_p*.hip   instantiations of the fused kernel (tsem_fused.h), one team size per unit
+//   tsem_model.h     the model's scalar arithmetic (numerator, closed forms, twin rule, prior scale) for tsem_em / _cellem / _boot
 //
 // A kernel is launched only from the unit that defines it; other units go through the host functions declared here.
 #pragma once
@@ -33,6 +34,7 @@
 #include "tsem_common.h"
 #include "tsem_device.h"
 #include "tsem_fused.h"
+#include "tsem_model.h"
 
 constexpr int RS_SUB = 16, RP_SUB = 16;     // lanes per row of the 16-lane row passes (set-up / report)
 extern std::string g_create_err;           // why the last tsem_create / stateless primitive failed (tsem_last_error(NULL))

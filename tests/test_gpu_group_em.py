@@ -251,6 +251,28 @@ def test_spread_and_one_workgroup_groups_in_one_call(gpu_device, params):
     tl.em_cells(cor, n, use_likelihood=params[2])            # (leave the shared object as it was)
 
 
+# ---- one arithmetic under both launch strategies ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize('params', R.B_PARAMS)
+def test_spread_has_the_one_workgroup_bits_where_the_orders_of_sums_coincide(gpu_device, params):
+    """One group of 177 rows, 300 compacted columns and 600 entries, two per column at most: in the 256-thread LDS class, and one
+    chunk of rows, a row per thread at most, two columns per thread at most, every column in the one-lane tier — so every sum of the
+    spread class (the chunks' parts, the columns, diff, lnl) is taken in the one-workgroup class's order, and what is left to differ
+    is the arithmetic of a row and of a column: the two classes share it, bit for bit."""
+    raw, cor, _ = R.boundary_matrix(51, 2000, [(300, 600)])
+    per_column = GR.column_counts(raw, cor, 0)
+    n_rows = int(np.sum(cor == 0))
+    assert (n_rows, len(per_column), raw.nnz, max(per_column)) == (177, 300, 600, 2) and n_rows == raw.shape[0]
+    assert _old_class(raw, cor, 0) == 1                                                # 256 threads, the tables in LDS
+    assert n_rows <= GR.SP_ROWS and n_rows <= GR.SP_T                                  # one chunk; a row per thread at most
+    assert len(per_column) <= 2 * GR.SP_T and max(per_column) <= GR.SP_LANE            # two columns per thread; one lane per column
+    one, spread = [_EngineFit(gpu_device, raw, cor, 1, params[0], params[1], params[2], spread=s) for s in (0, 1)]
+    assert _counts(one.eng) == (0, (0, 1, 0, 0)) and _counts(spread.eng) == (1, (0, 0, 0, 0))
+    print('one order %s: %d iterations, lnl %r' % (params, int(one.fits.n_iter[0]), float(one.fits.lnl[0])))
+    _assert_same_fit(one.fits, one.z_aligned, spread.fits, spread.z_aligned, ('one order', params))
+    one.eng.close()
+    spread.eng.close()
+
+
 # ---- determinism, twins, the host's looks ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('seed', [1, 4])
 def test_two_spread_runs_on_fresh_objects_are_bit_identical(gpu_device, seed):

@@ -71,6 +71,11 @@ int  tsem_set_stream(tsem_ctx* h, void* hip_stream); /* launch on this hipStream
  *   "em_kernel"    TSEM_EMK_*                      "block_rows", "parts"  override the layout geometry
  *   "value_format" 0 auto (2-byte score codes + LDS score table when the fused kernel runs and the table
  *                  has <= 2048 entries), 1 fp64 Q values, 2 codes (error if not possible)
+ *   "index_format" index of fp64 entries under the fused kernel: 0 auto, 1 three bytes per entry, 2 the quad index — one 64-bit
+ *                  word per four entries, 10 B per entry in all (error where it cannot apply: score codes, the split layout,
+ *                  the strand-transposed fill, "reproducible", more than 512 row slots per block).  Auto takes the quad index where
+ *                  it can apply, the dummy entries it needs stay within 0.5 % of the entries, and 11 B x the entries of the
+ *                  ambiguous rows reach "index_auto_min_bytes" (default 1 GiB); see tsem_layout_info_n [40]-[43]
  *   "hot_split"    1 (default): very popular columns get several accumulator slots
  *   "row_offset"   global index of this rank's first row (synthetic generator, column signatures)
  *   "report_shortcuts" 1 (default): tsem_reassign answers `all` (initial) and `unique` from counts taken at
@@ -718,7 +723,7 @@ int  tsem_report_info_n(tsem_ctx* h, int64_t* info, int32_t n);
 int  tsem_phase_times(tsem_ctx* h, int reset, double* ms6, int64_t* n_iter);
 /* Free / total bytes of the device's memory (hipMemGetInfo; h may be NULL, then `device` is asked) and, with a handle, the bytes its
  * matrix keeps resident: resident5 = { CSR row pointers + scores | CSR column ids (0 after option "drop_csr_indices") | popularity
- * ids | blocked layout (its index at 3 or 4 B per padded entry, see tsem_layout_info_n [32]) | per-row arrays }.  What a capacity plan needs: 14 B per stored entry by default (score codes), 10 after
+ * ids | blocked layout (its index at 2, 3 or 4 B per padded entry, see tsem_layout_info_n [32]) | per-row arrays }.  What a capacity plan needs: 14 B per stored entry by default (score codes), 10 after
  * the drop, + ~20 B per row. */
 int  tsem_device_memory(tsem_ctx* h, int device, int64_t* free_bytes, int64_t* total_bytes, int64_t* resident5);
 /* Facts about the resident layout, 32 values (the Python binding names them: _lib.Engine.layout_info).  Of the later ones: [23] the
@@ -736,8 +741,14 @@ int  tsem_layout_info(tsem_ctx* h, int64_t* info32);
  * tables in a global workspace — all 0 before a fit; [37] the groups the last tsem_cell_em spread over the grid (option
  * "cell_em_spread_entries"): a spread group is counted here and in none of [33]-[36]; [38], [39] the lanes per row (1, 2, 4, 8 or
  * 16, sixteen entries per lane) of the last tsem_rowstats's row-statistics and column-signature kernels — from the mean row length,
- * and from the row-length histogram (the smallest group that takes 99.5 % of the rows in one step) —, 0 before one ran. */
-#define TSEM_LAYOUT_INFO_N 40
+ * and from the row-length histogram (the smallest group that takes 99.5 % of the rows in one step) —, 0 before one ran; [40] the
+ * index format of the blocked layout (0: one 32-bit word per entry, 1: three bytes per entry, 2: the quad index — one 64-bit word per
+ * four entries of a row-ordered sub-block, [32] == 2; option "index_format" 0 auto / 1 / 2); [41] the dummy entries (column slot 0,
+ * value 0) a quad layout stores so that every row of a block has an entry in every part: counted in nnz_pad, not in nnz_amb; [42] the
+ * quads the pack kernel could not represent (0 by construction: anything else is a fault of the set-up, and the layout then keeps the
+ * 3-byte index); [43] option "index_auto_min_bytes": the smallest 3-byte stream (11 B x nnz_amb) for which auto takes the quad
+ * index (default 1 GiB). */
+#define TSEM_LAYOUT_INFO_N 44
 int  tsem_layout_info_n(tsem_ctx* h, int64_t* info, int32_t n);
 /* per-block shader-clock stamps of team 0 / member 0 of the fused kernel (option "fused_prof") */
 int  tsem_debug_fused_prof(tsem_ctx* h, uint64_t* out512);
@@ -760,6 +771,11 @@ int  tsem_debug_valmap(int32_t nq, uint32_t* pos);
  * the 12 bytes of a quad of the 3-byte index — entry k is the 24-bit little-endian number row << 13 | column at bytes 3k .. 3k+2 —
  * and unpacked again into back4, both with the inline functions the fill kernels and the fused kernel use */
 int  tsem_debug_idx24(const uint32_t* rc4, uint8_t* out12, uint32_t* back4);
+/* host only, no device: four local row << 16 | local column words packed into the 64-bit word of the quad index — 13-bit column slots
+ * at bits 0, 13, 26 and 39, the steps row[k] - row[k-1] (0 or 1) at bits 52-54, the first entry's row slot at bits 55-63 — and unpacked
+ * again into back4, with the inline functions the pack kernel and the fused kernel use; TSEM_ERR_ARG for a quad the format cannot hold.
+ * *stored (may be null): 1 when `probe` names a stored quad, 0 when its low half is the fused kernel's idle mark 0xFFFFFFFF */
+int  tsem_debug_quad64(const uint32_t* rc4, uint64_t* word, uint32_t* back4, uint64_t probe, int32_t* stored);
 /* y[i] = the device log1p the lnl passes use (finite x >= 0), for accuracy tests against libm */
 int  tsem_debug_log1p(int device, int32_t n, const double* x, double* y);
 /* out[i] = the PHRED lookup of tsem_entry_tags for p[i] (the table as there), for tests against numpy */

@@ -271,6 +271,7 @@ def lib():
     L.tsem_debug_stream_read.argtypes = [C.c_int, i64, i32, C.POINTER(dbl)]
     L.tsem_debug_subblock.argtypes = [vp, C.c_int64, C.c_int32, vp, C.c_int64]
     L.tsem_debug_idx24.argtypes = [vp, vp, vp]
+    L.tsem_debug_quad64.argtypes = [vp, vp, vp, C.c_uint64, vp]
     L.tsem_debug_subblock_values.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int64]
     L.tsem_debug_valmap.argtypes = [C.c_int32, vp]
     for name in exported_symbols():
@@ -788,14 +789,18 @@ class Engine(object):
             raise EngineError('tsem_debug_subblock_values failed (%d)' % n)
         return out[:n], rows[:n], cols[:n]
 
-    def layout_info(self):
-        info = np.zeros(40, np.int64)
+    def layout_info(self, extended=False):
+        """Facts about the resident layout (include/telescope_em.h, tsem_layout_info_n).  extended: also the values appended behind
+        the first 40 — the index format in use, its dummy entries, the pack kernel's count of unrepresentable quads and the auto
+        rule's size threshold."""
+        info = np.zeros(44 if extended else 40, np.int64)
         self._ck(self._L.tsem_layout_info_n(self._h, ptr(info), info.size))
         return dict(zip(('P', 'Kp', 'R', 'nb', 'N_amb', 'N_uni', 'nnz_amb', 'nnz_pad', 'twin_cols',
                          'G1', 'G2', 'fused', 'slow_path', 'max_subblock', 'value_bytes', 'hot_cols',
                          'lds_bytes', 'row_order', 'geometry', 'fallbacks', 'bin_repeats', 'reproducible', 'exact_single', 'lnl_fused', 'split', 'single_part_rows', 'row_pass_em', 'lnl_tables', 'lnl_linear', 'lnl_mid_entries', 'lnl_mid_limit', 'near_tie_rows', 'index_bytes',
                          'cell_em_wave', 'cell_em_256', 'cell_em_512', 'cell_em_global', 'cell_em_spread',
-                         'rowstats_lanes', 'colsig_lanes'), info.tolist()))
+                         'rowstats_lanes', 'colsig_lanes',
+                         'index_format', 'index_dummies', 'index_unrepresentable', 'index_auto_min_bytes'), info.tolist()))
 
 
 def legacy_randint(counts):

@@ -28,7 +28,8 @@
 //   * entries are an index (local row, local column) + either the fp64 Q value (FMT 0, 2) or
 //     its 2-byte score code, looked up in an LDS copy of the score table (FMT 1): the
 //     same fp64 number at half the HBM bytes.  The index is 3 B next to fp64 values (11 B
-//     per entry: the pass is bound by the bytes it reads; tsem_idx24.h) and 4 B elsewhere;
+//     per entry: the pass is bound by the bytes it reads; tsem_idx24.h), 2 B where the layout
+//     build chose the quad index (one 8-byte word per four entries, tsem_quad64.h) and 4 B elsewhere;
 //   * a sub-block is stored in row order, so the row sums are reduced in registers and
 //     across lanes (fz_row_sums) and only the end of each run of equal rows issues an
 //     LDS atomic: ds_add_f64 costs 3x a gather (profiles/r01_lds_ubench.log).
@@ -37,6 +38,7 @@
 // time; every wait is bounded and reports through an error word.
 #pragma once
 #include "tsem_idx24.h"
+#include "tsem_quad64.h"
 #include "tsem_valmap.h"
 
 constexpr int FZ_NT = 1024;            // threads per workgroup
@@ -83,7 +85,7 @@ struct FusedArgs {
   const double* lut;        // FMT 1: the score table, copied to LDS [lut_len]
   int lut_len;
   const uint16_t* wcode;    // FMT 1: [N_amb_pad] row weight as a code, w_i = lut[max code of the row]
-  const uint32_t* prc;      // entry index: 3 B per entry where fz_idx24(MODE, FMT), else one lrow << 16 | lcol word
+  const uint32_t* prc;      // entry index: 8 B per quad (FZ_IXQ), 3 B per entry (FZ_IX24), else one lrow << 16 | lcol word (FZ_IX32): fz_index()
   const double* ctab;
   const double* ctab2;  // lnl mode: pi*theta of the CURRENT params (ctab then holds the previous ones); MODE 4: of the PREVIOUS params
   double* lnl_out;      // lnl mode: one partial sum per workgroup [grid]
@@ -301,8 +303,8 @@ __device__ __forceinline__ double fz_logq_of(double q, const double* __restrict_
   return lqS[min(idx, (unsigned)(lq_n - 1))];              // (Q = 0, the padding: some finite entry; its z is 0)
 }
 
-struct FzRegs {            // 4 entries per thread: 12 VGPRs (packed index: 11; FMT 1: 6 until phase 1 turns the codes into numerators)
-  uint4 rc;                // packed index: the quad's three words in x, y, z (w is never read: no register)
+struct FzRegs {            // 4 entries per thread: 12 VGPRs (packed index: 11, quad index: 10; FMT 1: 6 until phase 1 turns the codes into numerators)
+  uint4 rc;                // packed index: the quad's three words in x, y, z (w is never read: no register); quad index: its two halves in x, y
   double2 v0, v1;
   uint2 cd;
 };
@@ -312,15 +314,26 @@ struct FzRegs {            // 4 entries per thread: 12 VGPRs (packed index: 11; 
 __host__ __device__ constexpr bool fz_idx24(int mode, int fmt) {
   return fmt != 1 && (mode == 0 || mode == 1 || mode == 2 || mode == 3 || mode == 9);
 }
+// The index format of an instantiation: one 32-bit word per entry, the 3-byte packed index, or the 8-byte quad index (tsem_quad64.h).
+// The quad index is a second instantiation of the passes that read a 3-byte layout outside option "reproducible" — the EM pass and
+// both forms of the lnl pass — on the geometries whose row slots fit its 9 bits; the layout build decides which of the two a layout
+// stores (tsem_setup.hip, h->quad64), the host launches the matching kernel.
+constexpr int FZ_IX32 = 0, FZ_IX24 = 1, FZ_IXQ = 2;
+__host__ __device__ constexpr int fz_index(int mode, int fmt) { return fz_idx24(mode, fmt) ? FZ_IX24 : FZ_IX32; }
+__host__ __device__ constexpr bool fz_quad_ok(int mode, int fmt, int geo) {
+  return fmt != 1 && (mode == 0 || mode == 1 || mode == 9) && fz_rmax(geo) <= TS_QUAD64_MAX_R;
+}
 // Row slot / column slot of entry K of a register set.  The packed index is unpacked HERE, at each use (phase 1, and again in
 // phase 2 four steps later), from the three words the load left: unpacked at the load, the issue would wait for the data.
 constexpr uint32_t FZ_IDLE = 0xFFFFFFFFu;                  // rc.x of a set that holds nothing (packed: row slot 2047, which no layout has)
-template <bool I24, int K> __device__ __forceinline__ uint32_t fz_row(const uint4& rc) {
-  if constexpr (I24) return ts_idx24_row<K>(rc.x, rc.y, rc.z);
+template <int IX, int K> __device__ __forceinline__ uint32_t fz_row(const uint4& rc) {
+  if constexpr (IX == FZ_IXQ) return ts_quad64_row<K>(rc.x, rc.y);
+  else if constexpr (IX == FZ_IX24) return ts_idx24_row<K>(rc.x, rc.y, rc.z);
   else return (K == 0 ? rc.x : (K == 1 ? rc.y : (K == 2 ? rc.z : rc.w))) >> 16;
 }
-template <bool I24, int K> __device__ __forceinline__ uint32_t fz_col(const uint4& rc) {
-  if constexpr (I24) return ts_idx24_col<K>(rc.x, rc.y, rc.z);
+template <int IX, int K> __device__ __forceinline__ uint32_t fz_col(const uint4& rc) {
+  if constexpr (IX == FZ_IXQ) return ts_quad64_col<K>(rc.x, rc.y);
+  else if constexpr (IX == FZ_IX24) return ts_idx24_col<K>(rc.x, rc.y, rc.z);
   else return (K == 0 ? rc.x : (K == 1 ? rc.y : (K == 2 ? rc.z : rc.w))) & 0xFFFFu;
 }
 
@@ -603,8 +616,9 @@ __device__ __forceinline__ void fz_xchg(const FusedArgs& A, const FzX& X) {
 
 // PROF: the timeline instantiation (option "fused_prof": tools/fused_prof.py, tools/startup_prof.py).  Every time stamp below sits under
 // `if constexpr (PROF)`: the kernels the product launches hold none of them, not even the test of A.prof.
-template <int PT, int MODE, int FMT, int GEO, bool PROF = false>
+template <int PT, int MODE, int FMT, int GEO, bool PROF = false, int IX = fz_index(MODE, FMT)>
 __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
+  static_assert(IX == fz_index(MODE, FMT) || (IX == FZ_IXQ && fz_quad_ok(MODE, FMT, GEO)), "no such index format for this pass");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int P = PT;
   constexpr int FZ_DT = fz_dt(GEO);
@@ -614,7 +628,6 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
   constexpr bool LAG = MODE == 4;                  // EM pass + the log-likelihood of the previous iteration
   constexpr bool LNL1 = MODE == 1 || MODE == 9;    // the dedicated log-likelihood pass; MODE 9: log tables in LDS (score table in LDS: FMT 1, 2)
   constexpr bool SPA = MODE == 5, SPB = MODE == 7, SPL = MODE == 8;   // split layout (see FusedArgs): ONE table of Kp entries, or two of Kh
-  constexpr bool I24 = fz_idx24(MODE, FMT);        // 3-byte packed entry index (else 4 B)
   const int KT = SPL ? A.Kh : Kp;                  // entries per LDS table
   double* c = reinterpret_cast<double*>(smem);
   double* acc = (SPA || SPB) ? c : c + KT;         // (MODE 5 has no accumulators, MODE 7 no pi*theta table)
@@ -780,7 +793,10 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
     auto load_blk = [&](FzRegs& rr, uint32_t oq0v, uint32_t oq1v, int64_t k) {
       const uint32_t oq0 = __builtin_amdgcn_readfirstlane(oq0v);
       const uint32_t nq = (k >= 0 && k < nblk) ? __builtin_amdgcn_readfirstlane(oq1v) - oq0 : 0u;
-      if constexpr (I24) {                                // the quad's index: 12 bytes, one load
+      if constexpr (IX == FZ_IXQ) {                       // the quad's index: one 8-byte word
+        fz_u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(fz_rsrc(A.prc, (uint64_t)oq0 * 8, nq * 8), (unsigned)tid * 8, 0, FZ_STREAM);
+        rr.rc = make_uint4(t.x, t.y, 0u, 0u);
+      } else if constexpr (IX == FZ_IX24) {               // the quad's index: 12 bytes, one load
         fz_u32x3 t = __builtin_amdgcn_raw_buffer_load_b96(fz_rsrc(A.prc, (uint64_t)oq0 * 12, nq * 12), (unsigned)tid * 12, 0, FZ_STREAM);
         rr.rc = make_uint4(t.x, t.y, t.z, 0u);
       } else {
@@ -822,18 +838,18 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
           q0 = make_double2(lutS[rr.cd.x & 0xFFFFu], lutS[rr.cd.x >> 16]);
           q1 = make_double2(lutS[rr.cd.y & 0xFFFFu], lutS[rr.cd.y >> 16]);
         }
-        m0 = q0.x * c[fz_col<I24, 0>(rr.rc)]; m1 = q0.y * c[fz_col<I24, 1>(rr.rc)];
-        m2 = q1.x * c[fz_col<I24, 2>(rr.rc)]; m3 = q1.y * c[fz_col<I24, 3>(rr.rc)];
+        m0 = q0.x * c[fz_col<IX, 0>(rr.rc)]; m1 = q0.y * c[fz_col<IX, 1>(rr.rc)];
+        m2 = q1.x * c[fz_col<IX, 2>(rr.rc)]; m3 = q1.y * c[fz_col<IX, 3>(rr.rc)];
         // EM: the set keeps the numerators for phase 2.  lnl: phase 2 needs Q itself (twice) — the fp64
         // layout has it in the set already, the code layout looks it up again (2 registers per set
         // instead of 8: with four log1p expansions in flight the lnl kernel would spill otherwise)
         if (!lnl) { rr.v0 = make_double2(m0, m1); rr.v1 = make_double2(m2, m3); }
       }
       if (A.sorted) {
-        fz_row_sums(yb, idle, fz_row<I24, 0>(rr.rc), fz_row<I24, 1>(rr.rc), fz_row<I24, 2>(rr.rc), fz_row<I24, 3>(rr.rc), m0, m1, m2, m3);
+        fz_row_sums(yb, idle, fz_row<IX, 0>(rr.rc), fz_row<IX, 1>(rr.rc), fz_row<IX, 2>(rr.rc), fz_row<IX, 3>(rr.rc), m0, m1, m2, m3);
       } else if (!idle) {                                  // strand-transposed order: neighbouring entries never share a row
-        lds_add(&yb[fz_row<I24, 0>(rr.rc)], m0); lds_add(&yb[fz_row<I24, 1>(rr.rc)], m1);
-        lds_add(&yb[fz_row<I24, 2>(rr.rc)], m2); lds_add(&yb[fz_row<I24, 3>(rr.rc)], m3);
+        lds_add(&yb[fz_row<IX, 0>(rr.rc)], m0); lds_add(&yb[fz_row<IX, 1>(rr.rc)], m1);
+        lds_add(&yb[fz_row<IX, 2>(rr.rc)], m2); lds_add(&yb[fz_row<IX, 3>(rr.rc)], m3);
       }
       if (idle) rr.rc.x = FZ_IDLE;
     };
@@ -869,10 +885,10 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
           };
           if (FMT == 1) {
             const uint32_t k0 = rr.cd.x & 0xFFFFu, k1 = rr.cd.x >> 16, k2 = rr.cd.y & 0xFFFFu, k3 = rr.cd.y >> 16;
-            const uint32_t j0 = fz_col<I24, 0>(rr.rc), j1 = fz_col<I24, 1>(rr.rc), j2 = fz_col<I24, 2>(rr.rc), j3 = fz_col<I24, 3>(rr.rc);
+            const uint32_t j0 = fz_col<IX, 0>(rr.rc), j1 = fz_col<IX, 1>(rr.rc), j2 = fz_col<IX, 2>(rr.rc), j3 = fz_col<IX, 3>(rr.rc);
             const double q0 = lutS[k0], q1 = lutS[k1], q2 = lutS[k2], q3 = lutS[k3];
-            const double z0 = (q0 * c[j0]) * sb[fz_row<I24, 0>(rr.rc)], z1 = (q1 * c[j1]) * sb[fz_row<I24, 1>(rr.rc)];
-            const double z2 = (q2 * c[j2]) * sb[fz_row<I24, 2>(rr.rc)], z3 = (q3 * c[j3]) * sb[fz_row<I24, 3>(rr.rc)];
+            const double z0 = (q0 * c[j0]) * sb[fz_row<IX, 0>(rr.rc)], z1 = (q1 * c[j1]) * sb[fz_row<IX, 1>(rr.rc)];
+            const double z2 = (q2 * c[j2]) * sb[fz_row<IX, 2>(rr.rc)], z3 = (q3 * c[j3]) * sb[fz_row<IX, 3>(rr.rc)];
             const bool lin = A.lq_lin != 0;                // (a kernel argument: wave-uniform)
             double l0, l1, l2, l3;
             bool f0 = false, f1 = false, f2 = false, f3 = false;
@@ -889,28 +905,28 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
             lsum = fma(z3, fz_log1p_of_log<true>(L3, [&]() { return q3 * cg[j3]; }, logtab, f3, z3 != 0.0), lsum);
           } else {
             pair(rr.v0.x, rr.v0.y, fz_logq_of(rr.v0.x, lqS, A.lq_n, A.lq_shift, A.lq_base), fz_logq_of(rr.v0.y, lqS, A.lq_n, A.lq_shift, A.lq_base),
-                 fz_row<I24, 0>(rr.rc), fz_row<I24, 1>(rr.rc), fz_col<I24, 0>(rr.rc), fz_col<I24, 1>(rr.rc));
+                 fz_row<IX, 0>(rr.rc), fz_row<IX, 1>(rr.rc), fz_col<IX, 0>(rr.rc), fz_col<IX, 1>(rr.rc));
             pair(rr.v1.x, rr.v1.y, fz_logq_of(rr.v1.x, lqS, A.lq_n, A.lq_shift, A.lq_base), fz_logq_of(rr.v1.y, lqS, A.lq_n, A.lq_shift, A.lq_base),
-                 fz_row<I24, 2>(rr.rc), fz_row<I24, 3>(rr.rc), fz_col<I24, 2>(rr.rc), fz_col<I24, 3>(rr.rc));
+                 fz_row<IX, 2>(rr.rc), fz_row<IX, 3>(rr.rc), fz_col<IX, 2>(rr.rc), fz_col<IX, 3>(rr.rc));
           }
           return;
         }
         if (FMT == 1) {
-          term(lutS[rr.cd.x & 0xFFFFu], fz_row<I24, 0>(rr.rc), fz_col<I24, 0>(rr.rc)); term(lutS[rr.cd.x >> 16], fz_row<I24, 1>(rr.rc), fz_col<I24, 1>(rr.rc));
-          term(lutS[rr.cd.y & 0xFFFFu], fz_row<I24, 2>(rr.rc), fz_col<I24, 2>(rr.rc)); term(lutS[rr.cd.y >> 16], fz_row<I24, 3>(rr.rc), fz_col<I24, 3>(rr.rc));
+          term(lutS[rr.cd.x & 0xFFFFu], fz_row<IX, 0>(rr.rc), fz_col<IX, 0>(rr.rc)); term(lutS[rr.cd.x >> 16], fz_row<IX, 1>(rr.rc), fz_col<IX, 1>(rr.rc));
+          term(lutS[rr.cd.y & 0xFFFFu], fz_row<IX, 2>(rr.rc), fz_col<IX, 2>(rr.rc)); term(lutS[rr.cd.y >> 16], fz_row<IX, 3>(rr.rc), fz_col<IX, 3>(rr.rc));
         } else {
-          term(rr.v0.x, fz_row<I24, 0>(rr.rc), fz_col<I24, 0>(rr.rc)); term(rr.v0.y, fz_row<I24, 1>(rr.rc), fz_col<I24, 1>(rr.rc));
-          term(rr.v1.x, fz_row<I24, 2>(rr.rc), fz_col<I24, 2>(rr.rc)); term(rr.v1.y, fz_row<I24, 3>(rr.rc), fz_col<I24, 3>(rr.rc));
+          term(rr.v0.x, fz_row<IX, 0>(rr.rc), fz_col<IX, 0>(rr.rc)); term(rr.v0.y, fz_row<IX, 1>(rr.rc), fz_col<IX, 1>(rr.rc));
+          term(rr.v1.x, fz_row<IX, 2>(rr.rc), fz_col<IX, 2>(rr.rc)); term(rr.v1.y, fz_row<IX, 3>(rr.rc), fz_col<IX, 3>(rr.rc));
         }
         return;
       }
       // all four gathers first: an LDS atomic may alias a later LDS read as far as the compiler knows,
       // so `add(acc, v * s[..])` four times in a row serialises gather -> wait -> atomic -> gather ...
-      const double s0 = sb[fz_row<I24, 0>(rr.rc)], s1 = sb[fz_row<I24, 1>(rr.rc)], s2 = sb[fz_row<I24, 2>(rr.rc)], s3 = sb[fz_row<I24, 3>(rr.rc)];
-      lds_add(&acc[fz_col<I24, 0>(rr.rc)], rr.v0.x * s0);
-      lds_add(&acc[fz_col<I24, 1>(rr.rc)], rr.v0.y * s1);
-      lds_add(&acc[fz_col<I24, 2>(rr.rc)], rr.v1.x * s2);
-      lds_add(&acc[fz_col<I24, 3>(rr.rc)], rr.v1.y * s3);
+      const double s0 = sb[fz_row<IX, 0>(rr.rc)], s1 = sb[fz_row<IX, 1>(rr.rc)], s2 = sb[fz_row<IX, 2>(rr.rc)], s3 = sb[fz_row<IX, 3>(rr.rc)];
+      lds_add(&acc[fz_col<IX, 0>(rr.rc)], rr.v0.x * s0);
+      lds_add(&acc[fz_col<IX, 1>(rr.rc)], rr.v0.y * s1);
+      lds_add(&acc[fz_col<IX, 2>(rr.rc)], rr.v1.x * s2);
+      lds_add(&acc[fz_col<IX, 3>(rr.rc)], rr.v1.y * s3);
     };
     FzRegs r0, r1, r2, r3, r4, r5;
     {
@@ -971,14 +987,14 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       // 4.30 ms, with the select deferred to phase 2 3.57 -> 3.73 ms (codes) / 4.09 -> 4.19 ms: the ballot, the
       // compares and the selects cost more issue slots than the two broadcast reads they save.)
       double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-      if (!SPA) { s0 = sb[fz_row<I24, 0>(a)]; s1 = sb[fz_row<I24, 1>(a)]; s2 = sb[fz_row<I24, 2>(a)]; s3 = sb[fz_row<I24, 3>(a)]; }
+      if (!SPA) { s0 = sb[fz_row<IX, 0>(a)]; s1 = sb[fz_row<IX, 1>(a)]; s2 = sb[fz_row<IX, 2>(a)]; s3 = sb[fz_row<IX, 3>(a)]; }
       double2 q0 = rp.v0, q1 = rp.v1;
       if (FMT == 1) {                                     // Q from the score table: the same fp64 the fp64 layout stores
         q0 = make_double2(lutS[rp.cd.x & 0xFFFFu], lutS[rp.cd.x >> 16]);
         q1 = make_double2(lutS[rp.cd.y & 0xFFFFu], lutS[rp.cd.y >> 16]);
       }
       double c0 = 1.0, c1 = 1.0, c2 = 1.0, c3 = 1.0;           // (MODE 7 scatters Q * s: the column's pi*theta is applied by k_colreduce)
-      if (!SPB) { c0 = c[fz_col<I24, 0>(rp.rc)]; c1 = c[fz_col<I24, 1>(rp.rc)]; c2 = c[fz_col<I24, 2>(rp.rc)]; c3 = c[fz_col<I24, 3>(rp.rc)]; }
+      if (!SPB) { c0 = c[fz_col<IX, 0>(rp.rc)]; c1 = c[fz_col<IX, 1>(rp.rc)]; c2 = c[fz_col<IX, 2>(rp.rc)]; c3 = c[fz_col<IX, 3>(rp.rc)]; }
       // ---- phase 1 of block i: numerators stay in the set, partial row sums into y(i) ----
       const double m0 = q0.x * c0, m1 = q0.y * c1, m2 = q1.x * c2, m3 = q1.y * c3;
       rp.v0 = make_double2(m0, m1); rp.v1 = make_double2(m2, m3);
@@ -987,11 +1003,11 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       if (SPB) {
         // no row sums in the scatter pass
       } else if (A.sorted) {
-        fz_row_sums(yb, idle, fz_row<I24, 0>(rp.rc), fz_row<I24, 1>(rp.rc), fz_row<I24, 2>(rp.rc), fz_row<I24, 3>(rp.rc), m0, m1, m2, m3);
+        fz_row_sums(yb, idle, fz_row<IX, 0>(rp.rc), fz_row<IX, 1>(rp.rc), fz_row<IX, 2>(rp.rc), fz_row<IX, 3>(rp.rc), m0, m1, m2, m3);
       } else {                                            // strand-transposed order: neighbouring entries never share a row
         double* d = dum + lane_id;
-        lds_add(idle ? d : &yb[fz_row<I24, 0>(rp.rc)], m0); lds_add(idle ? d : &yb[fz_row<I24, 1>(rp.rc)], m1);
-        lds_add(idle ? d : &yb[fz_row<I24, 2>(rp.rc)], m2); lds_add(idle ? d : &yb[fz_row<I24, 3>(rp.rc)], m3);
+        lds_add(idle ? d : &yb[fz_row<IX, 0>(rp.rc)], m0); lds_add(idle ? d : &yb[fz_row<IX, 1>(rp.rc)], m1);
+        lds_add(idle ? d : &yb[fz_row<IX, 2>(rp.rc)], m2); lds_add(idle ? d : &yb[fz_row<IX, 3>(rp.rc)], m3);
       }
       if (idle) rp.rc.x = FZ_IDLE;
       if constexpr (PROF) { if (pr) A.prof[i * FZ_PROF_SLOTS + 3] = clock64(); }
@@ -1000,8 +1016,8 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
       // ---- phase 2 of block i-LAG: w*z into the part's column accumulators; ALWAYS four atomics, issued last ----
       if (!SPA) {
         const uint32_t dj = (uint32_t)(dum - acc) + (uint32_t)lane_id;   // the lane's dummy slot as an index into acc[]
-        const uint32_t j0 = idle2 ? dj : fz_col<I24, 0>(a), j1 = idle2 ? dj : fz_col<I24, 1>(a);
-        const uint32_t j2 = idle2 ? dj : fz_col<I24, 2>(a), j3 = idle2 ? dj : fz_col<I24, 3>(a);
+        const uint32_t j0 = idle2 ? dj : fz_col<IX, 0>(a), j1 = idle2 ? dj : fz_col<IX, 1>(a);
+        const uint32_t j2 = idle2 ? dj : fz_col<IX, 2>(a), j3 = idle2 ? dj : fz_col<IX, 3>(a);
         if (EXACT) {
           // Exact accumulation (Demmel-Nguyen style pre-rounding on a per-slot grid): v = hi + lo + rest with hi a multiple of
           // 2^(E-30) and lo a multiple of 2^(E-60); the sums of the hi pieces (and of the lo pieces) of up to 2^23 contributions
@@ -1054,16 +1070,16 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
         };
         if (FMT == 1) {
           const double g0 = lutS[rp.cd.x & 0xFFFFu], g1 = lutS[rp.cd.x >> 16], g2 = lutS[rp.cd.y & 0xFFFFu], g3 = lutS[rp.cd.y >> 16];
-          const double p0 = cprev[fz_col<I24, 0>(e)], p1 = cprev[fz_col<I24, 1>(e)], p2 = cprev[fz_col<I24, 2>(e)], p3 = cprev[fz_col<I24, 3>(e)];
-          const double f0 = rb[fz_row<I24, 0>(e)], f1 = rb[fz_row<I24, 1>(e)], f2 = rb[fz_row<I24, 2>(e)], f3 = rb[fz_row<I24, 3>(e)];
+          const double p0 = cprev[fz_col<IX, 0>(e)], p1 = cprev[fz_col<IX, 1>(e)], p2 = cprev[fz_col<IX, 2>(e)], p3 = cprev[fz_col<IX, 3>(e)];
+          const double f0 = rb[fz_row<IX, 0>(e)], f1 = rb[fz_row<IX, 1>(e)], f2 = rb[fz_row<IX, 2>(e)], f3 = rb[fz_row<IX, 3>(e)];
           term(g0, p0, f0, m0); term(g1, p1, f1, m1); term(g2, p2, f2, m2); term(g3, p3, f3, m3);
         } else {                                          // fp64 entries keep Q alive (8 VGPRs): two entries per round trip
           {
-            const double p0 = cprev[fz_col<I24, 0>(e)], p1 = cprev[fz_col<I24, 1>(e)], f0 = rb[fz_row<I24, 0>(e)], f1 = rb[fz_row<I24, 1>(e)];
+            const double p0 = cprev[fz_col<IX, 0>(e)], p1 = cprev[fz_col<IX, 1>(e)], f0 = rb[fz_row<IX, 0>(e)], f1 = rb[fz_row<IX, 1>(e)];
             term(q0.x, p0, f0, m0); term(q0.y, p1, f1, m1);
           }
           {
-            const double p2 = cprev[fz_col<I24, 2>(e)], p3 = cprev[fz_col<I24, 3>(e)], f2 = rb[fz_row<I24, 2>(e)], f3 = rb[fz_row<I24, 3>(e)];
+            const double p2 = cprev[fz_col<IX, 2>(e)], p3 = cprev[fz_col<IX, 3>(e)], f2 = rb[fz_row<IX, 2>(e)], f3 = rb[fz_row<IX, 3>(e)];
             term(q1.x, p2, f2, m2); term(q1.y, p3, f3, m3);
           }
         }

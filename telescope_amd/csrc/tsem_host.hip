@@ -204,6 +204,14 @@ int tsem_set_option(tsem_ctx* h, const char* key, int64_t v) {
   else if (k == "hot_split") h->opt_hot_split = v;
   else if (k == "geometry") h->opt_geo = v;
   else if (k == "sorted_fill") h->opt_sorted = v;
+  else if (k == "index_format") {                          // index of fp64 entries under the fused kernel: 0 auto, 1 three bytes per entry, 2 the 8-byte quad index
+    if (v < 0 || v > 2) TSEM_FAIL(TSEM_ERR_ARG, "index_format must be 0 (auto), 1 (3-byte index) or 2 (quad index)");
+    h->opt_index = v;
+  }
+  else if (k == "index_auto_min_bytes") {                  // index_format = 0: the smallest 3-byte stream (11 B x entries) that takes the quad index
+    if (v < 0) TSEM_FAIL(TSEM_ERR_ARG, "index_auto_min_bytes must be a number of bytes");
+    h->opt_quad_min_bytes = v;
+  }
   else if (k == "deconflict") h->opt_deconflict = v;
   else if (k == "reproducible") h->opt_reproducible = v;
   else if (k == "em_precision") h->opt_precision = v;
@@ -510,7 +518,7 @@ int tsem_kernel_stats(tsem_ctx* h, int reset, double* em_ms, int64_t* em_launche
   // one EM pass must read every stored entry of the ambiguous rows once:
   // 4 B packed local row/col + the value AS STORED (8 B fp64 Q, or a 2 B score code) per entry,
   // + 2 B row weight code per row
-  if (algo_bytes) *algo_bytes = h->nnz_amb * (h->fmt_code ? 6 : (h->idx24 ? 11 : 12)) + h->N_amb * 2;
+  if (algo_bytes) *algo_bytes = h->nnz_amb * (h->fmt_code ? 6 : (h->quad64 ? 10 : (h->idx24 ? 11 : 12))) + h->N_amb * 2;
   if (reset) { h->em_ms_acc = 0; h->em_launches = 0; h->em_timed = 0; }
   return TSEM_OK;
 }
@@ -544,7 +552,7 @@ int tsem_device_memory(tsem_ctx* h, int device, int64_t* free_bytes, int64_t* to
     resident5[0] = h->d_indptr ? 8 * (h->N + 1) + (h->d_raw ? 2 * nz : 0) : 0;
     resident5[1] = h->d_indices ? 4 * nz : 0;
     resident5[2] = h->d_rid16 ? 2 * nz : 0;
-    resident5[3] = (h->d_prc ? (h->idx24 ? 3 : 4) * h->nnz_pad : 0) + (h->d_pcode ? 2 * h->nnz_pad : 0) + (h->d_pval ? 8 * h->nnz_pad : 0) +
+    resident5[3] = (h->d_prc ? (h->quad64 ? 2 : (h->idx24 ? 3 : 4)) * h->nnz_pad : 0) + (h->d_pcode ? 2 * h->nnz_pad : 0) + (h->d_pval ? 8 * h->nnz_pad : 0) +
                    (h->d_sb_off ? 12 * (h->nb * h->P + 2) : 0);
     resident5[4] = (h->d_row_code ? 3 * h->N : 0) + (h->d_amb_row ? 6 * h->N_amb : 0) + (h->d_slot_row ? 6 * h->N_amb_pad : 0) +
                    (h->d_uni_col ? 6 * h->N_uni : 0) + (h->d_amb_w ? 8 * h->N_amb_pad : 0) + (h->d_rinv ? 8 * h->N_amb_pad : 0) +
@@ -693,6 +701,17 @@ int64_t tsem_debug_subblock(tsem_ctx* h, int64_t block, int32_t part, uint32_t* 
   int64_t o[2];
   if (hipMemcpy(o, h->d_sb_off + block * h->P + part, 16, hipMemcpyDeviceToHost) != hipSuccess) return TSEM_ERR_HIP;
   const int64_t n = std::min(cap, o[1] - o[0]);
+  if (h->quad64) {                                         // one 64-bit word per quad, through the shared unpack
+    const int64_t nq = (n + 3) / 4;
+    std::vector<uint64_t> raw((size_t)std::max<int64_t>(1, nq));
+    if (nq > 0 && hipMemcpy(raw.data(), reinterpret_cast<const uint8_t*>(h->d_prc) + o[0] * 2, (size_t)nq * 8, hipMemcpyDeviceToHost) != hipSuccess) return TSEM_ERR_HIP;
+    for (int64_t q = 0; q < nq; ++q) {
+      uint32_t rc[4];
+      ts_quad64_unpack_words(raw[q], rc);
+      for (int k = 0; k < 4 && q * 4 + k < n; ++k) out[q * 4 + k] = rc[k];
+    }
+    return n;
+  }
   if (h->idx24) {                                          // 3 bytes per entry: whole quads through the shared unpack (sub-blocks are multiples of 64 entries)
     const int64_t nq = (n + 3) / 4;
     std::vector<uint8_t> raw((size_t)std::max<int64_t>(1, nq * 12));
@@ -759,6 +778,17 @@ int tsem_debug_idx24(const uint32_t* rc4, uint8_t* out12, uint32_t* back4) {
   return TSEM_OK;
 }
 
+/* host only: four lrow << 16 | lcol words through the quad index of tsem_quad64.h — *word the 64-bit word, back4 the words unpacked
+ * from it again; TSEM_ERR_ARG for a quad the format cannot hold (a row step other than 0 or 1, r0 >= 512, a column >= 8191).
+ * *stored: whether `probe` — any 64-bit word, e.g. one whose low half is the fused kernel's idle mark — names a stored quad */
+int tsem_debug_quad64(const uint32_t* rc4, uint64_t* word, uint32_t* back4, uint64_t probe, int32_t* stored) {
+  if (!rc4 || !word || !back4) return TSEM_ERR_ARG;
+  if (stored) *stored = ts_quad64_stored(probe) ? 1 : 0;
+  if (!ts_quad64_pack_words(rc4, word)) return TSEM_ERR_ARG;
+  ts_quad64_unpack_words(*word, back4);
+  return TSEM_OK;
+}
+
 /* the 32 values every caller's buffer has room for; values appended since come through tsem_layout_info_n */
 int tsem_layout_info(tsem_ctx* h, int64_t* info) {
   return tsem_layout_info_n(h, info, 32);
@@ -767,7 +797,11 @@ int tsem_layout_info(tsem_ctx* h, int64_t* info) {
 int tsem_layout_info_n(tsem_ctx* h, int64_t* out, int32_t n) {
   if (!h || !out || n < 0) return TSEM_ERR_ARG;
   int64_t info[TSEM_LAYOUT_INFO_N] = {};
-  info[32] = h->idx24 ? 3 : 4;                             // bytes of index per stored entry (3: the packed index of tsem_idx24.h)
+  info[32] = h->quad64 ? 2 : (h->idx24 ? 3 : 4);           // bytes of index per stored entry (3: the packed index of tsem_idx24.h, 2: the quad index of tsem_quad64.h)
+  info[40] = h->quad64 ? 2 : (h->idx24 ? 1 : 0);           // the index format in use, as fz_index(): 0 one word per entry, 1 three bytes, 2 the quad index
+  info[41] = h->quad_slots ? h->n_dummies : 0;             // dummy entries (column slot 0, value 0) that give every row an entry in every part: in nnz_pad, not in nnz_amb
+  info[42] = h->n_quad_bad;                                // quads the pack kernel could not represent (0 by construction; otherwise the layout kept the 3-byte index)
+  info[43] = h->opt_quad_min_bytes;                        // option "index_auto_min_bytes"
   for (int k = 0; k < 4; ++k) info[33 + k] = h->ce_class_n[k];   // cells per class of the last tsem_cell_em (tsem_cellem.hip; 0 before a fit)
   info[37] = h->ce_spread_n;                               // ... and the groups it spread over the grid (in none of the four)
   info[38] = h->rowstats_G; info[39] = h->colsig_G;        // lanes per row of the last k_rowstats / k_colsig (tsem_rowstats; 0: none launched)

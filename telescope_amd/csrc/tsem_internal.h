@@ -138,24 +138,29 @@ static inline int ensure_device(tsem_ctx* h) {
 // live in eight translation units compiled in parallel (tsem_fz_p1.hip ... tsem_fz_p8.hip, tsem_fused_inst.h); each exports one
 // look-up function.  The host launches through the pointer.
 typedef void (*fz_fn)(FusedArgs);
-fz_fn tsem_fz_kernel_p1(int P, int mode, int fmt, int geo, bool prof);
-fz_fn tsem_fz_kernel_p2(int P, int mode, int fmt, int geo, bool prof);
-fz_fn tsem_fz_kernel_p3(int P, int mode, int fmt, int geo, bool prof);
-fz_fn tsem_fz_kernel_p4(int P, int mode, int fmt, int geo, bool prof);
-fz_fn tsem_fz_kernel_p5(int P, int mode, int fmt, int geo, bool prof);
-fz_fn tsem_fz_kernel_p6(int P, int mode, int fmt, int geo, bool prof);
-fz_fn tsem_fz_kernel_p7(int P, int mode, int fmt, int geo, bool prof);
-fz_fn tsem_fz_kernel_p8(int P, int mode, int fmt, int geo, bool prof);
+fz_fn tsem_fz_kernel_p1(int P, int mode, int fmt, int geo, bool prof, bool quad);
+fz_fn tsem_fz_kernel_p2(int P, int mode, int fmt, int geo, bool prof, bool quad);
+fz_fn tsem_fz_kernel_p3(int P, int mode, int fmt, int geo, bool prof, bool quad);
+fz_fn tsem_fz_kernel_p4(int P, int mode, int fmt, int geo, bool prof, bool quad);
+fz_fn tsem_fz_kernel_p5(int P, int mode, int fmt, int geo, bool prof, bool quad);
+fz_fn tsem_fz_kernel_p6(int P, int mode, int fmt, int geo, bool prof, bool quad);
+fz_fn tsem_fz_kernel_p7(int P, int mode, int fmt, int geo, bool prof, bool quad);
+fz_fn tsem_fz_kernel_p8(int P, int mode, int fmt, int geo, bool prof, bool quad);
 static inline int fz_fmt(const tsem_ctx* h) { return h->fmt_code ? 1 : (h->fmt_wcode ? 2 : 0); }
-static inline fz_fn fz_kernel(int P, int mode, int fmt, int geo, bool prof = false) {
+// quad: the instantiation that reads the 8-byte quad index (a layout with h->quad64; tsem_quad64.h) — callers pass fz_quad(h, mode)
+static inline fz_fn fz_kernel(int P, int mode, int fmt, int geo, bool prof = false, bool quad = false) {
   switch (P) {
-    case 1: return tsem_fz_kernel_p1(P, mode, fmt, geo, prof); case 2: return tsem_fz_kernel_p2(P, mode, fmt, geo, prof);
-    case 3: return tsem_fz_kernel_p3(P, mode, fmt, geo, prof); case 4: return tsem_fz_kernel_p4(P, mode, fmt, geo, prof);
-    case 5: return tsem_fz_kernel_p5(P, mode, fmt, geo, prof); case 6: return tsem_fz_kernel_p6(P, mode, fmt, geo, prof);
-    case 7: return tsem_fz_kernel_p7(P, mode, fmt, geo, prof); case 8: return tsem_fz_kernel_p8(P, mode, fmt, geo, prof);
+    case 1: return tsem_fz_kernel_p1(P, mode, fmt, geo, prof, quad); case 2: return tsem_fz_kernel_p2(P, mode, fmt, geo, prof, quad);
+    case 3: return tsem_fz_kernel_p3(P, mode, fmt, geo, prof, quad); case 4: return tsem_fz_kernel_p4(P, mode, fmt, geo, prof, quad);
+    case 5: return tsem_fz_kernel_p5(P, mode, fmt, geo, prof, quad); case 6: return tsem_fz_kernel_p6(P, mode, fmt, geo, prof, quad);
+    case 7: return tsem_fz_kernel_p7(P, mode, fmt, geo, prof, quad); case 8: return tsem_fz_kernel_p8(P, mode, fmt, geo, prof, quad);
     default: return nullptr;
   }
 }
+
+// does pass `mode` of this layout read the quad index?  (a quad layout exists only where every pass that reads it has the kernel:
+// layout_decide_format)
+static inline bool fz_quad(const tsem_ctx* h, int mode) { return h->quad64 && (mode == 0 || mode == 1 || mode == 9); }
 
 // code16 entry format: only with the fused kernel, and only while the score table is small enough to
 // sit in LDS beside the column tables (uint16 scores allow 65536 entries; alignments give a few hundred).

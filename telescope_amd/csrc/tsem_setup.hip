@@ -347,6 +347,48 @@ __global__ __launch_bounds__(256) void k_single_part_rows(int64_t na, const unsi
   const int t = sg_sum_i<64>((int)n);
   if ((threadIdx.x & 63) == 0 && t) atomicAdd(out, (unsigned long long)t);
 }
+// Quad index (tsem_quad64.h): a quad's rows may step by 0 or 1 from entry to entry, so every row of a block must have an entry in every
+// part's sub-block.  Everything downstream of the per-row part counts — the block boundaries, the sub-block sizes, the fill's cursors —
+// derives from them, so the empty (row, part) cells are counted (raise = 0: out[0] the cells, out[1] the entries) and then set to 1
+// (raise = 1); k_sb_fill_sorted writes a dummy entry (column slot 0, value 0: what padding is) into each.  Rows without any entry
+// stay as they are.
+__global__ __launch_bounds__(256) void k_pc_raise(int64_t na, int P, unsigned long long* __restrict__ pc, int raise,
+    unsigned long long* __restrict__ out) {
+  unsigned empty = 0, entries = 0;
+  for (int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < na; a += (int64_t)gridDim.x * blockDim.x) {
+    unsigned long long w[2] = {pc[2 * a], pc[2 * a + 1]};
+    if ((w[0] | w[1]) == 0ull) continue;
+    bool changed = false;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      if (q >= P) break;
+      const unsigned c = (unsigned)((w[q >> 2] >> (16 * (q & 3))) & 0xFFFF);
+      entries += c;
+      if (c == 0u) { empty += 1u; w[q >> 2] |= 1ull << (16 * (q & 3)); changed = true; }
+    }
+    if (raise && changed) { pc[2 * a] = w[0]; pc[2 * a + 1] = w[1]; }
+  }
+  const int te = sg_sum_i<64>((int)empty);
+  const unsigned long long tn = (unsigned long long)sg_sum_i<64>((int)(entries & 0xFFFFu)) + ((unsigned long long)sg_sum_i<64>((int)(entries >> 16)) << 16);
+  if (!raise && (threadIdx.x & 63) == 0) { if (te) atomicAdd(&out[0], (unsigned long long)te); if (tn) atomicAdd(&out[1], tn); }
+}
+// the staged 3-byte index of a row-ordered layout -> one 64-bit word per quad (one thread per quad); bad[0] counts the quads that do
+// not fit the format (their word is 0).  By construction there are none: the count is what tells a fault in the set-up apart.
+__global__ __launch_bounds__(256) void k_quad_pack(int64_t nquads, const uint32_t* __restrict__ stage, unsigned long long* __restrict__ out,
+    unsigned long long* __restrict__ bad) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int miss = 0;
+  if (t < nquads) {
+    const uint32_t w0 = stage[3 * t], w1 = stage[3 * t + 1], w2 = stage[3 * t + 2];
+    const uint32_t row[4] = {ts_idx24_row<0>(w0, w1, w2), ts_idx24_row<1>(w0, w1, w2), ts_idx24_row<2>(w0, w1, w2), ts_idx24_row<3>(w0, w1, w2)};
+    const uint32_t col[4] = {ts_idx24_col<0>(w0, w1, w2), ts_idx24_col<1>(w0, w1, w2), ts_idx24_col<2>(w0, w1, w2), ts_idx24_col<3>(w0, w1, w2)};
+    const bool ok = ts_quad64_fits(row, col);
+    out[t] = ok ? (unsigned long long)ts_quad64_pack(row, col) : 0ull;
+    miss = ok ? 0 : 1;
+  }
+  const int tm = sg_sum_i<64>(miss);
+  if ((threadIdx.x & 63) == 0 && tm) atomicAdd(bad, (unsigned long long)tm);
+}
 __global__ void k_fixed_blocks(int64_t nb, int R, int64_t na, int64_t* __restrict__ bstart) {
   int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b <= nb) bstart[b] = min(na, b * R);
@@ -441,7 +483,8 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
     const int64_t* __restrict__ bstart, const unsigned long long* __restrict__ pc,
     const uint16_t* __restrict__ rid /* popularity ids (slot * P + part) instead of the column-map gather, or null */,
     uint32_t magicP /* ceil(2^32 / P) */, int nsplit /* ids below this may be split columns */, const uint8_t* __restrict__ lgtab,
-    int idx24 /* store the 3-byte packed index (sb_store_index) */, int valmap /* fp64 values at their slot of tsem_valmap.h */) {
+    int idx24 /* store the 3-byte packed index (sb_store_index) */, int valmap /* fp64 values at their slot of tsem_valmap.h */,
+    int dummies /* k_pc_raise reserved a slot in every part for every row: fill the ones no real entry takes */) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fl_lds[];
   uint32_t* const cnt = reinterpret_cast<uint32_t*>(fl_lds);                   // [row slot][part]: counts, then write cursors
   int64_t* const rstart = reinterpret_cast<int64_t*>(cnt + ((R * P + 1) & ~1));   // [row slot] first entry of the row in the CSR
@@ -536,6 +579,19 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
       sb_store_index(prc, pos, (uint32_t)lr, (cm & CM_SM) + (t & ((1u << ((cm >> CM_LS) & 7u)) - 1u)), idx24);   // hot column: deal over its slots
     }
   };
+  // quad index: behind a row's entries, one dummy (this row slot, column slot 0, value 0: what padding is, and as harmless — +0.0 to
+  // the row sum, 0 * s to column slot 0) for each part in which the row has no real entry.  `run` holds the row's real counts per part
+  // (the same in all 16 lanes); the raised count reserved exactly one position at the part's cursor.  Lane q serves part q.
+  auto fill_dummies = [&](int lr, const unsigned long long (&run)[2]) {
+    if (!dummies || rlen[lr] == 0 || lane >= P) return;
+    const uint32_t real = (uint32_t)(run[lane >> 2] >> ((lane & 3) * 16)) & 0xFFFFu;
+    if (real != 0u) return;
+    const uint32_t t = cnt[lr * P + lane];
+    const int64_t pos = sbase[lane] + t;
+    if (pcode) pcode[pos] = (uint16_t)0;
+    else pval[sbase[lane] + ts_valmap_slot(t, snq[lane], valmap)] = 0.0;
+    sb_store_index(prc, pos, (uint32_t)lr, 0u, idx24);
+  };
   auto cm_of_id = [&](uint32_t id) -> uint32_t {           // the ids k_row_partcounts wrote: a coalesced 2-byte read instead of a gather
     const uint32_t slot = P == 1 ? id : __umulhi(id, magicP);   // id / P, exact for 16-bit ids and 2 <= P <= 8 (ceil(2^32 / 1) does not fit 32 bits)
     const uint32_t lg = (int)id < nsplit ? (uint32_t)lgtab[id] : 0u;
@@ -566,6 +622,7 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
         const uint32_t id = valid ? (uint32_t)rid[s0 + k0 + lane] : 0u;
         place(lr, run, valid, cm_of_id(id), valid ? (uint32_t)raw[s0 + k0 + lane] : 0u);
       }
+      fill_dummies(lr, run);
     }
   } else {
     for (int lr = sub; lr < R; lr += subs) {
@@ -576,6 +633,7 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
         const bool valid = k0 + lane < len;
         place(lr, run, valid, valid ? colmap[indices[s0 + k0 + lane]] : 0u, valid ? (uint32_t)raw[s0 + k0 + lane] : 0u);
       }
+      fill_dummies(lr, run);
     }
   }
   for (int p = 0; p < P; ++p) {                            // padding: value 0 (written here: the buffers of this path are not zero-filled), row = last row
@@ -1160,6 +1218,7 @@ static int layout_identity_map(tsem_ctx* h) {
   h->nb = 0; h->N_amb_pad = 1; h->nnz_pad = 0; h->max_subblock = 0; h->n_hot_cols = 0;
   h->nnz_amb = h->nnz - h->N_uni;
   h->fmt_code = h->fmt_wcode = false; h->sorted_layout = false; h->idx24 = false; h->valmap = false;
+  h->quad64 = false; h->quad_slots = false; h->n_dummies = 0; h->n_quad_bad = 0;
   h->G1 = h->G2 = 1;
   return TSEM_OK;
 }
@@ -1229,6 +1288,19 @@ static int layout_column_map(tsem_ctx* h, LayoutBuild& b) {
   return TSEM_OK;
 }
 
+// Can this build store the quad index (tsem_quad64.h), as far as the geometry and the options say?  Asked before the blocks are cut
+// (the dummies must be in the counts the blocks derive from) and again when the format is decided: the fused kernel reading fp64
+// entries of a non-split, row-ordered layout, outside option "reproducible", row slots within 9 bits (geometry 0 or 1), and a kernel
+// for every pass that reads the layout.  Nothing here depends on the matrix: the dummy cap and the size rule follow the count.
+static bool quad_possible(const tsem_ctx* h) {
+  if (h->opt_index == 1 || !h->use_fused || h->split || h->opt_reproducible || h->P > FZ_MAX_P) return false;
+  if (h->geo > 1 || h->R > TS_QUAD64_MAX_R || h->Kp >= TS_QUAD64_MAX_KP) return false;
+  if (fz_wants_codes(h) && fz_lds_bytes(h, true) <= (size_t)TS_LDS_MAX - 1024) return false;          // score codes (layout_decide_format)
+  if (!(h->R * h->P <= FILL_MAX_RP && (h->opt_sorted >= 0 ? h->opt_sorted != 0 : true))) return false;   // row order
+  const int fmt = (h->lut_len > 0 && h->lut_len <= 2048 && fz_lds_bytes(h, true) <= (size_t)TS_LDS_MAX - 1024) ? 2 : 0;
+  return fz_kernel(h->P, 0, fmt, h->geo, false, true) != nullptr && fz_kernel(h->P, 1, fmt, h->geo, false, true) != nullptr;
+}
+
 // the fused layout's blocks (no part may exceed FZ_CAP entries, at most R rows); a row that overflows the tile: use_fused goes, no b.d_bs
 static int layout_greedy_blocks(tsem_ctx* h, LayoutBuild& b, int64_t& nb) {
   const int K = h->K, P = h->P, R = h->R;
@@ -1259,6 +1331,26 @@ static int layout_greedy_blocks(tsem_ctx* h, LayoutBuild& b, int64_t& nb) {
   TSEM_HIP(hipMemcpyAsync(&nsp, t_sp.p, 8, hipMemcpyDeviceToHost, h->stream));
   TSEM_HIP(hipStreamSynchronize(h->stream));
   h->n_single_part = (int64_t)nsp;
+  if (quad_possible(h)) {
+    // the empty (row, part) cells: option "index_format" = 2 takes the quad index whatever they cost; auto takes it when they stay
+    // within 0.5 % of the entries and the 3-byte stream is one that HBM certainly serves
+    DevTmp t_q;
+    TSEM_TMP(t_q, 16);
+    TSEM_HIP(hipMemsetAsync(t_q.p, 0, 16, h->stream));
+    const unsigned qgrid = (unsigned)std::min<int64_t>(4096, (na + 255) / 256);
+    k_pc_raise<<<qgrid, 256, 0, h->stream>>>(na, P, b.d_pc, 0, t_q.as<unsigned long long>());
+    unsigned long long cells[2] = {0, 0};
+    TSEM_HIP(hipMemcpyAsync(cells, t_q.p, 16, hipMemcpyDeviceToHost, h->stream));
+    TSEM_HIP(hipStreamSynchronize(h->stream));
+    const bool take = h->opt_index == 2 ||
+                      (cells[0] * 200ull <= cells[1] && (long double)cells[1] * 11.0L >= (long double)h->opt_quad_min_bytes);
+    if (take) {
+      k_pc_raise<<<qgrid, 256, 0, h->stream>>>(na, P, b.d_pc, 1, t_q.as<unsigned long long>());
+      TSEM_HIP(hipGetLastError());
+      h->quad_slots = true;
+      h->n_dummies = (int64_t)cells[0];
+    }
+  }
   const int cap = fz_cap(h->geo) - TS_STRANDS * 4;          // sub-blocks are padded to TS_STRANDS*4 entries
   // chunk length: >= 64 blocks' worth of rows (the forced break at a chunk end costs ~0.8 % more blocks; round 2 used 256 blocks' worth,
   // 484 sequential waves for 47M rows: 2 x 2.5 ms; four times as many waves walk a quarter each)
@@ -1277,7 +1369,7 @@ static int layout_greedy_blocks(tsem_ctx* h, LayoutBuild& b, int64_t& nb) {
   TSEM_HIP(hipMemcpyAsync(&nb, d_off + nch, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
   TSEM_HIP(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   TSEM_HIP(hipStreamSynchronize(h->stream));
-  if (flag) { h->use_fused = false; nb = 0; }              // one row overflows the register tile
+  if (flag) { h->use_fused = false; nb = 0; h->quad_slots = false; h->n_dummies = 0; }   // one row overflows the register tile (the raised counts go with b.d_pc)
   if (h->use_fused) {
     TSEM_ALLOC(b.d_bs, nb + 1);
     k_block_greedy<<<(unsigned)nch, 64, 0, h->stream>>>(na, P, R, cap, L, 1, b.d_pc, d_cnt, d_off, b.d_bs, d_flag);
@@ -1350,7 +1442,7 @@ static int layout_subblock_offsets(tsem_ctx* h, LayoutBuild& b) {
   } else {
     TSEM_HIP(hipMemsetAsync(h->d_sb_off, 0, 8, h->stream));
   }
-  h->nnz_amb += (int64_t)st[1];
+  h->nnz_amb += (int64_t)st[1] - (h->quad_slots ? h->n_dummies : 0);   // (the raised counts hold the dummies: stored, not entries of the matrix)
   h->nnz_pad = off;
   if (h->use_fused) {
     h->max_subblock = (int64_t)st[0];
@@ -1395,6 +1487,13 @@ static int layout_decide_format(tsem_ctx* h) {
   // row 2.70 -> 2.48 (profiles/r02_sweep.txt, r02_sweep_short.txt).
   h->sorted_layout = h->use_fused && R * h->P <= FILL_MAX_RP &&   // (the fill kernel keeps R x P counters in LDS)
                      (h->opt_sorted >= 0 ? h->opt_sorted != 0 : true);
+  // The quad index (2 B per entry, tsem_quad64.h) where this build reserved a slot for every (row, part) cell and everything asked
+  // before the blocks were cut still holds.  The fill stages the 3-byte index (idx24 stays set until the pack kernel has replaced it).
+  h->quad64 = h->quad_slots && h->idx24 && h->sorted_layout && quad_possible(h) && h->nb > 0;
+  h->n_quad_bad = 0;
+  if (h->opt_index == 2 && !h->quad64)
+    TSEM_FAIL(TSEM_ERR_ARG, "index_format=2 (quad index) needs the fused kernel on fp64 entries (value_format=1 or a score table too large for LDS) "
+                            "of a non-split, row-ordered layout with at most 512 row slots per block (geometry 0 or 1), and not option reproducible");
   return TSEM_OK;
 }
 
@@ -1446,8 +1545,21 @@ static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
     k_sb_fill_sorted<<<(unsigned)nb, 256, fill_lds_bytes(R, P), h->stream>>>(na, R, P, h->d_slot_row, h->d_indptr, h->d_indices, h->d_raw, h->d_lut,
                                                          h->d_colmap, h->d_sb_off, h->d_pval, h->d_pcode, h->d_prc,
                                                          b.d_pc ? b.d_bs : nullptr, b.d_pc, rid_fill, magicP, nsplit, d_lgtab, h->idx24 ? 1 : 0,
-                                                         h->valmap ? 1 : 0);
+                                                         h->valmap ? 1 : 0, (h->quad_slots && b.d_pc) ? 1 : 0);
     TSEM_HIP(hipGetLastError());
+    // quad index: entries were placed one at a time from many threads, and 13-bit fields share bytes — so the fill wrote whole bytes
+    // (the 3-byte form) and one thread per quad now writes the final words.  3 + 2 B of index per entry are resident until the
+    // staging array goes: the peak of the set-up.
+    uint32_t* d_quad = nullptr;
+    TSEM_SCOPED(d_quad);
+    DevTmp t_bad;
+    if (h->quad64) {
+      TSEM_TMP(t_bad, 8);
+      TSEM_HIP(hipMemsetAsync(t_bad.p, 0, 8, h->stream));
+      TSEM_ALLOC(d_quad, off / 2);                         // (8 B per quad)
+      k_quad_pack<<<cdiv64(off / 4, 256), 256, 0, h->stream>>>(off / 4, h->d_prc, reinterpret_cast<unsigned long long*>(d_quad), t_bad.as<unsigned long long>());
+      TSEM_HIP(hipGetLastError());
+    }
     if (deconflict) {
       const int64_t n_win = off / 64;
       k_sb_deconflict<<<(unsigned)std::min<int64_t>(n_win / DC_NT + 1, (int64_t)h->n_cu * 32), DC_NT, 0, h->stream>>>(
@@ -1456,10 +1568,17 @@ static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
     }
     // While the device fills the layout (15 ms at 2e9 entries) the host loads the code object of the fused kernel's unit — 3 ms in a
     // fresh process, at the first hipFuncSetAttribute / launch of one of its kernels — instead of doing so afterwards.
-    fz_fn f0 = P <= FZ_MAX_P ? fz_kernel(P, h->split ? 5 : 0, fz_fmt(h), h->geo) : nullptr;
+    fz_fn f0 = P <= FZ_MAX_P ? fz_kernel(P, h->split ? 5 : 0, fz_fmt(h), h->geo, false, fz_quad(h, 0)) : nullptr;
     if (f0) (void)hipFuncSetAttribute((const void*)f0, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024);   // (a preload: its error is the later call's)
     tsem_report_preload();                                 // (round 6: the report unit's too — ~10 ms that used to sit in the first report)
     TSEM_HIP(hipStreamSynchronize(h->stream));
+    if (h->quad64) {
+      unsigned long long bad = 0;
+      TSEM_HIP(hipMemcpy(&bad, t_bad.p, 8, hipMemcpyDeviceToHost));
+      h->n_quad_bad = (int64_t)bad;
+      if (bad == 0) { dfree(h->d_prc); h->d_prc = d_quad; d_quad = nullptr; h->idx24 = false; }
+      else h->quad64 = false;             // (0 by construction; the staging array is a complete 3-byte index: it stays)
+    }
     // option "drop_csr_indices": the fill was the last reader of the CSR column ids (the report pass and this layout carry 2-byte
     // popularity ids; col = col_of_id[id]): 10 instead of 14 B per stored entry stay resident.
     if (rid_fill && h->d_col_of_id && drops_indices(h)) dfree(h->d_indices);
@@ -1505,7 +1624,7 @@ static int layout_launch_buffers(tsem_ctx* h) {
     TSEM_HIP(hipMemsetAsync(h->d_rinv, 0, sizeof(double) * h->N_amb_pad, h->stream));
   } else
     for (int mode = 0; mode < 2; ++mode)
-      if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, mode, fmt, geo))) return rc;
+      if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, mode, fmt, geo, false, fz_quad(h, mode)))) return rc;
   if (h->lnl3 && !(h->fmt_code && fz_kernel(P, 4, fmt, geo))) h->lnl3 = false;   // (not score codes after all: the per-iteration lnl pass stays)
   h->lag_valid = false;
   if (h->lnl3) {
@@ -1533,6 +1652,7 @@ int tsem_build_layout(tsem_ctx* h) {
   tsem_free_layout(h);
   h->nnz_amb = 0;
   h->n_single_part = 0;
+  h->quad_slots = false; h->n_dummies = 0; h->n_quad_bad = 0;
   if (h->em_rows) return layout_identity_map(h);
   if (int rc = layout_column_map(h, b)) return rc;         // 1., 2.: columns by popularity, dealt to the parts; hot columns split
   b.pt.lap("layout: maps to the device, rid16 alloc");

@@ -50,8 +50,10 @@ __global__ __launch_bounds__(1024) void k_stream(const u32x4* __restrict__ p, in
 // WGs, chunks dealt round-robin, non-temporal; DEPTH chunks in flight.
 // VT 0: the two value loads at lane stride 32 B (tid * 32 and tid * 32 + 16): each wave instruction spans 2 KB, half of every line
 // VT 1: each 1 KB-contiguous per wave (wave * 2048 + lane * 16 and + 1024): whole lines (tsem_valmap.h)
+// IB: bytes of index per thread — 12 (the 3-byte index, tsem_idx24.h) or 8 (the quad index, tsem_quad64.h: one 8-byte load)
 typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
-template <int DEPTH, int VT>
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+template <int DEPTH, int VT, int IB = 12>
 __global__ __launch_bounds__(1024) void k_burst(const char* __restrict__ idx, const char* __restrict__ val, int64_t nchunks, uint32_t* out) {
   u32x4 acc = {0, 0, 0, 0};
   const int tid = threadIdx.x;
@@ -62,7 +64,11 @@ __global__ __launch_bounds__(1024) void k_burst(const char* __restrict__ idx, co
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) {
       const int64_t cc = min(c + (int64_t)d * gridDim.x, nchunks - 1);   // (the last round re-reads the last chunk: no branch around a load)
-      a[d] = __builtin_nontemporal_load(reinterpret_cast<const u32x3*>(idx + cc * (1024 * 12) + tid * 12));
+      if (IB == 8) {
+        const u32x2 t = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(idx + cc * (1024 * 8) + tid * 8));
+        a[d] = u32x3{t.x, t.y, 0u};
+      } else
+        a[d] = __builtin_nontemporal_load(reinterpret_cast<const u32x3*>(idx + cc * (1024 * 12) + tid * 12));
       v0[d] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(val + cc * (1024 * 32) + o1));
       v1[d] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(val + cc * (1024 * 32) + o2));
     }
@@ -71,21 +77,21 @@ __global__ __launch_bounds__(1024) void k_burst(const char* __restrict__ idx, co
   }
   if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u) out[0] = acc.x;
 }
-template <int DEPTH, int VT>
+template <int DEPTH, int VT, int IB = 12>
 void run_burst(const char* name, const char* p, int64_t bytes, int grid, uint32_t* out) {
-  const int64_t nchunks = bytes / (1024 * 44);                // 12 KB of index + 32 KB of values per chunk
-  const char* idx = p; const char* val = p + ((nchunks * 1024 * 12 + 4095) & ~(int64_t)4095);
+  const int64_t nchunks = bytes / (1024 * (IB + 32));         // 12 (8) KB of index + 32 KB of values per chunk
+  const char* idx = p; const char* val = p + ((nchunks * 1024 * IB + 4095) & ~(int64_t)4095);
   hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
-  k_burst<DEPTH, VT><<<grid, 1024>>>(idx, val, nchunks, out);
+  k_burst<DEPTH, VT, IB><<<grid, 1024>>>(idx, val, nchunks, out);
   CK(hipDeviceSynchronize());
   float best = 1e9;
   for (int r = 0; r < 3; ++r) {
     CK(hipEventRecord(a));
-    k_burst<DEPTH, VT><<<grid, 1024>>>(idx, val, nchunks, out);
+    k_burst<DEPTH, VT, IB><<<grid, 1024>>>(idx, val, nchunks, out);
     CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
     float ms; CK(hipEventElapsedTime(&ms, a, b)); if (ms < best) best = ms;
   }
-  printf("%-58s grid %6d  %7.3f ms  %7.1f GB/s\n", name, grid, best, (double)nchunks * 1024 * 44 / best / 1e6);
+  printf("%-58s grid %6d  %7.3f ms  %7.1f GB/s\n", name, grid, best, (double)nchunks * 1024 * (IB + 32) / best / 1e6);
 }
 
 template <int UNROLL, int POLICY, int MAP>
@@ -125,9 +131,12 @@ int main() {
   const int64_t bb = bytes - (1 << 20);                        // (room for the alignment of the value region)
   run_burst<1, 0>("burst 12 + 2 x 16 B, values at lane stride 32 B, 1 chunk", (const char*)p, bb, 256, out);
   run_burst<1, 1>("burst 12 + 2 x 16 B, values 1 KB per wave, 1 chunk", (const char*)p, bb, 256, out);
+  run_burst<1, 1, 8>("burst 8 + 2 x 16 B, values 1 KB per wave, 1 chunk", (const char*)p, bb, 256, out);
   run_burst<2, 0>("burst 12 + 2 x 16 B, values at lane stride 32 B, 2 chunks", (const char*)p, bb, 256, out);
   run_burst<2, 1>("burst 12 + 2 x 16 B, values 1 KB per wave, 2 chunks", (const char*)p, bb, 256, out);
+  run_burst<2, 1, 8>("burst 8 + 2 x 16 B, values 1 KB per wave, 2 chunks", (const char*)p, bb, 256, out);
   run_burst<3, 0>("burst 12 + 2 x 16 B, values at lane stride 32 B, 3 chunks", (const char*)p, bb, 256, out);
   run_burst<3, 1>("burst 12 + 2 x 16 B, values 1 KB per wave, 3 chunks", (const char*)p, bb, 256, out);
+  run_burst<3, 1, 8>("burst 8 + 2 x 16 B, values 1 KB per wave, 3 chunks", (const char*)p, bb, 256, out);
   return 0;
 }

@@ -668,6 +668,24 @@ int  tsem_bgzf_inflate(tsem_bgzf* z, const uint8_t* bytes, int64_t n_bytes, cons
 /* HIP-event milliseconds summed over the calls so far: host-to-device, k_bgzf_inflate, device-to-host; *calls = how many; reset != 0
  * clears both. */
 int  tsem_bgzf_times(tsem_bgzf* z, int reset, double* ms3, int64_t* calls);
+/* The other direction (`--deflate device`): bytes[0, n_bytes), a HOST stream that begins on a block boundary, becomes the BGZF blocks
+ * of a file, one behind the other in out[0, *out_bytes): the stream is cut every 0xff00 bytes (the last block may be shorter; n_bytes
+ * = 0 gives no block), every block is 18 header bytes (1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, 'B' 'C' 2 0, BSIZE - 1), a raw
+ * DEFLATE stream of at most len + 5 bytes, CRC-32 and ISIZE.  *n_blocks = how many.  The EOF block is NOT written: that is the file
+ * writer's business.  One upload (the stream) and one download (the finished image; its size, 8 bytes, travels ahead of it); in
+ * between k_bgzf_deflate (one wave per block: hash-table LZ77, greedy parse, the smaller of a stored, a fixed and a dynamic block;
+ * telescope_amd/csrc/tsem_bgzf_deflate.h), k_bgzf_offsets and k_bgzf_pack.  The handle keeps 1 B per stream byte, 2 B per byte for
+ * the slots and the image and 4 B per byte for the tokens.  Checked before the handle is looked at, TSEM_ERR_ARG with a message: a
+ * NULL pointer, a negative size, 2^31 - 1 blocks or more, out_cap below the worst case n_bytes + 31 per block (a stored block: 5 bytes
+ * of DEFLATE framing, 26 of BGZF); then a NULL handle.  TSEM_ERR_HIP / TSEM_ERR_NOMEM as for tsem_bgzf_inflate.
+ * tsem_bgzf_deflate_host: the same contract and the same body with one lane on the CPU, no device and no handle; it gives the bytes
+ * that the kernel gives (the body's result does not depend on the number of lanes). */
+int  tsem_bgzf_deflate(tsem_bgzf* z, const uint8_t* bytes, int64_t n_bytes, uint8_t* out, int64_t out_cap, int64_t* out_bytes,
+                       int64_t* n_blocks);
+int  tsem_bgzf_deflate_host(const uint8_t* bytes, int64_t n_bytes, uint8_t* out, int64_t out_cap, int64_t* out_bytes, int64_t* n_blocks);
+/* HIP-event milliseconds summed over the tsem_bgzf_deflate calls so far: host-to-device, k_bgzf_deflate, k_bgzf_offsets + k_bgzf_pack,
+ * device-to-host; *calls = how many; reset != 0 clears both.  tsem_bgzf_times is not touched by them. */
+int  tsem_bgzf_deflate_times(tsem_bgzf* z, int reset, double* ms4, int64_t* calls);
 
 /* ---- csr_matrix_plus primitives on arbitrary fp64 CSR (sparse_plus.py) ---- */
 /* All three: indptr[n_rows + 1] is a HOST array and is checked on the host before the device is touched. TSEM_ERR_ARG (text in

@@ -252,6 +252,9 @@ def lib():
     L.tsem_bgzf_close.argtypes = [vp]
     L.tsem_bgzf_inflate.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, vp, C.POINTER(i64)]
     L.tsem_bgzf_times.argtypes = [vp, C.c_int, vp, C.POINTER(i64)]
+    L.tsem_bgzf_deflate.argtypes = [vp, vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.tsem_bgzf_deflate_host.argtypes = [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.tsem_bgzf_deflate_times.argtypes = [vp, C.c_int, vp, C.POINTER(i64)]
     L.tsem_csr_norm_rows.argtypes = [C.c_int, i64, vp, vp, vp]
     L.tsem_csr_binmax_rows.argtypes = [C.c_int, i64, i32, vp, vp, vp]
     L.tsem_csr_scale.argtypes = [C.c_int, C.c_int, i64, i32, vp, vp, vp]
@@ -1022,6 +1025,60 @@ class BgzfInflater(object):
         if rc != OK:
             raise _csr_error('tsem_bgzf_times', rc)
         return dict(zip(('h2d', 'k_bgzf_inflate', 'd2h'), ms.tolist()), batches=n.value)
+
+
+BGZF_BLOCK_IN = 0xff00                  # input bytes per block of the deflate entries (bam_out._BLOCK_IN)
+
+
+def _bgzf_deflate_call(fn, name, handle, stream):
+    buf = np.frombuffer(stream, dtype=np.uint8)
+    nb = (buf.size + BGZF_BLOCK_IN - 1) // BGZF_BLOCK_IN
+    cap = buf.size + 31 * nb
+    out = np.empty(cap, np.uint8)
+    n_out, n_blk = C.c_int64(), C.c_int64()
+    args = (ptr(buf) if buf.size else None, buf.size, ptr(out) if cap else None, cap, C.byref(n_out), C.byref(n_blk))
+    rc = fn(*(((handle,) if handle is not None else ()) + args))
+    if rc != OK:
+        raise _csr_error(name, rc)
+    assert n_blk.value == nb and n_out.value <= cap
+    return out[:n_out.value]
+
+
+def bgzf_deflate_host(stream):
+    """The BGZF blocks (no EOF block) of a byte stream cut every 0xff00 bytes, by the kernel's body with one lane on the CPU
+    (tsem_bgzf_deflate_host, no device): uint8 array, the bytes that BgzfDeflater.deflate gives."""
+    return _bgzf_deflate_call(lib().tsem_bgzf_deflate_host, 'tsem_bgzf_deflate_host', None, stream)
+
+
+class BgzfDeflater(object):
+    """The device side of `--deflate device` (tsem_bgzf_open / tsem_bgzf_deflate): one handle, one GPU, its buffers kept between batches."""
+
+    def __init__(self, device=0):
+        L = lib()
+        h = C.c_void_p()
+        rc = L.tsem_bgzf_open(C.byref(h), int(device))
+        if rc != OK:
+            raise _csr_error('tsem_bgzf_open', rc)
+        self._L, self._h = L, h
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._L.tsem_bgzf_close(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def deflate(self, stream):
+        """-> uint8 array: the BGZF blocks of `stream` (cut every 0xff00 bytes, the last one shorter), one behind the other; no EOF block"""
+        return _bgzf_deflate_call(self._L.tsem_bgzf_deflate, 'tsem_bgzf_deflate', self._h, stream)
+
+    def times(self, reset=False):
+        """HIP-event milliseconds summed over the batches so far, and their number."""
+        ms, n = np.zeros(4), C.c_int64()
+        rc = self._L.tsem_bgzf_deflate_times(self._h, int(reset), ptr(ms), C.byref(n))
+        if rc != OK:
+            raise _csr_error('tsem_bgzf_deflate_times', rc)
+        return dict(zip(('h2d', 'k_bgzf_deflate', 'pack', 'd2h'), ms.tolist()), batches=n.value)
 
 
 def bam_scan(data, cap=None):

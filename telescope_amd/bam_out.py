@@ -81,12 +81,29 @@ class BgzfWriter(object):
 
 
 class BamWriter(object):
-    """`header`: the dict `read_bam(..., raw=True)` returns (text, refs_block); records go in as raw bytes (no block size)."""
+    """`header`: the dict `read_bam(..., raw=True)` returns (text, refs_block); records go in as raw bytes (no block size).
+    `deflate`: 'host' (zlib level 6 on this core) or 'device' (`--deflate device`: the blocks are deflated on GPU `device`,
+    bgzf.DeviceBgzfWriter; the same cuts and the same inflated bytes, other compressed ones)."""
 
-    def __init__(self, path, header, text=None):
-        self._z = BgzfWriter(path)
+    def __init__(self, path, header, text=None, deflate='host', device=0):
+        if deflate not in ('host', 'device'):
+            raise ValueError("deflate must be 'host' or 'device', not %r" % (deflate,))
+        if deflate == 'device':
+            from . import bgzf                              # (only here: this module's default path needs the standard library alone)
+            self._z = bgzf.DeviceBgzfWriter(path, device=device)
+        else:
+            self._z = BgzfWriter(path)
+        self.deflate = deflate
         t = (header['text'] if text is None else text).encode()
-        self._z.write(b'BAM\x01' + struct.pack('<i', len(t)) + t + header['refs_block'])
+        try:
+            self._z.write(b'BAM\x01' + struct.pack('<i', len(t)) + t + header['refs_block'])
+        except BaseException:
+            self._z.close()
+            raise
+
+    def device_stats(self):
+        """(blocks, batches, tsem_bgzf_deflate_times) of a 'device' writer so far, None for a 'host' one"""
+        return (self._z.blocks, self._z.batches, self._z.times()) if self.deflate == 'device' else None
 
     def write(self, rec):
         self._z.write(struct.pack('<i', len(rec)) + rec)
@@ -103,6 +120,18 @@ class BamWriter(object):
 
     def __exit__(self, *exc):
         self.close()
+
+
+def sum_device_stats(writers):
+    """dict(deflate_blocks, deflate_batches, deflate_ms) over BamWriters with deflate='device' (closed ones too)"""
+    out = dict(deflate_blocks=0, deflate_batches=0, deflate_ms=dict(h2d=0., k_bgzf_deflate=0., pack=0., d2h=0.))
+    for w in writers:
+        blocks, batches, ms = w.device_stats()
+        out['deflate_blocks'] += blocks
+        out['deflate_batches'] += batches
+        for k in out['deflate_ms']:
+            out['deflate_ms'][k] += ms[k]
+    return out
 
 
 def header_with_pg(text, version, command_line):

@@ -8,6 +8,12 @@ wave per block, CRC-32 and length checked against the trailer), and the partial 
   DeviceBgzfReader(path)     a readable binary file object over the inflated stream: what loader.read_bam_header and
                              loader_device.bam_chunks take in place of gzip.open(path)
 
+The other direction (`assign --updated_sam --deflate device`; csrc/tsem_bgzf_deflate.h): a stream cut every 0xff00 bytes, every block
+deflated by one wave (k_bgzf_deflate), header, stream and trailer of every block packed into one file image on the device.
+
+  deflate(data)              bytes -> a whole BGZF byte string, EOF block included
+  DeviceBgzfWriter(path)     a writable binary file object: what bam_out.BamWriter(deflate='device') writes through
+
 A block whose trailer claims more than 65,536 inflated bytes (the format forbids it; a gzip member can say so) is inflated with zlib on
 the host and counted in `fallbacks`.  A file that is gzip but not BGZF — no BC subfield in its first header, a BAM written by plain
 gzip — is read with Python's gzip as the host path does, `inflate` of the reader says 'host'.
@@ -19,7 +25,8 @@ import zlib
 
 import numpy as np
 
-from ._lib import BGZF_HOST, BGZF_STATUS, BgzfInflater, EngineError, bgzf_scan
+from ._lib import BGZF_BLOCK_IN, BGZF_HOST, BGZF_STATUS, BgzfDeflater, BgzfInflater, EngineError, bgzf_scan
+from .bam_out import BGZF_EOF
 
 DEFAULT_BATCH_BYTES = 64 << 20
 MAX_BLOCK = 65536                      # bytes of a whole BGZF block at most: BSIZE is 16 bits
@@ -71,6 +78,87 @@ def inflate(data, device=0):
     finally:
         dev.close()
     return out.tobytes()
+
+
+def deflate(data, device=0):
+    """The whole BGZF byte string of `data`, EOF block included, every block deflated on GPU `device` in one call (the mirror of
+    `inflate`): blocks of 0xff00 input bytes, the last one shorter, as bam_out.BgzfWriter cuts them."""
+    dev = BgzfDeflater(device)
+    try:
+        out = dev.deflate(bytes(data))
+    finally:
+        dev.close()
+    return out.tobytes() + BGZF_EOF
+
+
+class DeviceBgzfWriter(object):
+    """bam_out.BgzfWriter with the blocks deflated on the device (`--deflate device`; k_bgzf_deflate, one wave per block): write(data),
+    close(), context manager.  The stream is cut every 0xff00 bytes however the bytes arrive, as BgzfWriter cuts it.  Whole blocks
+    collect until `batch_bytes` of them are there (default 64 MiB) and go through one device call, which returns the finished file
+    image of the batch; the partial block at the end goes at close(), followed by the EOF block.  `blocks`, `batches`: what went
+    through the device so far; times(): tsem_bgzf_deflate_times."""
+
+    def __init__(self, path, device=0, batch_bytes=DEFAULT_BATCH_BYTES):
+        if int(batch_bytes) < 1:
+            raise ValueError('batch_bytes must be >= 1')
+        self.name, self.blocks, self.batches = path, 0, 0
+        self._batch = max(1, int(batch_bytes) // BGZF_BLOCK_IN) * BGZF_BLOCK_IN     # whole blocks per device call
+        self._buf, self._times = bytearray(), None
+        self._dev = None
+        self._fh = open(path, 'wb')
+        try:
+            self._dev = BgzfDeflater(device)
+        except BaseException:
+            self._release()
+            raise
+
+    def _release(self):
+        if self._dev is not None:
+            self._times = self._dev.times()
+        for x in ('_fh', '_dev'):
+            if getattr(self, x, None) is not None:
+                getattr(self, x).close()
+                setattr(self, x, None)
+
+    def _send(self, n):
+        """the first n bytes of the buffer through the device and into the file"""
+        out = self._dev.deflate(memoryview(self._buf)[:n])
+        self._fh.write(memoryview(out))
+        self.blocks += (n + BGZF_BLOCK_IN - 1) // BGZF_BLOCK_IN
+        self.batches += 1
+        del out
+        self._buf = self._buf[n:]
+
+    def write(self, data):
+        if self._fh is None:
+            raise ValueError('write to a closed file')
+        try:
+            self._buf += memoryview(data).cast('B')
+            while len(self._buf) >= self._batch:
+                self._send(self._batch)
+        except BaseException:
+            self._release()
+            raise
+
+    def times(self):
+        """dict(h2d, k_bgzf_deflate, pack, d2h in HIP-event milliseconds over the batches so far, batches)"""
+        return self._dev.times() if self._dev is not None else dict(self._times or dict(h2d=0., k_bgzf_deflate=0., pack=0., d2h=0., batches=0))
+
+    def close(self):
+        if self._fh is None:
+            return
+        try:
+            if self._buf:
+                self._send(len(self._buf))
+            self._fh.write(BGZF_EOF)
+        finally:
+            self._release()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class DeviceBgzfReader(object):

@@ -114,6 +114,10 @@ def _assign_args(asg):
     g.add_argument('--inflate', default='host', choices=['host', 'device'],
                    help='host (default): the BGZF blocks of the BAM are inflated by gzip on one host core.  device (with --loader device): '
                         'they are inflated on the GPU as well, one wave per block.')
+    g.add_argument('--deflate', default='host', choices=['host', 'device'],
+                   help='host (default): the BGZF blocks of the BAMs of --updated_sam are deflated by zlib on one host core.  device (with '
+                        '--updated_sam; any --loader and --rewrite): they are deflated on the GPU, one wave per block; the files inflate '
+                        'to the same bytes, their compressed bytes differ.')
     g.add_argument('--tempdir', help='(accepted for compatibility; no temporary files are written)')
     g = asg.add_argument_group('Reporting Options')
     g.add_argument('--quiet', action='store_true', help='Silence (most) output.')
@@ -379,6 +383,13 @@ def _refuse_device_inflate(args):
                          'its records from gzip\'s stream); add --loader device')
 
 
+def _refuse_device_deflate(args):
+    """`--deflate device` without `--updated_sam`: refused before anything is read (there is no BAM to write)."""
+    if getattr(args, 'deflate', 'host') == 'device' and not getattr(args, 'updated_sam', False):
+        raise SystemExit('telescope assign: --deflate device without --updated_sam is not supported (there is no BAM to write); '
+                         'add --updated_sam')
+
+
 def collapse_umis(ts, opts):
     """`sc assign --umi_tag` / `sc resume` of a checkpoint with UMIs: the run goes on with the kept fragments (scTelescope.collapse_umis)
     unless --ignore_umi; <exp_tag>-umi_stats.tsv lists them per barcode."""
@@ -489,6 +500,7 @@ def run_assign(args, sc=False):
     _refuse_umi_updated_sam(args)
     _refuse_device_updated_sam(args)
     _refuse_device_inflate(args)
+    _refuse_device_deflate(args)
     opts = ResumeOptions(args)
     configure_logging(opts)
     if opts.ncpu != 1:
@@ -522,6 +534,8 @@ def run_assign(args, sc=False):
             stime = time()
             if opts.updated_sam:
                 os.makedirs(opts.outdir, exist_ok=True)          # (the load writes <exp_tag>-other.bam and -tmp_tele.bam there)
+                if getattr(opts, 'deflate', 'host') == 'device':
+                    lg.info('--deflate device: the BGZF blocks of other, tmp_tele and updated are deflated on GPU %d' % getattr(opts, 'device', 0))
             if opts.loader == 'device' and warm is not None:
                 warm.join()                                      # (the device loader's first call finds the device up)
             ts.load_alignment(annot)

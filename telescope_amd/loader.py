@@ -32,6 +32,7 @@ are what it shares with this loader) or the reference's pysam loader and `telesc
 """
 import gzip
 import io
+import logging as lg
 import re
 import struct
 from array import array
@@ -360,7 +361,7 @@ CODE_DESC = OrderedDict([('SU', 'single_unmapped'), ('SM', 'single_mapped'), ('P
 
 def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_mode='threshold',
                    overlap_threshold=0.2, stranded_mode='None', barcode_tag=None, updated_sam=None, umi_tag=None, loader='python',
-                   device=0, chunk_bytes=None, record_cap=4096, inflate='host', rewrite='host'):
+                   device=0, chunk_bytes=None, record_cap=4096, inflate='host', rewrite='host', deflate='host'):
     """-> dict(raw_scores uint16 CSR, read_index, feat_index, feature_length, run_info fields).  With `barcode_tag` (scTelescope,
     model.py:245-247,311-316) also cell_of_row (int32 per row, -1 = no barcode) and barcodes (the cell names): the tag is read from
     the first read of every mapped fragment; only fragments that become rows count; cells are ordered by the first appearance of
@@ -375,7 +376,9 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
     records is left to this module's code); with `updated_sam` only under `rewrite='device'`: the records of the two BAMs are then
     rewritten on the GPU as well (the same files, byte for byte), and loader_device.LAST_TMP_TABLE holds what update_sam needs per
     record of the tmp BAM.  `inflate='device'` (with loader='device' only): the file's BGZF
-    blocks are inflated on the GPU as well (bgzf.py) instead of by gzip on one host core."""
+    blocks are inflated on the GPU as well (bgzf.py) instead of by gzip on one host core.  `deflate='device'` (with `updated_sam`, either
+    loader): the BGZF blocks of both BAMs are deflated on the GPU (bgzf.DeviceBgzfWriter) instead of by zlib on one host core; the
+    files inflate to the same bytes."""
     if overlap_mode != 'threshold':
         raise NotImplementedError('only overlap_mode "threshold" is implemented (as in the reference, '
                                   'model.py:899-903)')
@@ -387,20 +390,25 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
         raise ValueError("rewrite must be 'host' or 'device', not %r" % (rewrite,))
     if rewrite == 'device' and not (loader == 'device' and updated_sam):
         raise ValueError("rewrite='device' needs loader='device' and updated_sam")
+    if deflate not in ('host', 'device'):
+        raise ValueError("deflate must be 'host' or 'device', not %r" % (deflate,))
+    if deflate == 'device' and not updated_sam:
+        raise ValueError("deflate='device' needs updated_sam")
     if loader == 'device':
         if updated_sam and rewrite != 'device':
             raise ValueError('the device loader does not write the BAMs of --updated_sam')
         from .loader_device import load_alignment_device
         return load_alignment_device(samfile, annotation, no_feature_key, overlap_threshold, stranded_mode, barcode_tag, umi_tag,
                                      device=device, chunk_bytes=chunk_bytes, record_cap=record_cap, inflate=inflate,
-                                     updated_sam=updated_sam if rewrite == 'device' else None)
+                                     updated_sam=updated_sam if rewrite == 'device' else None, deflate=deflate)
     if loader != 'python':
         raise ValueError("loader must be 'python' or 'device', not %r" % (loader,))
     bam_u = bam_t = None
     if updated_sam:
         from .bam_out import BamWriter
         refs, records, header = read_bam(samfile, barcode_tag, raw=True, umi_tag=umi_tag)
-        bam_u, bam_t = BamWriter(updated_sam[0], header), BamWriter(updated_sam[1], header)
+        bam_u = BamWriter(updated_sam[0], header, deflate=deflate, device=device)
+        bam_t = BamWriter(updated_sam[1], header, deflate=deflate, device=device)
 
         def write(bam, pairs):
             for p in pairs:
@@ -450,8 +458,14 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
                 write(bam_t, alns)
     finally:                                               # (a failed load still ends both files with the EOF block)
         if bam_u is not None:
-            bam_u.close()
-            bam_t.close()
+            try:
+                bam_u.close()
+            finally:                                       # (whatever the first close does: the second writer's handles are released too)
+                bam_t.close()
+    if bam_u is not None and deflate == 'device':
+        from .bam_out import sum_device_stats
+        st = sum_device_stats([bam_u, bam_t])
+        lg.info('device deflate: %d BGZF blocks of other and tmp_tele in %d batches' % (st['deflate_blocks'], st['deflate_batches']))
 
     return mappings_to_result(annotation, info, ridx, fidx, np.frombuffer(m_row, dtype=np.int64), np.frombuffer(m_col, dtype=np.int32),
                               np.frombuffer(m_as, dtype=np.int32), np.frombuffer(m_len, dtype=np.int32), min_as, max_as,

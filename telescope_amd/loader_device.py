@@ -161,7 +161,7 @@ def host_bundle(data, off, s, e, btag, utag, assign, no_feature_key, streams=Fal
 
 def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', overlap_threshold=0.2, stranded_mode='None',
                           barcode_tag=None, umi_tag=None, device=0, chunk_bytes=None, record_cap=4096, max_bundles=None,
-                          on_chunk=None, inflate='host', updated_sam=None):
+                          on_chunk=None, inflate='host', updated_sam=None, deflate='host'):
     """loader.load_alignment(..., loader='device').  `on_chunk(data, rec_off, out)`: called with every chunk's raw device outputs
     (tests); `max_bundles`: at most so many bundles per device call (tests).  `inflate`: 'host' (Python's gzip) or 'device' (the BGZF
     blocks are inflated on the GPU, bgzf.py; a gzip file that is not BGZF is still read by gzip: LAST_STATS['inflate'] says which).
@@ -169,13 +169,17 @@ def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', ov
     rewrites the records into two framed streams (tsem_bam_rewrite_size / _fetch), the records of the bundles left to the host are
     spliced in at their bundles' offsets, bam_out.BgzfWriter deflates on the host.  LAST_TMP_TABLE then holds, per record of the tmp
     BAM in order, row (the fragment's row of the matrix, int32), col (the pair's column, int32) and kind (uint8: 0 unchanged, 1 SEC,
-    2 PRI) for Telescope.update_sam; it is not part of the returned dict or of the checkpoint."""
+    2 PRI) for Telescope.update_sam; it is not part of the returned dict or of the checkpoint.  `deflate='device'`: both writers deflate
+    their blocks on the GPU instead (bgzf.DeviceBgzfWriter): the same inflated bytes; LAST_STATS['deflate_blocks'], ['deflate_batches'] and
+    ['deflate_ms'] say what went through the device."""
     global LAST_STATS, LAST_TMP_TABLE
     LAST_TMP_TABLE = None
     if no_feature_key in annotation.loci:
         raise ValueError('the device loader needs a no_feature_key that is not a locus of the annotation (%r is)' % no_feature_key)
     if inflate not in ('host', 'device'):
         raise ValueError("inflate must be 'host' or 'device', not %r" % (inflate,))
+    if deflate not in ('host', 'device'):
+        raise ValueError("deflate must be 'host' or 'device', not %r" % (deflate,))
     chunk_bytes = DEFAULT_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
     if chunk_bytes < 1:
         raise ValueError('chunk_bytes must be >= 1')
@@ -200,7 +204,8 @@ def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', ov
         if updated_sam:
             dev.names(loc_names + [no_feature_key])
             header = dict(text=_text.split(b'\x00', 1)[0].decode(), refs_block=_block)
-            w_other, w_tmp = bam_out.BamWriter(updated_sam[0], header), bam_out.BamWriter(updated_sam[1], header)
+            w_other = bam_out.BamWriter(updated_sam[0], header, deflate=deflate, device=device)
+            w_tmp = bam_out.BamWriter(updated_sam[1], header, deflate=deflate, device=device)
             stats.update(records_other=0, records_tmp=0, bytes_other=0, bytes_tmp=0, rewrite_s=0., splice_s=0., deflate_s=0.)
 
         def assign(pair):
@@ -342,12 +347,17 @@ def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', ov
         fh.close()
         if dev is not None:
             dev.close()
-        if w_other is not None:                              # (a failed load still ends both files with the EOF block)
-            t0 = perf_counter()
-            w_other.close()
-        if w_tmp is not None:
-            w_tmp.close()
-            stats['deflate_s'] += perf_counter() - t0
+        t0 = perf_counter()
+        try:
+            if w_other is not None:                          # (a failed load still ends both files with the EOF block)
+                w_other.close()
+        finally:                                             # (whatever the first close does: the second writer's handles are released too)
+            if w_tmp is not None:
+                w_tmp.close()
+                stats['deflate_s'] += perf_counter() - t0
+    if deflate == 'device' and w_other is not None and w_tmp is not None:
+        stats['deflate'] = 'device'
+        stats.update(bam_out.sum_device_stats([w_other, w_tmp]))
     t0 = perf_counter()
     info['total_fragments'] = int(n_code.sum())
     for c, k in zip(CODES, n_code.tolist()):
@@ -366,6 +376,8 @@ def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', ov
     LAST_STATS = stats
     if stats['inflate_fallbacks']:
         lg.info('device inflate: %d of %d BGZF blocks were left to zlib on the host' % (stats['inflate_fallbacks'], stats['inflate_blocks']))
+    if stats.get('deflate') == 'device':
+        lg.info('device deflate: %d BGZF blocks of other and tmp_tele in %d batches' % (stats['deflate_blocks'], stats['deflate_batches']))
     if stats['fallbacks']:
         lg.info('device loader: %d of %d fragments were left to the host loader' % (stats['fallbacks'], stats['bundles']))
     lg.debug('device loader: %d records in %d chunks' % (stats['records'], stats['chunks']))

@@ -132,7 +132,7 @@ class Telescope(object):
         r = loader.load_alignment(o.samfile, annotation, o.no_feature_key, o.overlap_mode,
                                   o.overlap_threshold, o.stranded_mode, updated_sam=self._updated_sam_paths(),
                                   loader=getattr(o, 'loader', 'python'), device=getattr(o, 'device', 0), inflate=getattr(o, 'inflate', 'host'),
-                                  rewrite=getattr(o, 'rewrite', 'host'))
+                                  rewrite=getattr(o, 'rewrite', 'host'), deflate=getattr(o, 'deflate', 'host'))
         self._take_tmp_table()
         self.feature_length = r['feature_length']
         self.read_index, self.feat_index = r['read_index'], r['feat_index']
@@ -335,8 +335,9 @@ class Telescope(object):
         _, records, header = loader.read_bam(self.tmp_bam, raw=True)
         text = bam_out.header_with_pg(header['text'], self.run_info.get('version', getattr(self.opts, 'version', '')),
                                       ' '.join(sys.argv) if command_line is None else command_line)
+        deflate = getattr(self.opts, 'deflate', 'host')
         try:
-            with bam_out.BamWriter(filename, header, text) as out:
+            with bam_out.BamWriter(filename, header, text, deflate=deflate, device=getattr(self.opts, 'device', 0)) as out:
                 for _code, pairs in loader._fragments(records):
                     if not pairs:
                         continue
@@ -355,8 +356,19 @@ class Telescope(object):
                             w = word(ridx, self.feat_index[bam_out.get_tag(recs[0], 'ZF')])
                         for r in bam_out.update_pair(recs, zt, w):
                             out.write(r)
+            self._log_device_deflate(out)
         finally:
             tiles.close()
+
+    @staticmethod
+    def _log_device_deflate(out):
+        """one line after a BamWriter with deflate='device' is closed: the blocks and batches that went through the device"""
+        from . import bam_out
+        if out is not None and out.deflate == 'device':
+            st = bam_out.sum_device_stats([out])
+            lg.info('device deflate: %d BGZF blocks of updated in %d batches' % (st['deflate_blocks'], st['deflate_batches']))
+            return st
+        return None
 
     def _take_tmp_table(self):
         """after a load: the device loader's table of the tmp BAM's records (`--rewrite device`), None otherwise"""
@@ -419,7 +431,7 @@ class Telescope(object):
             header = dict(text=text.split(b'\x00', 1)[0].decode(), refs_block=block)
             text = bam_out.header_with_pg(header['text'], self.run_info.get('version', getattr(self.opts, 'version', '')),
                                           ' '.join(sys.argv) if command_line is None else command_line)
-            out = bam_out.BamWriter(filename, header, text)
+            out = bam_out.BamWriter(filename, header, text, deflate=getattr(self.opts, 'deflate', 'host'), device=device)
             dev = BamLoader(device, z, z, z, z, z, z, z)
             done, tail = 0, b''
             while True:
@@ -465,6 +477,9 @@ class Telescope(object):
                 t0 = perf_counter()
                 out.close()
                 stats['deflate_s'] += perf_counter() - t0
+        st = self._log_device_deflate(out)
+        if st:
+            stats.update(st, deflate='device')
         stats['total_s'] = perf_counter() - t_all
         Telescope.LAST_UPDATE_STATS = stats
 
@@ -587,7 +602,7 @@ class scTelescope(Telescope):
         r = loader.load_alignment(o.samfile, annotation, o.no_feature_key, o.overlap_mode, o.overlap_threshold, o.stranded_mode,
                                   barcode_tag=o.barcode_tag, updated_sam=self._updated_sam_paths(), umi_tag=getattr(o, 'umi_tag', None),
                                   loader=getattr(o, 'loader', 'python'), device=getattr(o, 'device', 0), inflate=getattr(o, 'inflate', 'host'),
-                                  rewrite=getattr(o, 'rewrite', 'host'))
+                                  rewrite=getattr(o, 'rewrite', 'host'), deflate=getattr(o, 'deflate', 'host'))
         self._take_tmp_table()
         self.feature_length = r['feature_length']
         self.read_index, self.feat_index = r['read_index'], r['feat_index']

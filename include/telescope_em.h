@@ -94,7 +94,11 @@ int  tsem_set_stream(tsem_ctx* h, void* hip_stream); /* launch on this hipStream
  *                  entries on; 0 never; 1 always
  *   "deconflict"   conflict-aware entry order inside the rows of the row-ordered code layout (LDS bank conflicts of the
  *                  column scatter 3.2 -> 2.4 lanes per class: -6 % per EM pass for ~4 ms of setup at 2e9 entries);
- *                  default -1 = on, 0 = off
+ *                  default -1 = on, 0 = off.  fp64 entries under the fused kernel (a non-split, row-ordered layout read through the
+ *                  value map, 3-byte or quad index, not "reproducible"): the entries INSIDE each quad of four are ordered the same
+ *                  way, among positions of one row (3.1 -> 2.2 lanes per class); 0 off, 1 on, -1 (default) on where 11 B x the
+ *                  entries of the ambiguous rows reach "deconflict_min_bytes" (default 1 GiB).  Every other layout is left as it
+ *                  is; see tsem_layout_info_n [44], [45]
  *   "reproducible" 1: ORDER-INDEPENDENT column sums in the fused EM pass.  Every contribution w*z is cut into a high and a low piece on
  *                  a per-column power-of-two grid; sums of such pieces are exact in fp64, so the unordered LDS atomics add up to
  *                  the same bits whatever their order: pi, theta, lnl and the iteration count are bit-identical from run to run
@@ -765,8 +769,9 @@ int  tsem_layout_info(tsem_ctx* h, int64_t* info32);
  * value 0) a quad layout stores so that every row of a block has an entry in every part: counted in nnz_pad, not in nnz_amb; [42] the
  * quads the pack kernel could not represent (0 by construction: anything else is a fault of the set-up, and the layout then keeps the
  * 3-byte index); [43] option "index_auto_min_bytes": the smallest 3-byte stream (11 B x nnz_amb) for which auto takes the quad
- * index (default 1 GiB). */
-#define TSEM_LAYOUT_INFO_N 44
+ * index (default 1 GiB); [44] the conflict-aware entry order the layout got (0 none, 1 the walk over the rows of a score-code layout,
+ * 2 the order inside the quads of fp64 entries) and [45] the quads the latter permuted. */
+#define TSEM_LAYOUT_INFO_N 46
 int  tsem_layout_info_n(tsem_ctx* h, int64_t* info, int32_t n);
 /* per-block shader-clock stamps of team 0 / member 0 of the fused kernel (option "fused_prof") */
 int  tsem_debug_fused_prof(tsem_ctx* h, uint64_t* out512);
@@ -794,6 +799,11 @@ int  tsem_debug_idx24(const uint32_t* rc4, uint8_t* out12, uint32_t* back4);
  * again into back4, with the inline functions the pack kernel and the fused kernel use; TSEM_ERR_ARG for a quad the format cannot hold.
  * *stored (may be null): 1 when `probe` names a stored quad, 0 when its low half is the fused kernel's idle mark 0xFFFFFFFF */
 int  tsem_debug_quad64(const uint32_t* rc4, uint64_t* word, uint32_t* back4, uint64_t probe, int32_t* stored);
+/* host only, no device: the conflict-aware order inside quads (option "deconflict" on fp64 entries) applied to n_win windows of 64
+ * consecutive local row << 16 | local column words: codes[16 w + l] is the permutation of quad l of window w — entry (code >> 2 j) & 3
+ * of the quad goes to position j, 0xE4 is the identity —, *moved (may be null) the quads that change; by the inline functions the
+ * set-up kernel uses */
+int  tsem_quad_order_host(int64_t n_win, const uint32_t* rc, uint8_t* codes, int64_t* moved);
 /* y[i] = the device log1p the lnl passes use (finite x >= 0), for accuracy tests against libm */
 int  tsem_debug_log1p(int device, int32_t n, const double* x, double* y);
 /* out[i] = the PHRED lookup of tsem_entry_tags for p[i] (the table as there), for tests against numpy */

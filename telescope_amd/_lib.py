@@ -277,6 +277,7 @@ def lib():
     L.tsem_debug_quad64.argtypes = [vp, vp, vp, C.c_uint64, vp]
     L.tsem_debug_subblock_values.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int64]
     L.tsem_debug_valmap.argtypes = [C.c_int32, vp]
+    L.tsem_quad_order_host.argtypes = [C.c_int64, vp, vp, vp]
     for name in exported_symbols():
         fn = getattr(L, name)
         if name not in ('tsem_destroy', 'tsem_last_error', 'tsem_comm_destroy', 'tsem_comm_last_error',
@@ -795,15 +796,32 @@ class Engine(object):
     def layout_info(self, extended=False):
         """Facts about the resident layout (include/telescope_em.h, tsem_layout_info_n).  extended: also the values appended behind
         the first 40 — the index format in use, its dummy entries, the pack kernel's count of unrepresentable quads and the auto
-        rule's size threshold."""
-        info = np.zeros(44 if extended else 40, np.int64)
+        rule's size threshold, the conflict-aware entry order applied (0 none, 1 the score-code walk, 2 the quad order) and the
+        quads the quad order permuted."""
+        info = np.zeros(46 if extended else 40, np.int64)
         self._ck(self._L.tsem_layout_info_n(self._h, ptr(info), info.size))
         return dict(zip(('P', 'Kp', 'R', 'nb', 'N_amb', 'N_uni', 'nnz_amb', 'nnz_pad', 'twin_cols',
                          'G1', 'G2', 'fused', 'slow_path', 'max_subblock', 'value_bytes', 'hot_cols',
                          'lds_bytes', 'row_order', 'geometry', 'fallbacks', 'bin_repeats', 'reproducible', 'exact_single', 'lnl_fused', 'split', 'single_part_rows', 'row_pass_em', 'lnl_tables', 'lnl_linear', 'lnl_mid_entries', 'lnl_mid_limit', 'near_tie_rows', 'index_bytes',
                          'cell_em_wave', 'cell_em_256', 'cell_em_512', 'cell_em_global', 'cell_em_spread',
                          'rowstats_lanes', 'colsig_lanes',
-                         'index_format', 'index_dummies', 'index_unrepresentable', 'index_auto_min_bytes'), info.tolist()))
+                         'index_format', 'index_dummies', 'index_unrepresentable', 'index_auto_min_bytes',
+                         'order_kind', 'order_quads_moved'), info.tolist()))
+
+
+def quad_order_host(words):
+    """The conflict-aware order inside quads (csrc/tsem_quadorder.h) on the host: `words` holds whole windows of 64 local row << 16 |
+    local column words.  Returns (codes, moved): one permutation code per quad — entry (code >> 2 j) & 3 goes to position j — and the
+    number of quads that change."""
+    words = np.ascontiguousarray(words, np.uint32).ravel()
+    if words.size % 64:
+        raise ValueError('whole windows of 64 entries')
+    codes = np.zeros(max(1, words.size // 4), np.uint8)
+    moved = C.c_int64(0)
+    rc = lib().tsem_quad_order_host(words.size // 64, ptr(words) if words.size else ptr(np.zeros(1, np.uint32)), ptr(codes), C.byref(moved))
+    if rc != OK:
+        raise EngineError('tsem_quad_order_host failed (%d)' % rc)
+    return codes[:words.size // 4], int(moved.value)
 
 
 def legacy_randint(counts):

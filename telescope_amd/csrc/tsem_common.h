@@ -167,6 +167,11 @@ struct tsem_ctx {
   int64_t n_bin_repeats = 0;        // passes repeated because an exponent had to move
   int64_t opt_deconflict = -1;      // conflict-aware entry order inside the rows of the row-ordered code layout (k_sb_deconflict): -1 auto = on
                                     //    (round 3: 4 ms of setup at 2e9 entries for -6 % per EM pass; round 2's version cost 14 ms and was opt-in)
+  // fp64 entries: the order inside the quads (k_quad_order, tsem_quadorder.h) on the layouts that qualify: 0 off, 1 on, -1 auto = from
+  // 11 B x nnz_amb >= opt_deconflict_min_bytes on (option "deconflict_min_bytes", default 1 GiB: every smaller layout stays as it was)
+  int64_t opt_deconflict_min_bytes = 1ll << 30;
+  int order_kind = 0;               // conflict-aware order of this layout: 0 none, 1 the score-code walk, 2 the quad order
+  int64_t n_quads_moved = 0;        // quads k_quad_order permuted
   int64_t opt_geo = -1;             // -1 auto; 0 / 2 force the geometry of teams of 1-4 (experiments)
   double run_len_est = 0.0;         // mean entries per ambiguous row and column part (set by tsem_rowstats)
   bool sorted_layout = false;       // sub-blocks stored in row order (k_sb_fill_sorted)

@@ -17,6 +17,7 @@
 //   (profiles/r01_primitives_ubench.log), hence every per-entry gather and
 //   scatter of the hot loop goes through LDS.
 #include "tsem_internal.h"
+#include "tsem_quadorder.h"
 #include <rocprim/device/device_scan.hpp>
 
 // ============================================================================
@@ -213,6 +214,10 @@ int tsem_set_option(tsem_ctx* h, const char* key, int64_t v) {
     h->opt_quad_min_bytes = v;
   }
   else if (k == "deconflict") h->opt_deconflict = v;
+  else if (k == "deconflict_min_bytes") {                  // deconflict = -1, fp64 entries: the smallest 3-byte stream (11 B x entries) whose quads are ordered
+    if (v < 0) TSEM_FAIL(TSEM_ERR_ARG, "deconflict_min_bytes must be a number of bytes");
+    h->opt_deconflict_min_bytes = v;
+  }
   else if (k == "reproducible") h->opt_reproducible = v;
   else if (k == "em_precision") h->opt_precision = v;
   else if (k == "kernel_timing") h->opt_timing = v;
@@ -789,6 +794,25 @@ int tsem_debug_quad64(const uint32_t* rc4, uint64_t* word, uint32_t* back4, uint
   return TSEM_OK;
 }
 
+/* host only: the rule of tsem_quadorder.h on n_win windows of 64 lrow << 16 | lcol words each: codes[16 w + l] is the permutation of quad
+ * l of window w (entry (code >> 2 j) & 3 goes to position j), *moved (may be null) the quads whose code is not the identity */
+int tsem_quad_order_host(int64_t n_win, const uint32_t* rc, uint8_t* codes, int64_t* moved) {
+  if (n_win < 0 || !rc || !codes) return TSEM_ERR_ARG;
+  int64_t m = 0;
+  for (int64_t w = 0; w < n_win; ++w) {
+    uint32_t words[TS_QO_QUADS];
+    for (int l = 0; l < TS_QO_QUADS; ++l) {
+      uint32_t row[4], col[4];
+      for (int k = 0; k < 4; ++k) { const uint32_t x = rc[64 * w + 4 * l + k]; row[k] = x >> 16; col[k] = x & 0xFFFFu; }
+      words[l] = ts_qo_word(row, col);
+    }
+    ts_qo_window(words, codes + TS_QO_QUADS * w);
+    for (int l = 0; l < TS_QO_QUADS; ++l) m += codes[TS_QO_QUADS * w + l] != TS_QO_IDENTITY;
+  }
+  if (moved) *moved = m;
+  return TSEM_OK;
+}
+
 /* the 32 values every caller's buffer has room for; values appended since come through tsem_layout_info_n */
 int tsem_layout_info(tsem_ctx* h, int64_t* info) {
   return tsem_layout_info_n(h, info, 32);
@@ -802,6 +826,8 @@ int tsem_layout_info_n(tsem_ctx* h, int64_t* out, int32_t n) {
   info[41] = h->quad_slots ? h->n_dummies : 0;             // dummy entries (column slot 0, value 0) that give every row an entry in every part: in nnz_pad, not in nnz_amb
   info[42] = h->n_quad_bad;                                // quads the pack kernel could not represent (0 by construction; otherwise the layout kept the 3-byte index)
   info[43] = h->opt_quad_min_bytes;                        // option "index_auto_min_bytes"
+  info[44] = h->order_kind;                                // conflict-aware entry order applied: 0 none, 1 the score-code walk, 2 the quad order
+  info[45] = h->n_quads_moved;                             // quads the quad order permuted
   for (int k = 0; k < 4; ++k) info[33 + k] = h->ce_class_n[k];   // cells per class of the last tsem_cell_em (tsem_cellem.hip; 0 before a fit)
   info[37] = h->ce_spread_n;                               // ... and the groups it spread over the grid (in none of the four)
   info[38] = h->rowstats_G; info[39] = h->colsig_G;        // lanes per row of the last k_rowstats / k_colsig (tsem_rowstats; 0: none launched)

@@ -1,6 +1,7 @@
 // libtelescope_em.so, set-up unit: row statistics (Y, w, W_tot, W_amb, pisum0: model.py:679-699), column signatures (exact twins),
 // the column partition and the blocked layout of the ambiguous rows (tsem_build_layout), model and parameter set-up.
 #include "tsem_internal.h"
+#include "tsem_quadorder.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -788,6 +789,93 @@ __global__ __launch_bounds__(DC_NT) void k_sb_deconflict(int64_t n_win, const ui
   }
 }
 
+// Conflict-aware order INSIDE the quads of a row-ordered layout with fp64 entries (tsem_quadorder.h has the rule and why it may be
+// applied): in place on the staged 3-byte index and on the values at their slots of tsem_valmap.h, between the fill and the quad
+// pack, so both index forms get it.  Only column slots and values move; every position keeps its row slot.  One WAVE per
+// sub-block (~50 windows at the benchmark's shapes), 1024 quads = 64 windows at a time:
+//   A  a lane per quad, coalesced 12-byte loads as the fused kernel's load_blk does them; each quad becomes the word of ts_qo_word
+//      in an LDS tile (a window's 16 words in a row of QO_S words: the b128 reads of phase B are conflict-free per 16 lanes);
+//   B  a lane per window walks its 16 words with the counts in registers and leaves the permutation codes in their place;
+//   C  a lane per quad again: quads whose code is not the identity re-read their index and their two value pairs, permute, store.
+constexpr int QO_NT = 256, QO_CHUNK = 1024, QO_S = 20;
+typedef double qo_f64x2 __attribute__((ext_vector_type(2)));
+__global__ __launch_bounds__(QO_NT) void k_quad_order(int64_t n_sb, const int64_t* __restrict__ sb_off, uint32_t* __restrict__ prc,
+                                                       double* __restrict__ pval, unsigned long long* __restrict__ moved) {
+  __shared__ __attribute__((aligned(16))) uint32_t qo_tile[QO_NT / 64][(QO_CHUNK / TS_QO_QUADS) * QO_S];
+  uint32_t* const tile = qo_tile[threadIdx.x >> 6];
+  const uint32_t ln = threadIdx.x & 63u;
+  const int64_t wave = ((int64_t)blockIdx.x * QO_NT + threadIdx.x) >> 6, nwave = ((int64_t)gridDim.x * QO_NT) >> 6;
+  auto at = [](uint32_t q) -> uint32_t { return (q / TS_QO_QUADS) * QO_S + (q % TS_QO_QUADS); };
+  uint32_t n_moved = 0;
+  for (int64_t sb = wave; sb < n_sb; sb += nwave) {
+    const int64_t e0 = sb_off[sb];
+    const uint32_t nq = (uint32_t)((sb_off[sb + 1] - e0) >> 2);   // a multiple of 16
+    uint32_t* const ix = prc + (e0 >> 2) * 3;               // three words per quad
+    double* const val = pval + e0;
+    for (uint32_t c0 = 0; c0 < nq; c0 += QO_CHUNK) {
+      const uint32_t cq = min((uint32_t)QO_CHUNK, nq - c0);
+      for (uint32_t q = ln; q < cq; q += 64u) {
+        const uint32_t* const p = ix + 3 * (size_t)(c0 + q);
+        const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
+        const uint32_t row[4] = {ts_idx24_row<0>(w0, w1, w2), ts_idx24_row<1>(w0, w1, w2), ts_idx24_row<2>(w0, w1, w2), ts_idx24_row<3>(w0, w1, w2)};
+        const uint32_t col[4] = {ts_idx24_col<0>(w0, w1, w2), ts_idx24_col<1>(w0, w1, w2), ts_idx24_col<2>(w0, w1, w2), ts_idx24_col<3>(w0, w1, w2)};
+        tile[at(q)] = ts_qo_word(row, col);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      if (ln < cq / TS_QO_QUADS) {
+        uint32_t w[TS_QO_QUADS];
+#pragma unroll
+        for (int t = 0; t < TS_QO_QUADS / 4; ++t) {
+          const uint4 r = *reinterpret_cast<const uint4*>(tile + ln * QO_S + 4 * t);
+          w[4 * t] = r.x; w[4 * t + 1] = r.y; w[4 * t + 2] = r.z; w[4 * t + 3] = r.w;
+        }
+        unsigned long long h[4] = {0ull, 0ull, 0ull, 0ull};
+#pragma unroll
+        for (int l = 0; l < TS_QO_QUADS; ++l) w[l] = ts_qo_step(w[l], h);
+#pragma unroll
+        for (int t = 0; t < TS_QO_QUADS / 4; ++t)
+          *reinterpret_cast<uint4*>(tile + ln * QO_S + 4 * t) = make_uint4(w[4 * t], w[4 * t + 1], w[4 * t + 2], w[4 * t + 3]);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      for (uint32_t q = ln; q < cq; q += 64u) {
+        const uint32_t code = tile[at(q)];
+        if (code == TS_QO_IDENTITY) continue;
+        ++n_moved;
+        uint32_t* const p = ix + 3 * (size_t)(c0 + q);
+        const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
+        const uint32_t e[4] = {ts_idx24_raw<0>(w0, w1, w2), ts_idx24_raw<1>(w0, w1, w2), ts_idx24_raw<2>(w0, w1, w2), ts_idx24_raw<3>(w0, w1, w2)};
+        // the quad's value pairs: entries 4 q, 4 q + 1 and 4 q + 2, 4 q + 3 of the sub-block, each pair 16 bytes
+        qo_f64x2* const pa = reinterpret_cast<qo_f64x2*>(val + ts_valmap_pos(4u * (c0 + q), nq));
+        qo_f64x2* const pb = reinterpret_cast<qo_f64x2*>(val + ts_valmap_pos(4u * (c0 + q) + 2u, nq));
+        const qo_f64x2 a = *pa, b = *pb;
+        const double v[4] = {a.x, a.y, b.x, b.y};
+        uint32_t ne[4];
+        double nv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                       // position j: its own row slot, the column slot and the value of entry k
+          const uint32_t k = (code >> (2 * j)) & 3u;
+          const uint32_t src = k == 0u ? e[0] : (k == 1u ? e[1] : (k == 2u ? e[2] : e[3]));
+          nv[j] = k == 0u ? v[0] : (k == 1u ? v[1] : (k == 2u ? v[2] : v[3]));
+          const uint32_t cmask = (uint32_t)TS_IDX24_MAX_KP - 1u;
+          ne[j] = (e[j] & (0xFFFFFFu & ~cmask)) | (src & cmask);
+        }
+        p[0] = ne[0] | (ne[1] << 24);
+        p[1] = (ne[1] >> 8) | (ne[2] << 16);
+        p[2] = (ne[2] >> 16) | (ne[3] << 8);
+        qo_f64x2 na, nb;
+        na.x = nv[0]; na.y = nv[1]; nb.x = nv[2]; nb.y = nv[3];
+        *pa = na; *pb = nb;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the next chunk's words go where these codes were)
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+  const int tm = sg_sum_i<64>((int)n_moved);
+  if (ln == 0u && tm) atomicAdd(moved, (unsigned long long)tm);
+}
+
 __global__ void k_make_ctab(int K, const double* __restrict__ pi, const double* __restrict__ theta,
                             const uint32_t* __restrict__ colmap, int Kp, double* __restrict__ ctab) {
   int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1218,7 +1306,7 @@ static int layout_identity_map(tsem_ctx* h) {
   h->nb = 0; h->N_amb_pad = 1; h->nnz_pad = 0; h->max_subblock = 0; h->n_hot_cols = 0;
   h->nnz_amb = h->nnz - h->N_uni;
   h->fmt_code = h->fmt_wcode = false; h->sorted_layout = false; h->idx24 = false; h->valmap = false;
-  h->quad64 = false; h->quad_slots = false; h->n_dummies = 0; h->n_quad_bad = 0;
+  h->quad64 = false; h->quad_slots = false; h->n_dummies = 0; h->n_quad_bad = 0; h->order_kind = 0; h->n_quads_moved = 0;
   h->G1 = h->G2 = 1;
   return TSEM_OK;
 }
@@ -1497,7 +1585,7 @@ static int layout_decide_format(tsem_ctx* h) {
   return TSEM_OK;
 }
 
-// the entry buffers and the fill: k_sb_fill_sorted (+ k_sb_deconflict) in row order, or the strand-transposed k_sb_fill; ends synchronised
+// the entry buffers and the fill: k_sb_fill_sorted (+ k_sb_deconflict or k_quad_order) in row order, or the strand-transposed k_sb_fill; ends synchronised
 static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
   const int K = h->K, P = h->P, R = h->R;
   const int64_t na = h->N_amb, nb = h->nb, off = h->nnz_pad;
@@ -1541,6 +1629,10 @@ static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
     // (reproducible mode keeps the row order: a row's entries in a sub-block then form ONE run, which ends in at most two LDS
     // atomics on its row sum — two additions commute, three need not)
     const bool deconflict = h->fmt_code && h->opt_deconflict != 0 && !h->opt_reproducible && off >= 64;
+    // fp64 entries: the order inside the quads (k_quad_order) where the fused kernel reads them through the value map from a non-split
+    // layout with the 3-byte index staged or final; auto wants a stream HBM serves (option "deconflict_min_bytes", as the quad index's rule)
+    const bool quad_order = h->valmap && h->idx24 && !h->split && !h->fmt_code && !h->opt_reproducible && off >= 64 && h->opt_deconflict != 0 &&
+                            (h->opt_deconflict > 0 || 11 * h->nnz_amb >= h->opt_deconflict_min_bytes);
     const uint32_t magicP = (uint32_t)((0x100000000ull + (uint64_t)P - 1) / (uint64_t)P);
     k_sb_fill_sorted<<<(unsigned)nb, 256, fill_lds_bytes(R, P), h->stream>>>(na, R, P, h->d_slot_row, h->d_indptr, h->d_indices, h->d_raw, h->d_lut,
                                                          h->d_colmap, h->d_sb_off, h->d_pval, h->d_pcode, h->d_prc,
@@ -1550,6 +1642,14 @@ static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
     // quad index: entries were placed one at a time from many threads, and 13-bit fields share bytes — so the fill wrote whole bytes
     // (the 3-byte form) and one thread per quad now writes the final words.  3 + 2 B of index per entry are resident until the
     // staging array goes: the peak of the set-up.
+    DevTmp t_moved;
+    if (quad_order) {
+      TSEM_TMP(t_moved, 8);
+      TSEM_HIP(hipMemsetAsync(t_moved.p, 0, 8, h->stream));
+      k_quad_order<<<(unsigned)std::min<int64_t>(cdiv64(nb * P, QO_NT / 64), (int64_t)h->n_cu * 32), QO_NT, 0, h->stream>>>(
+          nb * P, h->d_sb_off, h->d_prc, h->d_pval, t_moved.as<unsigned long long>());
+      TSEM_HIP(hipGetLastError());
+    }
     uint32_t* d_quad = nullptr;
     TSEM_SCOPED(d_quad);
     DevTmp t_bad;
@@ -1572,6 +1672,13 @@ static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
     if (f0) (void)hipFuncSetAttribute((const void*)f0, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024);   // (a preload: its error is the later call's)
     tsem_report_preload();                                 // (round 6: the report unit's too — ~10 ms that used to sit in the first report)
     TSEM_HIP(hipStreamSynchronize(h->stream));
+    if (deconflict) h->order_kind = 1;
+    if (quad_order) {
+      unsigned long long moved = 0;
+      TSEM_HIP(hipMemcpy(&moved, t_moved.p, 8, hipMemcpyDeviceToHost));
+      h->order_kind = 2;
+      h->n_quads_moved = (int64_t)moved;
+    }
     if (h->quad64) {
       unsigned long long bad = 0;
       TSEM_HIP(hipMemcpy(&bad, t_bad.p, 8, hipMemcpyDeviceToHost));
@@ -1652,7 +1759,7 @@ int tsem_build_layout(tsem_ctx* h) {
   tsem_free_layout(h);
   h->nnz_amb = 0;
   h->n_single_part = 0;
-  h->quad_slots = false; h->n_dummies = 0; h->n_quad_bad = 0;
+  h->quad_slots = false; h->n_dummies = 0; h->n_quad_bad = 0; h->order_kind = 0; h->n_quads_moved = 0;
   if (h->em_rows) return layout_identity_map(h);
   if (int rc = layout_column_map(h, b)) return rc;         // 1., 2.: columns by popularity, dealt to the parts; hot columns split
   b.pt.lap("layout: maps to the device, rid16 alloc");

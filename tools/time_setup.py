@@ -21,4 +21,4 @@ stats, pisum0, cnt, hsh = eng.rowstats(); lap('rowstats')
 eng.set_model(stats, pisum0, cnt, hsh, 0.0, 200000.0); lap('set_model (layout)')
 eng.em_steps(1, False); lap('first EM step')
 eng.em_steps(1, False); lap('second EM step')
-print(eng.layout_info())
+print(eng.layout_info(extended=True))

@@ -799,6 +799,10 @@ int  tsem_debug_idx24(const uint32_t* rc4, uint8_t* out12, uint32_t* back4);
  * again into back4, with the inline functions the pack kernel and the fused kernel use; TSEM_ERR_ARG for a quad the format cannot hold.
  * *stored (may be null): 1 when `probe` names a stored quad, 0 when its low half is the fused kernel's idle mark 0xFFFFFFFF */
 int  tsem_debug_quad64(const uint32_t* rc4, uint64_t* word, uint32_t* back4, uint64_t probe, int32_t* stored);
+/* host only, no device: one cell of the table of fused-kernel instantiations — team size P, kernel mode, entry format (0 fp64, 1 score
+ * codes, 2 fp64 with the score table in LDS), geometry, timeline kernel (0 / 1), index format read (layout_info 'index_format': 0, 1, 2).
+ * *found: 1 when the library's look-up returns a kernel for the cell; *listed: 1 when the table's predicate lists it.  The two agree. */
+int  tsem_debug_fused_cell(int32_t P, int32_t mode, int32_t fmt, int32_t geo, int32_t prof, int32_t ix, int32_t* found, int32_t* listed);
 /* host only, no device: the conflict-aware order inside quads (option "deconflict" on fp64 entries) applied to n_win windows of 64
  * consecutive local row << 16 | local column words: codes[16 w + l] is the permutation of quad l of window w — entry (code >> 2 j) & 3
  * of the quad goes to position j, 0xE4 is the identity —, *moved (may be null) the quads that change; by the inline functions the

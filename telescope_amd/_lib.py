@@ -275,6 +275,7 @@ def lib():
     L.tsem_debug_subblock.argtypes = [vp, C.c_int64, C.c_int32, vp, C.c_int64]
     L.tsem_debug_idx24.argtypes = [vp, vp, vp]
     L.tsem_debug_quad64.argtypes = [vp, vp, vp, C.c_uint64, vp]
+    L.tsem_debug_fused_cell.argtypes = [C.c_int32] * 6 + [vp, vp]
     L.tsem_debug_subblock_values.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int64]
     L.tsem_debug_valmap.argtypes = [C.c_int32, vp]
     L.tsem_quad_order_host.argtypes = [C.c_int64, vp, vp, vp]

@@ -9,6 +9,7 @@
 #include <rccl/rccl.h>   // types and enum values only: the library is resolved at run time (nccl_api, tsem.hip), never linked
 
 #include "telescope_em.h"
+#include "tsem_index.h"
 
 #define TSEM_HIP(call)                                                           \
   do {                                                                           \
@@ -182,17 +183,19 @@ struct tsem_ctx {
   int hot_extra = 0;                // spare slots per part reserved for them
   int n_hot_cols = 0;               // columns that were split
   int64_t opt_format = 0;           // 0 auto (codes when the fused kernel runs and the table fits LDS), 1 fp64, 2 codes
-  uint32_t* d_prc = nullptr;        // [nnz_pad]  lrow<<16 | lcol — or, idx24, 3 bytes per entry (tsem_idx24.h)
+  uint32_t* d_prc = nullptr;        // [nnz_pad]  the entries' index in the format index_fmt names
   bool valmap = false;              // d_pval holds every sub-block's values grouped by wave (tsem_valmap.h): fused kernel, fp64 entries (set by every layout build)
-  bool idx24 = false;               // d_prc holds the 3-byte packed index: fused kernel, non-split layout, fp64 entries (set by every layout build)
+  // The format of d_prc (tsem_index.h): FZ_IX32 one lrow << 16 | lcol word per entry; FZ_IX24 3 bytes per entry (fused kernel, non-split
+  // layout, fp64 entries); FZ_IXQ the quad index.  Every layout build writes the FINAL format in one place (layout_decide_format; the
+  // quad pack's fall-back alone may demote FZ_IXQ to FZ_IX24), and the fused kernels are looked up by it (fz_kernel).
+  int index_fmt = FZ_IX32;
   // The 8-byte quad index (tsem_quad64.h; 2 B of index per entry).  Option "index_format": 0 auto, 1 the 3-byte index, 2 the quad
   // index (an error where it cannot apply).  Auto takes it where the fused kernel reads fp64 entries of a non-split, row-ordered
   // layout outside option "reproducible", geometry 0 or 1, with dummies of at most 0.5 % of nnz_amb and a 3-byte stream of at least
   // opt_quad_min_bytes (option "index_auto_min_bytes"; default 1 GiB: four times the Infinity Cache, a stream HBM certainly serves).
   int64_t opt_index = 0;
   int64_t opt_quad_min_bytes = 1ll << 30;
-  bool quad_slots = false;          // this build raised the per-row part counts: every row of a block has an entry (a real one or a dummy) in every part
-  bool quad64 = false;              // d_prc holds the quad index (then idx24 is false); set by every layout build
+  bool quad_slots = false;          // this build raised the per-row part counts: every row of a block has an entry (a real one or a dummy) in every part (a property of the block cut, not of index_fmt)
   int64_t n_dummies = 0;            // dummy entries (column slot 0, value 0) of this layout: in nnz_pad, not in nnz_amb
   int64_t n_quad_bad = 0;           // quads the pack kernel could not represent (0 by construction; otherwise the layout keeps the 3-byte index)
   double* d_ypart = nullptr;        // [P][N_amb_pad] partial row sums

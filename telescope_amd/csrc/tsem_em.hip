@@ -611,7 +611,7 @@ static int ensure_log_tables(tsem_ctx* h) {
   TSEM_ALLOC(h->d_lqtab, tab.size());
   TSEM_HIP(hipMemcpyAsync(h->d_lqtab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream));
   TSEM_HIP(hipStreamSynchronize(h->stream));               // (tab is a local)
-  fz_fn f9 = fz_kernel(h->P, 9, fmt, h->geo, false, fz_quad(h, 9));
+  fz_fn f9 = fz_kernel(h->P, 9, fmt, h->geo, false, h->index_fmt);
   if (!f9) return TSEM_OK;
   TSEM_HIP(hipFuncSetAttribute((const void*)f9, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
   TSEM_ALLOC(h->d_lctab, h->Kpad);
@@ -702,7 +702,7 @@ static int launch_fused(tsem_ctx* h, int mode, hipEvent_t* pair, int bin = 0) {
     }
   }
   if ((lnl || mode == 8) && h->fz_grid > 2048) TSEM_FAIL(TSEM_ERR_ARG, "fused lnl: more workgroups than partial slots");
-  fz_fn fn = fz_kernel(h->P, kmode, fz_fmt(h), h->geo, prof, fz_quad(h, kmode));
+  fz_fn fn = fz_kernel(h->P, kmode, fz_fmt(h), h->geo, prof, h->index_fmt);
   if (!fn && prof) TSEM_FAIL(TSEM_ERR_ARG, "option fused_prof: the timeline kernel exists for the plain EM pass of teams of 1-4 with the score table in LDS "
                                            "only (not with use_likelihood, the split layout, more than 4 column parts or a score table too large for LDS)");
   if (!fn) TSEM_FAIL(TSEM_ERR_ARG, mode >= 2 ? "reproducible mode needs the fused kernel with a score table of at most 2048 entries"
@@ -712,7 +712,7 @@ static int launch_fused(tsem_ctx* h, int mode, hipEvent_t* pair, int bin = 0) {
   fn<<<h->fz_grid, FZ_NT, ldsf, h->stream>>>(A);
   TSEM_HIP(hipGetLastError());
   if (kmode == 9 && A.sel) {                                // ... and the per-entry-logarithm form behind it: exactly one of the two runs
-    fz_fn f1 = fz_kernel(h->P, 1, fz_fmt(h), h->geo, false, fz_quad(h, 1));
+    fz_fn f1 = fz_kernel(h->P, 1, fz_fmt(h), h->geo, false, h->index_fmt);
     if (!f1) TSEM_FAIL(TSEM_ERR_ARG, "fused lnl: no kernel for this team size / geometry");
     FusedArgs B = A;
     B.lctab = nullptr; B.lqtab = nullptr; B.lq_n = 0; B.lq_lin = 0; B.sel_want = 1;

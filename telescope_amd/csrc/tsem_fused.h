@@ -29,7 +29,8 @@
 //     its 2-byte score code, looked up in an LDS copy of the score table (FMT 1): the
 //     same fp64 number at half the HBM bytes.  The index is 3 B next to fp64 values (11 B
 //     per entry: the pass is bound by the bytes it reads; tsem_idx24.h), 2 B where the layout
-//     build chose the quad index (one 8-byte word per four entries, tsem_quad64.h) and 4 B elsewhere;
+//     build chose the quad index (one 8-byte word per four entries, tsem_quad64.h) and 4 B elsewhere: one format per layout
+//     (tsem_index.h), read by the instantiations that fz_exists — the one table of what is compiled — lists for it;
 //   * a sub-block is stored in row order, so the row sums are reduced in registers and
 //     across lanes (fz_row_sums) and only the end of each run of equal rows issues an
 //     LDS atomic: ds_add_f64 costs 3x a gather (profiles/r01_lds_ubench.log).
@@ -38,6 +39,7 @@
 // time; every wait is bounded and reports through an error word.
 #pragma once
 #include "tsem_idx24.h"
+#include "tsem_index.h"
 #include "tsem_quad64.h"
 #include "tsem_valmap.h"
 
@@ -85,7 +87,7 @@ struct FusedArgs {
   const double* lut;        // FMT 1: the score table, copied to LDS [lut_len]
   int lut_len;
   const uint16_t* wcode;    // FMT 1: [N_amb_pad] row weight as a code, w_i = lut[max code of the row]
-  const uint32_t* prc;      // entry index: 8 B per quad (FZ_IXQ), 3 B per entry (FZ_IX24), else one lrow << 16 | lcol word (FZ_IX32): fz_index()
+  const uint32_t* prc;      // entry index: 8 B per quad (FZ_IXQ), 3 B per entry (FZ_IX24), else one lrow << 16 | lcol word (FZ_IX32): tsem_index.h
   const double* ctab;
   const double* ctab2;  // lnl mode: pi*theta of the CURRENT params (ctab then holds the previous ones); MODE 4: of the PREVIOUS params
   double* lnl_out;      // lnl mode: one partial sum per workgroup [grid]
@@ -308,20 +310,37 @@ struct FzRegs {            // 4 entries per thread: 12 VGPRs (packed index: 11, 
   double2 v0, v1;
   uint2 cd;
 };
-// Which instantiations read the packed 3-byte index (tsem_idx24.h): fp64 entries on the non-split layout.  The layout build stores
-// it under the same condition (tsem_setup.hip, h->idx24): the width is a property of the instantiation, never a run-time branch.
-// (MODE 4 exists for score codes only; the split layout's parts of up to 15 424 columns do not fit 13 bits.)
-__host__ __device__ constexpr bool fz_idx24(int mode, int fmt) {
-  return fmt != 1 && (mode == 0 || mode == 1 || mode == 2 || mode == 3 || mode == 9);
+// The index format (tsem_index.h) of the layouts pass `mode` reads entries of format `fmt` from, the quad index aside: the packed
+// 3-byte index next to fp64 values on the non-split layout, one 32-bit word elsewhere.  (MODE 4 exists for score codes only; the
+// split layout's parts of up to 15 424 columns do not fit 13 bits.)
+__host__ __device__ constexpr int fz_index(int mode, int fmt) {
+  return (fmt != 1 && (mode == 0 || mode == 1 || mode == 2 || mode == 3 || mode == 9)) ? FZ_IX24 : FZ_IX32;
 }
-// The index format of an instantiation: one 32-bit word per entry, the 3-byte packed index, or the 8-byte quad index (tsem_quad64.h).
-// The quad index is a second instantiation of the passes that read a 3-byte layout outside option "reproducible" — the EM pass and
-// both forms of the lnl pass — on the geometries whose row slots fit its 9 bits; the layout build decides which of the two a layout
-// stores (tsem_setup.hip, h->quad64), the host launches the matching kernel.
-constexpr int FZ_IX32 = 0, FZ_IX24 = 1, FZ_IXQ = 2;
-__host__ __device__ constexpr int fz_index(int mode, int fmt) { return fz_idx24(mode, fmt) ? FZ_IX24 : FZ_IX32; }
-__host__ __device__ constexpr bool fz_quad_ok(int mode, int fmt, int geo) {
-  return fmt != 1 && (mode == 0 || mode == 1 || mode == 9) && fz_rmax(geo) <= TS_QUAD64_MAX_R;
+// THE table of k_em_fused's instantiations: team size x mode x entry format x geometry x timeline x index format.  The look-up
+// (tsem_fused_inst.h) is generated from it, the kernel asserts it, and host code that asks whether a kernel exists calls it.  `ix` is
+// the index format the instantiation READS: a property of the instantiation, never a run-time branch.  The layout build stores one
+// format per layout (tsem_ctx::index_fmt) and the host looks kernels up by it, so a kernel that reads another format is not found.
+__host__ __device__ constexpr bool fz_exists(int P, int mode, int fmt, int geo, bool prof, int ix) {
+  if (P < 1 || P > FZ_MAX_P || fmt < 0 || fmt > 2) return false;
+  if (P > 4 ? !(geo == 1 || geo == 2) : !(geo == 0 || geo == 2 || geo == 3)) return false;   // the geometries of a team size (above)
+  if (ix == FZ_IXQ) {
+    // the quad index: a second instantiation of the passes that read a 3-byte layout outside option "reproducible" — the EM pass and
+    // both forms of the lnl pass — on the geometries whose row slots fit its 9 bits (0 and 1)
+    if (fz_index(mode, fmt) != FZ_IX24 || !(mode == 0 || mode == 1 || mode == 9) || fz_rmax(geo) > TS_QUAD64_MAX_R) return false;
+  } else if (ix != fz_index(mode, fmt)) return false;      // every other pass reads exactly one format
+  // the timeline kernel (option "fused_prof"): what tools/fused_prof.py and tools/startup_prof.py launch — the plain EM pass of teams
+  // of 1-4 with the score table in LDS — and nothing else: every instantiation is build time
+  if (prof) return P <= 4 && mode == 0 && fmt != 0;
+  switch (mode) {
+    case 0: case 1: return true;                            // the EM pass, the lnl pass with a logarithm per entry: every format
+    case 2: return fmt != 0;                                // exact (binned) column sums: needs the score table in LDS
+    case 3: return fmt == 1;                                // ... both pieces in one pass: score codes only (a second accumulator table)
+    case 4: return fmt == 1 && geo != 3;                    // EM pass + the previous iteration's lnl: needs the score table in LDS; with fp64
+                                                            // entries, or on geometry 3, the log1p finds no registers
+    case 5: case 7: case 8: return P > 4;                   // split layout (parts of more than 7680 columns): teams of 5-8 only
+    case 9: return fmt != 0;                                // the lnl pass with log tables: needs the score table in LDS
+    default: return false;
+  }
 }
 // Row slot / column slot of entry K of a register set.  The packed index is unpacked HERE, at each use (phase 1, and again in
 // phase 2 four steps later), from the three words the load left: unpacked at the load, the issue would wait for the data.
@@ -618,7 +637,7 @@ __device__ __forceinline__ void fz_xchg(const FusedArgs& A, const FzX& X) {
 // `if constexpr (PROF)`: the kernels the product launches hold none of them, not even the test of A.prof.
 template <int PT, int MODE, int FMT, int GEO, bool PROF = false, int IX = fz_index(MODE, FMT)>
 __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
-  static_assert(IX == fz_index(MODE, FMT) || (IX == FZ_IXQ && fz_quad_ok(MODE, FMT, GEO)), "no such index format for this pass");
+  static_assert(fz_exists(PT, MODE, FMT, GEO, PROF, IX), "not in the table of instantiations (fz_exists)");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int P = PT;
   constexpr int FZ_DT = fz_dt(GEO);

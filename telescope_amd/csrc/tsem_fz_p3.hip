@@ -1,9 +1,6 @@
 // Fused-kernel instantiations for teams of 3 members (one of eight such translation units compiled in parallel, telescope_amd/_lib.py).
 #include "tsem_fused_inst.h"
 
-fz_fn tsem_fz_kernel_p3(int P, int mode, int fmt, int geo, bool prof, bool quad) {
-  switch (P) {
-    case 3: return fz_pick<3>(mode, fmt, geo, prof, quad);
-    default: return nullptr;
-  }
+fz_fn tsem_fz_kernel_p3(int P, int mode, int fmt, int geo, bool prof, int ix) {
+  return P == 3 ? fz_pick<3>(mode, fmt, geo, prof, ix) : nullptr;
 }

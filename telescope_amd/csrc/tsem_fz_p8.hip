@@ -1,6 +1,6 @@
 // Fused-kernel instantiations for teams of 8 members (one of eight such translation units compiled in parallel, telescope_amd/_lib.py).
 #include "tsem_fused_inst.h"
 
-fz_fn tsem_fz_kernel_p8(int P, int mode, int fmt, int geo, bool prof, bool quad) {
-  return P == 8 ? fz_pick<8>(mode, fmt, geo, prof, quad) : nullptr;
+fz_fn tsem_fz_kernel_p8(int P, int mode, int fmt, int geo, bool prof, int ix) {
+  return P == 8 ? fz_pick<8>(mode, fmt, geo, prof, ix) : nullptr;
 }

@@ -523,7 +523,7 @@ int tsem_kernel_stats(tsem_ctx* h, int reset, double* em_ms, int64_t* em_launche
   // one EM pass must read every stored entry of the ambiguous rows once:
   // 4 B packed local row/col + the value AS STORED (8 B fp64 Q, or a 2 B score code) per entry,
   // + 2 B row weight code per row
-  if (algo_bytes) *algo_bytes = h->nnz_amb * (h->fmt_code ? 6 : (h->quad64 ? 10 : (h->idx24 ? 11 : 12))) + h->N_amb * 2;
+  if (algo_bytes) *algo_bytes = h->nnz_amb * (h->fmt_code ? 6 : 8 + fz_index_bytes(h->index_fmt)) + h->N_amb * 2;
   if (reset) { h->em_ms_acc = 0; h->em_launches = 0; h->em_timed = 0; }
   return TSEM_OK;
 }
@@ -557,7 +557,7 @@ int tsem_device_memory(tsem_ctx* h, int device, int64_t* free_bytes, int64_t* to
     resident5[0] = h->d_indptr ? 8 * (h->N + 1) + (h->d_raw ? 2 * nz : 0) : 0;
     resident5[1] = h->d_indices ? 4 * nz : 0;
     resident5[2] = h->d_rid16 ? 2 * nz : 0;
-    resident5[3] = (h->d_prc ? (h->quad64 ? 2 : (h->idx24 ? 3 : 4)) * h->nnz_pad : 0) + (h->d_pcode ? 2 * h->nnz_pad : 0) + (h->d_pval ? 8 * h->nnz_pad : 0) +
+    resident5[3] = (h->d_prc ? fz_index_bytes(h->index_fmt) * h->nnz_pad : 0) + (h->d_pcode ? 2 * h->nnz_pad : 0) + (h->d_pval ? 8 * h->nnz_pad : 0) +
                    (h->d_sb_off ? 12 * (h->nb * h->P + 2) : 0);
     resident5[4] = (h->d_row_code ? 3 * h->N : 0) + (h->d_amb_row ? 6 * h->N_amb : 0) + (h->d_slot_row ? 6 * h->N_amb_pad : 0) +
                    (h->d_uni_col ? 6 * h->N_uni : 0) + (h->d_amb_w ? 8 * h->N_amb_pad : 0) + (h->d_rinv ? 8 * h->N_amb_pad : 0) +
@@ -706,29 +706,23 @@ int64_t tsem_debug_subblock(tsem_ctx* h, int64_t block, int32_t part, uint32_t* 
   int64_t o[2];
   if (hipMemcpy(o, h->d_sb_off + block * h->P + part, 16, hipMemcpyDeviceToHost) != hipSuccess) return TSEM_ERR_HIP;
   const int64_t n = std::min(cap, o[1] - o[0]);
-  if (h->quad64) {                                         // one 64-bit word per quad, through the shared unpack
-    const int64_t nq = (n + 3) / 4;
-    std::vector<uint64_t> raw((size_t)std::max<int64_t>(1, nq));
-    if (nq > 0 && hipMemcpy(raw.data(), reinterpret_cast<const uint8_t*>(h->d_prc) + o[0] * 2, (size_t)nq * 8, hipMemcpyDeviceToHost) != hipSuccess) return TSEM_ERR_HIP;
-    for (int64_t q = 0; q < nq; ++q) {
-      uint32_t rc[4];
-      ts_quad64_unpack_words(raw[q], rc);
-      for (int k = 0; k < 4 && q * 4 + k < n; ++k) out[q * 4 + k] = rc[k];
-    }
+  if (h->index_fmt == FZ_IX32) {
+    if (n > 0 && hipMemcpy(out, h->d_prc + o[0], sizeof(uint32_t) * n, hipMemcpyDeviceToHost) != hipSuccess) return TSEM_ERR_HIP;
     return n;
   }
-  if (h->idx24) {                                          // 3 bytes per entry: whole quads through the shared unpack (sub-blocks are multiples of 64 entries)
-    const int64_t nq = (n + 3) / 4;
-    std::vector<uint8_t> raw((size_t)std::max<int64_t>(1, nq * 12));
-    if (nq > 0 && hipMemcpy(raw.data(), reinterpret_cast<const uint8_t*>(h->d_prc) + o[0] * 3, (size_t)nq * 12, hipMemcpyDeviceToHost) != hipSuccess) return TSEM_ERR_HIP;
-    for (int64_t q = 0; q < nq; ++q) {
-      uint32_t rc[4];
-      ts_idx24_unpack_quad(raw.data() + q * 12, rc);
-      for (int k = 0; k < 4 && q * 4 + k < n; ++k) out[q * 4 + k] = rc[k];
+  // the packed formats: whole quads through the shared unpacks (sub-blocks are multiples of 64 entries)
+  const int64_t nq = (n + 3) / 4, eb = fz_index_bytes(h->index_fmt);
+  std::vector<uint8_t> raw((size_t)std::max<int64_t>(1, nq * 4 * eb));
+  if (nq > 0 && hipMemcpy(raw.data(), reinterpret_cast<const uint8_t*>(h->d_prc) + o[0] * eb, (size_t)(nq * 4 * eb), hipMemcpyDeviceToHost) != hipSuccess) return TSEM_ERR_HIP;
+  for (int64_t q = 0; q < nq; ++q) {
+    uint32_t rc[4];
+    switch (h->index_fmt) {
+      case FZ_IXQ: { uint64_t w; std::memcpy(&w, raw.data() + q * 8, 8); ts_quad64_unpack_words(w, rc); break; }   // one 64-bit word per quad
+      case FZ_IX24: ts_idx24_unpack_quad(raw.data() + q * 12, rc); break;                                           // 3 bytes per entry
+      default: return TSEM_ERR_ARG;
     }
-    return n;
+    for (int k = 0; k < 4 && q * 4 + k < n; ++k) out[q * 4 + k] = rc[k];
   }
-  if (n > 0 && hipMemcpy(out, h->d_prc + o[0], sizeof(uint32_t) * n, hipMemcpyDeviceToHost) != hipSuccess) return TSEM_ERR_HIP;
   return n;
 }
 
@@ -794,6 +788,15 @@ int tsem_debug_quad64(const uint32_t* rc4, uint64_t* word, uint32_t* back4, uint
   return TSEM_OK;
 }
 
+/* host only: one cell of the table of fused-kernel instantiations — what the look-up returns (fz_kernel) and what the predicate it is
+ * generated from says (fz_exists, tsem_fused.h) */
+int tsem_debug_fused_cell(int32_t P, int32_t mode, int32_t fmt, int32_t geo, int32_t prof, int32_t ix, int32_t* found, int32_t* listed) {
+  if (!found || !listed) return TSEM_ERR_ARG;
+  *found = fz_kernel(P, mode, fmt, geo, prof != 0, ix) != nullptr ? 1 : 0;
+  *listed = fz_exists(P, mode, fmt, geo, prof != 0, ix) ? 1 : 0;
+  return TSEM_OK;
+}
+
 /* host only: the rule of tsem_quadorder.h on n_win windows of 64 lrow << 16 | lcol words each: codes[16 w + l] is the permutation of quad
  * l of window w (entry (code >> 2 j) & 3 goes to position j), *moved (may be null) the quads whose code is not the identity */
 int tsem_quad_order_host(int64_t n_win, const uint32_t* rc, uint8_t* codes, int64_t* moved) {
@@ -821,8 +824,8 @@ int tsem_layout_info(tsem_ctx* h, int64_t* info) {
 int tsem_layout_info_n(tsem_ctx* h, int64_t* out, int32_t n) {
   if (!h || !out || n < 0) return TSEM_ERR_ARG;
   int64_t info[TSEM_LAYOUT_INFO_N] = {};
-  info[32] = h->quad64 ? 2 : (h->idx24 ? 3 : 4);           // bytes of index per stored entry (3: the packed index of tsem_idx24.h, 2: the quad index of tsem_quad64.h)
-  info[40] = h->quad64 ? 2 : (h->idx24 ? 1 : 0);           // the index format in use, as fz_index(): 0 one word per entry, 1 three bytes, 2 the quad index
+  info[32] = fz_index_bytes(h->index_fmt);                 // bytes of index per stored entry (3: the packed index of tsem_idx24.h, 2: the quad index of tsem_quad64.h)
+  info[40] = h->index_fmt;                                 // the index format in use (tsem_index.h): 0 one word per entry, 1 three bytes, 2 the quad index
   info[41] = h->quad_slots ? h->n_dummies : 0;             // dummy entries (column slot 0, value 0) that give every row an entry in every part: in nnz_pad, not in nnz_amb
   info[42] = h->n_quad_bad;                                // quads the pack kernel could not represent (0 by construction; otherwise the layout kept the 3-byte index)
   info[43] = h->opt_quad_min_bytes;                        // option "index_auto_min_bytes"

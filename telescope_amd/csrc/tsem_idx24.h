@@ -44,6 +44,11 @@ template <int K> __host__ __device__ inline uint32_t ts_idx24_row(uint32_t w0, u
 template <int K> __host__ __device__ inline uint32_t ts_idx24_col(uint32_t w0, uint32_t w1, uint32_t w2) {
   return ts_idx24_raw<K>(w0, w1, w2) & (uint32_t)(TS_IDX24_MAX_KP - 1);
 }
+// the row slots and the column slots of the quad's four entries
+__host__ __device__ inline void ts_idx24_quad(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t row[4], uint32_t col[4]) {
+  row[0] = ts_idx24_row<0>(w0, w1, w2); row[1] = ts_idx24_row<1>(w0, w1, w2); row[2] = ts_idx24_row<2>(w0, w1, w2); row[3] = ts_idx24_row<3>(w0, w1, w2);
+  col[0] = ts_idx24_col<0>(w0, w1, w2); col[1] = ts_idx24_col<1>(w0, w1, w2); col[2] = ts_idx24_col<2>(w0, w1, w2); col[3] = ts_idx24_col<3>(w0, w1, w2);
+}
 
 // host side: four lrow << 16 | lcol words <-> the 12 bytes of a quad
 inline void ts_idx24_pack_quad(const uint32_t rc[4], uint8_t out[12]) {
@@ -56,8 +61,7 @@ inline void ts_idx24_unpack_quad(const uint8_t in[12], uint32_t rc[4]) {
   uint32_t w[3];
   for (int j = 0; j < 3; ++j)
     w[j] = (uint32_t)in[4 * j] | ((uint32_t)in[4 * j + 1] << 8) | ((uint32_t)in[4 * j + 2] << 16) | ((uint32_t)in[4 * j + 3] << 24);
-  rc[0] = (ts_idx24_row<0>(w[0], w[1], w[2]) << 16) | ts_idx24_col<0>(w[0], w[1], w[2]);
-  rc[1] = (ts_idx24_row<1>(w[0], w[1], w[2]) << 16) | ts_idx24_col<1>(w[0], w[1], w[2]);
-  rc[2] = (ts_idx24_row<2>(w[0], w[1], w[2]) << 16) | ts_idx24_col<2>(w[0], w[1], w[2]);
-  rc[3] = (ts_idx24_row<3>(w[0], w[1], w[2]) << 16) | ts_idx24_col<3>(w[0], w[1], w[2]);
+  uint32_t row[4], col[4];
+  ts_idx24_quad(w[0], w[1], w[2], row, col);
+  for (int k = 0; k < 4; ++k) rc[k] = (row[k] << 16) | col[k];
 }

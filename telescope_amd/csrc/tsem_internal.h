@@ -16,7 +16,9 @@
 //                    the stages' bodies are host / device functions in tsem_bam_rec.h and tsem_bam_stages.h, the record chain in tsem_bam_scan.h)
 //   tsem_bgzf.hip    the BGZF blocks of a BAM file inflated on the device (tsem_bgzf_*; the body is the host / device function of
 //                    tsem_bgzf_inflate.h, the chain of block headers in tsem_bgzf_scan.h)
-//   tsem_fz_p*.hip   instantiations of the fused kernel (tsem_fused.h), one team size per unit
+//   tsem_fz_p*.hip   instantiations of the fused kernel, one team size per unit: the look-up generated (tsem_fused_inst.h) from the one
+//                    table of what exists, fz_exists (tsem_fused.h)
+//   tsem_index.h     the index formats of the layout's entries: tsem_ctx::index_fmt, fz_exists' `ix`, layout_info()
 //   tsem_model.h     the model's scalar arithmetic (numerator, closed forms, twin rule, prior scale) for tsem_em / _cellem / _boot
 //
 // A kernel is launched only from the unit that defines it; other units go through the host functions declared here.
@@ -134,33 +136,29 @@ static inline int ensure_device(tsem_ctx* h) {
   return TSEM_OK;
 }
 
-// The fused kernel's instantiations (team size x mode x entry format x geometry: ~200 kernels, most of the library's build time)
-// live in eight translation units compiled in parallel (tsem_fz_p1.hip ... tsem_fz_p8.hip, tsem_fused_inst.h); each exports one
-// look-up function.  The host launches through the pointer.
+// The fused kernel's instantiations (fz_exists, tsem_fused.h: 376 kernels, most of the library's build time) live in eight
+// translation units compiled in parallel (tsem_fz_p1.hip ... tsem_fz_p8.hip, tsem_fused_inst.h); each exports one look-up function.
+// The host launches through the pointer.  ix: the index format the kernel must read — callers pass the layout's, h->index_fmt, and a
+// kernel that reads another format is not returned.  Host code that only asks whether a kernel exists calls fz_exists.
 typedef void (*fz_fn)(FusedArgs);
-fz_fn tsem_fz_kernel_p1(int P, int mode, int fmt, int geo, bool prof, bool quad);
-fz_fn tsem_fz_kernel_p2(int P, int mode, int fmt, int geo, bool prof, bool quad);
-fz_fn tsem_fz_kernel_p3(int P, int mode, int fmt, int geo, bool prof, bool quad);
-fz_fn tsem_fz_kernel_p4(int P, int mode, int fmt, int geo, bool prof, bool quad);
-fz_fn tsem_fz_kernel_p5(int P, int mode, int fmt, int geo, bool prof, bool quad);
-fz_fn tsem_fz_kernel_p6(int P, int mode, int fmt, int geo, bool prof, bool quad);
-fz_fn tsem_fz_kernel_p7(int P, int mode, int fmt, int geo, bool prof, bool quad);
-fz_fn tsem_fz_kernel_p8(int P, int mode, int fmt, int geo, bool prof, bool quad);
+fz_fn tsem_fz_kernel_p1(int P, int mode, int fmt, int geo, bool prof, int ix);
+fz_fn tsem_fz_kernel_p2(int P, int mode, int fmt, int geo, bool prof, int ix);
+fz_fn tsem_fz_kernel_p3(int P, int mode, int fmt, int geo, bool prof, int ix);
+fz_fn tsem_fz_kernel_p4(int P, int mode, int fmt, int geo, bool prof, int ix);
+fz_fn tsem_fz_kernel_p5(int P, int mode, int fmt, int geo, bool prof, int ix);
+fz_fn tsem_fz_kernel_p6(int P, int mode, int fmt, int geo, bool prof, int ix);
+fz_fn tsem_fz_kernel_p7(int P, int mode, int fmt, int geo, bool prof, int ix);
+fz_fn tsem_fz_kernel_p8(int P, int mode, int fmt, int geo, bool prof, int ix);
 static inline int fz_fmt(const tsem_ctx* h) { return h->fmt_code ? 1 : (h->fmt_wcode ? 2 : 0); }
-// quad: the instantiation that reads the 8-byte quad index (a layout with h->quad64; tsem_quad64.h) — callers pass fz_quad(h, mode)
-static inline fz_fn fz_kernel(int P, int mode, int fmt, int geo, bool prof = false, bool quad = false) {
+static inline fz_fn fz_kernel(int P, int mode, int fmt, int geo, bool prof, int ix) {
   switch (P) {
-    case 1: return tsem_fz_kernel_p1(P, mode, fmt, geo, prof, quad); case 2: return tsem_fz_kernel_p2(P, mode, fmt, geo, prof, quad);
-    case 3: return tsem_fz_kernel_p3(P, mode, fmt, geo, prof, quad); case 4: return tsem_fz_kernel_p4(P, mode, fmt, geo, prof, quad);
-    case 5: return tsem_fz_kernel_p5(P, mode, fmt, geo, prof, quad); case 6: return tsem_fz_kernel_p6(P, mode, fmt, geo, prof, quad);
-    case 7: return tsem_fz_kernel_p7(P, mode, fmt, geo, prof, quad); case 8: return tsem_fz_kernel_p8(P, mode, fmt, geo, prof, quad);
+    case 1: return tsem_fz_kernel_p1(P, mode, fmt, geo, prof, ix); case 2: return tsem_fz_kernel_p2(P, mode, fmt, geo, prof, ix);
+    case 3: return tsem_fz_kernel_p3(P, mode, fmt, geo, prof, ix); case 4: return tsem_fz_kernel_p4(P, mode, fmt, geo, prof, ix);
+    case 5: return tsem_fz_kernel_p5(P, mode, fmt, geo, prof, ix); case 6: return tsem_fz_kernel_p6(P, mode, fmt, geo, prof, ix);
+    case 7: return tsem_fz_kernel_p7(P, mode, fmt, geo, prof, ix); case 8: return tsem_fz_kernel_p8(P, mode, fmt, geo, prof, ix);
     default: return nullptr;
   }
 }
-
-// does pass `mode` of this layout read the quad index?  (a quad layout exists only where every pass that reads it has the kernel:
-// layout_decide_format)
-static inline bool fz_quad(const tsem_ctx* h, int mode) { return h->quad64 && (mode == 0 || mode == 1 || mode == 9); }
 
 // code16 entry format: only with the fused kernel, and only while the score table is small enough to
 // sit in LDS beside the column tables (uint16 scores allow 65536 entries; alignments give a few hundred).

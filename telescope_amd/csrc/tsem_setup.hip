@@ -380,9 +380,8 @@ __global__ __launch_bounds__(256) void k_quad_pack(int64_t nquads, const uint32_
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int miss = 0;
   if (t < nquads) {
-    const uint32_t w0 = stage[3 * t], w1 = stage[3 * t + 1], w2 = stage[3 * t + 2];
-    const uint32_t row[4] = {ts_idx24_row<0>(w0, w1, w2), ts_idx24_row<1>(w0, w1, w2), ts_idx24_row<2>(w0, w1, w2), ts_idx24_row<3>(w0, w1, w2)};
-    const uint32_t col[4] = {ts_idx24_col<0>(w0, w1, w2), ts_idx24_col<1>(w0, w1, w2), ts_idx24_col<2>(w0, w1, w2), ts_idx24_col<3>(w0, w1, w2)};
+    uint32_t row[4], col[4];
+    ts_idx24_quad(stage[3 * t], stage[3 * t + 1], stage[3 * t + 2], row, col);
     const bool ok = ts_quad64_fits(row, col);
     out[t] = ok ? (unsigned long long)ts_quad64_pack(row, col) : 0ull;
     miss = ok ? 0 : 1;
@@ -427,17 +426,17 @@ __global__ __launch_bounds__(256) void k_sb_count(int64_t N_amb, int R, int P, c
   if (threadIdx.x < P) sb_cnt[b * P + threadIdx.x] = cnt[threadIdx.x];
 }
 
-// The index of entry `pos` of the blocked layout: the 3-byte packed form (tsem_idx24.h) where the fused kernel reads fp64 entries
-// of a non-split layout (h->idx24), one lrow << 16 | lcol word everywhere else.  Wave-uniform choice (a kernel argument).
-__device__ __forceinline__ void sb_store_index(uint32_t* __restrict__ prc, int64_t pos, uint32_t lrow, uint32_t lcol, int idx24) {
-  if (idx24) ts_idx24_store(reinterpret_cast<uint8_t*>(prc), pos, lrow, lcol);
+// The index of entry `pos` of the blocked layout as the fill stores it: the 3-byte packed form (FZ_IX24, tsem_idx24.h; also what the
+// fill stages for the quad pack) or one lrow << 16 | lcol word (FZ_IX32).  Wave-uniform choice (a kernel argument).
+__device__ __forceinline__ void sb_store_index(uint32_t* __restrict__ prc, int64_t pos, uint32_t lrow, uint32_t lcol, int ix) {
+  if (ix == FZ_IX24) ts_idx24_store(reinterpret_cast<uint8_t*>(prc), pos, lrow, lcol);
   else prc[pos] = (lrow << 16) | lcol;
 }
 
 __global__ __launch_bounds__(256) void k_sb_fill(int64_t N_amb, int R, int P, const int32_t* __restrict__ amb_row,
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, const uint16_t* __restrict__ raw,
     const double* __restrict__ lut, const uint32_t* __restrict__ colmap, const int64_t* __restrict__ sb_off,
-    double* __restrict__ pval, uint16_t* __restrict__ pcode, uint32_t* __restrict__ prc, int idx24,
+    double* __restrict__ pval, uint16_t* __restrict__ pcode, uint32_t* __restrict__ prc, int ix,
     int valmap /* fp64 values at their slot of tsem_valmap.h */) {
   __shared__ uint32_t cur[64];
   if (threadIdx.x < 64) cur[threadIdx.x] = 0;
@@ -461,7 +460,7 @@ __global__ __launch_bounds__(256) void k_sb_fill(int64_t N_amb, int R, int P, co
       int64_t pos = base + (int64_t)(t % TS_STRANDS) * L + t / TS_STRANDS;
       if (pcode) pcode[pos] = raw[k];
       else pval[base + ts_valmap_slot((uint32_t)(pos - base), L * (TS_STRANDS / 4), valmap)] = lut[raw[k]];
-      sb_store_index(prc, pos, (uint32_t)lr, (cm & CM_SM) + (t & ((1u << ((cm >> CM_LS) & 7u)) - 1u)), idx24);   // hot column: deal over its slots
+      sb_store_index(prc, pos, (uint32_t)lr, (cm & CM_SM) + (t & ((1u << ((cm >> CM_LS) & 7u)) - 1u)), ix);   // hot column: deal over its slots
     }
   }
 }
@@ -484,7 +483,7 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
     const int64_t* __restrict__ bstart, const unsigned long long* __restrict__ pc,
     const uint16_t* __restrict__ rid /* popularity ids (slot * P + part) instead of the column-map gather, or null */,
     uint32_t magicP /* ceil(2^32 / P) */, int nsplit /* ids below this may be split columns */, const uint8_t* __restrict__ lgtab,
-    int idx24 /* store the 3-byte packed index (sb_store_index) */, int valmap /* fp64 values at their slot of tsem_valmap.h */,
+    int ix /* FZ_IX24 or FZ_IX32 (sb_store_index) */, int valmap /* fp64 values at their slot of tsem_valmap.h */,
     int dummies /* k_pc_raise reserved a slot in every part for every row: fill the ones no real entry takes */) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fl_lds[];
   uint32_t* const cnt = reinterpret_cast<uint32_t*>(fl_lds);                   // [row slot][part]: counts, then write cursors
@@ -577,7 +576,7 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
       const int64_t pos = sbase[p] + t;
       if (pcode) pcode[pos] = (uint16_t)code;
       else pval[sbase[p] + ts_valmap_slot(t, snq[p], valmap)] = lut[code];
-      sb_store_index(prc, pos, (uint32_t)lr, (cm & CM_SM) + (t & ((1u << ((cm >> CM_LS) & 7u)) - 1u)), idx24);   // hot column: deal over its slots
+      sb_store_index(prc, pos, (uint32_t)lr, (cm & CM_SM) + (t & ((1u << ((cm >> CM_LS) & 7u)) - 1u)), ix);   // hot column: deal over its slots
     }
   };
   // quad index: behind a row's entries, one dummy (this row slot, column slot 0, value 0: what padding is, and as harmless — +0.0 to
@@ -591,7 +590,7 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
     const int64_t pos = sbase[lane] + t;
     if (pcode) pcode[pos] = (uint16_t)0;
     else pval[sbase[lane] + ts_valmap_slot(t, snq[lane], valmap)] = 0.0;
-    sb_store_index(prc, pos, (uint32_t)lr, 0u, idx24);
+    sb_store_index(prc, pos, (uint32_t)lr, 0u, ix);
   };
   auto cm_of_id = [&](uint32_t id) -> uint32_t {           // the ids k_row_partcounts wrote: a coalesced 2-byte read instead of a gather
     const uint32_t slot = P == 1 ? id : __umulhi(id, magicP);   // id / P, exact for 16-bit ids and 2 <= P <= 8 (ceil(2^32 / 1) does not fit 32 bits)
@@ -640,7 +639,7 @@ __global__ __launch_bounds__(256) void k_sb_fill_sorted(int64_t N_amb, int R, in
   for (int p = 0; p < P; ++p) {                            // padding: value 0 (written here: the buffers of this path are not zero-filled), row = last row
     const int64_t base = sbase[p], end = sb_off[b * P + p + 1];
     for (int64_t pos = base + total[p] + threadIdx.x; pos < end; pos += blockDim.x) {
-      sb_store_index(prc, pos, lastrow[p], 0u, idx24);
+      sb_store_index(prc, pos, lastrow[p], 0u, ix);
       if (pcode) pcode[pos] = (uint16_t)0; else pval[base + ts_valmap_slot((uint32_t)(pos - base), snq[p], valmap)] = 0.0;
     }
   }
@@ -816,9 +815,8 @@ __global__ __launch_bounds__(QO_NT) void k_quad_order(int64_t n_sb, const int64_
       const uint32_t cq = min((uint32_t)QO_CHUNK, nq - c0);
       for (uint32_t q = ln; q < cq; q += 64u) {
         const uint32_t* const p = ix + 3 * (size_t)(c0 + q);
-        const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
-        const uint32_t row[4] = {ts_idx24_row<0>(w0, w1, w2), ts_idx24_row<1>(w0, w1, w2), ts_idx24_row<2>(w0, w1, w2), ts_idx24_row<3>(w0, w1, w2)};
-        const uint32_t col[4] = {ts_idx24_col<0>(w0, w1, w2), ts_idx24_col<1>(w0, w1, w2), ts_idx24_col<2>(w0, w1, w2), ts_idx24_col<3>(w0, w1, w2)};
+        uint32_t row[4], col[4];
+        ts_idx24_quad(p[0], p[1], p[2], row, col);
         tile[at(q)] = ts_qo_word(row, col);
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -844,8 +842,8 @@ __global__ __launch_bounds__(QO_NT) void k_quad_order(int64_t n_sb, const int64_
         if (code == TS_QO_IDENTITY) continue;
         ++n_moved;
         uint32_t* const p = ix + 3 * (size_t)(c0 + q);
-        const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
-        const uint32_t e[4] = {ts_idx24_raw<0>(w0, w1, w2), ts_idx24_raw<1>(w0, w1, w2), ts_idx24_raw<2>(w0, w1, w2), ts_idx24_raw<3>(w0, w1, w2)};
+        uint32_t row[4], col[4];
+        ts_idx24_quad(p[0], p[1], p[2], row, col);
         // the quad's value pairs: entries 4 q, 4 q + 1 and 4 q + 2, 4 q + 3 of the sub-block, each pair 16 bytes
         qo_f64x2* const pa = reinterpret_cast<qo_f64x2*>(val + ts_valmap_pos(4u * (c0 + q), nq));
         qo_f64x2* const pb = reinterpret_cast<qo_f64x2*>(val + ts_valmap_pos(4u * (c0 + q) + 2u, nq));
@@ -856,10 +854,8 @@ __global__ __launch_bounds__(QO_NT) void k_quad_order(int64_t n_sb, const int64_
 #pragma unroll
         for (int j = 0; j < 4; ++j) {                       // position j: its own row slot, the column slot and the value of entry k
           const uint32_t k = (code >> (2 * j)) & 3u;
-          const uint32_t src = k == 0u ? e[0] : (k == 1u ? e[1] : (k == 2u ? e[2] : e[3]));
           nv[j] = k == 0u ? v[0] : (k == 1u ? v[1] : (k == 2u ? v[2] : v[3]));
-          const uint32_t cmask = (uint32_t)TS_IDX24_MAX_KP - 1u;
-          ne[j] = (e[j] & (0xFFFFFFu & ~cmask)) | (src & cmask);
+          ne[j] = ts_idx24_entry(row[j], k == 0u ? col[0] : (k == 1u ? col[1] : (k == 2u ? col[2] : col[3])));
         }
         p[0] = ne[0] | (ne[1] << 24);
         p[1] = (ne[1] >> 8) | (ne[2] << 16);
@@ -1305,8 +1301,8 @@ static int layout_identity_map(tsem_ctx* h) {
   TSEM_HIP(hipMemcpy(h->d_col_of_pc, cpc.data(), sizeof(int32_t) * h->Kpad, hipMemcpyHostToDevice));
   h->nb = 0; h->N_amb_pad = 1; h->nnz_pad = 0; h->max_subblock = 0; h->n_hot_cols = 0;
   h->nnz_amb = h->nnz - h->N_uni;
-  h->fmt_code = h->fmt_wcode = false; h->sorted_layout = false; h->idx24 = false; h->valmap = false;
-  h->quad64 = false; h->quad_slots = false; h->n_dummies = 0; h->n_quad_bad = 0; h->order_kind = 0; h->n_quads_moved = 0;
+  h->fmt_code = h->fmt_wcode = false; h->sorted_layout = false; h->index_fmt = FZ_IX32; h->valmap = false;
+  h->quad_slots = false; h->n_dummies = 0; h->n_quad_bad = 0; h->order_kind = 0; h->n_quads_moved = 0;
   h->G1 = h->G2 = 1;
   return TSEM_OK;
 }
@@ -1386,7 +1382,7 @@ static bool quad_possible(const tsem_ctx* h) {
   if (fz_wants_codes(h) && fz_lds_bytes(h, true) <= (size_t)TS_LDS_MAX - 1024) return false;          // score codes (layout_decide_format)
   if (!(h->R * h->P <= FILL_MAX_RP && (h->opt_sorted >= 0 ? h->opt_sorted != 0 : true))) return false;   // row order
   const int fmt = (h->lut_len > 0 && h->lut_len <= 2048 && fz_lds_bytes(h, true) <= (size_t)TS_LDS_MAX - 1024) ? 2 : 0;
-  return fz_kernel(h->P, 0, fmt, h->geo, false, true) != nullptr && fz_kernel(h->P, 1, fmt, h->geo, false, true) != nullptr;
+  return fz_exists(h->P, 0, fmt, h->geo, false, FZ_IXQ) && fz_exists(h->P, 1, fmt, h->geo, false, FZ_IXQ);
 }
 
 // the fused layout's blocks (no part may exceed FZ_CAP entries, at most R rows); a row that overflows the tile: use_fused goes, no b.d_bs
@@ -1561,9 +1557,8 @@ static int layout_decide_format(tsem_ctx* h) {
   if (h->opt_reproducible && !(h->use_fused && (h->fmt_code || h->fmt_wcode)))
     TSEM_FAIL(TSEM_ERR_ARG, "reproducible mode needs the fused kernel (at most 8 column parts, every row within the register tile) and a score "
                             "table of at most 2048 entries");
-  // fp64 entries under the fused kernel, non-split: 3 B of index per entry (the instantiations of fz_idx24(), tsem_fused.h).  Decided
-  // HERE for every build of the layout, the rebuild of the two-pass fall-back included (use_fused is false then: 4 B again).
-  h->idx24 = h->use_fused && !h->split && !h->fmt_code;
+  // fp64 entries under the fused kernel, non-split: 3 B of index per entry (what fz_index() names for their passes, tsem_fused.h).
+  const bool idx24 = h->use_fused && !h->split && !h->fmt_code;
   // ... and their values grouped by wave (tsem_valmap.h) wherever the fused kernel's load_blk reads fp64 entries: FMT 0 and 2, every
   // geometry, the split layout's passes too.  The two-pass kernels read the values entry by entry: their rebuild clears it.
   h->valmap = h->use_fused && !h->fmt_code;
@@ -1576,10 +1571,12 @@ static int layout_decide_format(tsem_ctx* h) {
   h->sorted_layout = h->use_fused && R * h->P <= FILL_MAX_RP &&   // (the fill kernel keeps R x P counters in LDS)
                      (h->opt_sorted >= 0 ? h->opt_sorted != 0 : true);
   // The quad index (2 B per entry, tsem_quad64.h) where this build reserved a slot for every (row, part) cell and everything asked
-  // before the blocks were cut still holds.  The fill stages the 3-byte index (idx24 stays set until the pack kernel has replaced it).
-  h->quad64 = h->quad_slots && h->idx24 && h->sorted_layout && quad_possible(h) && h->nb > 0;
+  // before the blocks were cut still holds.  The index format is decided HERE, in its final form, for every build of the layout, the
+  // rebuild of the two-pass fall-back included (use_fused is false then: 4 B again); how layout_fill gets there is its own business.
+  const bool quad = h->quad_slots && idx24 && h->sorted_layout && quad_possible(h) && h->nb > 0;
+  h->index_fmt = quad ? FZ_IXQ : (idx24 ? FZ_IX24 : FZ_IX32);
   h->n_quad_bad = 0;
-  if (h->opt_index == 2 && !h->quad64)
+  if (h->opt_index == 2 && !quad)
     TSEM_FAIL(TSEM_ERR_ARG, "index_format=2 (quad index) needs the fused kernel on fp64 entries (value_format=1 or a score table too large for LDS) "
                             "of a non-split, row-ordered layout with at most 512 row slots per block (geometry 0 or 1), and not option reproducible");
   return TSEM_OK;
@@ -1592,7 +1589,9 @@ static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
   // (zero-filled for the strand-transposed fill only, whose padding is whatever it does not write; the row-order fill writes
   //  every position, padding included — 12-24 GB of memsets, ~3 ms at 2e9 entries, went away with that)
   const bool row_order = h->sorted_layout && nb > 0;
-  const int64_t prc_words = h->idx24 ? (off * 3 + 3) / 4 : off;   // (sub-blocks are padded to 64 entries: a multiple of 192 B each)
+  // the format the fill kernels write: the layout's, or — the quad index: entries are placed one at a time — the staged 3-byte form
+  const int fill_ix = h->index_fmt == FZ_IX32 ? FZ_IX32 : FZ_IX24;
+  const int64_t prc_words = fill_ix == FZ_IX24 ? (off * 3 + 3) / 4 : off;   // (sub-blocks are padded to 64 entries: a multiple of 192 B each)
   TSEM_ALLOC(h->d_prc, prc_words);
   if (!row_order) TSEM_HIP(hipMemsetAsync(h->d_prc, 0, sizeof(uint32_t) * std::max<int64_t>(1, prc_words), h->stream));
   if (h->fmt_code) {
@@ -1631,12 +1630,12 @@ static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
     const bool deconflict = h->fmt_code && h->opt_deconflict != 0 && !h->opt_reproducible && off >= 64;
     // fp64 entries: the order inside the quads (k_quad_order) where the fused kernel reads them through the value map from a non-split
     // layout with the 3-byte index staged or final; auto wants a stream HBM serves (option "deconflict_min_bytes", as the quad index's rule)
-    const bool quad_order = h->valmap && h->idx24 && !h->split && !h->fmt_code && !h->opt_reproducible && off >= 64 && h->opt_deconflict != 0 &&
+    const bool quad_order = h->valmap && fill_ix == FZ_IX24 && !h->split && !h->fmt_code && !h->opt_reproducible && off >= 64 && h->opt_deconflict != 0 &&
                             (h->opt_deconflict > 0 || 11 * h->nnz_amb >= h->opt_deconflict_min_bytes);
     const uint32_t magicP = (uint32_t)((0x100000000ull + (uint64_t)P - 1) / (uint64_t)P);
     k_sb_fill_sorted<<<(unsigned)nb, 256, fill_lds_bytes(R, P), h->stream>>>(na, R, P, h->d_slot_row, h->d_indptr, h->d_indices, h->d_raw, h->d_lut,
                                                          h->d_colmap, h->d_sb_off, h->d_pval, h->d_pcode, h->d_prc,
-                                                         b.d_pc ? b.d_bs : nullptr, b.d_pc, rid_fill, magicP, nsplit, d_lgtab, h->idx24 ? 1 : 0,
+                                                         b.d_pc ? b.d_bs : nullptr, b.d_pc, rid_fill, magicP, nsplit, d_lgtab, fill_ix,
                                                          h->valmap ? 1 : 0, (h->quad_slots && b.d_pc) ? 1 : 0);
     TSEM_HIP(hipGetLastError());
     // quad index: entries were placed one at a time from many threads, and 13-bit fields share bytes — so the fill wrote whole bytes
@@ -1653,7 +1652,7 @@ static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
     uint32_t* d_quad = nullptr;
     TSEM_SCOPED(d_quad);
     DevTmp t_bad;
-    if (h->quad64) {
+    if (h->index_fmt == FZ_IXQ) {
       TSEM_TMP(t_bad, 8);
       TSEM_HIP(hipMemsetAsync(t_bad.p, 0, 8, h->stream));
       TSEM_ALLOC(d_quad, off / 2);                         // (8 B per quad)
@@ -1668,7 +1667,7 @@ static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
     }
     // While the device fills the layout (15 ms at 2e9 entries) the host loads the code object of the fused kernel's unit — 3 ms in a
     // fresh process, at the first hipFuncSetAttribute / launch of one of its kernels — instead of doing so afterwards.
-    fz_fn f0 = P <= FZ_MAX_P ? fz_kernel(P, h->split ? 5 : 0, fz_fmt(h), h->geo, false, fz_quad(h, 0)) : nullptr;
+    fz_fn f0 = P <= FZ_MAX_P ? fz_kernel(P, h->split ? 5 : 0, fz_fmt(h), h->geo, false, h->index_fmt) : nullptr;
     if (f0) (void)hipFuncSetAttribute((const void*)f0, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024);   // (a preload: its error is the later call's)
     tsem_report_preload();                                 // (round 6: the report unit's too — ~10 ms that used to sit in the first report)
     TSEM_HIP(hipStreamSynchronize(h->stream));
@@ -1679,19 +1678,19 @@ static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
       h->order_kind = 2;
       h->n_quads_moved = (int64_t)moved;
     }
-    if (h->quad64) {
+    if (h->index_fmt == FZ_IXQ) {
       unsigned long long bad = 0;
       TSEM_HIP(hipMemcpy(&bad, t_bad.p, 8, hipMemcpyDeviceToHost));
       h->n_quad_bad = (int64_t)bad;
-      if (bad == 0) { dfree(h->d_prc); h->d_prc = d_quad; d_quad = nullptr; h->idx24 = false; }
-      else h->quad64 = false;             // (0 by construction; the staging array is a complete 3-byte index: it stays)
+      if (bad == 0) { dfree(h->d_prc); h->d_prc = d_quad; d_quad = nullptr; }
+      else h->index_fmt = FZ_IX24;        // (0 by construction; the staging array is a complete 3-byte index: it stays)
     }
     // option "drop_csr_indices": the fill was the last reader of the CSR column ids (the report pass and this layout carry 2-byte
     // popularity ids; col = col_of_id[id]): 10 instead of 14 B per stored entry stay resident.
     if (rid_fill && h->d_col_of_id && drops_indices(h)) dfree(h->d_indices);
   } else if (nb) {
     k_sb_fill<<<(unsigned)nb, 256, 0, h->stream>>>(na, R, P, h->d_slot_row, h->d_indptr, h->d_indices, h->d_raw, h->d_lut,
-                                                  h->d_colmap, h->d_sb_off, h->d_pval, h->d_pcode, h->d_prc, h->idx24 ? 1 : 0, h->valmap ? 1 : 0);
+                                                  h->d_colmap, h->d_sb_off, h->d_pval, h->d_pcode, h->d_prc, fill_ix, h->valmap ? 1 : 0);
     TSEM_HIP(hipGetLastError());
   }
   TSEM_HIP(hipStreamSynchronize(h->stream));
@@ -1725,24 +1724,24 @@ static int layout_launch_buffers(tsem_ctx* h) {
   }
   if (h->split) {                                          // row-sum pass, scatter pass, log-likelihood over a column half
     for (int mode : {5, 7, 8})
-      if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, mode, fmt, geo), "split layout: no fused kernel for this team size / geometry")) return rc;
+      if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, mode, fmt, geo, false, h->index_fmt), "split layout: no fused kernel for this team size / geometry")) return rc;
     TSEM_ALLOC(h->d_rinv, h->N_amb_pad);                   // the row factors pass A hands to pass B
     TSEM_ALLOC(h->d_ypart, (int64_t)P * h->N_amb_pad);     // the members' partial row sums (row-sum pass -> k_row_factors)
     TSEM_HIP(hipMemsetAsync(h->d_rinv, 0, sizeof(double) * h->N_amb_pad, h->stream));
   } else
     for (int mode = 0; mode < 2; ++mode)
-      if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, mode, fmt, geo, false, fz_quad(h, mode)))) return rc;
-  if (h->lnl3 && !(h->fmt_code && fz_kernel(P, 4, fmt, geo))) h->lnl3 = false;   // (not score codes after all: the per-iteration lnl pass stays)
+      if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, mode, fmt, geo, false, h->index_fmt))) return rc;
+  if (h->lnl3 && !fz_exists(P, 4, fmt, geo, false, h->index_fmt)) h->lnl3 = false;   // (not score codes after all: the per-iteration lnl pass stays)
   h->lag_valid = false;
   if (h->lnl3) {
-    if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, 4, fmt, geo))) return rc;
+    if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, 4, fmt, geo, false, h->index_fmt))) return rc;
     TSEM_ALLOC(h->d_rinv, h->N_amb_pad);
     TSEM_HIP(hipMemsetAsync(h->d_rinv, 0, sizeof(double) * h->N_amb_pad, h->stream));
   }
   if (h->opt_reproducible) {
-    if (h->exact_single && !fz_kernel(P, 3, fmt, geo)) h->exact_single = false;   // (not score codes after all: fz_lds_bytes then counts two tables again)
+    if (h->exact_single && !fz_exists(P, 3, fmt, geo, false, h->index_fmt)) h->exact_single = false;   // (not score codes after all: fz_lds_bytes then counts two tables again)
     if (h->exact_single) TSEM_ALLOC(h->d_fpartial2, (int64_t)h->fz_teams * h->Kpad);
-    if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, h->exact_single ? 3 : 2, fmt, geo),
+    if (int rc = allow_large_lds(h, (const void*)fz_kernel(P, h->exact_single ? 3 : 2, fmt, geo, false, h->index_fmt),
                                  "reproducible mode needs the fused kernel with a score table of at most 2048 entries")) return rc;
     TSEM_ALLOC(h->d_ebias, h->Kpad); TSEM_ALLOC(h->d_ovf, h->Kpad); TSEM_ALLOC(h->d_red_hi, K + 2); TSEM_ALLOC(h->d_binflag, 4);
     TSEM_ALLOC(h->d_ehist, 2 * (size_t)K + 2);

@@ -3,7 +3,7 @@
     TSEM_LIB=<library> python tools/layout_fingerprint.py --out DIR      one run (a fresh process per library): DIR/lines.txt, DIR/values.npz
     python tools/layout_fingerprint.py --compare OLD1 OLD2 NEW           two runs of the old library against one of the new
 
-One line per item and case: the 40 fields of layout_info(), a SHA-256 over the decoded (row slot << 16 | column slot) words of every
+One line per item and case: the 46 fields of layout_info(extended=True), a SHA-256 over the decoded (row slot << 16 | column slot) words of every
 sub-block (as stored where the fill is the row-order fill, every sub-block sorted where it is k_sb_fill, whose order within a strand
 is the atomics'), the bits of pi, theta and lnl after 3 em_steps, and the column sums of reassign('exclude').  Every case asserts
 from layout_info() that the branch it was built for was taken.
@@ -48,6 +48,8 @@ def cases():
             ('no_ambiguous', (5000, 3000, p40, 1, 1.0), (), None, lambda i, m: i['nb'] == 0 and i['N_amb'] == 0),
             ('wide', (3000, 491521 + 64, p40, 0, 0.05), (), None, lambda i, m: i['row_pass_em'] == 1 and i['nb'] == 0),
             ('fp64', small, (('value_format', 1),), None, lambda i, m: i['index_bytes'] == 3 and i['value_bytes'] == 8 and i['fused'] == 1)]
+    out.append(('fp64_quad', small, (('value_format', 1), ('index_format', 2)), None,        # the quad index, which auto takes at 1 GiB only
+                lambda i, m: i['index_format'] == 2 and i['index_bytes'] == 2 and i['value_bytes'] == 8 and i['fused'] == 1))
     for p in (2, 4, 5, 8):
         out.append(('parts%d' % p, small, (('parts', p),), None, lambda i, m, p=p: i['P'] == p and i['fused'] == 1))
     for p, g in ((2, 2), (2, 3), (4, 2), (4, 3)):
@@ -116,7 +118,7 @@ def run(out_dir):
         eng.set_model(stats, pisum0, cnt, hsh, 0.0, 200000.0)
         if rebuild:
             getattr(eng, rebuild)()
-        info, mem = eng.layout_info(), eng.device_memory()['resident']
+        info, mem = eng.layout_info(extended=True), eng.device_memory()['resident']
         assert check(info, mem), ('case %s did not take its branch' % name, info, mem)
         lines += ['%s info.%s %d' % (name, key, v) for key, v in info.items()]
         lines += ['%s resident.%s %d' % (name, key, v) for key, v in mem.items()]

@@ -636,6 +636,31 @@ int  tsem_bam_rewrite_fetch(tsem_bam* b, uint8_t* other, int64_t n_other, uint8_
  * scans, k_bam_rw_write, device-to-host; *calls = sizing calls; reset != 0 clears both. */
 int  tsem_bam_rewrite_times(tsem_bam* b, int reset, double* ms5, int64_t* calls);
 
+/* ---- device loader: a BAM that is not name-collated (`--collate`; telescope_amd/csrc/tsem_bam_collate.hip, tsem_bam_collate.h) ----
+ * tsem_bam_chunk wants every alignment of a query name in one run of records.  tsem_bam_collate brings the records of a whole stream
+ * into that order.  bytes / rec_off / n_rec: the record part of an inflated BAM as tsem_bam_scan leaves it (HOST arrays; rec_off holds
+ * n_rec + 1 offsets).  A record's NAME is the l_read_name bytes at offset 36 of the framed record (its block_size included), the
+ * trailing NUL among them, compared as bytes; a GROUP is the set of records with equal names.  out[0, rec_off[n_rec] - rec_off[0]) gets
+ * the same framed records, byte for byte: the groups in the order of their first records, the records of a group in their input order.
+ * order[k] = the input index of output record k, *n_names = the number of groups.  A stream that is collated already comes back
+ * unchanged; the result depends on nothing but the input.
+ * status2[0] = 0, or why the first record in input order that cannot be collated was refused, status2[1] = that record: 1 shorter than
+ * the 32 fixed bytes and one byte of a name, 2 l_read_name is 0, 3 the name runs past the record's end.  The call then still returns
+ * TSEM_OK, and out / order / n_names are not to be used; no byte outside a record is read to find that out.
+ * hash_bits: 0, or (tests) so many bits of the names' 64-bit hash are kept: distinct names then share hash values and probe chains.
+ * On the device: k_collate_hash, k_collate_insert (open addressing in a table of the next power of two >= 2 n_rec slots),
+ * k_collate_key, rocprim's radix sort and scan, k_collate_gather.  ms (5 values, or NULL): HIP-event milliseconds of host-to-device,
+ * hash + insert + key, sort + scan, gather, device-to-host.  Device memory: twice the bytes and 44 to 60 B per record, all of it
+ * released when the call returns; TSEM_ERR_NOMEM with a message (tsem_last_error(NULL)) and nothing left allocated when that does not
+ * fit.  TSEM_ERR_ARG with a message, before the device is touched: a NULL pointer, a negative size, n_rec >= 2^32 - 1, hash_bits
+ * outside 0 .. 64, offsets that descend or leave [0, n_bytes].  n_rec = 0 is a valid call.  TSEM_ERR_HIP if a copy or a launch fails.
+ * tsem_bam_collate_host: the same contract and the same bodies on one CPU thread, no device; it gives the bytes and the order that the
+ * kernels give. */
+int  tsem_bam_collate(int device, const uint8_t* bytes, int64_t n_bytes, const int64_t* rec_off, int64_t n_rec, int32_t hash_bits,
+                      uint8_t* out /* n_bytes */, int64_t* order /* n_rec */, int64_t* n_names, int64_t* status2, double* ms /* 5 */);
+int  tsem_bam_collate_host(const uint8_t* bytes, int64_t n_bytes, const int64_t* rec_off, int64_t n_rec, int32_t hash_bits,
+                           uint8_t* out /* n_bytes */, int64_t* order /* n_rec */, int64_t* n_names, int64_t* status2);
+
 /* ---- device loader: the BGZF blocks of a BAM file inflated on the device (telescope_amd/csrc/tsem_bgzf.hip) ----
  * A BGZF file is a chain of gzip members ("blocks") of at most 64 KiB compressed and 64 KiB inflated bytes; each needs nothing from
  * its neighbours and carries the CRC-32 and the length (ISIZE) of its inflated bytes in its trailer.

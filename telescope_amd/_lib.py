@@ -27,14 +27,14 @@ class EngineError(RuntimeError):
 
 
 # host / ABI, set-up, EM support, report / row passes, collectives, CSR primitives, per-cell counts, per-cell fits, bootstrap,
-# UMI duplicates, device loader, BGZF inflate (telescope_amd/csrc/tsem_internal.h)
+# UMI duplicates, device loader, BGZF inflate, collate (telescope_amd/csrc/tsem_internal.h)
 LIB_UNITS = ('tsem_host', 'tsem_setup', 'tsem_em', 'tsem_report', 'tsem_comm', 'tsem_csr', 'tsem_cells', 'tsem_cellem', 'tsem_boot',
-             'tsem_umi', 'tsem_bam', 'tsem_bgzf')
+             'tsem_umi', 'tsem_bam', 'tsem_bgzf', 'tsem_bam_collate')
 FZ_UNITS = tuple('tsem_fz_p%d' % p for p in range(1, 9))
 
 
 def build_library(force=False, verbose=False, out=None):
-    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  Twenty translation units — the twelve of
+    """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU).  Twenty-one translation units — the thirteen of
     LIB_UNITS and the eight that instantiate the fused kernel for one team size each (most of the build time) — are compiled
     in parallel and linked into one shared object."""
     from concurrent.futures import ThreadPoolExecutor
@@ -247,6 +247,8 @@ def lib():
     L.tsem_bam_rewrite_slots.argtypes = [vp, vp, vp, i64]
     L.tsem_bam_rewrite_fetch.argtypes = [vp, vp, i64, vp, i64]
     L.tsem_bam_rewrite_times.argtypes = [vp, C.c_int, vp, C.POINTER(i64)]
+    L.tsem_bam_collate.argtypes = [C.c_int, vp, i64, vp, i64, i32, vp, vp, C.POINTER(i64), vp, vp]
+    L.tsem_bam_collate_host.argtypes = [vp, i64, vp, i64, i32, vp, vp, C.POINTER(i64), vp]
     L.tsem_bgzf_scan.argtypes = [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
     L.tsem_bgzf_open.argtypes = [C.POINTER(vp), C.c_int]
     L.tsem_bgzf_close.argtypes = [vp]
@@ -1110,6 +1112,48 @@ def bam_scan(data, cap=None):
     if rc != OK:
         raise _csr_error('tsem_bam_scan', rc)
     return off[:n.value + 1].copy(), used.value
+
+
+COLLATE_STATUS = {1: 'the record is shorter than its fixed fields and one byte of a name', 2: 'l_read_name is 0',
+                  3: 'the name runs past the end of the record'}
+
+
+def bam_collate(data, rec_off, device=None, hash_bits=0):
+    """The records of an inflated BAM record stream brought together by name (tsem_bam_collate on GPU `device`; device=None:
+    tsem_bam_collate_host, the same bodies on one CPU thread): the groups of equal names in the order of their first records, the
+    records of a group in their input order.  `rec_off` as bam_scan gives it.  -> (uint8 array of the collated stream, order int64 [n]
+    = the input index of every output record, the number of names, ms) with ms = the HIP-event milliseconds of h2d / hash_insert_key /
+    sort_scan / gather / d2h, None on the host.  A record that cannot be collated is a ValueError that names it.  `hash_bits` (tests):
+    keep so many bits of the names' hash, 0 = all.  The device holds the stream twice and 44 to 60 B per record during the call."""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    off = np.ascontiguousarray(rec_off, dtype=np.int64)
+    n = len(off) - 1
+    if n < 0:
+        raise ValueError('rec_off holds n + 1 offsets')
+    out, order = np.empty(buf.size, np.uint8), np.empty(n, np.int64)
+    names, st = C.c_int64(), np.zeros(2, np.int64)
+    args = (ptr(buf) if buf.size else None, buf.size, ptr(off), n, int(hash_bits), ptr(out) if buf.size else None, ptr(order) if n else None,
+            C.byref(names), ptr(st))
+    if device is None:
+        ms = None
+        rc = lib().tsem_bam_collate_host(*args)
+    else:
+        ms = np.zeros(5)
+        rc = lib().tsem_bam_collate(int(device), *(args + (ptr(ms),)))
+    if rc == ERR_NOMEM:
+        e = EngineError('--collate device: the inflated BAM (%d bytes, %d records) does not fit: the step holds the whole stream twice and '
+                        '44 to 60 B per record in device memory (%s); collate the file beforehand, or use --collate host'
+                        % (buf.size, n, lib().tsem_last_error(None).decode()))
+        e.code = rc
+        raise e
+    if rc != OK:
+        raise _csr_error('tsem_bam_collate' if device is not None else 'tsem_bam_collate_host', rc)
+    if st[0]:
+        raise ValueError('record %d: %s' % (int(st[1]), COLLATE_STATUS.get(int(st[0]), 'status %d' % int(st[0]))))
+    total = int(off[n] - off[0])
+    if ms is not None:
+        ms = dict(zip(('h2d', 'hash_insert_key', 'sort_scan', 'gather', 'd2h'), ms.tolist()))
+    return out[:total], order, names.value, ms
 
 
 def _tag16(tag):

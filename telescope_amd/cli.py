@@ -20,6 +20,8 @@ restatement of the reference's sequential loader; `--ncpu > 1` is not offered.  
 loader's per-record work on the GPU (telescope_amd/loader_device.py): the same matrix, checkpoint and reports.  `--updated_sam` writes `<exp_tag>-updated.bam`
 (model.py:479-521) beside `<exp_tag>-other.bam` and `<exp_tag>-tmp_tele.bam` of the load, on one GPU; with `--loader device --rewrite
 device` the records of all three are rewritten on the GPU (the same files, byte for byte; the BGZF compression stays on the host).
+`--loader device --collate device` (or `host`; not in the reference) takes a BAM that is not name-collated, coordinate-sorted for
+instance, and brings its records together by name first (telescope_amd/collate.py); the default `--collate none` reads the file as it is.
 """
 import argparse
 import logging as lg
@@ -114,6 +116,11 @@ def _assign_args(asg):
     g.add_argument('--inflate', default='host', choices=['host', 'device'],
                    help='host (default): the BGZF blocks of the BAM are inflated by gzip on one host core.  device (with --loader device): '
                         'they are inflated on the GPU as well, one wave per block.')
+    g.add_argument('--collate', default='none', choices=['none', 'host', 'device'],
+                   help='none (default): every alignment of a read name sits in one run of records, as the reference asks (a '
+                        'name-collated BAM).  host / device (with --loader device, without --updated_sam): the BAM may be in any order, '
+                        'coordinate-sorted for instance; its records are brought together by name first, on one host core or on the GPU.  '
+                        'The whole inflated BAM is held in host memory, and for device twice in GPU memory, during that step.')
     g.add_argument('--deflate', default='host', choices=['host', 'device'],
                    help='host (default): the BGZF blocks of the BAMs of --updated_sam are deflated by zlib on one host core.  device (with '
                         '--updated_sam; any --loader and --rewrite): they are deflated on the GPU, one wave per block; the files inflate '
@@ -224,6 +231,8 @@ class ResumeOptions(object):
             lines.append('    {:30}{}'.format('celltype_tsv:', self.celltype_tsv))
         if getattr(self, 'umi_tag', None) is not None:
             lines.append('    {:30}{}'.format('umi_tag:', self.umi_tag))
+        if getattr(self, 'collate', 'none') != 'none':
+            lines.append('    {:30}{}'.format('collate:', self.collate))
         return '\n'.join(lines)
 
 
@@ -390,6 +399,20 @@ def _refuse_device_deflate(args):
                          'add --updated_sam')
 
 
+def _refuse_collate(args):
+    """`--collate host | device` without `--loader device` or with `--updated_sam`: refused before anything is read (the python loader
+    streams record by record; the BAMs of --updated_sam would carry the input's @HD SO: line over records in another order)."""
+    how = getattr(args, 'collate', 'none')
+    if how == 'none':
+        return
+    if getattr(args, 'loader', 'python') != 'device':
+        raise SystemExit('telescope assign: --collate %s without --loader device is not supported (the python loader streams the '
+                         'BAM record by record); add --loader device' % how)
+    if getattr(args, 'updated_sam', False):
+        raise SystemExit('telescope assign: --collate %s with --updated_sam is not supported (the written BAMs would carry the '
+                         'input\'s @HD SO: line over records in another order); run the two separately' % how)
+
+
 def collapse_umis(ts, opts):
     """`sc assign --umi_tag` / `sc resume` of a checkpoint with UMIs: the run goes on with the kept fragments (scTelescope.collapse_umis)
     unless --ignore_umi; <exp_tag>-umi_stats.tsv lists them per barcode."""
@@ -498,6 +521,7 @@ def run_assign(args, sc=False):
     _refuse_sharded_sc(sc)
     _refuse_bootstrap(args)
     _refuse_umi_updated_sam(args)
+    _refuse_collate(args)
     _refuse_device_updated_sam(args)
     _refuse_device_inflate(args)
     _refuse_device_deflate(args)

@@ -16,6 +16,8 @@
 //                    the stages' bodies are host / device functions in tsem_bam_rec.h and tsem_bam_stages.h, the record chain in tsem_bam_scan.h)
 //   tsem_bgzf.hip    the BGZF blocks of a BAM file inflated on the device (tsem_bgzf_*; the body is the host / device function of
 //                    tsem_bgzf_inflate.h, the chain of block headers in tsem_bgzf_scan.h)
+//   tsem_bam_collate.hip  the records of a BAM that is not name-collated brought together by name (tsem_bam_collate; the bodies are the
+//                    host / device functions of tsem_bam_collate.h, which tsem_bam_collate_host runs on one CPU thread)
 //   tsem_fz_p*.hip   instantiations of the fused kernel, one team size per unit: the look-up generated (tsem_fused_inst.h) from the one
 //                    table of what exists, fz_exists (tsem_fused.h)
 //   tsem_index.h     the index formats of the layout's entries: tsem_ctx::index_fmt, fz_exists' `ix`, layout_info()

@@ -361,7 +361,7 @@ CODE_DESC = OrderedDict([('SU', 'single_unmapped'), ('SM', 'single_mapped'), ('P
 
 def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_mode='threshold',
                    overlap_threshold=0.2, stranded_mode='None', barcode_tag=None, updated_sam=None, umi_tag=None, loader='python',
-                   device=0, chunk_bytes=None, record_cap=4096, inflate='host', rewrite='host', deflate='host'):
+                   device=0, chunk_bytes=None, record_cap=4096, inflate='host', rewrite='host', deflate='host', collate='none'):
     """-> dict(raw_scores uint16 CSR, read_index, feat_index, feature_length, run_info fields).  With `barcode_tag` (scTelescope,
     model.py:245-247,311-316) also cell_of_row (int32 per row, -1 = no barcode) and barcodes (the cell names): the tag is read from
     the first read of every mapped fragment; only fragments that become rows count; cells are ordered by the first appearance of
@@ -378,7 +378,9 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
     record of the tmp BAM.  `inflate='device'` (with loader='device' only): the file's BGZF
     blocks are inflated on the GPU as well (bgzf.py) instead of by gzip on one host core.  `deflate='device'` (with `updated_sam`, either
     loader): the BGZF blocks of both BAMs are deflated on the GPU (bgzf.DeviceBgzfWriter) instead of by zlib on one host core; the
-    files inflate to the same bytes."""
+    files inflate to the same bytes.  `collate='host'` or `'device'` (with loader='device', without `updated_sam`): the BAM need not be
+    name-collated, its records are brought together by name first (collate.py), on one host core or on the GPU; the whole inflated
+    record stream is held in host memory, and for 'device' twice in device memory, during that step."""
     if overlap_mode != 'threshold':
         raise NotImplementedError('only overlap_mode "threshold" is implemented (as in the reference, '
                                   'model.py:899-903)')
@@ -394,13 +396,19 @@ def load_alignment(samfile, annotation, no_feature_key='__no_feature', overlap_m
         raise ValueError("deflate must be 'host' or 'device', not %r" % (deflate,))
     if deflate == 'device' and not updated_sam:
         raise ValueError("deflate='device' needs updated_sam")
+    if collate not in ('none', 'host', 'device'):
+        raise ValueError("collate must be 'none', 'host' or 'device', not %r" % (collate,))
+    if collate != 'none' and loader != 'device':
+        raise ValueError("collate=%r needs loader='device'" % (collate,))
+    if collate != 'none' and updated_sam:
+        raise ValueError('collate=%r with updated_sam is not supported: run the two separately' % (collate,))
     if loader == 'device':
         if updated_sam and rewrite != 'device':
             raise ValueError('the device loader does not write the BAMs of --updated_sam')
         from .loader_device import load_alignment_device
         return load_alignment_device(samfile, annotation, no_feature_key, overlap_threshold, stranded_mode, barcode_tag, umi_tag,
                                      device=device, chunk_bytes=chunk_bytes, record_cap=record_cap, inflate=inflate,
-                                     updated_sam=updated_sam if rewrite == 'device' else None, deflate=deflate)
+                                     updated_sam=updated_sam if rewrite == 'device' else None, deflate=deflate, collate=collate)
     if loader != 'python':
         raise ValueError("loader must be 'python' or 'device', not %r" % (loader,))
     bam_u = bam_t = None

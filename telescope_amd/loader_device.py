@@ -161,7 +161,7 @@ def host_bundle(data, off, s, e, btag, utag, assign, no_feature_key, streams=Fal
 
 def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', overlap_threshold=0.2, stranded_mode='None',
                           barcode_tag=None, umi_tag=None, device=0, chunk_bytes=None, record_cap=4096, max_bundles=None,
-                          on_chunk=None, inflate='host', updated_sam=None, deflate='host'):
+                          on_chunk=None, inflate='host', updated_sam=None, deflate='host', collate='none'):
     """loader.load_alignment(..., loader='device').  `on_chunk(data, rec_off, out)`: called with every chunk's raw device outputs
     (tests); `max_bundles`: at most so many bundles per device call (tests).  `inflate`: 'host' (Python's gzip) or 'device' (the BGZF
     blocks are inflated on the GPU, bgzf.py; a gzip file that is not BGZF is still read by gzip: LAST_STATS['inflate'] says which).
@@ -171,7 +171,10 @@ def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', ov
     BAM in order, row (the fragment's row of the matrix, int32), col (the pair's column, int32) and kind (uint8: 0 unchanged, 1 SEC,
     2 PRI) for Telescope.update_sam; it is not part of the returned dict or of the checkpoint.  `deflate='device'`: both writers deflate
     their blocks on the GPU instead (bgzf.DeviceBgzfWriter): the same inflated bytes; LAST_STATS['deflate_blocks'], ['deflate_batches'] and
-    ['deflate_ms'] say what went through the device."""
+    ['deflate_ms'] say what went through the device.  `collate`: 'none' (the BAM is name-collated, as the reference asks), 'host' or
+    'device': the records behind the header are first brought together by name (collate.py: groups in the order of their first records,
+    inside a group the input order), on one host core or on the GPU; LAST_STATS then has 'collate', 'collate_s' and 'collate_ms'.  The
+    whole inflated record stream is held in host memory, and for 'device' twice in device memory, during that step."""
     global LAST_STATS, LAST_TMP_TABLE
     LAST_TMP_TABLE = None
     if no_feature_key in annotation.loci:
@@ -180,6 +183,8 @@ def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', ov
         raise ValueError("inflate must be 'host' or 'device', not %r" % (inflate,))
     if deflate not in ('host', 'device'):
         raise ValueError("deflate must be 'host' or 'device', not %r" % (deflate,))
+    if collate not in ('none', 'host', 'device'):
+        raise ValueError("collate must be 'none', 'host' or 'device', not %r" % (collate,))
     chunk_bytes = DEFAULT_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
     if chunk_bytes < 1:
         raise ValueError('chunk_bytes must be >= 1')
@@ -197,6 +202,10 @@ def load_alignment_device(samfile, annotation, no_feature_key='__no_feature', ov
     side = ([], [], [])                                      # per chunk: pre-trim row, column, kind of every tmp record
     try:
         refs, _text, _block = pyl.read_bam_header(fh, samfile)
+        if collate != 'none':
+            from . import collate as col
+            fh = col.collated_stream(fh, samfile, collate, device)
+            stats.update(collate=collate, collate_s=col.LAST['collate_s'], collate_ms=col.LAST['ms'])
         arrs = annotation_arrays(annotation, refs)
         loc_names = arrs[-1]
         loc_id = {n: i for i, n in enumerate(loc_names)}

@@ -132,7 +132,7 @@ class Telescope(object):
         r = loader.load_alignment(o.samfile, annotation, o.no_feature_key, o.overlap_mode,
                                   o.overlap_threshold, o.stranded_mode, updated_sam=self._updated_sam_paths(),
                                   loader=getattr(o, 'loader', 'python'), device=getattr(o, 'device', 0), inflate=getattr(o, 'inflate', 'host'),
-                                  rewrite=getattr(o, 'rewrite', 'host'), deflate=getattr(o, 'deflate', 'host'))
+                                  rewrite=getattr(o, 'rewrite', 'host'), deflate=getattr(o, 'deflate', 'host'), collate=getattr(o, 'collate', 'none'))
         self._take_tmp_table()
         self.feature_length = r['feature_length']
         self.read_index, self.feat_index = r['read_index'], r['feat_index']
@@ -602,7 +602,7 @@ class scTelescope(Telescope):
         r = loader.load_alignment(o.samfile, annotation, o.no_feature_key, o.overlap_mode, o.overlap_threshold, o.stranded_mode,
                                   barcode_tag=o.barcode_tag, updated_sam=self._updated_sam_paths(), umi_tag=getattr(o, 'umi_tag', None),
                                   loader=getattr(o, 'loader', 'python'), device=getattr(o, 'device', 0), inflate=getattr(o, 'inflate', 'host'),
-                                  rewrite=getattr(o, 'rewrite', 'host'), deflate=getattr(o, 'deflate', 'host'))
+                                  rewrite=getattr(o, 'rewrite', 'host'), deflate=getattr(o, 'deflate', 'host'), collate=getattr(o, 'collate', 'none'))
         self._take_tmp_table()
         self.feature_length = r['feature_length']
         self.read_index, self.feat_index = r['read_index'], r['feat_index']

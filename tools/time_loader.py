@@ -1,6 +1,7 @@
 """Time the device loader (`assign --loader device`) on the bundled BAM's record stream tiled K times.
 
     python tools/time_loader.py [--records 10000000] [--out profiles/r21_device_loader.txt] [--chunk_bytes N] [--inflate device]
+                                [--collate device]
 
 Every tile is the bundled file's 66,414 records with four characters of each query name overwritten by the tile's number (numpy, in
 place: the records keep their length, the 1,000 fragments of every tile stay distinct from all others), so the load sees K x 1,000
@@ -11,6 +12,10 @@ count, and the condition of the design: the four kernels plus both copies agains
 `--inflate device`: the same file is then loaded a second time with the BGZF blocks inflated on the GPU (telescope_amd/bgzf.py); the
 report holds the inflate stage and the whole load of both paths side by side, and the upload, kernel and download times of
 tsem_bgzf_times.
+`--collate device`: the same records are written a second time in coordinate order (every record of the bundled file sorted by
+(ref, pos), the copies of all tiles side by side, as a coordinate sort of the tiled file leaves them) and loaded with `collate='device'`:
+the collate stage's wall time and its five HIP-event parts, tsem_bam_collate_host on one core over the same bytes, the whole load
+with and without the step, and the gather's bytes/s.
 """
 import argparse
 import gzip
@@ -54,6 +59,80 @@ def tiled_bam(path, tiles):
     return len(pos) * tiles
 
 
+def sorted_tiled_bam(path, tiles):
+    """-> records written.  The records of tiled_bam(..., tiles) in coordinate order: the bundled file's records sorted by (ref, pos),
+    unmapped last, and behind each one its copies in the other tiles (equal position; tile numbers ascending)."""
+    from telescope_amd import loader
+    from telescope_amd.bam_out import BamWriter
+    bam = os.path.join(GOLD, 'bundled_alignment.bam')
+    with gzip.open(bam, 'rb') as g:
+        raw = g.read()
+    fh = io.BytesIO(raw)
+    _refs, text, refs_block = loader.read_bam_header(fh, bam)
+    body = np.frombuffer(raw[fh.tell():], dtype=np.uint8)
+    recs, p = [], 0
+    while p < body.size:
+        bs = int(body[p:p + 4].view('<i4')[0])
+        ref, pos = (int(x) for x in body[p + 4:p + 12].view('<i4'))
+        name = body[p + 36:p + 36 + int(body[p + 12]) - 1].tobytes()
+        recs.append((ref if ref >= 0 else 1 << 31, pos, p, 4 + bs, 36 + name.index(b'/') + 1))
+        p += 4 + bs
+    recs.sort(key=lambda r: r[:2])
+    t = np.arange(tiles)
+    digits = DIGITS[np.stack([(t >> 15) & 31, (t >> 10) & 31, (t >> 5) & 31, t & 31], axis=1)]
+    w = BamWriter(path, dict(text=text.split(b'\x00', 1)[0].decode(), refs_block=refs_block))
+    w._z._level = 1
+    batch, held = [], 0
+    for _ref, _pos, at, size, name_at in recs:
+        block = np.tile(body[at:at + size], (tiles, 1))
+        block[:, name_at:name_at + 4] = digits
+        batch.append(block.tobytes()); held += block.size
+        if held >= 16 << 20:
+            w._z.write(b''.join(batch)); batch, held = [], 0
+    w._z.write(b''.join(batch))
+    w.close()
+    return len(recs) * tiles
+
+
+def collate_report(path, ann, a, say, res, t_plain):
+    """the --collate device part of the report: `path` is the coordinate-sorted file, res / t_plain the load of the name-ordered one"""
+    from telescope_amd import _lib, collate, loader, loader_device
+    t0 = time.perf_counter()
+    res3 = loader.load_alignment(path, ann, loader='device', device=a.device, chunk_bytes=a.chunk_bytes, collate='device', inflate=a.inflate)
+    t_col = time.perf_counter() - t0
+    s3, c = dict(loader_device.LAST_STATS), dict(collate.LAST)
+    ms = c['ms']
+    same = res3['run_info'] == res['run_info'] and res3['raw_scores'].shape == res['raw_scores'].shape and res3['raw_scores'].nnz == res['raw_scores'].nnz
+    say('--collate device: the same records in coordinate order: %d records, %d names, %d records moved; run_info, shape and stored '
+        'entries equal to the load of the name-ordered file: %s' % (c['records'], c['names'], c['moved'], same))
+    say('whole load with the step (inflate %s): %.3f s = %.0f records/s; the name-ordered file without it (inflate %s): %.3f s'
+        % (a.inflate, t_col, c['records'] / t_col, a.inflate, t_plain))
+    say('collate stage, wall (scan, the call, the copy of the result): %.4f s; reading the whole stream in front of it: %.4f s'
+        % (c['collate_s'], c['read_s']))
+    for name in ('h2d', 'hash_insert_key', 'sort_scan', 'gather', 'd2h'):
+        say('  %-28s %9.4f' % (name, ms[name] / 1e3))
+    with gzip.open(path, 'rb') as g:
+        raw = g.read()
+    fh = io.BytesIO(raw)
+    loader.read_bam_header(fh, path)
+    data = raw[fh.tell():]
+    del raw
+    off, _used = _lib.bam_scan(data)
+    t0 = time.perf_counter()
+    h_out, h_order, h_names, _ = _lib.bam_collate(data, off, device=None)
+    t_host = time.perf_counter() - t0
+    d_out, d_order, d_names, ms2 = _lib.bam_collate(data, off, device=a.device)
+    equal = bool(np.array_equal(h_order, d_order) and h_names == d_names and np.array_equal(h_out, d_out))
+    dev = sum(ms.values()) / 1e3
+    say('tsem_bam_collate_host, one core, the same %.1f MB: %.3f s; tsem_bam_collate (five parts): %.3f s = %.1fx; equal bytes, order '
+        'and names: %s' % (len(data) / 1e6, t_host, dev, t_host / dev, equal))
+    say('second call on the warm device (five parts): %s' % ', '.join('%s %.4f' % (k, v / 1e3) for k, v in ms2.items()))
+    g = 2 * len(data) / (ms2['gather'] / 1e3) / 1e9
+    say('k_collate_gather: %.1f MB read and as many written in %.4f s = %.0f GB/s (a streaming read on this chip: about 6,500 GB/s, '
+        'profiles/r02_stream_ubench.log)' % (len(data) / 1e6, ms2['gather'] / 1e3, g))
+    return 0 if same and equal and s3['fallbacks'] == 0 else 1
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--records', type=int, default=10000000, help='at least so many records (whole tiles)')
@@ -62,6 +141,8 @@ def main():
     ap.add_argument('--device', type=int, default=0)
     ap.add_argument('--inflate', default='host', choices=['host', 'device'],
                     help='device: after the load with the host inflate, load the same file again with the device inflate and compare')
+    ap.add_argument('--collate', default='none', choices=['none', 'device'],
+                    help='device: write the same records in coordinate order as well and load them with collate=device')
     a = ap.parse_args()
     from telescope_amd import _lib, loader, loader_device
     bam, gtf = os.path.join(GOLD, 'bundled_alignment.bam'), os.path.join(GOLD, 'bundled_annotation.gtf')
@@ -148,6 +229,13 @@ def main():
                '%.2fx' % (s['inflate_s'] / s2['inflate_s'])))
         if not same or s2['inflate_fallbacks'] or s2['inflate'] != 'device':
             status = 1
+    if a.collate == 'device':
+        with tempfile.TemporaryDirectory() as d:
+            spath = os.path.join(d, 'sorted.bam')
+            t0 = time.perf_counter()
+            sorted_tiled_bam(spath, tiles)
+            print('coordinate-sorted input written in %.1f s' % (time.perf_counter() - t0), flush=True)
+            status = collate_report(spath, ann, a, say, res, t_dev2 if a.inflate == 'device' else t_dev) or status
     if a.out:
         with open(a.out, 'w') as fh:
             fh.write('\n'.join(lines) + '\n')

@@ -1003,23 +1003,43 @@ def bgzf_scan(data, cap=None):
     return blk[:n.value].copy(), used.value, bool(nb.value)
 
 
-class BgzfInflater(object):
-    """The device side of `--inflate device` (tsem_bgzf_open / tsem_bgzf_inflate): one handle, one GPU, its buffers kept between batches."""
+class _StageHandle(object):
+    """A handle of the device loader's units (tsem_bgzf_*, tsem_bam_*): opened through a tsem_*_open, closed through the class's
+    `_close` when the object is closed or collected; its stage times read through a tsem_*_times."""
 
-    def __init__(self, device=0):
+    _close = None
+
+    def _open(self, fn, *args):
         L = lib()
         h = C.c_void_p()
-        rc = L.tsem_bgzf_open(C.byref(h), int(device))
+        rc = getattr(L, fn)(C.byref(h), *args)
         if rc != OK:
-            raise _csr_error('tsem_bgzf_open', rc)
+            raise _csr_error(fn, rc)
         self._L, self._h = L, h
 
     def close(self):
         if getattr(self, '_h', None):
-            self._L.tsem_bgzf_close(self._h)
+            getattr(self._L, self._close)(self._h)
             self._h = None
 
     __del__ = close
+
+    def _times(self, fn, names, count_key, reset):
+        """{name: HIP-event milliseconds summed over the calls so far, count_key: their number}"""
+        ms, n = np.zeros(len(names)), C.c_int64()
+        rc = getattr(self._L, fn)(self._h, int(reset), ptr(ms), C.byref(n))
+        if rc != OK:
+            raise _csr_error(fn, rc)
+        return dict(zip(names, ms.tolist()), **{count_key: n.value})
+
+
+class BgzfInflater(_StageHandle):
+    """The device side of `--inflate device` (tsem_bgzf_open / tsem_bgzf_inflate): one handle, one GPU, its buffers kept between batches."""
+
+    _close = 'tsem_bgzf_close'
+
+    def __init__(self, device=0):
+        self._open('tsem_bgzf_open', int(device))
 
     def inflate(self, data, blocks):
         """-> (uint8 array of the inflated bytes of the blocks that are not left to the host, in order; int32 status per block;
@@ -1041,11 +1061,7 @@ class BgzfInflater(object):
 
     def times(self, reset=False):
         """HIP-event milliseconds summed over the batches so far, and their number."""
-        ms, n = np.zeros(3), C.c_int64()
-        rc = self._L.tsem_bgzf_times(self._h, int(reset), ptr(ms), C.byref(n))
-        if rc != OK:
-            raise _csr_error('tsem_bgzf_times', rc)
-        return dict(zip(('h2d', 'k_bgzf_inflate', 'd2h'), ms.tolist()), batches=n.value)
+        return self._times('tsem_bgzf_times', ('h2d', 'k_bgzf_inflate', 'd2h'), 'batches', reset)
 
 
 BGZF_BLOCK_IN = 0xff00                  # input bytes per block of the deflate entries (bam_out._BLOCK_IN)
@@ -1071,23 +1087,13 @@ def bgzf_deflate_host(stream):
     return _bgzf_deflate_call(lib().tsem_bgzf_deflate_host, 'tsem_bgzf_deflate_host', None, stream)
 
 
-class BgzfDeflater(object):
+class BgzfDeflater(_StageHandle):
     """The device side of `--deflate device` (tsem_bgzf_open / tsem_bgzf_deflate): one handle, one GPU, its buffers kept between batches."""
 
+    _close = 'tsem_bgzf_close'
+
     def __init__(self, device=0):
-        L = lib()
-        h = C.c_void_p()
-        rc = L.tsem_bgzf_open(C.byref(h), int(device))
-        if rc != OK:
-            raise _csr_error('tsem_bgzf_open', rc)
-        self._L, self._h = L, h
-
-    def close(self):
-        if getattr(self, '_h', None):
-            self._L.tsem_bgzf_close(self._h)
-            self._h = None
-
-    __del__ = close
+        self._open('tsem_bgzf_open', int(device))
 
     def deflate(self, stream):
         """-> uint8 array: the BGZF blocks of `stream` (cut every 0xff00 bytes, the last one shorter), one behind the other; no EOF block"""
@@ -1095,11 +1101,7 @@ class BgzfDeflater(object):
 
     def times(self, reset=False):
         """HIP-event milliseconds summed over the batches so far, and their number."""
-        ms, n = np.zeros(4), C.c_int64()
-        rc = self._L.tsem_bgzf_deflate_times(self._h, int(reset), ptr(ms), C.byref(n))
-        if rc != OK:
-            raise _csr_error('tsem_bgzf_deflate_times', rc)
-        return dict(zip(('h2d', 'k_bgzf_deflate', 'pack', 'd2h'), ms.tolist()), batches=n.value)
+        return self._times('tsem_bgzf_deflate_times', ('h2d', 'k_bgzf_deflate', 'pack', 'd2h'), 'batches', reset)
 
 
 def bam_scan(data, cap=None):
@@ -1165,26 +1167,16 @@ def _tag16(tag):
     return t[0] | (t[1] << 8)
 
 
-class BamLoader(object):
+class BamLoader(_StageHandle):
     """The device side of the device loader (tsem_bam_open / tsem_bam_chunk): the annotation's arrays on one GPU and the four
     kernels per chunk.  `ref_lo`, `ref_hi` per BAM reference; `starts`, `maxend`, `ends`, `locus`, `strand` per interval."""
 
+    _close = 'tsem_bam_close'
+
     def __init__(self, device, ref_lo, ref_hi, starts, maxend, ends, locus, strand):
-        L = lib()
         a = [np.ascontiguousarray(x, dtype=t) for x, t in ((ref_lo, np.int32), (ref_hi, np.int32), (starts, np.int64), (maxend, np.int64),
                                                            (ends, np.int64), (locus, np.int32), (strand, np.int8))]
-        h = C.c_void_p()
-        rc = L.tsem_bam_open(C.byref(h), int(device), len(a[0]), ptr(a[0]), ptr(a[1]), len(a[2]), *[ptr(x) for x in a[2:]])
-        if rc != OK:
-            raise _csr_error('tsem_bam_open', rc)
-        self._L, self._h = L, h
-
-    def close(self):
-        if getattr(self, '_h', None):
-            self._L.tsem_bam_close(self._h)
-            self._h = None
-
-    __del__ = close
+        self._open('tsem_bam_open', int(device), len(a[0]), ptr(a[0]), ptr(a[1]), len(a[2]), *[ptr(x) for x in a[2:]])
 
     def chunk(self, data, rec_off, barcode_tag=None, umi_tag=None, run_stranded=False, stranded_mode='None', overlap_threshold=0.2,
               record_cap=4096):
@@ -1203,11 +1195,7 @@ class BamLoader(object):
 
     def times(self, reset=False):
         """HIP-event milliseconds summed over the chunks so far, and their number."""
-        ms, n = np.zeros(6), C.c_int64()
-        rc = self._L.tsem_bam_times(self._h, int(reset), ptr(ms), C.byref(n))
-        if rc != OK:
-            raise _csr_error('tsem_bam_times', rc)
-        return dict(zip(('h2d', 'k_bam_decode', 'k_bam_pair', 'k_bam_overlap', 'k_bam_fragment', 'd2h'), ms.tolist()), chunks=n.value)
+        return self._times('tsem_bam_times', ('h2d', 'k_bam_decode', 'k_bam_pair', 'k_bam_overlap', 'k_bam_fragment', 'd2h'), 'chunks', reset)
 
     # ---- the BAMs of --updated_sam (tsem_bam_names / _rewrite_size / _update_size / _rewrite_slots / _rewrite_fetch)
     def names(self, names):
@@ -1260,11 +1248,7 @@ class BamLoader(object):
         return other, tmp
 
     def rewrite_times(self, reset=False):
-        ms, n = np.zeros(5), C.c_int64()
-        rc = self._L.tsem_bam_rewrite_times(self._h, int(reset), ptr(ms), C.byref(n))
-        if rc != OK:
-            raise _csr_error('tsem_bam_rewrite_times', rc)
-        return dict(zip(('h2d', 'k_bam_rw_plan', 'k_bam_rw_size', 'k_bam_rw_write', 'd2h'), ms.tolist()), calls=n.value)
+        return self._times('tsem_bam_rewrite_times', ('h2d', 'k_bam_rw_plan', 'k_bam_rw_size', 'k_bam_rw_write', 'd2h'), 'calls', reset)
 
 
 def _csr_error(fn, rc):

@@ -40,34 +40,35 @@
 #include <rocprim/device/device_scan.hpp>
 #include "tsem_bam_edit.h"
 #include "tsem_bam_scan.h"
+#include "tsem_stage.h"
+
+enum { CK_H2D, CK_DECODE, CK_PAIR, CK_OVERLAP, CK_FRAGMENT, CK_D2H, CK_N };      // the stages of tsem_bam_times
+enum { RW_H2D, RW_PLAN, RW_SIZE, RW_WRITE, RW_D2H, RW_N };                      // ... of tsem_bam_rewrite_times (size: with both scans)
 
 struct tsem_bam {
   int device = 0;
   int32_t n_ref = 0;
   int64_t n_iv = 0;
-  int32_t *d_ref_lo = nullptr, *d_ref_hi = nullptr, *d_locus = nullptr;
-  int64_t *d_starts = nullptr, *d_maxend = nullptr, *d_ends = nullptr;
-  int8_t* d_strand = nullptr;
-  uint8_t* d_bytes = nullptr; size_t cap_bytes = 0;
-  int64_t* d_off = nullptr; int32_t* d_cols = nullptr; size_t cap_rec = 0;
-  unsigned long long* d_status = nullptr;
-  unsigned long long h_status = 0;                // (the word's host copy: it must outlive a call that fails behind the copy's launch)
-  hipEvent_t ev[7] = {};
-  bool have_ev = false;
-  double ms[6] = {0, 0, 0, 0, 0, 0};             // host-to-device, decode, pair, overlap, fragment, device-to-host
-  int64_t calls = 0;
+  DevBuf<int32_t> ref_lo, ref_hi, locus;          // the annotation (tsem_bam_open)
+  DevBuf<int64_t> starts, maxend, ends;
+  DevBuf<int8_t> strand;
+  DevBuf<uint8_t> bytes;                          // the chunk: its records, their offsets [n + 1], the result matrix
+  DevBuf<int64_t> off;
+  DevBuf<int32_t> cols;
+  StatusWord status;
+  StageClock<CK_N + 1, CK_N> clock;
   // ---- the rewriting of --updated_sam
   int32_t max_locus = -1;                         // the largest locus id of the annotation: the name table must reach it
-  uint8_t* d_names = nullptr; int64_t* d_name_off = nullptr; int32_t n_loci = -1;   // tsem_bam_names (-1: none yet)
+  DevBuf<uint8_t> names; DevBuf<int64_t> name_off; int32_t n_loci = -1;   // tsem_bam_names (-1: none yet)
   int64_t chunk_n = -1;                           // records of the chunk the device holds (-1: none a rewrite may use)
   int64_t sized_n = -1;                           // slots of the last *_size call (-1: nothing to fetch)
   int64_t total_other = 0, total_tmp = 0;         // ... and the lengths of its streams
   bool sized_update = false;
-  int32_t* d_rw = nullptr; int64_t* d_pos = nullptr; uint32_t* d_words = nullptr; size_t cap_rw = 0;
-  void* d_scan = nullptr; size_t cap_scan = 0;
-  uint8_t *d_other = nullptr, *d_tmp = nullptr; size_t cap_other = 0, cap_tmp = 0;
-  double rw_ms[5] = {0, 0, 0, 0, 0};              // host-to-device, plan, size and scan, write, device-to-host
-  int64_t rw_calls = 0;
+  DevBuf<int32_t> rw;                             // of n slots: rec, pair, kind [n] each (bam_rw_of)
+  DevBuf<int64_t> pos;                            //   ... and both streams' lengths, then offsets [n + 1] each
+  DevBuf<uint32_t> words;
+  DevBuf<uint8_t> scan, other, tmp;               // rocprim's scratch; the streams of the fetch
+  StageClock<5, RW_N> rw_clock;                   // (one timing over the sizing call and its fetch; the sizing calls are counted)
 };
 
 // (file scope, not the unnamed namespace: a profile lists them as k_bam_decode, k_bam_pair, k_bam_overlap, k_bam_fragment)
@@ -116,13 +117,11 @@ __global__ __launch_bounds__(256) void k_bam_rw_write(int64_t N, const uint8_t* 
 
 namespace {
 
-int bam_fail(int rc, const std::string& msg) { g_create_err = msg; return rc; }
-#define BAM_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bam_fail(TSEM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-
+// an array that stays as it is until the handle closes (the annotation) or is replaced (the names)
 template <typename T>
-int bam_upload(T** d, const T* h, size_t n) {
-  if (hipMalloc((void**)d, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) { *d = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_open: hipMalloc failed"); }
-  if (n) BAM_HIP(hipMemcpy(*d, h, n * sizeof(T), hipMemcpyHostToDevice));
+int bam_upload(const char* fn, DevBuf<T>& d, const T* h, size_t n, const char* what) {
+  if (int rc = d.alloc(n, what, fn)) return rc;
+  if (n) STAGE_HIP(hipMemcpy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice));
   return TSEM_OK;
 }
 
@@ -132,54 +131,47 @@ extern "C" {
 
 int tsem_bam_scan(const uint8_t* bytes, int64_t n_bytes, int64_t* rec_off, int64_t cap, int64_t* n_rec, int64_t* consumed) {
   if (n_bytes < 0 || cap < 0 || (!bytes && n_bytes) || !rec_off || !n_rec || !consumed)
-    return bam_fail(TSEM_ERR_ARG, "tsem_bam_scan: NULL pointer or negative size");
+    return stage_fail(TSEM_ERR_ARG, "tsem_bam_scan: NULL pointer or negative size");
   char msg[200];
-  if (tsem_bam_scan_chain(bytes, n_bytes, rec_off, cap, n_rec, consumed, msg, sizeof msg)) return bam_fail(TSEM_ERR_ARG, msg);
+  if (tsem_bam_scan_chain(bytes, n_bytes, rec_off, cap, n_rec, consumed, msg, sizeof msg)) return stage_fail(TSEM_ERR_ARG, msg);
   return TSEM_OK;
 }
 
 int tsem_bam_close(tsem_bam* b) {
   if (!b) return TSEM_OK;
   (void)hipSetDevice(b->device);
-  dfree(b->d_ref_lo); dfree(b->d_ref_hi); dfree(b->d_locus); dfree(b->d_starts); dfree(b->d_maxend); dfree(b->d_ends); dfree(b->d_strand);
-  dfree(b->d_bytes); dfree(b->d_off); dfree(b->d_cols); dfree(b->d_status);
-  dfree(b->d_names); dfree(b->d_name_off); dfree(b->d_rw); dfree(b->d_pos); dfree(b->d_words); dfree(b->d_scan); dfree(b->d_other); dfree(b->d_tmp);
-  if (b->have_ev) for (hipEvent_t& e : b->ev) (void)hipEventDestroy(e);
-  delete b;
+  delete b;                                       // (every buffer and event is a member that releases itself)
   return TSEM_OK;
 }
 
 int tsem_bam_open(tsem_bam** out, int device, int32_t n_ref, const int32_t* ref_lo, const int32_t* ref_hi, int64_t n_iv,
                   const int64_t* starts, const int64_t* maxend, const int64_t* ends, const int32_t* locus, const int8_t* strand) {
-  if (!out) return bam_fail(TSEM_ERR_ARG, "tsem_bam_open: out is NULL");
+  if (!out) return stage_fail(TSEM_ERR_ARG, "tsem_bam_open: out is NULL");
   *out = nullptr;
-  if (n_ref < 0 || n_iv < 0 || n_iv >= (int64_t)INT32_MAX) return bam_fail(TSEM_ERR_ARG, "tsem_bam_open: n_ref or n_intervals out of range");
+  if (n_ref < 0 || n_iv < 0 || n_iv >= (int64_t)INT32_MAX) return stage_fail(TSEM_ERR_ARG, "tsem_bam_open: n_ref or n_intervals out of range");
   if ((n_ref && (!ref_lo || !ref_hi)) || (n_iv && (!starts || !maxend || !ends || !locus || !strand)))
-    return bam_fail(TSEM_ERR_ARG, "tsem_bam_open: NULL array");
+    return stage_fail(TSEM_ERR_ARG, "tsem_bam_open: NULL array");
   for (int32_t r = 0; r < n_ref; ++r)
     if (ref_lo[r] < 0 || ref_hi[r] < ref_lo[r] || (int64_t)ref_hi[r] > n_iv)
-      return bam_fail(TSEM_ERR_ARG, "tsem_bam_open: reference " + std::to_string(r) + " has an interval range outside [0, n_intervals]");
+      return stage_fail(TSEM_ERR_ARG, "tsem_bam_open: reference " + std::to_string(r) + " has an interval range outside [0, n_intervals]");
   for (int32_t r = 0; r < n_ref; ++r)
     for (int32_t j = ref_lo[r]; j + 1 < ref_hi[r]; ++j)
       if (starts[j + 1] < starts[j] || maxend[j + 1] < maxend[j])
-        return bam_fail(TSEM_ERR_ARG, "tsem_bam_open: starts / maxend of reference " + std::to_string(r) + " do not ascend");
-  if (hipSetDevice(device) != hipSuccess) return bam_fail(TSEM_ERR_HIP, "hipSetDevice failed (no usable HIP device)");
+        return stage_fail(TSEM_ERR_ARG, "tsem_bam_open: starts / maxend of reference " + std::to_string(r) + " do not ascend");
+  if (hipSetDevice(device) != hipSuccess) return stage_fail(TSEM_ERR_HIP, "hipSetDevice failed (no usable HIP device)");
   tsem_bam* b = new tsem_bam;
   b->device = device; b->n_ref = n_ref; b->n_iv = n_iv;
   for (int64_t j = 0; j < n_iv; ++j) b->max_locus = std::max(b->max_locus, locus[j]);
-  int rc = bam_upload(&b->d_ref_lo, ref_lo, (size_t)n_ref);
-  if (!rc) rc = bam_upload(&b->d_ref_hi, ref_hi, (size_t)n_ref);
-  if (!rc) rc = bam_upload(&b->d_starts, starts, (size_t)n_iv);
-  if (!rc) rc = bam_upload(&b->d_maxend, maxend, (size_t)n_iv);
-  if (!rc) rc = bam_upload(&b->d_ends, ends, (size_t)n_iv);
-  if (!rc) rc = bam_upload(&b->d_locus, locus, (size_t)n_iv);
-  if (!rc) rc = bam_upload(&b->d_strand, strand, (size_t)n_iv);
-  if (!rc && hipMalloc((void**)&b->d_status, 8) != hipSuccess) { b->d_status = nullptr; rc = bam_fail(TSEM_ERR_NOMEM, "tsem_bam_open: hipMalloc failed"); }
-  if (!rc) {
-    for (hipEvent_t& e : b->ev)
-      if (hipEventCreate(&e) != hipSuccess) rc = bam_fail(TSEM_ERR_HIP, "tsem_bam_open: hipEventCreate failed");
-    b->have_ev = rc == TSEM_OK;
-  }
+  const char* fn = "tsem_bam_open";
+  int rc = bam_upload(fn, b->ref_lo, ref_lo, (size_t)n_ref, "annotation");
+  if (!rc) rc = bam_upload(fn, b->ref_hi, ref_hi, (size_t)n_ref, "annotation");
+  if (!rc) rc = bam_upload(fn, b->starts, starts, (size_t)n_iv, "annotation");
+  if (!rc) rc = bam_upload(fn, b->maxend, maxend, (size_t)n_iv, "annotation");
+  if (!rc) rc = bam_upload(fn, b->ends, ends, (size_t)n_iv, "annotation");
+  if (!rc) rc = bam_upload(fn, b->locus, locus, (size_t)n_iv, "annotation");
+  if (!rc) rc = bam_upload(fn, b->strand, strand, (size_t)n_iv, "annotation");
+  if (!rc) rc = b->status.create(fn);
+  if (!rc && (b->clock.create() != hipSuccess || b->rw_clock.create() != hipSuccess)) rc = stage_fail(TSEM_ERR_HIP, "tsem_bam_open: hipEventCreate failed");
   if (rc) { tsem_bam_close(b); return rc; }
   *out = b;
   return TSEM_OK;
@@ -188,83 +180,56 @@ int tsem_bam_open(tsem_bam** out, int device, int32_t n_ref, const int32_t* ref_
 int tsem_bam_chunk(tsem_bam* b, const uint8_t* bytes, int64_t n_bytes, const int64_t* rec_off, int64_t n_rec, int32_t barcode_tag,
                    int32_t umi_tag, int32_t run_stranded, int32_t first_f, int32_t last_f, double overlap_threshold, int32_t record_cap,
                    int32_t* out, int64_t* status2) {
-  if (!b) return bam_fail(TSEM_ERR_ARG, "tsem_bam_chunk: NULL handle");
+  if (!b) return stage_fail(TSEM_ERR_ARG, "tsem_bam_chunk: NULL handle");
   if (n_rec < 0 || n_bytes < 0 || n_rec >= (int64_t)INT32_MAX || !rec_off || !status2 || (n_rec && (!bytes || !out)))
-    return bam_fail(TSEM_ERR_ARG, "tsem_bam_chunk: NULL pointer, negative size or more than 2^31 - 2 records");
-  if (record_cap < 1) return bam_fail(TSEM_ERR_ARG, "tsem_bam_chunk: record_cap must be >= 1");
-  // the offsets bound every read of the kernels: checked here, before the device sees them
-  if (rec_off[0] < 0 || rec_off[n_rec] > n_bytes) return bam_fail(TSEM_ERR_ARG, "tsem_bam_chunk: rec_off leaves the chunk");
-  for (int64_t i = 0; i < n_rec; ++i)
-    if (rec_off[i + 1] - rec_off[i] < 36 || rec_off[i + 1] - rec_off[i] > (int64_t)INT32_MAX)
-      return bam_fail(TSEM_ERR_ARG, "tsem_bam_chunk: record " + std::to_string(i) + " is shorter than 36 bytes or longer than 2^31 - 1 (rec_off must ascend)");
+    return stage_fail(TSEM_ERR_ARG, "tsem_bam_chunk: NULL pointer, negative size or more than 2^31 - 2 records");
+  if (record_cap < 1) return stage_fail(TSEM_ERR_ARG, "tsem_bam_chunk: record_cap must be >= 1");
+  if (int rc = stage_check_rec_off("tsem_bam_chunk", rec_off, n_rec, n_bytes)) return rc;
   status2[0] = 0; status2[1] = -1;
   b->chunk_n = -1; b->sized_n = -1;
   if (n_rec == 0) return TSEM_OK;
-  BAM_HIP(hipSetDevice(b->device));
-  const size_t nb = (size_t)rec_off[n_rec];
-  if (nb > b->cap_bytes) {
-    dfree(b->d_bytes); b->cap_bytes = 0;
-    if (hipMalloc((void**)&b->d_bytes, nb + nb / 4) != hipSuccess) { b->d_bytes = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_chunk: hipMalloc(" + std::to_string(nb + nb / 4) + " B) failed"); }
-    b->cap_bytes = nb + nb / 4;
-  }
-  if ((size_t)n_rec > b->cap_rec) {
-    dfree(b->d_off); dfree(b->d_cols); b->cap_rec = 0;
-    const size_t cr = (size_t)n_rec + (size_t)n_rec / 4;
-    if (hipMalloc((void**)&b->d_off, (cr + 1) * 8) != hipSuccess) { b->d_off = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_chunk: hipMalloc failed"); }
-    if (hipMalloc((void**)&b->d_cols, cr * 4 * TSEM_BAM_COLS) != hipSuccess) { b->d_cols = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_chunk: hipMalloc failed"); }
-    b->cap_rec = cr;
-  }
-  const unsigned long long none = ~0ull;
-  unsigned long long& st = b->h_status;
-  st = none;
-  BamCols C{b->d_cols, n_rec};
-  BamAnnot A{b->n_ref, b->d_ref_lo, b->d_ref_hi, b->d_locus, b->d_starts, b->d_maxend, b->d_ends, b->d_strand};
+  STAGE_HIP(hipSetDevice(b->device));
+  if (int rc = b->cols.reserve((size_t)n_rec * TSEM_BAM_COLS, "result matrix", "tsem_bam_chunk")) return rc;
+  if (int rc = stage_upload_chunk("tsem_bam_chunk", b->bytes, b->off, bytes, rec_off, n_rec, b->clock)) return rc;
+  BamCols C{b->cols.p, n_rec};
+  BamAnnot A{b->n_ref, b->ref_lo.p, b->ref_hi.p, b->locus.p, b->starts.p, b->maxend.p, b->ends.p, b->strand.p};
   const int grid = cdiv64(n_rec, 256);
-  BAM_HIP(hipEventRecord(b->ev[0], 0));
-  BAM_HIP(hipMemcpyAsync(b->d_bytes, bytes, nb, hipMemcpyHostToDevice, 0));
-  BAM_HIP(hipMemcpyAsync(b->d_off, rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, 0));
-  BAM_HIP(hipMemsetAsync(b->d_status, 0xFF, 8, 0));
-  BAM_HIP(hipEventRecord(b->ev[1], 0));
-  k_bam_decode<<<grid, 256>>>(n_rec, b->d_bytes, b->d_off, barcode_tag, umi_tag, C, b->d_status);
-  BAM_HIP(hipGetLastError());
-  BAM_HIP(hipEventRecord(b->ev[2], 0));
+  STAGE_HIP(b->status.arm());
+  STAGE_HIP(b->clock.mark());
+  k_bam_decode<<<grid, 256>>>(n_rec, b->bytes.p, b->off.p, barcode_tag, umi_tag, C, b->status.d.p);
+  STAGE_HIP(hipGetLastError());
+  STAGE_HIP(b->clock.mark());
   k_bam_pair<<<grid, 256>>>(n_rec, record_cap, C);
-  BAM_HIP(hipGetLastError());
-  BAM_HIP(hipEventRecord(b->ev[3], 0));
-  k_bam_overlap<<<grid, 256>>>(n_rec, b->d_bytes, b->d_off, C, A, run_stranded, first_f, last_f, overlap_threshold, b->d_status);
-  BAM_HIP(hipGetLastError());
-  BAM_HIP(hipEventRecord(b->ev[4], 0));
+  STAGE_HIP(hipGetLastError());
+  STAGE_HIP(b->clock.mark());
+  k_bam_overlap<<<grid, 256>>>(n_rec, b->bytes.p, b->off.p, C, A, run_stranded, first_f, last_f, overlap_threshold, b->status.d.p);
+  STAGE_HIP(hipGetLastError());
+  STAGE_HIP(b->clock.mark());
   k_bam_fragment<<<grid, 256>>>(n_rec, C);
-  BAM_HIP(hipGetLastError());
-  BAM_HIP(hipEventRecord(b->ev[5], 0));
-  BAM_HIP(hipMemcpyAsync(out, b->d_cols, (size_t)n_rec * 4 * TSEM_BAM_COLS, hipMemcpyDeviceToHost, 0));
-  BAM_HIP(hipMemcpyAsync(&st, b->d_status, 8, hipMemcpyDeviceToHost, 0));
-  BAM_HIP(hipEventRecord(b->ev[6], 0));
-  BAM_HIP(hipStreamSynchronize(0));
-  for (int k = 0; k < 6; ++k) {
-    float ms = 0.f;
-    BAM_HIP(hipEventElapsedTime(&ms, b->ev[k], b->ev[k + 1]));
-    b->ms[k] += ms;
-  }
-  ++b->calls;
-  if (st != none) { status2[0] = (int64_t)(st & 0xFF); status2[1] = (int64_t)(st >> 8); }
-  else b->chunk_n = n_rec;
+  STAGE_HIP(hipGetLastError());
+  STAGE_HIP(b->clock.mark());
+  STAGE_HIP(hipMemcpyAsync(out, b->cols.p, (size_t)n_rec * 4 * TSEM_BAM_COLS, hipMemcpyDeviceToHost, 0));
+  STAGE_HIP(b->status.fetch());
+  STAGE_HIP(b->clock.mark());
+  STAGE_HIP(hipStreamSynchronize(0));
+  STAGE_HIP(b->clock.finish({CK_H2D, CK_DECODE, CK_PAIR, CK_OVERLAP, CK_FRAGMENT, CK_D2H}));
+  if (!b->status.decode(status2)) b->chunk_n = n_rec;
   return TSEM_OK;
 }
 
 int tsem_bam_names(tsem_bam* b, const uint8_t* bytes, const int64_t* off, int32_t n_names) {
-  if (!b) return bam_fail(TSEM_ERR_ARG, "tsem_bam_names: NULL handle");
-  if (n_names < 1 || !off) return bam_fail(TSEM_ERR_ARG, "tsem_bam_names: no offsets, or fewer than one name (the last one is the no_feature_key)");
+  if (!b) return stage_fail(TSEM_ERR_ARG, "tsem_bam_names: NULL handle");
+  if (n_names < 1 || !off) return stage_fail(TSEM_ERR_ARG, "tsem_bam_names: no offsets, or fewer than one name (the last one is the no_feature_key)");
   if ((int64_t)n_names - 1 <= (int64_t)b->max_locus)
-    return bam_fail(TSEM_ERR_ARG, "tsem_bam_names: " + std::to_string(n_names - 1) + " locus names, the annotation's locus ids reach " + std::to_string(b->max_locus));
-  if (off[0] != 0) return bam_fail(TSEM_ERR_ARG, "tsem_bam_names: off[0] must be 0");
+    return stage_fail(TSEM_ERR_ARG, "tsem_bam_names: " + std::to_string(n_names - 1) + " locus names, the annotation's locus ids reach " + std::to_string(b->max_locus));
+  if (off[0] != 0) return stage_fail(TSEM_ERR_ARG, "tsem_bam_names: off[0] must be 0");
   for (int32_t j = 0; j < n_names; ++j)
-    if (off[j + 1] < off[j]) return bam_fail(TSEM_ERR_ARG, "tsem_bam_names: the offsets of name " + std::to_string(j) + " descend");
-  if (off[n_names] && !bytes) return bam_fail(TSEM_ERR_ARG, "tsem_bam_names: NULL bytes");
-  BAM_HIP(hipSetDevice(b->device));
-  dfree(b->d_names); dfree(b->d_name_off); b->n_loci = -1;
-  int rc = bam_upload(&b->d_names, bytes, (size_t)off[n_names]);
-  if (!rc) rc = bam_upload(&b->d_name_off, off, (size_t)n_names + 1);
+    if (off[j + 1] < off[j]) return stage_fail(TSEM_ERR_ARG, "tsem_bam_names: the offsets of name " + std::to_string(j) + " descend");
+  if (off[n_names] && !bytes) return stage_fail(TSEM_ERR_ARG, "tsem_bam_names: NULL bytes");
+  STAGE_HIP(hipSetDevice(b->device));
+  b->n_loci = -1;
+  int rc = bam_upload("tsem_bam_names", b->names, bytes, (size_t)off[n_names], "locus names");
+  if (!rc) rc = bam_upload("tsem_bam_names", b->name_off, off, (size_t)n_names + 1, "locus names");
   if (rc) return rc;
   b->n_loci = n_names - 1;
   return TSEM_OK;
@@ -274,47 +239,31 @@ namespace {
 
 // the slot arrays of n slots, and the scan's scratch
 int bam_rw_reserve(tsem_bam* b, int64_t n) {
-  if ((size_t)n > b->cap_rw) {
-    dfree(b->d_rw); dfree(b->d_pos); dfree(b->d_words); b->cap_rw = 0;
-    const size_t cr = (size_t)n + (size_t)n / 4;
-    if (hipMalloc((void**)&b->d_rw, cr * 12) != hipSuccess) { b->d_rw = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam rewrite: hipMalloc failed"); }
-    if (hipMalloc((void**)&b->d_pos, (cr + 1) * 16) != hipSuccess) { b->d_pos = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam rewrite: hipMalloc failed"); }
-    if (hipMalloc((void**)&b->d_words, cr * 4) != hipSuccess) { b->d_words = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam rewrite: hipMalloc failed"); }
-    b->cap_rw = cr;
-  }
+  const char* fn = "tsem_bam rewrite";
+  if (int rc = b->rw.reserve(3 * (size_t)n, "slots", fn)) return rc;
+  if (int rc = b->pos.reserve(2 * ((size_t)n + 1), "slot offsets", fn)) return rc;
+  if (int rc = b->words.reserve((size_t)n, "slot words", fn)) return rc;
   size_t tb = 0;
-  BAM_HIP(rocprim::exclusive_scan(nullptr, tb, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), 0));
-  if (tb > b->cap_scan) {
-    dfree(b->d_scan); b->cap_scan = 0;
-    if (hipMalloc(&b->d_scan, tb) != hipSuccess) { b->d_scan = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam rewrite: hipMalloc failed"); }
-    b->cap_scan = tb;
-  }
-  return TSEM_OK;
+  STAGE_HIP(rocprim::exclusive_scan(nullptr, tb, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), 0));
+  return b->scan.reserve(tb, "scan's storage", fn);
 }
-BamRw bam_rw_of(tsem_bam* b, int64_t n) {
-  return BamRw{b->d_rw, b->d_rw + b->cap_rw, b->d_rw + 2 * b->cap_rw, b->d_pos, b->d_pos + n + 1};
-}
+// (the arrays of a sizing call and of its fetch lie at the same places: both pass the same n, and only a sizing call reserves)
+BamRw bam_rw_of(tsem_bam* b, int64_t n) { return BamRw{b->rw.p, b->rw.p + n, b->rw.p + 2 * n, b->pos.p, b->pos.p + n + 1}; }
 // behind the size kernel: both scans, the positions and the status word to the host
 int bam_rw_scan_fetch(tsem_bam* b, int64_t n, int64_t* pos_other, int64_t* pos_tmp, int64_t* status2) {
   BamRw W = bam_rw_of(b, n);
-  size_t tb = b->cap_scan;
-  BAM_HIP(rocprim::exclusive_scan(b->d_scan, tb, W.pos_other, W.pos_other, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), 0));
-  tb = b->cap_scan;
-  BAM_HIP(rocprim::exclusive_scan(b->d_scan, tb, W.pos_tmp, W.pos_tmp, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), 0));
-  BAM_HIP(hipEventRecord(b->ev[3], 0));
-  if (pos_other) BAM_HIP(hipMemcpyAsync(pos_other, W.pos_other, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, 0));
-  BAM_HIP(hipMemcpyAsync(pos_tmp, W.pos_tmp, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, 0));
-  BAM_HIP(hipMemcpyAsync(&b->h_status, b->d_status, 8, hipMemcpyDeviceToHost, 0));
-  BAM_HIP(hipEventRecord(b->ev[4], 0));
-  BAM_HIP(hipStreamSynchronize(0));
-  static const int slot[4] = {0, 1, 2, 4};                    // ev[k] .. ev[k + 1]: h2d, plan, size and scan, d2h
-  for (int k = 0; k < 4; ++k) {
-    float ms = 0.f;
-    BAM_HIP(hipEventElapsedTime(&ms, b->ev[k], b->ev[k + 1]));
-    b->rw_ms[slot[k]] += ms;
-  }
-  ++b->rw_calls;
-  if (b->h_status != ~0ull) { status2[0] = (int64_t)(b->h_status & 0xFF); status2[1] = (int64_t)(b->h_status >> 8); return TSEM_OK; }
+  size_t tb = b->scan.cap;
+  STAGE_HIP(rocprim::exclusive_scan(b->scan.p, tb, W.pos_other, W.pos_other, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), 0));
+  tb = b->scan.cap;
+  STAGE_HIP(rocprim::exclusive_scan(b->scan.p, tb, W.pos_tmp, W.pos_tmp, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), 0));
+  STAGE_HIP(b->rw_clock.mark());
+  if (pos_other) STAGE_HIP(hipMemcpyAsync(pos_other, W.pos_other, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, 0));
+  STAGE_HIP(hipMemcpyAsync(pos_tmp, W.pos_tmp, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, 0));
+  STAGE_HIP(b->status.fetch());
+  STAGE_HIP(b->rw_clock.mark());
+  STAGE_HIP(hipStreamSynchronize(0));
+  STAGE_HIP(b->rw_clock.finish({RW_H2D, RW_PLAN, RW_SIZE, RW_D2H}));
+  if (b->status.decode(status2)) return TSEM_OK;
   b->sized_n = n; b->total_tmp = pos_tmp[n]; b->total_other = pos_other ? pos_other[n] : 0;
   return TSEM_OK;
 }
@@ -322,129 +271,97 @@ int bam_rw_scan_fetch(tsem_bam* b, int64_t n, int64_t* pos_other, int64_t* pos_t
 }  // namespace
 
 int tsem_bam_rewrite_size(tsem_bam* b, int64_t* pos_other, int64_t* pos_tmp, int64_t* status2) {
-  if (!b || !pos_other || !pos_tmp || !status2) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_size: NULL pointer");
+  if (!b || !pos_other || !pos_tmp || !status2) return stage_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_size: NULL pointer");
   status2[0] = 0; status2[1] = -1;
   b->sized_n = -1;
-  if (b->chunk_n < 1) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_size: no chunk on the device (tsem_bam_chunk with status 0 comes first)");
-  if (b->n_loci < 0) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_size: no names (tsem_bam_names comes first)");
+  if (b->chunk_n < 1) return stage_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_size: no chunk on the device (tsem_bam_chunk with status 0 comes first)");
+  if (b->n_loci < 0) return stage_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_size: no names (tsem_bam_names comes first)");
   const int64_t n = b->chunk_n;
-  BAM_HIP(hipSetDevice(b->device));
+  STAGE_HIP(hipSetDevice(b->device));
   if (int rc = bam_rw_reserve(b, n)) return rc;
-  BamCols C{b->d_cols, n};
+  BamCols C{b->cols.p, n};
   BamRw W = bam_rw_of(b, n);
-  BamNames nm{b->d_names, b->d_name_off, b->n_loci};
+  BamNames nm{b->names.p, b->name_off.p, b->n_loci};
   b->sized_update = false;
-  BAM_HIP(hipEventRecord(b->ev[0], 0));
-  BAM_HIP(hipMemsetAsync(b->d_status, 0xFF, 8, 0));
-  BAM_HIP(hipEventRecord(b->ev[1], 0));
+  STAGE_HIP(b->rw_clock.begin());
+  STAGE_HIP(b->status.arm());
+  STAGE_HIP(b->rw_clock.mark());
   k_bam_rw_plan<<<cdiv64(n, 256), 256>>>(n, C, W);
-  BAM_HIP(hipGetLastError());
-  BAM_HIP(hipEventRecord(b->ev[2], 0));
-  k_bam_rw_size<<<cdiv64(n + 1, 256), 256>>>(n, b->d_bytes, b->d_off, C, nm, W, b->d_status);
-  BAM_HIP(hipGetLastError());
+  STAGE_HIP(hipGetLastError());
+  STAGE_HIP(b->rw_clock.mark());
+  k_bam_rw_size<<<cdiv64(n + 1, 256), 256>>>(n, b->bytes.p, b->off.p, C, nm, W, b->status.d.p);
+  STAGE_HIP(hipGetLastError());
   return bam_rw_scan_fetch(b, n, pos_other, pos_tmp, status2);
 }
 
 int tsem_bam_update_size(tsem_bam* b, const uint8_t* bytes, int64_t n_bytes, const int64_t* rec_off, int64_t n_rec, const uint32_t* words,
                          int64_t* pos, int64_t* status2) {
-  if (!b) return bam_fail(TSEM_ERR_ARG, "tsem_bam_update_size: NULL handle");
+  if (!b) return stage_fail(TSEM_ERR_ARG, "tsem_bam_update_size: NULL handle");
   if (n_rec < 0 || n_bytes < 0 || n_rec >= (int64_t)INT32_MAX || !rec_off || !status2 || !pos || (n_rec && (!bytes || !words)))
-    return bam_fail(TSEM_ERR_ARG, "tsem_bam_update_size: NULL pointer, negative size or more than 2^31 - 2 records");
-  if (rec_off[0] < 0 || rec_off[n_rec] > n_bytes) return bam_fail(TSEM_ERR_ARG, "tsem_bam_update_size: rec_off leaves the chunk");
-  for (int64_t i = 0; i < n_rec; ++i)
-    if (rec_off[i + 1] - rec_off[i] < 36 || rec_off[i + 1] - rec_off[i] > (int64_t)INT32_MAX)
-      return bam_fail(TSEM_ERR_ARG, "tsem_bam_update_size: record " + std::to_string(i) + " is shorter than 36 bytes or longer than 2^31 - 1 (rec_off must ascend)");
+    return stage_fail(TSEM_ERR_ARG, "tsem_bam_update_size: NULL pointer, negative size or more than 2^31 - 2 records");
+  if (int rc = stage_check_rec_off("tsem_bam_update_size", rec_off, n_rec, n_bytes)) return rc;
   status2[0] = 0; status2[1] = -1;
-  b->chunk_n = -1; b->sized_n = -1;
+  b->chunk_n = -1; b->sized_n = -1;                            // (the chunk's bytes and offsets are overwritten below; its matrix is not used here)
   pos[0] = 0;
   if (n_rec == 0) return TSEM_OK;
-  BAM_HIP(hipSetDevice(b->device));
-  const size_t nb = (size_t)rec_off[n_rec];
-  if (nb > b->cap_bytes) {
-    dfree(b->d_bytes); b->cap_bytes = 0;
-    if (hipMalloc((void**)&b->d_bytes, nb + nb / 4) != hipSuccess) { b->d_bytes = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_update_size: hipMalloc(" + std::to_string(nb + nb / 4) + " B) failed"); }
-    b->cap_bytes = nb + nb / 4;
-  }
-  if ((size_t)n_rec > b->cap_rec) {                            // (d_cols is not used here, but one capacity covers both arrays)
-    dfree(b->d_off); dfree(b->d_cols); b->cap_rec = 0;
-    const size_t cr = (size_t)n_rec + (size_t)n_rec / 4;
-    if (hipMalloc((void**)&b->d_off, (cr + 1) * 8) != hipSuccess) { b->d_off = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_update_size: hipMalloc failed"); }
-    if (hipMalloc((void**)&b->d_cols, cr * 4 * TSEM_BAM_COLS) != hipSuccess) { b->d_cols = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_update_size: hipMalloc failed"); }
-    b->cap_rec = cr;
-  }
+  STAGE_HIP(hipSetDevice(b->device));
   if (int rc = bam_rw_reserve(b, n_rec)) return rc;
+  if (int rc = stage_upload_chunk("tsem_bam_update_size", b->bytes, b->off, bytes, rec_off, n_rec, b->rw_clock)) return rc;
   BamRw W = bam_rw_of(b, n_rec);
   b->sized_update = true;
-  BAM_HIP(hipEventRecord(b->ev[0], 0));
-  BAM_HIP(hipMemcpyAsync(b->d_bytes, bytes, nb, hipMemcpyHostToDevice, 0));
-  BAM_HIP(hipMemcpyAsync(b->d_off, rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, 0));
-  BAM_HIP(hipMemcpyAsync(b->d_words, words, (size_t)n_rec * 4, hipMemcpyHostToDevice, 0));
-  BAM_HIP(hipMemsetAsync(b->d_status, 0xFF, 8, 0));
-  BAM_HIP(hipEventRecord(b->ev[1], 0));
-  BAM_HIP(hipEventRecord(b->ev[2], 0));
-  k_bam_upd_size<<<cdiv64(n_rec + 1, 256), 256>>>(n_rec, b->d_bytes, b->d_off, b->d_words, W, b->d_status);
-  BAM_HIP(hipGetLastError());
+  STAGE_HIP(hipMemcpyAsync(b->words.p, words, (size_t)n_rec * 4, hipMemcpyHostToDevice, 0));
+  STAGE_HIP(b->status.arm());
+  STAGE_HIP(b->rw_clock.mark());
+  STAGE_HIP(b->rw_clock.mark());                                 // (no plan stage: its slot gets the time between two events)
+  k_bam_upd_size<<<cdiv64(n_rec + 1, 256), 256>>>(n_rec, b->bytes.p, b->off.p, b->words.p, W, b->status.d.p);
+  STAGE_HIP(hipGetLastError());
   return bam_rw_scan_fetch(b, n_rec, nullptr, pos, status2);
 }
 
 int tsem_bam_rewrite_fetch(tsem_bam* b, uint8_t* other, int64_t n_other, uint8_t* tmp, int64_t n_tmp) {
-  if (!b) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_fetch: NULL handle");
-  if (b->sized_n < 1) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_fetch: nothing sized (tsem_bam_rewrite_size or tsem_bam_update_size with status 0 comes first)");
+  if (!b) return stage_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_fetch: NULL handle");
+  if (b->sized_n < 1) return stage_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_fetch: nothing sized (tsem_bam_rewrite_size or tsem_bam_update_size with status 0 comes first)");
   if (n_other != b->total_other || n_tmp != b->total_tmp || (n_other && !other) || (n_tmp && !tmp))
-    return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_fetch: the buffers must hold exactly " + std::to_string(b->total_other) + " and " +
+    return stage_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_fetch: the buffers must hold exactly " + std::to_string(b->total_other) + " and " +
                                   std::to_string(b->total_tmp) + " bytes");
   const int64_t n = b->sized_n;
   b->sized_n = -1;
-  BAM_HIP(hipSetDevice(b->device));
-  if ((size_t)n_other > b->cap_other) {
-    dfree(b->d_other); b->cap_other = 0;
-    if (hipMalloc((void**)&b->d_other, (size_t)n_other + (size_t)n_other / 4) != hipSuccess) { b->d_other = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_rewrite_fetch: hipMalloc failed"); }
-    b->cap_other = (size_t)n_other + (size_t)n_other / 4;
-  }
-  if ((size_t)n_tmp > b->cap_tmp) {
-    dfree(b->d_tmp); b->cap_tmp = 0;
-    if (hipMalloc((void**)&b->d_tmp, (size_t)n_tmp + (size_t)n_tmp / 4) != hipSuccess) { b->d_tmp = nullptr; return bam_fail(TSEM_ERR_NOMEM, "tsem_bam_rewrite_fetch: hipMalloc failed"); }
-    b->cap_tmp = (size_t)n_tmp + (size_t)n_tmp / 4;
-  }
-  BamCols C{b->d_cols, n};
-  BamNames nm{b->d_names, b->d_name_off, b->n_loci};
-  BAM_HIP(hipEventRecord(b->ev[0], 0));
-  k_bam_rw_write<<<cdiv64(n, 256), 256>>>(n, b->d_bytes, b->d_off, C, nm, b->d_words, bam_rw_of(b, n), b->d_other, b->d_tmp);
-  BAM_HIP(hipGetLastError());
-  BAM_HIP(hipEventRecord(b->ev[1], 0));
-  if (n_other) BAM_HIP(hipMemcpyAsync(other, b->d_other, (size_t)n_other, hipMemcpyDeviceToHost, 0));
-  if (n_tmp) BAM_HIP(hipMemcpyAsync(tmp, b->d_tmp, (size_t)n_tmp, hipMemcpyDeviceToHost, 0));
-  BAM_HIP(hipEventRecord(b->ev[2], 0));
-  BAM_HIP(hipStreamSynchronize(0));
-  float ms = 0.f;
-  BAM_HIP(hipEventElapsedTime(&ms, b->ev[0], b->ev[1])); b->rw_ms[3] += ms;
-  BAM_HIP(hipEventElapsedTime(&ms, b->ev[1], b->ev[2])); b->rw_ms[4] += ms;
+  STAGE_HIP(hipSetDevice(b->device));
+  if (int rc = b->other.reserve((size_t)n_other, "other stream", "tsem_bam_rewrite_fetch")) return rc;
+  if (int rc = b->tmp.reserve((size_t)n_tmp, "tmp stream", "tsem_bam_rewrite_fetch")) return rc;
+  BamCols C{b->cols.p, n};
+  BamNames nm{b->names.p, b->name_off.p, b->n_loci};
+  STAGE_HIP(b->rw_clock.begin());
+  k_bam_rw_write<<<cdiv64(n, 256), 256>>>(n, b->bytes.p, b->off.p, C, nm, b->words.p, bam_rw_of(b, n), b->other.p, b->tmp.p);
+  STAGE_HIP(hipGetLastError());
+  STAGE_HIP(b->rw_clock.mark());
+  if (n_other) STAGE_HIP(hipMemcpyAsync(other, b->other.p, (size_t)n_other, hipMemcpyDeviceToHost, 0));
+  if (n_tmp) STAGE_HIP(hipMemcpyAsync(tmp, b->tmp.p, (size_t)n_tmp, hipMemcpyDeviceToHost, 0));
+  STAGE_HIP(b->rw_clock.mark());
+  STAGE_HIP(hipStreamSynchronize(0));
+  STAGE_HIP(b->rw_clock.finish({RW_WRITE, RW_D2H}, false));      // (the sizing call was counted)
   return TSEM_OK;
 }
 
 int tsem_bam_rewrite_slots(tsem_bam* b, int32_t* kind, int32_t* pair, int64_t n) {
-  if (!b || !kind || !pair) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_slots: NULL pointer");
-  if (b->sized_n < 1 || n != b->sized_n) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_slots: n is not the slot count of the last size call");
-  BAM_HIP(hipSetDevice(b->device));
+  if (!b || !kind || !pair) return stage_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_slots: NULL pointer");
+  if (b->sized_n < 1 || n != b->sized_n) return stage_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_slots: n is not the slot count of the last size call");
+  STAGE_HIP(hipSetDevice(b->device));
   const BamRw W = bam_rw_of(b, n);
-  BAM_HIP(hipMemcpy(kind, W.kind, (size_t)n * 4, hipMemcpyDeviceToHost));
-  BAM_HIP(hipMemcpy(pair, W.pair, (size_t)n * 4, hipMemcpyDeviceToHost));
+  STAGE_HIP(hipMemcpy(kind, W.kind, (size_t)n * 4, hipMemcpyDeviceToHost));
+  STAGE_HIP(hipMemcpy(pair, W.pair, (size_t)n * 4, hipMemcpyDeviceToHost));
   return TSEM_OK;
 }
 
 int tsem_bam_rewrite_times(tsem_bam* b, int reset, double* ms5, int64_t* calls) {
-  if (!b || !ms5 || !calls) return bam_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_times: NULL pointer");
-  for (int k = 0; k < 5; ++k) ms5[k] = b->rw_ms[k];
-  *calls = b->rw_calls;
-  if (reset) { for (double& m : b->rw_ms) m = 0; b->rw_calls = 0; }
+  if (!b || !ms5 || !calls) return stage_fail(TSEM_ERR_ARG, "tsem_bam_rewrite_times: NULL pointer");
+  b->rw_clock.read(reset, ms5, calls);
   return TSEM_OK;
 }
 
 int tsem_bam_times(tsem_bam* b, int reset, double* ms6, int64_t* calls) {
-  if (!b || !ms6 || !calls) return bam_fail(TSEM_ERR_ARG, "tsem_bam_times: NULL pointer");
-  for (int k = 0; k < 6; ++k) ms6[k] = b->ms[k];
-  *calls = b->calls;
-  if (reset) { for (double& m : b->ms) m = 0; b->calls = 0; }
+  if (!b || !ms6 || !calls) return stage_fail(TSEM_ERR_ARG, "tsem_bam_times: NULL pointer");
+  b->clock.read(reset, ms6, calls);
   return TSEM_OK;
 }
 

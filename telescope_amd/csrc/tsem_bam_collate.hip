@@ -20,6 +20,7 @@
 // total, which the host checks against the input's size before the gather is launched.
 #include "tsem_internal.h"
 #include "tsem_bam_collate.h"
+#include "tsem_stage.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -87,27 +88,26 @@ __global__ __launch_bounds__(256) void k_collate_gather(int64_t n, const uint8_t
 
 namespace {
 
-int col_fail(int rc, const std::string& msg) { g_create_err = msg; return rc; }
-#define COL_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return col_fail(TSEM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-#define COL_TMP(tmp, bytes, what) do { if (hipMalloc(&(tmp).p, std::max<size_t>(1, (size_t)(bytes))) != hipSuccess) { (tmp).p = nullptr; \
-    return col_fail(TSEM_ERR_NOMEM, std::string("tsem_bam_collate: hipMalloc(") + std::to_string((size_t)(bytes)) + " B) for the " + (what) + \
-                    " failed: the step holds the whole stream twice and 44 to 60 B per record on the device"); } } while (0)
+// a buffer of this call alone (the unit keeps nothing between calls); TSEM_ERR_NOMEM is what the caller's advice hangs on
+int col_tmp(DevTmp& tmp, size_t bytes, const char* what) {
+  if (hipMalloc(&tmp.p, std::max<size_t>(1, bytes)) == hipSuccess) return TSEM_OK;
+  tmp.p = nullptr;
+  return stage_fail(TSEM_ERR_NOMEM, "tsem_bam_collate: hipMalloc(" + std::to_string(bytes) + " B) for the " + what +
+                                        " failed: the step holds the whole stream twice and 44 to 60 B per record on the device");
+}
 
-struct Events {
-  hipEvent_t e[6] = {}; int n = 0;
-  ~Events() { for (int k = 0; k < n; ++k) (void)hipEventDestroy(e[k]); }
-};
-
-// the argument checks that both entries share; *total = the bytes of the records
+// the argument checks that both entries share; *total = the bytes of the records.  The offsets are held to bam_collate_chain, not to
+// stage_check_rec_off: this step accepts every chain that does not descend and stays inside the bytes, and a record too short to
+// hold a name is the kernels' to report (bam_collate_check, status 1, with the record's number) — not an argument error of the call.
 int col_args(const char* fn, const uint8_t* bytes, int64_t n_bytes, const int64_t* rec_off, int64_t n_rec, int32_t hash_bits, uint8_t* out,
              int64_t* order, int64_t* n_names, int64_t* status2, int64_t* total) {
   const std::string f(fn);
   if (n_bytes < 0 || n_rec < 0 || !rec_off || !n_names || !status2 || (n_bytes && (!bytes || !out)) || (n_rec && !order))
-    return col_fail(TSEM_ERR_ARG, f + ": NULL pointer or negative size");
-  if (n_rec >= (int64_t)0xFFFFFFFFll) return col_fail(TSEM_ERR_ARG, f + ": 2^32 - 1 records or more");
-  if (hash_bits < 0 || hash_bits > 64) return col_fail(TSEM_ERR_ARG, f + ": hash_bits must be 0 .. 64");
+    return stage_fail(TSEM_ERR_ARG, f + ": NULL pointer or negative size");
+  if (n_rec >= (int64_t)0xFFFFFFFFll) return stage_fail(TSEM_ERR_ARG, f + ": 2^32 - 1 records or more");
+  if (hash_bits < 0 || hash_bits > 64) return stage_fail(TSEM_ERR_ARG, f + ": hash_bits must be 0 .. 64");
   const int64_t bad = bam_collate_chain(rec_off, n_rec, n_bytes);
-  if (bad >= 0) return col_fail(TSEM_ERR_ARG, f + ": the offsets of record " + std::to_string(bad) + " descend or leave the bytes");
+  if (bad >= 0) return stage_fail(TSEM_ERR_ARG, f + ": the offsets of record " + std::to_string(bad) + " descend or leave the bytes");
   *total = rec_off[n_rec] - rec_off[0];
   *n_names = 0; status2[0] = 0; status2[1] = -1;
   return TSEM_OK;
@@ -128,7 +128,7 @@ int tsem_bam_collate_host(const uint8_t* bytes, int64_t n_bytes, const int64_t* 
   std::vector<bam_col_slot> table((size_t)bam_collate_table_slots(n_rec));
   const unsigned long long st = bam_collate_run(bam_col_stream{bytes, rec_off}, n_rec, hash_bits, out, order, n_names, hash.data(), slot.data(),
                                                 key.data(), table.data(), [](uint64_t* k, int64_t m) { std::sort(k, k + m); });
-  if (st != ~0ull) { status2[0] = (int64_t)(st & 0xFF); status2[1] = (int64_t)(st >> 8); }
+  (void)stage_status_decode(st, status2);
   return TSEM_OK;
 }
 
@@ -138,25 +138,26 @@ int tsem_bam_collate(int device, const uint8_t* bytes, int64_t n_bytes, const in
   if (int rc = col_args("tsem_bam_collate", bytes, n_bytes, rec_off, n_rec, hash_bits, out, order, n_names, status2, &total)) return rc;
   if (ms) for (int k = 0; k < 5; ++k) ms[k] = 0;
   if (n_rec == 0) return TSEM_OK;
-  if (hipSetDevice(device) != hipSuccess) return col_fail(TSEM_ERR_HIP, "tsem_bam_collate: hipSetDevice failed (no usable HIP device)");
+  if (hipSetDevice(device) != hipSuccess) return stage_fail(TSEM_ERR_HIP, "tsem_bam_collate: hipSetDevice failed (no usable HIP device)");
   const size_t n = (size_t)n_rec;
   const uint64_t cap = bam_collate_table_slots(n_rec);
   const int bits = [&] { int b = 1; while (b < 32 && ((uint64_t)(n_rec - 1) >> b) != 0) ++b; return b; }();   // of a record index
   size_t sort_b = 0, scan_b = 0;
-  COL_HIP(rocprim::radix_sort_keys(nullptr, sort_b, (uint64_t*)nullptr, (uint64_t*)nullptr, n, 32, 32 + bits, (hipStream_t)0));
-  COL_HIP(rocprim::exclusive_scan(nullptr, scan_b, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, n, rocprim::plus<int64_t>(), (hipStream_t)0));
+  STAGE_HIP(rocprim::radix_sort_keys(nullptr, sort_b, (uint64_t*)nullptr, (uint64_t*)nullptr, n, 32, 32 + bits, (hipStream_t)0));
+  STAGE_HIP(rocprim::exclusive_scan(nullptr, scan_b, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, n, rocprim::plus<int64_t>(), (hipStream_t)0));
   // every buffer is freed when the call returns, on every path (DevTmp)
   DevTmp t_in, t_out, t_off, t_a, t_b, t_slot, t_table, t_tmp, t_word;
   const size_t in_bytes = (((size_t)n_bytes + 3) & ~(size_t)3) + 8;
-  COL_TMP(t_in, in_bytes, "stream");
-  COL_TMP(t_out, (size_t)total + 4, "collated stream");
-  COL_TMP(t_off, (n + 1) * 8, "record offsets");
-  COL_TMP(t_a, n * 8, "keys");
-  COL_TMP(t_b, n * 8, "hashes");
-  COL_TMP(t_slot, n * 4, "slots");
-  COL_TMP(t_table, (size_t)cap * sizeof(bam_col_slot), "name table");
-  COL_TMP(t_tmp, std::max(sort_b, scan_b), "sort's storage");
-  COL_TMP(t_word, 16, "status words");
+  int rc = col_tmp(t_in, in_bytes, "stream");
+  if (!rc) rc = col_tmp(t_out, (size_t)total + 4, "collated stream");
+  if (!rc) rc = col_tmp(t_off, (n + 1) * 8, "record offsets");
+  if (!rc) rc = col_tmp(t_a, n * 8, "keys");
+  if (!rc) rc = col_tmp(t_b, n * 8, "hashes");
+  if (!rc) rc = col_tmp(t_slot, n * 4, "slots");
+  if (!rc) rc = col_tmp(t_table, (size_t)cap * sizeof(bam_col_slot), "name table");
+  if (!rc) rc = col_tmp(t_tmp, std::max(sort_b, scan_b), "sort's storage");
+  if (!rc) rc = col_tmp(t_word, 16, "status words");
+  if (rc) return rc;
   uint8_t *d_in = t_in.as<uint8_t>(), *d_out = t_out.as<uint8_t>();
   int64_t* d_off = t_off.as<int64_t>();
   uint64_t *d_key = t_a.as<uint64_t>(), *d_hash = t_b.as<uint64_t>(), *d_key2 = d_hash;       // (the hashes are done with before the sort)
@@ -165,67 +166,63 @@ int tsem_bam_collate(int device, const uint8_t* bytes, int64_t n_bytes, const in
   bam_col_slot* d_table = t_table.as<bam_col_slot>();
   unsigned long long *d_bad = t_word.as<unsigned long long>(), *d_names = d_bad + 1;
   static_assert(sizeof(bam_col_slot) == 8, "the output offsets take the table's place: 8 B per record fit into >= 2 slots per record");
-  Events ev;
-  for (; ev.n < 6; ++ev.n) COL_HIP(hipEventCreate(&ev.e[ev.n]));
+  StageClock<6, 5> clock;                                       // h2d, hash / insert / key, sort and scan, gather, d2h
+  STAGE_HIP(clock.create());
   const unsigned grid = (unsigned)cdiv64(n_rec, 256);
   unsigned long long h_word[2] = {~0ull, 0};
 
-  COL_HIP(hipEventRecord(ev.e[0], 0));
-  COL_HIP(hipMemsetAsync(d_in + ((size_t)n_bytes & ~(size_t)3), 0, in_bytes - ((size_t)n_bytes & ~(size_t)3), 0));   // (the padding: read by the gather, never used)
-  if (n_bytes) COL_HIP(hipMemcpyAsync(d_in, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, 0));
-  COL_HIP(hipMemcpyAsync(d_off, rec_off, (n + 1) * 8, hipMemcpyHostToDevice, 0));
-  COL_HIP(hipMemsetAsync(d_bad, 0xFF, 8, 0));
-  COL_HIP(hipMemsetAsync(d_names, 0, 8, 0));
-  COL_HIP(hipMemsetAsync(d_table, 0xFF, (size_t)cap * sizeof(bam_col_slot), 0));
-  COL_HIP(hipEventRecord(ev.e[1], 0));
+  STAGE_HIP(clock.begin());
+  STAGE_HIP(hipMemsetAsync(d_in + ((size_t)n_bytes & ~(size_t)3), 0, in_bytes - ((size_t)n_bytes & ~(size_t)3), 0));   // (the padding: read by the gather, never used)
+  if (n_bytes) STAGE_HIP(hipMemcpyAsync(d_in, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, 0));
+  STAGE_HIP(hipMemcpyAsync(d_off, rec_off, (n + 1) * 8, hipMemcpyHostToDevice, 0));
+  STAGE_HIP(hipMemsetAsync(d_bad, 0xFF, 8, 0));
+  STAGE_HIP(hipMemsetAsync(d_names, 0, 8, 0));
+  STAGE_HIP(hipMemsetAsync(d_table, 0xFF, (size_t)cap * sizeof(bam_col_slot), 0));
+  STAGE_HIP(clock.mark());
   k_collate_hash<<<grid, 256>>>(n_rec, d_in, d_off, hash_bits, d_hash, d_bad);
-  COL_HIP(hipGetLastError());
-  COL_HIP(hipMemcpyAsync(&h_word[0], d_bad, 8, hipMemcpyDeviceToHost, 0));
-  COL_HIP(hipStreamSynchronize(0));
-  if (h_word[0] != ~0ull) {                                                                  // refused: nothing behind the check runs
-    status2[0] = (int64_t)(h_word[0] & 0xFF); status2[1] = (int64_t)(h_word[0] >> 8);
-    return TSEM_OK;
-  }
+  STAGE_HIP(hipGetLastError());
+  STAGE_HIP(hipMemcpyAsync(&h_word[0], d_bad, 8, hipMemcpyDeviceToHost, 0));
+  STAGE_HIP(hipStreamSynchronize(0));
+  if (stage_status_decode(h_word[0], status2)) return TSEM_OK;                               // refused: nothing behind the check runs
   k_collate_insert<<<grid, 256>>>(n_rec, d_in, d_off, d_hash, d_table, cap, d_slot);
-  COL_HIP(hipGetLastError());
+  STAGE_HIP(hipGetLastError());
   k_collate_key<<<grid, 256>>>(n_rec, d_table, d_slot, d_key, d_names);
-  COL_HIP(hipGetLastError());
-  COL_HIP(hipEventRecord(ev.e[2], 0));
+  STAGE_HIP(hipGetLastError());
+  STAGE_HIP(clock.mark());
   size_t tb = sort_b;
-  COL_HIP(rocprim::radix_sort_keys(t_tmp.p, tb, d_key, d_key2, n, 32, 32 + bits, (hipStream_t)0));
+  STAGE_HIP(rocprim::radix_sort_keys(t_tmp.p, tb, d_key, d_key2, n, 32, 32 + bits, (hipStream_t)0));
   k_collate_size<<<grid, 256>>>(n_rec, d_key2, d_off, d_size);
-  COL_HIP(hipGetLastError());
+  STAGE_HIP(hipGetLastError());
   tb = scan_b;
-  COL_HIP(rocprim::exclusive_scan(t_tmp.p, tb, d_size, d_pos, (int64_t)0, n, rocprim::plus<int64_t>(), (hipStream_t)0));
-  COL_HIP(hipEventRecord(ev.e[3], 0));
+  STAGE_HIP(rocprim::exclusive_scan(t_tmp.p, tb, d_size, d_pos, (int64_t)0, n, rocprim::plus<int64_t>(), (hipStream_t)0));
+  STAGE_HIP(clock.mark());
   // the last record's offset and length bound every write of the gather: checked before it runs
   int64_t h_last[2] = {0, 0};
-  COL_HIP(hipMemcpyAsync(&h_last[0], d_pos + (n - 1), 8, hipMemcpyDeviceToHost, 0));
-  COL_HIP(hipMemcpyAsync(&h_last[1], d_size + (n - 1), 8, hipMemcpyDeviceToHost, 0));
-  COL_HIP(hipStreamSynchronize(0));
+  STAGE_HIP(hipMemcpyAsync(&h_last[0], d_pos + (n - 1), 8, hipMemcpyDeviceToHost, 0));
+  STAGE_HIP(hipMemcpyAsync(&h_last[1], d_size + (n - 1), 8, hipMemcpyDeviceToHost, 0));
+  STAGE_HIP(hipStreamSynchronize(0));
   if (h_last[0] + h_last[1] != total)
-    return col_fail(TSEM_ERR_HIP, "tsem_bam_collate: the output offsets end at " + std::to_string(h_last[0] + h_last[1]) + ", the records hold " +
+    return stage_fail(TSEM_ERR_HIP, "tsem_bam_collate: the output offsets end at " + std::to_string(h_last[0] + h_last[1]) + ", the records hold " +
                                       std::to_string(total) + " bytes");
   if (total / n_rec >= 1024)
     k_collate_gather<64><<<(unsigned)cdiv64(n_rec * 64, 256), 256>>>(n_rec, d_in, d_off, d_key2, d_pos, d_out);
   else
     k_collate_gather<16><<<(unsigned)cdiv64(n_rec * 16, 256), 256>>>(n_rec, d_in, d_off, d_key2, d_pos, d_out);
-  COL_HIP(hipGetLastError());
-  COL_HIP(hipEventRecord(ev.e[4], 0));
+  STAGE_HIP(hipGetLastError());
+  STAGE_HIP(clock.mark());
   std::vector<uint64_t> h_key(n);
-  if (total) COL_HIP(hipMemcpyAsync(out, d_out, (size_t)total, hipMemcpyDeviceToHost, 0));
-  COL_HIP(hipMemcpyAsync(h_key.data(), d_key2, n * 8, hipMemcpyDeviceToHost, 0));
-  COL_HIP(hipMemcpyAsync(&h_word[1], d_names, 8, hipMemcpyDeviceToHost, 0));
-  COL_HIP(hipEventRecord(ev.e[5], 0));
-  COL_HIP(hipStreamSynchronize(0));
+  if (total) STAGE_HIP(hipMemcpyAsync(out, d_out, (size_t)total, hipMemcpyDeviceToHost, 0));
+  STAGE_HIP(hipMemcpyAsync(h_key.data(), d_key2, n * 8, hipMemcpyDeviceToHost, 0));
+  STAGE_HIP(hipMemcpyAsync(&h_word[1], d_names, 8, hipMemcpyDeviceToHost, 0));
+  STAGE_HIP(clock.mark());
+  STAGE_HIP(hipStreamSynchronize(0));
   for (size_t k = 0; k < n; ++k) order[k] = (int64_t)(h_key[k] & 0xFFFFFFFFull);
   *n_names = (int64_t)h_word[1];
-  if (ms)
-    for (int k = 0; k < 5; ++k) {
-      float m = 0.f;
-      COL_HIP(hipEventElapsedTime(&m, ev.e[k], ev.e[k + 1]));
-      ms[k] = m;
-    }
+  if (ms) {
+    int64_t calls = 0;
+    STAGE_HIP(clock.finish({0, 1, 2, 3, 4}));
+    clock.read(0, ms, &calls);
+  }
   return TSEM_OK;
 }
 

@@ -18,6 +18,8 @@
 //                    tsem_bgzf_inflate.h, the chain of block headers in tsem_bgzf_scan.h)
 //   tsem_bam_collate.hip  the records of a BAM that is not name-collated brought together by name (tsem_bam_collate; the bodies are the
 //                    host / device functions of tsem_bam_collate.h, which tsem_bam_collate_host runs on one CPU thread)
+//   tsem_stage.h     the host side that these three units share (host code only, included by them alone): one failure function and
+//                    HIP-call macro, the grow-only device buffer, the stage clock, the status word, the rec_off check and chunk upload
 //   tsem_fz_p*.hip   instantiations of the fused kernel, one team size per unit: the look-up generated (tsem_fused_inst.h) from the one
 //                    table of what exists, fz_exists (tsem_fused.h)
 //   tsem_index.h     the index formats of the layout's entries: tsem_ctx::index_fmt, fz_exists' `ix`, layout_info()

@@ -4,7 +4,8 @@
 
 `records` are framed (block_size and body).  cases() builds the streams that tsem_bam_collate_host and the kernels are held to;
 reordered_files() writes the fixture and fuzz BAMs with their records sorted by (ref, pos) and shuffled, and each one's reference-collated
-copy.
+copy.  These inputs stay inside one block of the device's sort; tests/_collate_streams.py has the sizes above it (a vectorised
+definition, held to collate() in tests/test_collate_streams_host.py).
 """
 import os
 import random

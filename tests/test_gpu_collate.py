@@ -1,6 +1,7 @@
 """`--collate device` on the GPU (telescope_amd/csrc/tsem_bam_collate.hip): the kernels against tsem_bam_collate_host on the small
 inputs of _collate_reference (bytes, order and the number of names; a failure names the stage), the device loader on reordered BAMs
-against the python loader on their reference-collated copies, and the command line end to end."""
+against the python loader on their reference-collated copies, and the command line end to end.  Sizes above one block of the
+device's sort, every alignment of the gather and both of its widths: tests/test_gpu_collate_scale.py (streams of _collate_streams)."""
 import functools
 import os
 import subprocess

@@ -828,6 +828,15 @@ int  tsem_debug_quad64(const uint32_t* rc4, uint64_t* word, uint32_t* back4, uin
  * codes, 2 fp64 with the score table in LDS), geometry, timeline kernel (0 / 1), index format read (layout_info 'index_format': 0, 1, 2).
  * *found: 1 when the library's look-up returns a kernel for the cell; *listed: 1 when the table's predicate lists it.  The two agree. */
 int  tsem_debug_fused_cell(int32_t P, int32_t mode, int32_t fmt, int32_t geo, int32_t prof, int32_t ix, int32_t* found, int32_t* listed);
+/* host only, nothing on the device: the launch census of a handle.  Every launch of the fused kernel is counted under the cell it was
+ * looked up by — the six values above, in the order team size 1..8 x mode 0..9 x entry format 0..2 x geometry 0..3 x timeline x index
+ * format, row-major: 5760 cells.  out[2 c]: launches that run unconditionally; out[2 c + 1]: launches enqueued with the device's
+ * choice between the two forms of the lnl pass armed (which of the two did the work the host cannot know).  cap: int64 slots of
+ * `out`, at least 11520 (TSEM_ERR_ARG otherwise).  tsem_debug_fused_launches_clear zeroes the counters. */
+int  tsem_debug_fused_launches(tsem_ctx* h, int64_t* out, int64_t cap);
+int  tsem_debug_fused_launches_clear(tsem_ctx* h);
+/* host only: the position c of a cell in that order, -1 outside the enumerated ranges (not an error code) */
+int  tsem_debug_fused_census_index(int32_t P, int32_t mode, int32_t fmt, int32_t geo, int32_t prof, int32_t ix);
 /* host only, no device: the conflict-aware order inside quads (option "deconflict" on fp64 entries) applied to n_win windows of 64
  * consecutive local row << 16 | local column words: codes[16 w + l] is the permutation of quad l of window w — entry (code >> 2 j) & 3
  * of the quad goes to position j, 0xE4 is the identity —, *moved (may be null) the quads that change; by the inline functions the

@@ -5,6 +5,7 @@ is usable, every entry point raises — the product path never computes on the
 host.
 """
 import ctypes as C
+import itertools
 import os
 import sys
 import subprocess
@@ -20,6 +21,9 @@ OK, ERR_ARG, ERR_HIP, ERR_NOMEM, ERR_TIMEOUT = 0, -1, -2, -3, -4
 RA_CODE = {'exclude': 0, 'choose': 1, 'average': 2, 'conf': 3, 'unique': 4, 'all': 5}
 Z_PREV, Z_CUR, Z_INITIAL, Z_FIRST, Z_USER = 0, 1, 2, 3, 4
 EMK_AUTO, EMK_TWOPASS, EMK_FUSED = 0, 1, 2
+# the cells of the fused kernel's table in the order of the launch census (fz_census_cell, csrc/tsem_index.h): team size, mode, entry
+# format, geometry, timeline, index format; tests/test_fused_cells_host.py ties the order to the library's
+FUSED_CELLS = tuple(itertools.product(range(1, 9), range(10), range(3), range(4), (0, 1), range(3)))
 
 
 class EngineError(RuntimeError):
@@ -279,6 +283,9 @@ def lib():
     L.tsem_debug_quad64.argtypes = [vp, vp, vp, C.c_uint64, vp]
     L.tsem_debug_fused_cell.argtypes = [C.c_int32] * 6 + [vp, vp]
     L.tsem_debug_subblock_values.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int64]
+    L.tsem_debug_fused_launches.argtypes = [vp, vp, C.c_int64]
+    L.tsem_debug_fused_launches_clear.argtypes = [vp]
+    L.tsem_debug_fused_census_index.argtypes = [C.c_int32] * 6
     L.tsem_debug_valmap.argtypes = [C.c_int32, vp]
     L.tsem_quad_order_host.argtypes = [C.c_int64, vp, vp, vp]
     for name in exported_symbols():
@@ -795,6 +802,18 @@ class Engine(object):
         if n < 0:
             raise EngineError('tsem_debug_subblock_values failed (%d)' % n)
         return out[:n], rows[:n], cols[:n]
+
+    def fused_launches(self):
+        """The launch census of this handle (tsem_debug_fused_launches; host only): {cell: (n, n_conditional)} over the cells of the
+        fused kernel's table that were launched since the counters were cleared — cell = (team size, mode, entry format, geometry,
+        timeline, index format); n the launches that ran unconditionally, n_conditional those enqueued with the device's choice
+        between the two forms of the lnl pass armed."""
+        out = np.zeros(2 * len(FUSED_CELLS), np.int64)
+        self._ck(self._L.tsem_debug_fused_launches(self._h, ptr(out), out.size))
+        return {FUSED_CELLS[c]: (int(out[2 * c]), int(out[2 * c + 1])) for c in np.flatnonzero(out.reshape(-1, 2).any(axis=1)).tolist()}
+
+    def clear_fused_launches(self):
+        self._ck(self._L.tsem_debug_fused_launches_clear(self._h))
 
     def layout_info(self, extended=False):
         """Facts about the resident layout (include/telescope_em.h, tsem_layout_info_n).  extended: also the values appended behind

@@ -159,6 +159,11 @@ struct tsem_ctx {
   double lq_lo = 0, lq_hi = 0;      // log Q of the smallest / largest stored score (> 0): which columns may reach the exact branch of the log form
   unsigned long long* d_lq_mid = nullptr;   // [1] stored entries of such columns, counted by k_log_tab before every lnl pass (the device picks the form)
   int64_t lq_choice[2] = {0, 0};    // lnl passes enqueued with the selection armed | (diagnostic) reserved
+  // The launch census (host only; tsem_debug_fused_launches): per cell of the table of instantiations, in the order team size 1..8 x
+  // mode 0..9 x entry format 0..2 x geometry 0..3 x timeline x index format, [2 c] the launches that run whatever the device finds and
+  // [2 c + 1] those enqueued with the selection armed (the device decides which of the two forms works: never coverage).
+  // Sized at the first fused launch of the handle (fz_count): a handle that never launches the fused kernel holds nothing.
+  std::vector<int64_t> fz_census;
   bool lag_agreed = false;          // row-sharded runs: EVERY rank can run MODE 4 (decided once per run, dropped for good after a time-out anywhere)
   bool lag_valid = false;           // the iteration committed last still owes its lnl, and d_rinv / d_ctab_prev are what the next MODE 4 pass needs for it
   bool exact_single = false;        // reproducible: both pieces in ONE pass (three tables per part fit the LDS with <= 8 parts)

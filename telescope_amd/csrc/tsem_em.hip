@@ -633,6 +633,12 @@ static int ensure_log_tables(tsem_ctx* h) {
   return TSEM_OK;
 }
 
+// the launch census (tsem_ctx::fz_census): one launch the runtime accepted, under the cell it was looked up by
+static inline void fz_count(tsem_ctx* h, int cell, bool armed) {
+  if (h->fz_census.empty()) h->fz_census.assign(2 * (size_t)TS_FZ_CENSUS_CELLS, 0);
+  h->fz_census[2 * (size_t)cell + (armed ? 1 : 0)] += 1;
+}
+
 // One launch of the persistent fused kernel.  mode 0: EM pass (column sums of w*z into d_fpartial);
 // mode 1: log-likelihood of the ambiguous rows (one partial per workgroup into d_lnl_part).
 static int launch_fused(tsem_ctx* h, int mode, hipEvent_t* pair, int bin = 0) {
@@ -711,6 +717,7 @@ static int launch_fused(tsem_ctx* h, int mode, hipEvent_t* pair, int bin = 0) {
   if (pair) TSEM_HIP(hipEventRecord(pair[0], h->stream));   // time the kernel, not the memsets
   fn<<<h->fz_grid, FZ_NT, ldsf, h->stream>>>(A);
   TSEM_HIP(hipGetLastError());
+  fz_count(h, fz_census_cell(h->P, kmode, fz_fmt(h), h->geo, prof, h->index_fmt), A.sel != nullptr);   // (fn exists: the cell is in range)
   if (kmode == 9 && A.sel) {                                // ... and the per-entry-logarithm form behind it: exactly one of the two runs
     fz_fn f1 = fz_kernel(h->P, 1, fz_fmt(h), h->geo, false, h->index_fmt);
     if (!f1) TSEM_FAIL(TSEM_ERR_ARG, "fused lnl: no kernel for this team size / geometry");
@@ -718,6 +725,7 @@ static int launch_fused(tsem_ctx* h, int mode, hipEvent_t* pair, int bin = 0) {
     B.lctab = nullptr; B.lqtab = nullptr; B.lq_n = 0; B.lq_lin = 0; B.sel_want = 1;
     f1<<<h->fz_grid, FZ_NT, fz_lds_bytes(h, fz_fmt(h) != 0), h->stream>>>(B);
     TSEM_HIP(hipGetLastError());
+    fz_count(h, fz_census_cell(h->P, 1, fz_fmt(h), h->geo, false, h->index_fmt), true);   // (always behind an armed selection)
   }
   h->fused_launched = true;
   return TSEM_OK;

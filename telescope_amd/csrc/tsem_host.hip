@@ -797,6 +797,25 @@ int tsem_debug_fused_cell(int32_t P, int32_t mode, int32_t fmt, int32_t geo, int
   return TSEM_OK;
 }
 
+/* host only: the launch census of a handle — per cell of the table, in the order team size 1..8 x mode 0..9 x entry format 0..2 x
+ * geometry 0..3 x timeline x index format, out[2 c] the launches of k_em_fused that run unconditionally and out[2 c + 1] those enqueued
+ * with the device's choice between the two forms of the lnl pass armed; counted where launch_fused (tsem_em.hip) launches */
+int tsem_debug_fused_launches(tsem_ctx* h, int64_t* out, int64_t cap) {
+  if (!h || !out || cap < 2 * (int64_t)TS_FZ_CENSUS_CELLS) return TSEM_ERR_ARG;
+  std::fill(out, out + 2 * (size_t)TS_FZ_CENSUS_CELLS, (int64_t)0);   // (a handle that has launched nothing holds no counters)
+  std::copy(h->fz_census.begin(), h->fz_census.end(), out);
+  return TSEM_OK;
+}
+/* host only: the position of a cell in that order (fz_census_cell, tsem_index.h); -1 outside the enumerated ranges */
+int tsem_debug_fused_census_index(int32_t P, int32_t mode, int32_t fmt, int32_t geo, int32_t prof, int32_t ix) {
+  return fz_census_cell(P, mode, fmt, geo, prof != 0, ix);
+}
+int tsem_debug_fused_launches_clear(tsem_ctx* h) {
+  if (!h) return TSEM_ERR_ARG;
+  std::fill(h->fz_census.begin(), h->fz_census.end(), (int64_t)0);
+  return TSEM_OK;
+}
+
 /* host only: the rule of tsem_quadorder.h on n_win windows of 64 lrow << 16 | lcol words each: codes[16 w + l] is the permutation of quad
  * l of window w (entry (code >> 2 j) & 3 goes to position j), *moved (may be null) the quads whose code is not the identity */
 int tsem_quad_order_host(int64_t n_win, const uint32_t* rc, uint8_t* codes, int64_t* moved) {

@@ -99,11 +99,17 @@ class Model(object):
 
 def _check_pass(m, ref, label, limit_of=None):
     """check 1; returns the largest error as a fraction of its bound"""
-    path, P = m.path()
     m.eng.em_pass()
-    red = m.eng.read_reduce(0, m.K + 2)
+    return _check_red(m, ref, m.eng.read_reduce(0, m.K + 2), label, limit_of)
+
+
+def _check_red(m, ref, red, label, limit_of=None, slots=True):
+    """check 1 on a reduce buffer that is already read (an EM pass the caller ran, in a chunk for instance).  slots=False: the caller
+    has read the buffer where slots K and K + 1 hold log-likelihoods (after a chunk's flush) and checks the time-out another way"""
+    path, P = m.path()
     assert not np.any(np.isnan(red)), (label, 'NaN in the reduce buffer', np.flatnonzero(np.isnan(red))[:5])
-    assert red[m.K] == 0.0 and red[m.K + 1] == 0.0, (label, 'time-out word / carried value', red[m.K:])
+    if slots:
+        assert red[m.K] == 0.0 and red[m.K + 1] == 0.0, (label, 'time-out word / carried value', red[m.K:])
     limit = None if limit_of is None else limit_of(ref, P)
     frac, j = E.colsum_fraction(red[:m.K], ref.sums, ref.cnt, ref.lenmax, ref.gradual, path, P, limit=limit)
     zero = (ref.sums == 0) & (ref.gradual == 0)
@@ -130,10 +136,12 @@ def _check_lnl(m, ref, label):
     return frac
 
 
-def _check_update(m, red, pi_set, theta_set, label):
-    """check 3; returns (|diff_est - exact| as a fraction of its bound, the new parameters, how many twins took their representative's sum)"""
+def _check_update(m, red, pi_set, theta_set, label, diff=None):
+    """check 3; returns (|diff_est - exact| as a fraction of its bound, the new parameters, how many twins took their representative's sum).
+    diff: the diff_est of an update the caller has run already (a chunk's); None: em_update runs here"""
     from telescope_amd._lib import Z_CUR, Z_PREV
-    diff = m.eng.em_update()
+    if diff is None:
+        diff = m.eng.em_update()
     pi_c, th_c = m.eng.get_params(Z_CUR)
     pi_p, th_p = m.eng.get_params(Z_PREV)
     assert np.array_equal(pi_p.view(np.uint64), pi_set.view(np.uint64)) and np.array_equal(th_p.view(np.uint64), theta_set.view(np.uint64)), (label, 'Z_PREV')
@@ -159,7 +167,8 @@ def _forms(m):
 
 
 def _leg(m, mkey, pnames, label, forms=True, limit_of=None):
-    """checks 1 - 4 for every parameter set; returns the largest fractions (column sums, lnl, diff_est)"""
+    """checks 1 - 4 for every parameter set; returns the largest fractions (column sums, lnl, diff_est).  forms: True every form the
+    layout has, False the unforced pass alone, or the tuple of fused_dbg values to run"""
     top = [0.0, 0.0, 0.0]
     for pname in pnames:
         ref = _ref(mkey, m.raw, pname)
@@ -167,7 +176,7 @@ def _leg(m, mkey, pnames, label, forms=True, limit_of=None):
         m.eng.set_params(ref.pi, ref.theta)
         m.eng.set_params(ref.pi, ref.theta)                         # previous = current
         lf = []
-        for form in (_forms(m) if forms else (0,)):
+        for form in (forms if isinstance(forms, tuple) else (_forms(m) if forms else (0,))):
             m.eng.set_option('fused_dbg', form)
             lf.append(_check_lnl(m, ref, lab + '/form %d' % form))
         m.eng.set_option('fused_dbg', 0)

@@ -828,6 +828,13 @@ int  tsem_debug_quad64(const uint32_t* rc4, uint64_t* word, uint32_t* back4, uin
  * codes, 2 fp64 with the score table in LDS), geometry, timeline kernel (0 / 1), index format read (layout_info 'index_format': 0, 1, 2).
  * *found: 1 when the library's look-up returns a kernel for the cell; *listed: 1 when the table's predicate lists it.  The two agree. */
 int  tsem_debug_fused_cell(int32_t P, int32_t mode, int32_t fmt, int32_t geo, int32_t prof, int32_t ix, int32_t* found, int32_t* listed);
+/* host only: the fused kernel's dynamic LDS for one cell of that table and the sizes (Kp, R, lut_len, lq_n, lq_lin) — regions[26]: byte
+ * offset and bytes of each of its 13 regions (may be null), *kernel_end where the last ends — and for a layout of these flags (1 split,
+ * 2 exact_single, 4 lnl3, 8 reproducible, 16 score table in LDS): *launch_bytes the dynamic LDS the cell is launched with, *rmax the
+ * most row slots per block the set-up chooses, *room the bytes left for the log-Q table */
+int  tsem_debug_fused_lds(int32_t P, int32_t mode, int32_t fmt, int32_t geo, int32_t prof, int32_t ix, int32_t Kp, int32_t R, int32_t lut_len,
+                          int32_t lq_n, int32_t lq_lin, int32_t flags, int32_t* regions, int32_t* kernel_end, int32_t* launch_bytes,
+                          int32_t* rmax, int32_t* room);
 /* host only, nothing on the device: the launch census of a handle.  Every launch of the fused kernel is counted under the cell it was
  * looked up by — the six values above, in the order team size 1..8 x mode 0..9 x entry format 0..2 x geometry 0..3 x timeline x index
  * format, row-major: 5760 cells.  out[2 c]: launches that run unconditionally; out[2 c + 1]: launches enqueued with the device's

@@ -282,6 +282,7 @@ def lib():
     L.tsem_debug_idx24.argtypes = [vp, vp, vp]
     L.tsem_debug_quad64.argtypes = [vp, vp, vp, C.c_uint64, vp]
     L.tsem_debug_fused_cell.argtypes = [C.c_int32] * 6 + [vp, vp]
+    L.tsem_debug_fused_lds.argtypes = [C.c_int32] * 12 + [vp] * 5
     L.tsem_debug_subblock_values.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int64]
     L.tsem_debug_fused_launches.argtypes = [vp, vp, C.c_int64]
     L.tsem_debug_fused_launches_clear.argtypes = [vp]

@@ -562,7 +562,7 @@ int ce_launch(tsem_ctx* h, CeArgs A, const int32_t* d_list, int n, int kc_max) {
   if (n <= 0) return TSEM_OK;
   const size_t lds = 8 * ((size_t)CE_RED + (LDS ? 5 * (size_t)kc_max : 0));
   if (lds > 48 * 1024)
-    TSEM_HIP(hipFuncSetAttribute((const void*)k_cell_em<T, LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+    TSEM_HIP(hipFuncSetAttribute((const void*)k_cell_em<T, LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_DYN_MAX));
   A.cells = d_list;
   k_cell_em<T, LDS><<<n, T, lds, h->stream>>>(A);
   TSEM_HIP(hipGetLastError());

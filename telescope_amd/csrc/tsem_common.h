@@ -52,9 +52,11 @@ __host__ __device__ inline uint64_t ts_hash3(uint64_t seed, uint64_t row, uint64
 // LDS budget for the per-part tables (c and acc, 8 B each per column).
 constexpr int TS_LDS_TABLE_BYTES = 120 * 1024;
 constexpr int TS_MAX_KP = TS_LDS_TABLE_BYTES / 16;   // 7680 columns per part
-constexpr int TS_MAX_KP_LNL = 5120;                  // ... when a part keeps pi*theta of TWO parameter sets and the accumulators (option "use_likelihood": 24 B per column)
-constexpr int TS_MAX_KP3 = 4800;                     // ... when a part keeps THREE tables in LDS (option "reproducible", one pass: 26 B per column)
+constexpr int TS_MAX_KP_LNL = 5120;                  // ... when a part keeps pi*theta of TWO parameter sets and the accumulators (option "use_likelihood")
+constexpr int TS_MAX_KP3 = 4800;                     // ... when a part keeps THREE tables and the exponent table in LDS (option "reproducible", one pass)
+// (what each of the three leaves of the LDS at 64 row slots and a 2048-entry score table: the static_asserts behind fz_lds_bytes, tsem_internal.h)
 constexpr int TS_LDS_MAX = 160 * 1024;
+constexpr int TS_LDS_DYN_MAX = TS_LDS_MAX - 1024;    // the dynamic LDS a kernel may ask for: what hipFuncSetAttribute is handed and launch sizes are held to
 constexpr int TS_ENTRY_PAD = 320;   // entries of padding behind indices[] / raw[] (k_report_rows reads 16-entry lanes past a row's end)
 constexpr int TS_STRANDS = 16;   // strand-transposed entry order inside a sub-block
 

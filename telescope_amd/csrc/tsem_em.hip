@@ -554,7 +554,7 @@ static int ensure_log_tables(tsem_ctx* h) {
   h->lq_n = 0;
   const int fmt = fz_fmt(h);
   if (fmt == 0 || !h->use_fused || h->split || h->lut_len <= 1 || (int)h->lut_host.size() != h->lut_len) return TSEM_OK;
-  const size_t room = (size_t)(TS_LDS_MAX - 1024) - fz_lds_bytes(h, true);
+  const size_t room = (size_t)TS_LDS_DYN_MAX - fz_lds_bytes(h, true);
   std::vector<double> tab;
   h->lq_lin = 0;
   if (fmt == 1) {
@@ -613,7 +613,7 @@ static int ensure_log_tables(tsem_ctx* h) {
   TSEM_HIP(hipStreamSynchronize(h->stream));               // (tab is a local)
   fz_fn f9 = fz_kernel(h->P, 9, fmt, h->geo, false, h->index_fmt);
   if (!f9) return TSEM_OK;
-  TSEM_HIP(hipFuncSetAttribute((const void*)f9, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+  TSEM_HIP(hipFuncSetAttribute((const void*)f9, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_DYN_MAX));
   TSEM_ALLOC(h->d_lctab, h->Kpad);
   // the range of log Q over the stored scores, for the choice between the two forms of the pass (k_log_tab)
   h->lq_lo = 0.0; h->lq_hi = 0.0;
@@ -682,7 +682,7 @@ static int launch_fused(tsem_ctx* h, int mode, hipEvent_t* pair, int bin = 0) {
   A.ebias = h->d_ebias; A.bin = bin; A.ovf = h->d_ovf; A.partial2 = h->d_fpartial2;
 
   A.pcode = h->d_pcode; A.lut = h->d_lut; A.lut_len = fz_fmt(h) ? h->lut_len : 0; A.wcode = h->d_amb_wcode;
-  size_t ldsf = fz_lds_bytes(h, fz_fmt(h) != 0);
+  int lq_lds = 0;                                          // entries of the log-Q table the launch keeps in LDS
   A.lctab = nullptr; A.lqtab = nullptr; A.lq_n = 0; A.lq_shift = 0; A.lq_base = 0; A.lq_lin = 0; A.lq_c0 = 0; A.lq_a = 0; A.lq_b = 0;
   A.sel = nullptr; A.sel_thr = 0; A.sel_want = 0;
   if (mode == 1 && !(h->opt_dbg & 8192)) {                  // (fused_dbg bit 13: the per-entry logarithm, for A/B timing and tests)
@@ -703,7 +703,7 @@ static int launch_fused(tsem_ctx* h, int mode, hipEvent_t* pair, int bin = 0) {
       A.lctab = h->d_lctab; A.lqtab = h->d_lqtab; A.lq_n = h->lq_n; A.lq_shift = h->lq_shift; A.lq_base = h->lq_base;
       A.lq_lin = (fz_fmt(h) == 1 && !((h->opt_dbg & 16384) && h->lq_tab_fits)) ? h->lq_lin : 0;   // (fused_dbg bit 14: the look-up even where the arithmetic form applies — tests)
       A.lq_c0 = h->lq_c0; A.lq_a = h->lq_a; A.lq_b = h->lq_b;
-      if (!A.lq_lin) ldsf += (size_t)h->lq_n * 8;
+      if (!A.lq_lin) lq_lds = h->lq_n;
       kmode = 9;
     }
   }
@@ -713,9 +713,9 @@ static int launch_fused(tsem_ctx* h, int mode, hipEvent_t* pair, int bin = 0) {
                                            "only (not with use_likelihood, the split layout, more than 4 column parts or a score table too large for LDS)");
   if (!fn) TSEM_FAIL(TSEM_ERR_ARG, mode >= 2 ? "reproducible mode needs the fused kernel with a score table of at most 2048 entries"
                                                : "fused kernel supports at most 8 column parts");
-  if (prof) TSEM_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));   // (the layout build allowed it for the product kernels)
+  if (prof) TSEM_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_DYN_MAX));   // (the layout build allowed it for the product kernels)
   if (pair) TSEM_HIP(hipEventRecord(pair[0], h->stream));   // time the kernel, not the memsets
-  fn<<<h->fz_grid, FZ_NT, ldsf, h->stream>>>(A);
+  fn<<<h->fz_grid, FZ_NT, fz_lds_bytes(h, fz_fmt(h) != 0, lq_lds), h->stream>>>(A);
   TSEM_HIP(hipGetLastError());
   fz_count(h, fz_census_cell(h->P, kmode, fz_fmt(h), h->geo, prof, h->index_fmt), A.sel != nullptr);   // (fn exists: the cell is in range)
   if (kmode == 9 && A.sel) {                                // ... and the per-entry-logarithm form behind it: exactly one of the two runs
@@ -1010,7 +1010,7 @@ static int launch_update(tsem_ctx* h, double* d_diff_slot, bool chunked = false,
 int tsem_twopass_attributes(tsem_ctx* h) {
   TSEM_HIP(hipFuncSetAttribute((const void*)k_phase1<512>, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX));
   TSEM_HIP(hipFuncSetAttribute((const void*)k_phase2_em<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX));
-  TSEM_HIP(hipFuncSetAttribute((const void*)k_phase2_lnl<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+  TSEM_HIP(hipFuncSetAttribute((const void*)k_phase2_lnl<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_DYN_MAX));
   return TSEM_OK;
 }
 

@@ -38,6 +38,7 @@
 // their size and the block round-robin all derive from tickets taken at run
 // time; every wait is bounded and reports through an error word.
 #pragma once
+#include "tsem_fused_lds.h"
 #include "tsem_idx24.h"
 #include "tsem_index.h"
 #include "tsem_quad64.h"
@@ -253,7 +254,6 @@ __device__ __forceinline__ void fz_row_sums(double* yb, bool idle, uint32_t r0, 
 // CERR = false (the carrying pass, MODE 4, whose step is bound by its arithmetic): without the correction for the rounding of 1 + x —
 // an error of at most 2^-53 ABSOLUTE per evaluation, the size of the table's own (1 / c_i is rounded); relative accuracy for tiny x
 // is lost, which a SUM of z * log1p (terms of 1 ... 100 dominate) does not see.
-constexpr int FZ_LOGTAB = 64;
 template <bool CERR = true>
 __device__ __forceinline__ double fz_log1p_tab(double x, const double2* __restrict__ tab) {
   const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
@@ -647,15 +647,9 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
   constexpr bool LAG = MODE == 4;                  // EM pass + the log-likelihood of the previous iteration
   constexpr bool LNL1 = MODE == 1 || MODE == 9;    // the dedicated log-likelihood pass; MODE 9: log tables in LDS (score table in LDS: FMT 1, 2)
   constexpr bool SPA = MODE == 5, SPB = MODE == 7, SPL = MODE == 8;   // split layout (see FusedArgs): ONE table of Kp entries, or two of Kh
-  const int KT = SPL ? A.Kh : Kp;                  // entries per LDS table
-  double* c = reinterpret_cast<double*>(smem);
-  double* acc = (SPA || SPB) ? c : c + KT;         // (MODE 5 has no accumulators, MODE 7 no pi*theta table)
-  double* const acc2 = acc + Kp;                   // MODE 3: the low pieces' accumulators [Kp];  MODE 4: pi*theta of the previous parameters
-  double* const cprev = acc2;
-  double* y = acc + ((MODE == 3 || LAG) ? 2 : 1) * KT;   // y[FZ_YR][R]  partial row sums (ring)
-  double* s = y + FZ_YR * R;                       // s[2][R]      w_i / rowsum_i   (ring)
-  double* const rpS = s + 2 * R;                   // MODE 4: rp[2][R]  1 / rowsum_i of the previous pass (ring)
-  int* ibox = reinterpret_cast<int*>(s + (LAG ? 4 : 2) * R);   // [0]=ticket [1..8]=xcd counts
+  // what this instantiation keeps in LDS (tsem_fused_lds.h): the one statement of table count, entries per table and ring depths
+  const FzLdsIn L = fz_lds_kernel(MODE, FMT, FZ_YR, Kp, A.Kh, R, A.lut_len, A.lq_n, A.lq_lin);
+  const int KT = L.kt;                             // entries per LDS table (MODE 8: Kh)
   const int tid = threadIdx.x;
   uint32_t* const sync = A.sync;
   uint32_t* const err = sync + 9;
@@ -680,25 +674,35 @@ __global__ __launch_bounds__(FZ_NT) void k_em_fused(FusedArgs A) {
   unsigned xcc;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
   xcc &= 7u;
+  // every region of the dynamic LDS from the one map (tsem_fused_lds.h)
+  const FzLdsMap<double*> M = fz_lds_map(reinterpret_cast<double*>(smem), L);
+  double* c = M.c;
+  double* acc = M.acc;                             // (MODE 5 has no accumulators, MODE 7 no pi*theta table: one table)
+  double* const acc2 = M.acc2;                     // MODE 3: the low pieces' accumulators [Kp];  MODE 4: pi*theta of the previous parameters
+  double* const cprev = acc2;
+  double* y = M.y;                                 // y[FZ_YR][R]  partial row sums (ring)
+  double* s = M.s;                                 // s[2][R]      w_i / rowsum_i   (ring)
+  double* const rpS = M.rp;                        // MODE 4: rp[2][R]  1 / rowsum_i of the previous pass (ring)
+  int* ibox = reinterpret_cast<int*>(M.ibox);      // [0]=ticket [1..8]=xcd counts
+  uint32_t* offs = reinterpret_cast<uint32_t*>(M.offs);      // [8][2] sub-block quad ranges (ring), LDS
+  double* dum = M.dum;                                       // [64] one slot per lane: where idle lanes send their (zero) atomics
+  double* lutS = M.lut;                                      // FMT 1: score table [lut_len]
+  uint16_t* const eS = reinterpret_cast<uint16_t*>(M.exps);   // MODE 2: [Kp] the slots' exponent bounds
+  double* const lqS = M.lq;                                  // MODE 9: [lq_n] log Q behind the score table
+  // MODE 1: [FZ_LOGTAB] (1 / c_i, log c_i) for fz_log1p_tab, in the same place as MODE 2's table (the two modes never share a launch)
+  double2* const logtab = reinterpret_cast<double2*>(M.logtab);
   if (tid == 0) ibox[0] = (int)__hip_atomic_fetch_add(&sync[xcc], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   for (int t = tid; t < KT; t += FZ_NT) acc[t] = 0.0;   // (lnl mode: overwritten with ctab2 below)
   if (MODE == 3) for (int t = tid; t < Kp; t += FZ_NT) acc2[t] = 0.0;
   for (int t = tid; t < FZ_YR * R; t += FZ_NT) y[t] = 0.0;
-  for (int t = tid; t < (LAG ? 4 : 2) * R; t += FZ_NT) s[t] = 0.0;
-  uint32_t* offs = reinterpret_cast<uint32_t*>(ibox + 16);   // [8][2] sub-block quad ranges (ring), LDS
-  double* dum = reinterpret_cast<double*>(ibox + 32);        // [64] one slot per lane: where idle lanes send their (zero) atomics
-  double* lutS = dum + 64;                                   // FMT 1: score table [lut_len]
+  for (int t = tid; t < L.sr * R; t += FZ_NT) s[t] = 0.0;   // (s, and MODE 4's rp behind it)
   if (tid < 64) dum[tid] = 0.0;
   if (FMT != 0)
     for (int t = tid; t < A.lut_len; t += FZ_NT) lutS[t] = A.lut[t];
-  uint16_t* const eS = reinterpret_cast<uint16_t*>(lutS + A.lut_len);   // MODE 2: [Kp] the slots' exponent bounds
   // MODE 1 / 4 with log tables: log Q behind the score table [lq_n]
   constexpr bool LT = MODE == 9;
-  double* const lqS = lutS + A.lut_len;
   if (LT && !(FMT == 1 && A.lq_lin))
     for (int t = tid; t < A.lq_n; t += FZ_NT) lqS[t] = A.lqtab[t];
-  // MODE 1: [FZ_LOGTAB] (1 / c_i, log c_i) for fz_log1p_tab, in the same place as MODE 2's table (the two modes never share a launch)
-  double2* const logtab = reinterpret_cast<double2*>((reinterpret_cast<uintptr_t>(lutS + A.lut_len + ((LT && !(FMT == 1 && A.lq_lin)) ? A.lq_n : 0)) + 15) & ~(uintptr_t)15);
   if ((LNL1 || LAG || SPL) && tid < FZ_LOGTAB) {
     const double ci = 1.0 + (double)tid * (1.0 / FZ_LOGTAB);
     logtab[tid] = make_double2(1.0 / ci, ts_log1p_pos((double)tid * (1.0 / FZ_LOGTAB)));

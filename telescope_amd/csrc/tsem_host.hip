@@ -797,6 +797,40 @@ int tsem_debug_fused_cell(int32_t P, int32_t mode, int32_t fmt, int32_t geo, int
   return TSEM_OK;
 }
 
+/* host only: the fused kernel's LDS (tsem_fused_lds.h) as the kernel and the host see it.  The cell and (Kp, R, lut_len, lq_n, lq_lin) give
+ * the kernel's map: regions[2 i], regions[2 i + 1] the byte offset and the bytes of region i (c, acc, acc2, y, s, rp, ibox, offs, dum, lut,
+ * lq, exps, logtab; 0 bytes: not used by the cell) and *kernel_end the end of the last; regions may be null, a cell outside the table is
+ * TSEM_ERR_ARG otherwise.  flags say what the layout is (1 split, 2 exact_single, 4 lnl3, 8 reproducible, 16 the score table in LDS):
+ * *launch_bytes what launch_fused starts the cell with, *rmax the most row slots tsem_choose_geometry gives such a layout, *room what
+ * the layout leaves the log-Q table. */
+int tsem_debug_fused_lds(int32_t P, int32_t mode, int32_t fmt, int32_t geo, int32_t prof, int32_t ix, int32_t Kp, int32_t R, int32_t lut_len,
+                         int32_t lq_n, int32_t lq_lin, int32_t flags, int32_t* regions, int32_t* kernel_end, int32_t* launch_bytes,
+                         int32_t* rmax, int32_t* room) {
+  if (!kernel_end || !launch_bytes || !rmax || !room || geo < 0 || geo > 3 || Kp < 0 || R < 0 || lut_len < 0 || lq_n < 0) return TSEM_ERR_ARG;
+  const bool split = flags & 1, exact_single = flags & 2, lnl3 = flags & 4, repro = flags & 8, codes = flags & 16;
+  const FzLdsIn in = fz_lds_kernel(mode, fmt, fz_yr(geo), Kp, (Kp + 1) / 2, R, fmt != 0 ? lut_len : 0, lq_n, lq_lin);
+  *kernel_end = 0;
+  if (regions) {
+    if (!fz_exists(P, mode, fmt, geo, prof != 0, ix)) return TSEM_ERR_ARG;
+    const FzLdsMap<int> m = fz_lds_map(0, in);
+    // TEST ONLY: what the kernel reads and writes of each region, in bytes, stated from the kernel's loops and NOT from the map's
+    // offsets — so that a region the map makes too short for its use overlaps its neighbour in tests/test_fused_lds_host.py
+    constexpr int N = 13;
+    const int at[N] = {m.c, m.acc, m.acc2, m.y, m.s, m.rp, m.ibox, m.offs, m.dum, m.lut, m.lq, m.exps, m.logtab};
+    const int bytes[N] = {in.kt * 8, in.ntab == 1 ? 0 : in.kt * 8, in.ntab == 3 ? in.Kp * 8 : 0, in.yr * in.R * 8, 2 * in.R * 8, (in.sr - 2) * in.R * 8,
+                          16 * 4, 8 * 2 * 4, 64 * 8, in.lut_len * 8, in.lq_n * 8, in.tail == FZ_TAIL_EXPS ? in.Kp * 2 : 0,
+                          in.tail == FZ_TAIL_LOG ? FZ_LOGTAB * 16 : 0};
+    for (int i = 0; i < N; ++i) {
+      regions[2 * i] = at[i] * 8; regions[2 * i + 1] = bytes[i];
+      if (regions[2 * i + 1] > 0) *kernel_end = std::max(*kernel_end, regions[2 * i] + regions[2 * i + 1]);
+    }
+  }
+  *launch_bytes = fz_lds_layout_bytes(Kp, R, fz_yr(geo), split, exact_single, lnl3, repro, codes ? lut_len : 0, in.lq_n);
+  *rmax = fz_layout_rmax(Kp, geo, split, exact_single, lnl3, repro, lut_len);
+  *room = TS_LDS_DYN_MAX - fz_lds_layout_bytes(Kp, R, fz_yr(geo), split, exact_single, lnl3, repro, lut_len, 0);
+  return TSEM_OK;
+}
+
 /* host only: the launch census of a handle — per cell of the table, in the order team size 1..8 x mode 0..9 x entry format 0..2 x
  * geometry 0..3 x timeline x index format, out[2 c] the launches of k_em_fused that run unconditionally and out[2 c + 1] those enqueued
  * with the device's choice between the two forms of the lnl pass armed; counted where launch_fused (tsem_em.hip) launches */

@@ -169,14 +169,34 @@ static inline fz_fn fz_kernel(int P, int mode, int fmt, int geo, bool prof, int 
 // With the round-2 exchange (branch-free, partner loads after the combine for short rows) codes in row order win
 // at every row length measured — 10 / 14 / 20 / 28 / 40 / 100 entries per row: 1.47 / 1.61 / 1.98 / 2.55 / 3.60 /
 // 3.76 ms against 1.71 / 1.96 / 2.57 / 3.26 / 4.23 / 4.39 ms with fp64 entries (profiles/r02_sweep_short.txt).
+constexpr bool fz_lut_fits(int lut_len) { return lut_len > 0 && lut_len <= 2048; }   // the score table goes into LDS beside the column tables
 static inline bool fz_wants_codes(const tsem_ctx* h) {
-  return h->opt_format != 1 && h->lut_len > 0 && h->lut_len <= 2048;
+  return h->opt_format != 1 && fz_lut_fits(h->lut_len);
 }
-static inline size_t fz_lds_bytes(const tsem_ctx* h, bool codes) {
-  // (split layout: one table of Kp entries, or — the lnl pass — two of (Kp + 1) / 2)
-  return (size_t)((h->split ? h->Kp + 2 : ((h->exact_single || h->lnl3) ? 3 : 2) * h->Kp) + (fz_yr(h->geo) + (h->lnl3 ? 4 : 2)) * h->R) * 8 + 192 + 512 + (codes ? (size_t)h->lut_len * 8 : 0) +
-         std::max<size_t>(h->opt_reproducible ? (size_t)h->Kp * 2 + 16 : 0, FZ_LOGTAB * 16 + 16);   // (+ the slots' exponent table | the lnl pass's log table)
+// Dynamic LDS of the layout's fused launches, from the kernel's own map (tsem_fused_lds.h: the bound over the passes the layout can
+// launch).  codes: the score table in LDS;  lq_n: entries of the log-Q table behind it (the lnl pass with log tables).
+static inline size_t fz_lds_bytes(const tsem_ctx* h, bool codes, int lq_n = 0) {
+  return (size_t)fz_lds_layout_bytes(h->Kp, h->R, fz_yr(h->geo), h->split, h->exact_single, h->lnl3, h->opt_reproducible != 0, codes ? h->lut_len : 0, lq_n);
 }
+// The most row slots the set-up gives a block of this layout: the geometry's, and the largest R for which the map — the score table in
+// LDS wherever it may go there — stays FZ_RMAX_RESERVE below the limit.  The reserve is what the choice of R has always kept beyond the
+// launch check; R hangs on it.
+constexpr int FZ_RMAX_RESERVE = 832;
+constexpr int fz_layout_rmax(int Kp, int geo, bool split, bool exact_single, bool lnl3, bool reproducible, int lut_len) {
+  const int lut = fz_lut_fits(lut_len) ? lut_len : 0;
+  const int fixed = fz_lds_layout_bytes(Kp, 0, fz_yr(geo), split, exact_single, lnl3, reproducible, lut, 0);
+  const int per_row = fz_lds_layout_bytes(Kp, 1, fz_yr(geo), split, exact_single, lnl3, reproducible, lut, 0) - fixed;
+  const int fit = (TS_LDS_DYN_MAX - FZ_RMAX_RESERVE - fixed) / per_row;
+  return fz_rmax(geo) < fit ? fz_rmax(geo) : fit;
+}
+// The column limits of a part, through the map: at that many columns, 64 row slots (the smallest block), a 2048-entry score table and
+// the class's tail, the layout fits the limit.  Per column: two tables 16 B; "use_likelihood" three tables 24 B; "reproducible" in one
+// pass three tables and 2 B of exponent bound, 26 B.
+static_assert(fz_lds_layout_bytes(TS_MAX_KP, 64, fz_yr(0), false, false, false, false, 2048, 0) <= TS_LDS_DYN_MAX, "TS_MAX_KP: two tables");
+static_assert(fz_lds_layout_bytes(TS_MAX_KP, 64, fz_yr(0), false, false, false, true, 2048, 0) <= TS_LDS_DYN_MAX, "TS_MAX_KP: reproducible, two passes");
+static_assert(fz_lds_layout_bytes(2 * TS_MAX_KP, 64, fz_yr(1), true, false, false, false, 2048, 0) <= TS_LDS_DYN_MAX, "2 * TS_MAX_KP: split layout");
+static_assert(fz_lds_layout_bytes(TS_MAX_KP_LNL, 64, fz_yr(0), false, false, true, false, 2048, 0) <= TS_LDS_DYN_MAX, "TS_MAX_KP_LNL: use_likelihood");
+static_assert(fz_lds_layout_bytes(TS_MAX_KP3, 64, fz_yr(0), false, true, false, true, 2048, 0) <= TS_LDS_DYN_MAX, "TS_MAX_KP3: reproducible, one pass");
 
 // ---- host functions shared between the units (defined in the unit named) ---------------------------------------------
 class CsrIds;

@@ -1121,12 +1121,12 @@ static int launch_rowpass(tsem_ctx* h, int mode, int meth, int grid, int block, 
     A.flag_n = reinterpret_cast<unsigned long long*>(h->d_flag_bits + words);
   }
   const RowKern k0 = rowpass_kern<false>(mode, meth);
-  if (lds > 48 * 1024) TSEM_HIP(hipFuncSetAttribute((const void*)k0, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+  if (lds > 48 * 1024) TSEM_HIP(hipFuncSetAttribute((const void*)k0, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_DYN_MAX));
   k0<<<grid, block, lds, h->stream>>>(A);
   TSEM_HIP(hipGetLastError());
   if (fix) {
     const RowKern k1 = rowpass_kern<true>(mode, meth);
-    if (lds > 48 * 1024) TSEM_HIP(hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+    if (lds > 48 * 1024) TSEM_HIP(hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_DYN_MAX));
     k1<<<std::min(grid, 128), block, lds, h->stream>>>(A);   // (returns at once when the pass flagged nothing)
     TSEM_HIP(hipGetLastError());
   }
@@ -1479,7 +1479,7 @@ static int report_packed(tsem_ctx* h, const ReportArgs& R, DevTmp& tabs, PhaseTi
   const int lut_sq = std::ilogb(lut_max(h)) - 40;          // lut 2^-lut_sq: the largest score table entry in [2^40, 2^41)
   k_rp32_tables<<<cdiv64(std::max(IDN + 1, R.lut_len), 256), 256, 0, h->stream>>>(IDN, R.cnat2, R.lut_len, R.lut, lut_sq, t32, l32);
   constexpr int nwv = 16;
-  const int words = (TS_LDS_MAX - 1024) / 4 - 8 - (E + 1) * (E / 2);   // LDS words for the table of the ids and the copies of the score table
+  const int words = TS_LDS_DYN_MAX / 4 - 8 - (E + 1) * (E / 2);   // LDS words for the table of the ids and the copies of the score table
   Rp32Args P;
   P.N = h->N; P.IDN = IDN; P.lut_len = R.lut_len; P.indptr = h->d_indptr; P.rid = h->d_rid16; P.raw = h->d_raw;
   P.HC = std::min(IDN, std::max(0, words - R.lut_len));
@@ -1494,14 +1494,14 @@ static int report_packed(tsem_ctx* h, const ReportArgs& R, DevTmp& tabs, PhaseTi
   void (*const pk)(Rp32Args) = inst.k;
   tsem_ctx::ReportLaunch& L = launch_record(h, 0, 4, false, 0);
   L.G = 64; L.E = inst.E; L.cold = inst.cold; L.HC = P.HC; L.lut_rep = P.lut_rep; L.grid = h->n_cu; L.block = nwv * 64;   // (a row takes up to 64 lanes)
-  TSEM_HIP(hipFuncSetAttribute((const void*)pk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+  TSEM_HIP(hipFuncSetAttribute((const void*)pk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_DYN_MAX));
   if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[0], h->stream));
   pk<<<h->n_cu, nwv * 64, lds, h->stream>>>(P);
   if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[1], h->stream));
   TSEM_HIP(hipGetLastError());
   pt.lap("report: k_report_pack32");
-  const int W = std::min(IDN, (TS_LDS_MAX - 1024) / 8);
-  TSEM_HIP(hipFuncSetAttribute((const void*)k_report_hist, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+  const int W = std::min(IDN, TS_LDS_DYN_MAX / 8);
+  TSEM_HIP(hipFuncSetAttribute((const void*)k_report_hist, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_DYN_MAX));
   for (int id0 = 0; id0 < IDN; id0 += W)
     k_report_hist<<<h->n_cu, 1024, (size_t)std::min(W, IDN - id0) * 8, h->stream>>>(h->N, P.win, id0, std::min(W, IDN - id0), R.g_n1, R.g_conf);
   return TSEM_OK;
@@ -1522,7 +1522,7 @@ static int report_streaming(tsem_ctx* h, ReportArgs& R, bool codes_only) {
   const ReportKern rk = ri.k;
   tsem_ctx::ReportLaunch& L = launch_record(h, 0, codes_only ? 3 : 2, init, 0);
   L.G = ri.G; L.E = ri.E; L.Hs = R.Hs; L.HC = R.HC; L.grid = h->n_cu; L.block = rr_nt(init);
-  TSEM_HIP(hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+  TSEM_HIP(hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_DYN_MAX));
   if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[0], h->stream));
   rk<<<h->n_cu, rr_nt(init), lds, h->stream>>>(R);
   if (h->rep_timed) TSEM_HIP(hipEventRecord(h->ev_rep[1], h->stream));
@@ -1721,7 +1721,7 @@ int tsem_reassign_rows(tsem_ctx* h, int method, double thresh, int which, const 
     if (codes_path_ok(h)) {
       const int Hs = std::min(h->Kpad, (TS_LDS_MAX - 2048) / 4);
       const int grid = (int)std::min<int64_t>(h->n_cu, std::max<int64_t>(1, (n + 63) / 64));
-      TSEM_HIP(hipFuncSetAttribute((const void*)k_choose_init_codes, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+      TSEM_HIP(hipFuncSetAttribute((const void*)k_choose_init_codes, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_DYN_MAX));
       k_choose_init_codes<<<grid, 1024, (size_t)Hs * 4, h->stream>>>(n, rows ? d_rows : h->d_tie_rows, d_picks, h->d_indptr, h->d_raw, h->d_rid16,
                                                                      h->d_col_of_id, d_cs, Hs);
       TSEM_HIP(hipGetLastError());
@@ -1970,7 +1970,7 @@ int tsem_reassign_groups(tsem_ctx* h, int method, double thresh, int which, cons
     L.G = ri.G; L.E = ri.E; L.HC = R.HC; L.grid = h->n_cu; L.block = rr_nt(init);
     rs = gm == 1 ? report_slow_kernel<1>(init) : gm == 2 ? report_slow_kernel<2>(init)
        : gm == 4 ? report_slow_kernel<4>(init) : report_slow_kernel<3>(init);
-    TSEM_HIP(hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+    TSEM_HIP(hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_DYN_MAX));
   }
   for (int g0 = 0; g0 < n_groups; g0 += tile) {
     const int g1 = std::min(n_groups, g0 + tile);

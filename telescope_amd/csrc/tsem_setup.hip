@@ -981,7 +981,7 @@ int tsem_choose_geometry(tsem_ctx* h) {
   // option "reproducible" = 1: both pieces of the exact sums in ONE pass if three tables per part fit the LDS with at most 8
   // parts (score codes; 26 B of LDS per column); else — or with "reproducible" = 2 — two passes over two tables
   h->exact_single = false;
-  if (h->opt_reproducible == 1 && h->em_kernel != TSEM_EMK_TWOPASS && h->opt_format != 1 && h->lut_len > 0 && h->lut_len <= 2048) {
+  if (h->opt_reproducible == 1 && h->em_kernel != TSEM_EMK_TWOPASS && h->opt_format != 1 && fz_lut_fits(h->lut_len)) {
     const int p3 = h->opt_P > 0 ? (int)h->opt_P : (K + TS_MAX_KP3 - 64 - 1) / (TS_MAX_KP3 - 64);
     // teams of 5-8 have ONE geometry (384 row slots): worth it only when the rows are long enough to fill their register
     // tiles (20M x 30k: 100 per row 9.4 -> 6.3 ms per iteration, 18 per row 2.4 -> 3.3; K = 15k, teams of 4: 3.9 -> 2.6 at
@@ -1065,8 +1065,7 @@ int tsem_choose_geometry(tsem_ctx* h) {
     if (h->opt_geo >= 0 && P <= 4) h->geo = (h->opt_geo == 2 || (h->opt_geo == 3 && !h->lnl3)) ? (int)h->opt_geo : 0;
     if (h->opt_geo >= 0 && P > 4) h->geo = h->opt_geo == 2 ? 2 : 1;
     double r = 1.07 * fz_cap(h->geo) * P / std::max(2.0, mean_len);
-    const int lut_bytes = (h->lut_len > 0 && h->lut_len <= 2048) ? h->lut_len * 8 : 0;   // the score table shares LDS with the rings
-    int rmax = std::min(fz_rmax(h->geo), (TS_LDS_MAX - 2560 - (h->split ? Kp + 2 : ((h->exact_single || h->lnl3) ? 3 : 2) * Kp) * 8 - lut_bytes - std::max(h->opt_reproducible ? Kp * 2 + 16 : 0, FZ_LOGTAB * 16 + 16)) / ((fz_yr(h->geo) + (h->lnl3 ? 4 : 2)) * 8));
+    int rmax = fz_layout_rmax(Kp, h->geo, h->split, h->exact_single, h->lnl3, h->opt_reproducible != 0, h->lut_len);   // (the score table shares LDS with the rings)
     rmax = std::min(rmax, FILL_MAX_RP / P);                // (k_sb_fill_sorted keeps R x P counters in LDS)
     R = (int)std::min<double>(r, rmax);
     R = std::max(64, (R + 63) / 64 * 64);
@@ -1284,7 +1283,7 @@ static int scan_i64(tsem_ctx* h, int64_t* in, int64_t* out, size_t n, DevTmp& sc
 // the large dynamic LDS for one kernel; a kernel that does not exist fails with `missing` where the caller has a text for it
 static int allow_large_lds(tsem_ctx* h, const void* f, const char* missing = nullptr) {
   if (!f && missing) TSEM_FAIL(TSEM_ERR_ARG, missing);
-  TSEM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024));
+  TSEM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_DYN_MAX));
   return TSEM_OK;
 }
 
@@ -1379,9 +1378,9 @@ static int layout_column_map(tsem_ctx* h, LayoutBuild& b) {
 static bool quad_possible(const tsem_ctx* h) {
   if (h->opt_index == 1 || !h->use_fused || h->split || h->opt_reproducible || h->P > FZ_MAX_P) return false;
   if (h->geo > 1 || h->R > TS_QUAD64_MAX_R || h->Kp >= TS_QUAD64_MAX_KP) return false;
-  if (fz_wants_codes(h) && fz_lds_bytes(h, true) <= (size_t)TS_LDS_MAX - 1024) return false;          // score codes (layout_decide_format)
+  if (fz_wants_codes(h) && fz_lds_bytes(h, true) <= (size_t)TS_LDS_DYN_MAX) return false;          // score codes (layout_decide_format)
   if (!(h->R * h->P <= FILL_MAX_RP && (h->opt_sorted >= 0 ? h->opt_sorted != 0 : true))) return false;   // row order
-  const int fmt = (h->lut_len > 0 && h->lut_len <= 2048 && fz_lds_bytes(h, true) <= (size_t)TS_LDS_MAX - 1024) ? 2 : 0;
+  const int fmt = (fz_lut_fits(h->lut_len) && fz_lds_bytes(h, true) <= (size_t)TS_LDS_DYN_MAX) ? 2 : 0;
   return fz_exists(h->P, 0, fmt, h->geo, false, FZ_IXQ) && fz_exists(h->P, 1, fmt, h->geo, false, FZ_IXQ);
 }
 
@@ -1545,13 +1544,13 @@ static int layout_subblock_offsets(tsem_ctx* h, LayoutBuild& b) {
 // context is written here and nowhere else in a build of the blocked layout (layout_identity_map clears them).  No device work.
 static int layout_decide_format(tsem_ctx* h) {
   const int R = h->R;
-  if (h->use_fused && (R > fz_rmax(h->geo) || (R & 1) || fz_lds_bytes(h, false) > (size_t)TS_LDS_MAX - 1024)) h->use_fused = false;
+  if (h->use_fused && (R > fz_rmax(h->geo) || (R & 1) || fz_lds_bytes(h, false) > (size_t)TS_LDS_DYN_MAX)) h->use_fused = false;
   // the packed index has 13 bits of column slot and 11 of row slot: every non-split fused layout fits by construction (Kp <= TS_MAX_KP,
   // R <= fz_rmax); one that did not would keep the 32-bit index and the two-pass kernels that read it
   if (h->use_fused && !h->split && (h->Kp > TS_IDX24_MAX_KP || R > TS_IDX24_MAX_R)) h->use_fused = false;
-  h->fmt_code = h->use_fused && fz_wants_codes(h) && fz_lds_bytes(h, true) <= (size_t)TS_LDS_MAX - 1024;
-  h->fmt_wcode = h->use_fused && !h->fmt_code && h->lut_len > 0 && h->lut_len <= 2048 &&
-                 fz_lds_bytes(h, true) <= (size_t)TS_LDS_MAX - 1024;
+  h->fmt_code = h->use_fused && fz_wants_codes(h) && fz_lds_bytes(h, true) <= (size_t)TS_LDS_DYN_MAX;
+  h->fmt_wcode = h->use_fused && !h->fmt_code && fz_lut_fits(h->lut_len) &&
+                 fz_lds_bytes(h, true) <= (size_t)TS_LDS_DYN_MAX;
   if (h->opt_format == 2 && !h->fmt_code)
     TSEM_FAIL(TSEM_ERR_ARG, "value_format=codes needs the fused kernel and a score table of at most 2048 entries");
   if (h->opt_reproducible && !(h->use_fused && (h->fmt_code || h->fmt_wcode)))
@@ -1668,7 +1667,7 @@ static int layout_fill(tsem_ctx* h, LayoutBuild& b) {
     // While the device fills the layout (15 ms at 2e9 entries) the host loads the code object of the fused kernel's unit — 3 ms in a
     // fresh process, at the first hipFuncSetAttribute / launch of one of its kernels — instead of doing so afterwards.
     fz_fn f0 = P <= FZ_MAX_P ? fz_kernel(P, h->split ? 5 : 0, fz_fmt(h), h->geo, false, h->index_fmt) : nullptr;
-    if (f0) (void)hipFuncSetAttribute((const void*)f0, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_MAX - 1024);   // (a preload: its error is the later call's)
+    if (f0) (void)hipFuncSetAttribute((const void*)f0, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_DYN_MAX);   // (a preload: its error is the later call's)
     tsem_report_preload();                                 // (round 6: the report unit's too — ~10 ms that used to sit in the first report)
     TSEM_HIP(hipStreamSynchronize(h->stream));
     if (deconflict) h->order_kind = 1;
@@ -1702,7 +1701,7 @@ static int layout_launch_buffers(tsem_ctx* h) {
   const int K = h->K, P = h->P, Kp = h->Kp, R = h->R;
   if (!h->use_fused) TSEM_ALLOC(h->d_ypart, (int64_t)P * h->N_amb_pad);   // partial row sums of the two-pass kernels
   const size_t lds1 = (size_t)(Kp + R) * 8, lds2 = (size_t)(2 * Kp + R) * 8;
-  if (lds2 > (size_t)TS_LDS_MAX - 1024 && !h->use_fused) TSEM_FAIL(TSEM_ERR_ARG, "LDS budget exceeded (reduce block_rows)");   // (the two-pass kernels' tables; the split layout has its own budget)
+  if (lds2 > (size_t)TS_LDS_DYN_MAX && !h->use_fused) TSEM_FAIL(TSEM_ERR_ARG, "LDS budget exceeded (reduce block_rows)");   // (the two-pass kernels' tables; the split layout has its own budget)
   int w1 = std::max(1, std::min(4, (int)(TS_LDS_MAX / lds1)));   // 512-thread WGs per CU
   int w2 = std::max(1, std::min(2, (int)(TS_LDS_MAX / lds2)));   // 1024-thread WGs per CU
   h->G1 = (int)std::max<int64_t>(1, std::min<int64_t>(h->nb, (int64_t)h->n_cu * w1 / P));
